@@ -3,7 +3,13 @@
 on ONE synthetic DrivAerNet++-shaped sample (BASELINE.json configs[1]: 500K points, latent 64x64x32, knn k=8
 encoder + flipped decoder, model section of the reference's pressure.yaml: C=32, P=2, d=256, h=8, F=1024, L=10, rope).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line (`ms_per_step` = wall time of the timed region / K).
+Everything else -- the secondary timings, the HBM copy peak, per-kernel HIP-event timings and the roofline figures built
+on them, the CPU baseline, at N>1 the exchange profiles and the overlap_dw A/B -- runs only with ``--full``.
+``--dump-outputs DIR``: after the timed steps, what the last one computed is written as float32 ``DIR/<name>.npy``
+(loss, predictions, the updated parameters and their gradients; a fixed, seeded sample of an array above its cap).
 
 N>1 from a plain shell: this process does NOT touch the GPU; it starts ``python -m torch.distributed.run --nnodes=1
 --nproc-per-node N --master-addr 127.0.0.1 ...`` as a fresh child (one rank per GPU over RCCL), relays the child's
@@ -94,6 +100,13 @@ def parse_args(argv=None):
                          "attention (all-to-all); head = replicated except the attention heads; replicated = not at all")
     ap.add_argument("--dry-run", action="store_true",
                     help="exercise launch + rendezvous only (gloo, no GPU work): prints a JSON line with n_ranks_seen")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: secondary timings (--no-secondary), HBM copy peak, "
+                         "per-kernel timings and roofline figures, CPU baseline (--no-cpu-baseline); N>1: exchange profiles, "
+                         "the overlap_dw A/B.  Default: set up, warm up, time --steps steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as float32 DIR/<name>.npy: loss, pred "
+                         "(N=1), params and grads (after the optimizer step); above DUMP_CAP elements a fixed, seeded sample")
     return ap.parse_args(argv)
 
 
@@ -299,10 +312,11 @@ def cpu_baseline(mode, layers, k, seed, atten_dropout, points, latent_full, cpu_
     # SURVEY 8d asks for the host's own cores.  MEASURED on the pool's 256-thread boxes: the full step on all 256 threads takes
     # 253.8 s against 28.3 s on 64 (profiles/archive/r5_j_bench_bf16_graph.json), the bounded step 214 s against 5.1 s on 16
     # (profiles/archive/r5_k_bench_default.json) -- the segmented reductions and the fp32 GEMMs of [16 384, 256] rows do not scale past a
-    # socket's worth, oversubscribed they collapse.  So the full-sample step runs on min(os.cpu_count(), 64) threads, the host's
-    # thread count and CPU model are named in the line, and --cpu-baseline-all-cores repeats the all-cores measurement on request
+    # socket's worth, oversubscribed they collapse.  So the full-sample step runs on at most 64 threads and never on more than the
+    # process may keep busy (usable_cpus), the host's thread count and CPU model are named in the line, and
+    # --cpu-baseline-all-cores repeats the all-cores measurement on request
     ncpu = os.cpu_count() or 1
-    cores = min(ncpu, 16) if mode == "sample" else min(ncpu, 64)
+    cores = min(usable_cpus(), 16 if mode == "sample" else 64)
     torch.set_num_threads(cores)
     cfg = model_config(latent, layers, k)
     torch.manual_seed(seed)
@@ -402,6 +416,65 @@ def cpu_baseline_auto(budget_s, layers, k, seed, atten_dropout, points, latent_f
         return red
     full["bounded_sample"] = {kk: red[kk] for kk in ("value", "cores", "seconds_per_step", "sample", "seconds_by_threads") if kk in red}
     return full
+
+
+# keys of the result line that only a --full run fills in (their measurements take runs of their own)
+FULL_ONLY_KEYS = ("kernel_launches_per_step", "foreign_kernel_nodes_per_step", "instrumented_eager_ms_per_step",
+                  "instrumented_eager_host_ms_per_step", "without_attention_dropout", "geometry_cached", "hbm_copy_peak_measured",
+                  "fp32_mode", "other_scaling", "roofline", "gno_hbm", "kernels")
+
+# --dump-outputs: at most this many elements per array (13 Mi float32 = 52 MiB in all; loss is one element)
+DUMP_CAP = {"pred": 3 << 20, "params": 5 << 20, "grads": 5 << 20}
+
+
+def dump_outputs(out_dir, loss, pred, params):
+    """what the step computed in its last run, as float32 .npy files: loss, pred (None: not written), and every parameter
+    after the optimizer step with its gradient, flattened and concatenated in named_parameters() order.  An array above its
+    DUMP_CAP is replaced by the elements at a fixed, seeded set of flat indices (the same set for params and grads).
+    -> {name: shape written}"""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    params = list(params)
+    arrays = {"loss": loss.detach().float().reshape(())}
+    if pred is not None:
+        arrays["pred"] = pred.detach().float()
+    arrays["params"] = torch.cat([p.detach().float().reshape(-1) for p in params])
+    arrays["grads"] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().float().reshape(-1)
+                                 for p in params])
+    written = {}
+    for name, t in arrays.items():
+        cap = DUMP_CAP.get(name)
+        if cap is not None and t.numel() > cap:
+            idx = np.sort(np.random.default_rng(20261016).choice(t.numel(), size=cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
+
+
+def usable_cpus():
+    """CPUs this process may keep busy: os.cpu_count() counts the whole host, so cap it by the affinity mask, the cgroup CPU
+    quota and OMP_NUM_THREADS when they are set"""
+    n = os.cpu_count() or 1
+    try:
+        n = min(n, len(os.sched_getaffinity(0)))
+    except (AttributeError, OSError):
+        pass
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, int(quota) // int(period)))
+    except (OSError, ValueError):
+        pass
+    try:
+        omp = int(os.environ["OMP_NUM_THREADS"])
+        if omp > 0:
+            n = min(n, omp)
+    except (KeyError, ValueError):
+        pass
+    return max(1, n)
 
 
 def csrc_sha16():
@@ -526,6 +599,7 @@ def main(argv=None):
     s_tok = m_lat // 8
 
     geometry_cached = {"on": False}
+    outputs = {}      # what the latest step returned beside its loss (N=1: the predictions)
 
     def build(n_total, atten_dropout, parallel):
         """model + optimizer + rank-local inputs + step() for one sample of n_total points"""
@@ -555,6 +629,7 @@ def main(argv=None):
             opt.zero_grad(set_to_none=True)
             if step_ctx is None:
                 pred = model(batch=batch, tokens_pos=tokens)
+                outputs["pred"] = pred.detach()     # --dump-outputs (of a captured step: the graph's own output buffer)
                 loss = GF.mse_loss(pred, batch.x)
                 loss.backward()
                 loss = loss.detach()    # nothing of the step's autograd graph outlives the step: a live AccumulateGrad node of
@@ -583,6 +658,7 @@ def main(argv=None):
                     step()
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
+            outputs.clear()     # an eager step's tensors are released here, not inside the capture
             try:
                 dot = os.environ.get("GAOT_BENCH_GRAPH_DOT")    # diagnostic: node / edge structure of the captured step
                 graph = torch.cuda.CUDAGraph(keep_graph=True)
@@ -712,8 +788,9 @@ def main(argv=None):
     eager_rec = seg_rec = None
     exchange_profile = {}
 
-    def sharded_modes(e_eager, loss_eager, th_eager, ms_eager):
+    def sharded_modes(e_eager, loss_eager, th_eager, ms_eager, profile):
         """N > 1: given the timed EAGER step, add its exchange profile, then record + time + profile the SEGMENTED replay
+        (profile=False: no exchange profiles, the two timings only)
         -> (eager record, segmented record, profiles, best = (elapsed, loss, host s, graph or None, per-step ms))"""
         from gaot_3d_amd import comm
         prof_out = {}
@@ -721,15 +798,16 @@ def main(argv=None):
                      host_ms_per_step=round(th_eager / args.steps * 1e3, 3))
         best = (e_eager, loss_eager, th_eager, None, list(ms_eager))
         # per-rank split of the EAGER step's device time first (no capture involved): exchange steps vs kernels
-        try:
-            k_prof = max(1, min(args.steps, 3))
-            with comm.eager_profile() as prof:
-                for _ in range(k_prof):
-                    step()
-            torch.cuda.synchronize()
-            prof_out["eager"] = prof.summary(k_prof)
-        except Exception as ex:
-            prof_out["eager"] = dict(error=f"{type(ex).__name__}: {ex}")
+        if profile:
+            try:
+                k_prof = max(1, min(args.steps, 3))
+                with comm.eager_profile() as prof:
+                    for _ in range(k_prof):
+                        step()
+                torch.cuda.synchronize()
+                prof_out["eager"] = prof.summary(k_prof)
+            except Exception as ex:
+                prof_out["eager"] = dict(error=f"{type(ex).__name__}: {ex}")
         sg = None
         seg_err = None
         try:
@@ -752,10 +830,11 @@ def main(argv=None):
                          graph_segments=sg.num_segments, exchanges=sg.num_exchanges,
                          host_launches_plus_collectives=sg.num_segments + sg.num_exchanges,
                          side_stream_closures=sum(len(v) for v in sg.side))
-            try:
-                prof_out["segmented"] = sg.replay_profiled(max(1, min(args.steps, 3)))
-            except Exception as ex:
-                prof_out["segmented"] = dict(error=f"{type(ex).__name__}: {ex}")
+            if profile:
+                try:
+                    prof_out["segmented"] = sg.replay_profiled(max(1, min(args.steps, 3)))
+                except Exception as ex:
+                    prof_out["segmented"] = dict(error=f"{type(ex).__name__}: {ex}")
             if e_s < e_eager:
                 best = (e_s, loss_s, th_s, sg, list(last_step_ms))
         else:
@@ -763,21 +842,26 @@ def main(argv=None):
         return e_rec, s_rec, prof_out, best
 
     if world > 1 and not args.no_graph and not args.no_segmented:
-        eager_rec, seg_rec, exchange_profile, best = sharded_modes(elapsed, loss, t_host_main, main_step_ms)
+        eager_rec, seg_rec, exchange_profile, best = sharded_modes(elapsed, loss, t_host_main, main_step_ms, args.full)
         elapsed, loss, t_host_main, graph, main_step_ms = best
+
+    if args.dump_outputs and rank == 0:
+        # before anything else runs a step: at N>1 the last step run is the last timed one of the launch mode timed last
+        written = dump_outputs(args.dump_outputs, loss, outputs.get("pred"), model.parameters())
+        print(f"[bench] outputs of the last timed step written to {args.dump_outputs}: {written}", file=sys.stderr)
 
     secondary = None
     fp32_mode = None
     weak = None
     geom_cached = None
     copy_peak = None
-    if world == 1:
+    if world == 1 and args.full:
         try:
             copy_peak = round(ops.stream_copy_gbps(), 1)     # float4 copy, 1 GiB, read + written bytes / HIP-event time
         except Exception as ex:
             copy_peak = None
             print(f"[bench] stream copy failed ({type(ex).__name__}: {ex})", file=sys.stderr)
-    if world == 1 and not args.no_secondary:
+    if world == 1 and args.full and not args.no_secondary:
         # the same step with the per-sample constants (neighbour lists, GeoEmbed statistics) served from the cache on the
         # batch, as the reference's offline edge precompute does (stat.py:126-224); SURVEY 8d asks for both figures
         try:
@@ -835,20 +919,21 @@ def main(argv=None):
                 gaot_3d_amd.set_precision(args.precision)
 
     # per-kernel durations: HIP events around the instrumented launches of two more (eager) steps on the same stream
-    ops.timing_reset(True)
-    ops.launch_count_reset()
-    t_e = time.perf_counter()
-    for _ in range(2):
-        step()
-    t_host = (time.perf_counter() - t_e) / 2
-    torch.cuda.synchronize()
-    t_eager = (time.perf_counter() - t_e) / 2
-    n_timed_steps = 2
-    timing = ops.timing_summary()
-    launches = ops.launch_count() / n_timed_steps
-    ops.timing_reset(False)
+    timing, launches, t_host, t_eager, n_timed_steps = {}, None, None, None, 2
+    if args.full:
+        ops.timing_reset(True)
+        ops.launch_count_reset()
+        t_e = time.perf_counter()
+        for _ in range(2):
+            step()
+        t_host = (time.perf_counter() - t_e) / 2
+        torch.cuda.synchronize()
+        t_eager = (time.perf_counter() - t_e) / 2
+        timing = ops.timing_summary()
+        launches = ops.launch_count() / n_timed_steps
+        ops.timing_reset(False)
 
-    if world > 1 and not args.no_secondary:
+    if world > 1 and args.full and not args.no_secondary:
         other = "weak" if args.scaling == "strong" else "strong"
         try:
             n2 = args.points * world if other == "weak" else args.points
@@ -995,7 +1080,7 @@ def main(argv=None):
                          "head": f"point-shard x{world}; latent Transformer replicated except the attention heads "
                                  f"(all-gather of head outputs)",
                          "replicated": f"point-shard x{world}; latent Transformer replicated"}[args.parallel]
-        return {
+        line = {
             "metric": metric,
             "value": n_total / (elapsed / args.steps),
             "unit": "points/s",
@@ -1028,12 +1113,13 @@ def main(argv=None):
             # census of the REPLAYED graph (HIP graph API): kernel nodes = our launches + whatever ATen / the runtime added
             "graph_nodes_per_step": main_capture["nodes"],
             "foreign_kernel_nodes_per_step": (main_capture["nodes"]["kernel"] - launches
-                                              if main_capture["nodes"] and "kernel" in main_capture["nodes"] else None),
+                                              if launches is not None and main_capture["nodes"] and "kernel" in main_capture["nodes"]
+                                              else None),
             "host_ms_per_step_timed_region": round(host_ms / args.steps * 1e3, 3),
             # wall / host time of the two instrumented eager steps (right after a capture the eager allocations go back
             # to hipMalloc, so with a captured graph these overstate a warmed-up eager step)
-            "instrumented_eager_ms_per_step": round(t_eager * 1e3, 3),
-            "instrumented_eager_host_ms_per_step": round(t_host * 1e3, 3),
+            "instrumented_eager_ms_per_step": round(t_eager * 1e3, 3) if t_eager is not None else None,
+            "instrumented_eager_host_ms_per_step": round(t_host * 1e3, 3) if t_host is not None else None,
             "without_attention_dropout": secondary,
             "geometry_cached": geom_cached,
             "hbm_copy_peak_measured": (dict(gbps=copy_peak, frac_of_8tbps=round(copy_peak / 8000.0, 4),
@@ -1047,7 +1133,12 @@ def main(argv=None):
             "step_roofline": troof,
             "kernels": {kname: {kk: (round(v, 4) if isinstance(v, float) else v) for kk, v in ent.items()}
                         for kname, ent in per_kernel.items()},
+            "full": args.full,
         }
+        if not args.full:       # figures that need runs of their own: --full
+            for kk in FULL_ONLY_KEYS:
+                del line[kk]
+        return line
 
     if world > 1 and graph is not None:
         launch_txt = (f"segmented hipGraph replay: {graph.num_segments} graph launches + {graph.num_exchanges} eagerly issued "
@@ -1060,7 +1151,7 @@ def main(argv=None):
         else:
             launch_txt = "eager"
     out = make_out(elapsed, launch_txt, t_host_main, main_step_ms) if rank == 0 else None
-    if world > 1:
+    if world > 1 and args.full:
         # one line that explains a flat curve: per rank, the device time inside exchange steps (per collective kind, with the
         # bytes moved) against the device time inside the kernels between them; MIN / MAX over the ranks
         gathered = [None] * world
@@ -1076,7 +1167,7 @@ def main(argv=None):
     # ---- N > 1: the same step with the weight-gradient GEMMs, bucket copies and bucket all-reduces on a SIDE stream
     # (ShardedStep(overlap_dw=True): gaot_3d_amd/comm.py side_run), both launch modes again, under a watchdog: a mode that
     # wedges reports the already measured line and leaves instead of hanging the job
-    if world > 1 and not args.no_graph and not args.no_segmented and not args.no_overlap_dw and step_ctx is not None:
+    if world > 1 and args.full and not args.no_graph and not args.no_segmented and not args.no_overlap_dw and step_ctx is not None:
         import threading
         ab_done = threading.Event()
 
@@ -1097,7 +1188,7 @@ def main(argv=None):
         try:
             step_ctx.set_overlap_dw(True)
             e_o, _, loss_o, th_o = measure(step, args.steps, args.warmup, False)
-            e_rec, s_rec, prof_o, best_o = sharded_modes(e_o, loss_o, th_o, list(last_step_ms))
+            e_rec, s_rec, prof_o, best_o = sharded_modes(e_o, loss_o, th_o, list(last_step_ms), True)
             ab = dict(eager=e_rec, segmented=s_rec)
             gathered = [None] * world
             dist.all_gather_object(gathered, prof_o)
@@ -1141,7 +1232,7 @@ def main(argv=None):
                     out = make_out(eg, "hipGraph replay of one captured step (RCCL collectives captured)", thg)
                     out.update(keep)
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             if args.cpu_baseline == "auto":
                 out["cpu_baseline"] = cpu_baseline_auto(args.cpu_baseline_budget, args.layers, args.knn, args.seed,
                                                         args.atten_dropout, 500000, latent, args.cpu_baseline_dropout,

@@ -27,7 +27,11 @@ def _stream() -> C.c_void_p:
 
 
 def _ptr(t: Optional[Tensor]) -> C.c_void_p:
-    return C.c_void_p(0 if t is None else t.data_ptr())
+    if t is None:
+        return C.c_void_p(0)
+    if not t.is_cuda:   # a host address reaches the kernels as an illegal access on the device: refuse it here
+        raise GaotError(f"expected a tensor on the GPU (the HIP path has no CPU fallback), got {t.device}")
+    return C.c_void_p(t.data_ptr())
 
 
 def _req(t: Tensor, dtype, name: str) -> Tensor:
@@ -1277,7 +1281,7 @@ def geoembed_from_moments(mom: Tensor) -> Tensor:
 def _ptr_array(ts):
     arr = (C.c_void_p * len(ts))()
     for i, t in enumerate(ts):
-        arr[i] = t.data_ptr()
+        arr[i] = _ptr(t).value
     return arr
 
 

@@ -15,6 +15,7 @@ Stubs:
 
 Usage:  python oracle/make_goldens.py     (needs /root/reference)
 """
+import glob
 import json
 import os
 import sys
@@ -99,14 +100,38 @@ def install_stubs():
     sys.modules["rotary_embedding_torch"] = rot
 
 
+MAX_FILE_BYTES = 1 << 20     # no committed file reaches 1 MiB: a larger golden is stored as name.npz + name.part1.npz + ...
+
+
 def save(name, meta, arrays):
     os.makedirs(OUT, exist_ok=True)
     flat = {"__meta__": np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)}
     for k, v in arrays.items():
         flat[k] = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
-    path = os.path.join(OUT, name + ".npz")
-    np.savez_compressed(path, **flat)
-    print(f"wrote {path}: {os.path.getsize(path) / 1024:.1f} KiB")
+    write_parts(name, flat)
+
+
+def write_parts(name, flat):
+    """flat as OUT/name.npz; while a file would reach MAX_FILE_BYTES, its run of keys is halved and the second half goes
+    into the next part file (key order kept across name.npz, name.part1.npz, ...; tests/golden_io.load joins them)"""
+    keys = list(flat)
+    runs = [keys]
+    while True:
+        for old in glob.glob(os.path.join(OUT, glob.escape(name) + ".part*.npz")):
+            os.remove(old)
+        paths = []
+        for i, run in enumerate(runs):
+            path = os.path.join(OUT, name + (".npz" if i == 0 else f".part{i}.npz"))
+            np.savez_compressed(path, **{k: flat[k] for k in run})
+            paths.append(path)
+        big = next((i for i, path in enumerate(paths) if os.path.getsize(path) >= MAX_FILE_BYTES), None)
+        if big is None:
+            break
+        if len(runs[big]) < 2:
+            raise RuntimeError(f"{name}: the array {runs[big][0]} alone compresses to {MAX_FILE_BYTES} bytes or more")
+        runs[big:big + 1] = [runs[big][:len(runs[big]) // 2], runs[big][len(runs[big]) // 2:]]
+    for path in paths:
+        print(f"wrote {path}: {os.path.getsize(path) / 1024:.1f} KiB")
 
 
 def grads_of(module):

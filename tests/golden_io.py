@@ -11,15 +11,26 @@ from gaot_3d_amd.data import MeshBatch
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
+def part_paths(name):
+    """name.npz, then name.part1.npz, name.part2.npz, ... while they exist (a golden that would reach the 1 MiB limit of a
+    committed file is stored in parts, oracle/make_goldens.py: write_parts)"""
+    paths = [os.path.join(GOLDEN_DIR, name + ".npz")]
+    while os.path.exists(os.path.join(GOLDEN_DIR, f"{name}.part{len(paths)}.npz")):
+        paths.append(os.path.join(GOLDEN_DIR, f"{name}.part{len(paths)}.npz"))
+    return paths
+
+
 def load(name):
-    z = np.load(os.path.join(GOLDEN_DIR, name + ".npz"))
-    meta = json.loads(bytes(z["__meta__"]).decode())
+    meta = None
     groups = {"sd": {}, "in": {}, "out": {}, "grad": {}}
-    for k in z.files:
-        if k == "__meta__":
-            continue
-        g, rest = k.split("/", 1)
-        groups[g][rest] = torch.from_numpy(np.array(z[k]))
+    for path in part_paths(name):
+        z = np.load(path)
+        for k in z.files:
+            if k == "__meta__":
+                meta = json.loads(bytes(z["__meta__"]).decode())
+                continue
+            g, rest = k.split("/", 1)
+            groups[g][rest] = torch.from_numpy(np.array(z[k]))
     return meta, groups
 
 

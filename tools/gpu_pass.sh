@@ -21,7 +21,7 @@ python3 tools/pmc_sq.py $out/${tag}_pmc_sq1 $out/${tag}_pmc_sq2 $out/${tag}_pmc_
 cp $out/${tag}_pmc_sq.json profiles/pmc_sq.json
 # the bench line reads the traffic file of THESE kernel sources (hash-stamped): refresh it before the timed run
 cp $out/${tag}_pmc_traffic.json profiles/pmc_traffic.json
-python bench.py --steps 10 --warmup 3 > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+python bench.py --full --steps 10 --warmup 3 > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 # keep only the small summaries of the traces
 find $out/${tag}_prof $out/${tag}_pmc_fetch $out/${tag}_pmc_write -name "*_kernel_trace.csv" -delete
 find $out/${tag}_pmc_fetch $out/${tag}_pmc_write $out/${tag}_pmc_sq1 $out/${tag}_pmc_sq2 -name "*_counter_collection.csv" -delete

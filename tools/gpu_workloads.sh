@@ -21,7 +21,7 @@ for w in $wls; do
   cd $GRAFT_REPO_ROOT
   python3 tools/pmc_traffic.py $out/${tag}_${w}_pmc_fetch $out/${tag}_${w}_pmc_write $out/${tag}_${w}_pmc_traffic.json ${tag}_${w} > /dev/null 2>$out/${tag}_${w}_pmc.err
   cp $out/${tag}_${w}_pmc_traffic.json profiles/pmc_traffic_${w}.json
-  python bench.py $wa --steps 10 --warmup 3 --no-cpu-baseline > $out/${tag}_${w}_bench.json 2> $out/${tag}_${w}_bench.err
+  python bench.py $wa --full --steps 10 --warmup 3 --no-cpu-baseline > $out/${tag}_${w}_bench.json 2> $out/${tag}_${w}_bench.err
   find $out/${tag}_${w}_prof $out/${tag}_${w}_pmc_fetch $out/${tag}_${w}_pmc_write -name "*_kernel_trace.csv" -delete
   find $out/${tag}_${w}_pmc_fetch $out/${tag}_${w}_pmc_write -name "*_counter_collection.csv" -delete
   head -c 600 $out/${tag}_${w}_bench.json; echo
