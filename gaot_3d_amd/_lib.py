@@ -45,11 +45,16 @@ SIGNATURES = {
     "gaot_gno_bwd_workspace_bytes": (_sz, [C.POINTER(MlpT), _i64, _i64]),
     "gaot_gno_bwd": (_i, [C.POINTER(MlpT), _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p,
                           C.POINTER(MlpGradT), _i, _p, _sz, _p]),
+    "gaot_gno_bwd_coords": (_i, [C.POINTER(MlpT), _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p,
+                                 C.POINTER(MlpGradT), _p, _i, _p, _sz, _p]),
     "gaot_geoembed_stats_workspace_bytes": (_sz, []),
     "gaot_geoembed_moments": (_i, [_p, _p, _p, _p, _i64, _p, _p]),
     "gaot_geoembed_from_moments": (_i, [_p, _i64, _p, _p, _sz, _p]),
     "gaot_geoembed_raw": (_i, [_p, _p, _p, _p, _i64, _p, _p, _p, _sz, _p]),
     "gaot_geoembed_finalize": (_i, [_p, _i64, _p, _i64, _p, _sz, _p]),
+    "gaot_geoembed_from_moments_bwd_workspace_bytes": (_sz, [_i64]),
+    "gaot_geoembed_from_moments_bwd": (_i, [_p, _p, _i64, _p, _p, _sz, _p]),
+    "gaot_geoembed_moments_bwd": (_i, [_p, _p, _p, _p, _i64, _p, _p, _p, _p]),
     "gaot_gemm_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "gaot_gemm": (_i, [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i, _i, _p, _i, _p, _i64, _p, _i, _p, _sz, _p]),
     "gaot_gemm_ex": (_i, [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i, _p, _i, _p, _i64, _p, _i, _p,

@@ -7,7 +7,8 @@
 // The reference spends 6 scatter passes + a batched LAPACK eigvalsh; here: one sweep over the
 // row-sorted neighbour list (8 lanes per row, two passes per row: centroid, then covariance, all
 // sums in fp64), a cyclic Jacobi 3x3 eigen-solve in registers, a two-stage column reduction and a
-// normalise pass.  Inputs are coordinates only (no autograd), so the result is cacheable per sample.
+// normalise pass.  Inputs are coordinates only, so the result is cacheable per sample; its backward in the coordinates
+// (gaot_geoembed_from_moments_bwd + gaot_geoembed_moments_bwd) is at the end of this file.
 #include "common.h"
 
 namespace {
@@ -271,6 +272,182 @@ __global__ void k_geo_normalize(float* __restrict__ feat, int64_t Q, const float
     feat[i] = (feat[i] - stats[c]) / stats[NF + c];
 }
 
+// ---- backward in the coordinates (autograd of geoembed.py:117-182), mirroring the moment split -----------------------
+// z-score statistics exactly as k_geo_colfinal forms them, plus whether the std was replaced by 1 (then it carries no gradient):
+// stats[0..8] mean, [9..17] std as used, [18..26] 1 if replaced
+__global__ void k_geo_bwd_stats(const double* __restrict__ sums, int64_t Q, float* __restrict__ stats) {
+    const int i = threadIdx.x;
+    if (i >= NF) return;
+    const double mean = sums[i] / (double)Q;
+    double var = (Q > 1) ? (sums[NF + i] - (double)Q * mean * mean) / (double)(Q - 1) : NAN;
+    if (var < 0) var = 0;
+    float sd = (float)sqrt(var);
+    const bool rep = sd < 1e-6f;
+    if (rep) sd = 1.f;
+    stats[i] = (float)mean;
+    stats[NF + i] = sd;
+    stats[2 * NF + i] = rep ? 1.f : 0.f;
+}
+
+// per-block partial column sums of g and g * y (y = the z-scored feature, recomputed as k_geo_normalize forms it), layout of
+// k_geo_colpart (reduced by k_geo_colsums)
+__global__ void k_geo_bwd_colpart(const float* __restrict__ feat, const float* __restrict__ gy, const float* __restrict__ stats,
+                                  int64_t Q, double* __restrict__ part) {
+    __shared__ double sm[4][2 * NF];
+    double s[NF], s2[NF];
+#pragma unroll
+    for (int i = 0; i < NF; ++i) { s[i] = 0; s2[i] = 0; }
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < Q; r += (int64_t)gridDim.x * blockDim.x) {
+#pragma unroll
+        for (int i = 0; i < NF; ++i) {
+            const double g = gy[r * NF + i];
+            const double y = (feat[r * NF + i] - stats[i]) / stats[NF + i];
+            s[i] += g;
+            s2[i] += g * y;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < NF; ++i) {
+        s[i] = wave_sum_d(s[i]);
+        s2[i] = wave_sum_d(s2[i]);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int i = 0; i < NF; ++i) { sm[threadIdx.x >> 6][i] = s[i]; sm[threadIdx.x >> 6][NF + i] = s2[i]; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * NF)
+        part[(int64_t)blockIdx.x * 2 * NF + threadIdx.x] =
+            sm[0][threadIdx.x] + sm[1][threadIdx.x] + sm[2][threadIdx.x] + sm[3][threadIdx.x];
+}
+
+// jacobi_rot that also applies the rotation to the columns p, q of the eigenvector matrix V (A' = J^T A J, V' = V J)
+template <int P, int Qc>
+__device__ __forceinline__ void jacobi_rot_v(double& app, double& aqq, double& apq, double& arp, double& arq, double (&v)[3][3]) {
+    if (fabs(apq) < 1e-300) return;
+    const double theta = (aqq - app) / (2.0 * apq);
+    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+    app -= t * apq;
+    aqq += t * apq;
+    apq = 0.0;
+    const double rp = c * arp - s * arq, rq = s * arp + c * arq;
+    arp = rp;
+    arq = rq;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const double vp = v[r][P], vq = v[r][Qc];
+        v[r][P] = c * vp - s * vq;
+        v[r][Qc] = s * vp + c * vq;
+    }
+}
+
+// dL/d features (z-scored) -> dL/d moments of one row: z-score, clamp, centroid, eigvalsh (dA = V diag(dlambda) V^T, the
+// 1e-6 I shift does not enter), covariance about the centroid in terms of the moments about the query
+__global__ void k_geo_from_moments_bwd(const double* __restrict__ mom, const float* __restrict__ feat,
+                                       const float* __restrict__ gy, const float* __restrict__ stats,
+                                       const double* __restrict__ gsums, int64_t Q, double* __restrict__ adj) {
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= Q) return;
+    const double* m = mom + row * NM;
+    double a[NM];
+#pragma unroll
+    for (int i = 0; i < NM; ++i) a[i] = 0.0;
+    const double n = m[0];
+    if (n > 0.5) {   // rows without neighbours were zeroed: no adjoint
+        double df[NF];
+#pragma unroll
+        for (int c = 0; c < NF; ++c) {
+            const double y = (feat[row * NF + c] - stats[c]) / stats[NF + c];
+            double d = (double)gy[row * NF + c] - gsums[c] / (double)Q;
+            if (stats[2 * NF + c] == 0.f) d = (d - y * gsums[NF + c] / (double)(Q - 1)) / (double)stats[NF + c];
+            df[c] = d;
+        }
+        const double inv = 1.0 / n;
+        const double davg = m[1] * inv;
+        const double dvar = m[2] * inv - davg * davg;
+        a[1] = df[1] * inv;
+        if (dvar >= 0.0) {   // torch.clamp(min=0): the gradient passes where the input is >= 0
+            a[2] = df[2] * inv;
+            a[1] -= 2.0 * davg * inv * df[2];
+        }
+        const double u[3] = {m[3] * inv, m[4] * inv, m[5] * inv};
+        double a00 = m[6] * inv - u[0] * u[0] + 1e-6, a11 = m[9] * inv - u[1] * u[1] + 1e-6, a22 = m[11] * inv - u[2] * u[2] + 1e-6;
+        double a01 = m[7] * inv - u[0] * u[1], a02 = m[8] * inv - u[0] * u[2], a12 = m[10] * inv - u[1] * u[2];
+        double v[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+#pragma unroll 1
+        for (int sweep = 0; sweep < 5; ++sweep) {   // the forward's sweeps, eigenvectors accumulated
+            jacobi_rot_v<0, 1>(a00, a11, a01, a02, a12, v);
+            jacobi_rot_v<0, 2>(a00, a22, a02, a01, a12, v);
+            jacobi_rot_v<1, 2>(a11, a22, a12, a01, a02, v);
+        }
+        // descending order as the forward sorts: ord[k] = eigen index of the k-th largest
+        const double lam[3] = {a00, a11, a22};
+        int ord[3] = {0, 1, 2}, t;
+        if (lam[ord[0]] < lam[ord[1]]) { t = ord[0]; ord[0] = ord[1]; ord[1] = t; }
+        if (lam[ord[0]] < lam[ord[2]]) { t = ord[0]; ord[0] = ord[2]; ord[2] = t; }
+        if (lam[ord[1]] < lam[ord[2]]) { t = ord[1]; ord[1] = ord[2]; ord[2] = t; }
+        double G[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int e = ord[k];
+            const double dl = df[6 + k];
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) G[i][j] += dl * v[i][e] * v[j][e];
+        }
+        // A = S_uu / n - u u^T:  dS_uu (stored upper triangle: off-diagonal entries stand for both of their positions)
+        a[6] = G[0][0] * inv; a[7] = (G[0][1] + G[1][0]) * inv; a[8] = (G[0][2] + G[2][0]) * inv;
+        a[9] = G[1][1] * inv; a[10] = (G[1][2] + G[2][1]) * inv; a[11] = G[2][2] * inv;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            double gu = 0.0;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) gu += (G[i][j] + G[j][i]) * u[j];
+            a[3 + i] = (df[3 + i] - gu) * inv;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < NM; ++i) adj[row * NM + i] = a[i];
+}
+
+// dL/d moments -> per-edge dL/du (u = source - query, by-query edge order) and dL/d query = -(row sum); 8 lanes per row as
+// k_geo_moments
+__global__ void k_geo_moments_bwd(const float* __restrict__ src_pos, const float* __restrict__ q_pos,
+                                  const int* __restrict__ rowptr, const int* __restrict__ src_sorted, int64_t Q,
+                                  const double* __restrict__ adj, float* __restrict__ gedge, float* __restrict__ gq) {
+    const int64_t row = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
+    const int gl = threadIdx.x % G;
+    if (row >= Q) return;
+    const int b = rowptr[row], e = rowptr[row + 1];
+    const double qx = q_pos[row * 3 + 0], qy = q_pos[row * 3 + 1], qz = q_pos[row * 3 + 2];
+    const double* a = adj + row * NM;
+    const double ad = a[1], ad2 = a[2], aux = a[3], auy = a[4], auz = a[5];
+    const double axx = a[6], axy = a[7], axz = a[8], ayy = a[9], ayz = a[10], azz = a[11];
+    double sx = 0, sy = 0, sz = 0;
+    for (int i = b + gl; i < e; i += G) {
+        const int s = src_sorted[i];
+        const double ux = (double)src_pos[(int64_t)s * 3 + 0] - qx, uy = (double)src_pos[(int64_t)s * 3 + 1] - qy,
+                     uz = (double)src_pos[(int64_t)s * 3 + 2] - qz;
+        const double r = sqrt(ux * ux + uy * uy + uz * uz);
+        const double w = (r > 0.0 ? ad / r : 0.0) + 2.0 * ad2;   // d|u|/du = u/|u| (0 at u = 0, as torch.norm)
+        const double gx = w * ux + aux + 2.0 * axx * ux + axy * uy + axz * uz;
+        const double gyv = w * uy + auy + axy * ux + 2.0 * ayy * uy + ayz * uz;
+        const double gz = w * uz + auz + axz * ux + ayz * uy + 2.0 * azz * uz;
+        gedge[(int64_t)i * 3 + 0] = (float)gx;
+        gedge[(int64_t)i * 3 + 1] = (float)gyv;
+        gedge[(int64_t)i * 3 + 2] = (float)gz;
+        sx += gx; sy += gyv; sz += gz;
+    }
+    sx = grp_sum(sx); sy = grp_sum(sy); sz = grp_sum(sz);
+    if (gl == 0) {
+        gq[row * 3 + 0] = (float)-sx;
+        gq[row * 3 + 1] = (float)-sy;
+        gq[row * 3 + 2] = (float)-sz;
+    }
+}
+
 }  // namespace
 
 extern "C" size_t gaot_geoembed_stats_workspace_bytes(void) { return sizeof(double) * 256 * 2 * NF + sizeof(float) * 2 * NF + 64; }
@@ -346,6 +523,50 @@ extern "C" int gaot_geoembed_finalize(float* features, int64_t num_queries, cons
     GAOT_KLAUNCH(k_geo_stats_from_sums, dim3(1), dim3(64), 0, st, colsums, num_queries_total, stats);
     GAOT_KLAUNCH(k_geo_normalize, dim3((unsigned)ceil_div(num_queries * NF, 256)), dim3(256), 0, st, features,
                        num_queries, stats);
+    GAOT_LAUNCH_CHECK();
+    return GAOT_OK;
+}
+
+// workspace: column partials (256 blocks), two sets of column sums, statistics, the un-normalised features [Q, 9]
+extern "C" size_t gaot_geoembed_from_moments_bwd_workspace_bytes(int64_t num_queries) {
+    return sizeof(double) * (256 * 2 * NF + 4 * NF) + sizeof(float) * (4 * NF) + sizeof(float) * (size_t)std::max<int64_t>(num_queries, 0) * NF + 256;
+}
+
+extern "C" int gaot_geoembed_from_moments_bwd(const double* moments, const float* grad_features, int64_t num_queries,
+                                              double* grad_moments, void* workspace, size_t workspace_bytes, gaot_stream_t stream) {
+    GAOT_ENTER();
+    GAOT_CHECK_ARG(num_queries >= 0, "negative size");
+    if (num_queries == 0) return GAOT_OK;
+    GAOT_CHECK_ARG(moments && grad_features && grad_moments && workspace, "null pointer");
+    GAOT_CHECK_ARG(workspace_bytes >= gaot_geoembed_from_moments_bwd_workspace_bytes(num_queries), "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    double* part = (double*)workspace;
+    double* sums = part + 256 * 2 * NF;
+    double* gsums = sums + 2 * NF;
+    float* stats = (float*)(gsums + 2 * NF);
+    float* feat = stats + 4 * NF;
+    const int nb = (int)std::min<int64_t>(256, ceil_div(num_queries, 256));
+    GAOT_KLAUNCH(k_geo_from_moments, dim3((unsigned)ceil_div(num_queries, 256)), dim3(256), 0, st, moments, num_queries, feat);
+    GAOT_KLAUNCH(k_geo_colpart, dim3(nb), dim3(256), 0, st, feat, num_queries, part);
+    GAOT_KLAUNCH(k_geo_colsums, dim3(1), dim3(256), 0, st, part, nb, sums);
+    GAOT_KLAUNCH(k_geo_bwd_stats, dim3(1), dim3(64), 0, st, sums, num_queries, stats);
+    GAOT_KLAUNCH(k_geo_bwd_colpart, dim3(nb), dim3(256), 0, st, feat, grad_features, stats, num_queries, part);
+    GAOT_KLAUNCH(k_geo_colsums, dim3(1), dim3(256), 0, st, part, nb, gsums);
+    GAOT_KLAUNCH(k_geo_from_moments_bwd, dim3((unsigned)ceil_div(num_queries, 256)), dim3(256), 0, st, moments, feat,
+                 grad_features, stats, gsums, num_queries, grad_moments);
+    GAOT_LAUNCH_CHECK();
+    return GAOT_OK;
+}
+
+extern "C" int gaot_geoembed_moments_bwd(const float* source_pos, const float* query_pos, const int32_t* rowptr_dst,
+                                         const int32_t* src_sorted, int64_t num_queries, const double* grad_moments,
+                                         float* grad_edge, float* grad_query, gaot_stream_t stream) {
+    GAOT_ENTER();
+    GAOT_CHECK_ARG(num_queries >= 0, "negative size");
+    if (num_queries == 0) return GAOT_OK;
+    GAOT_CHECK_ARG(source_pos && query_pos && rowptr_dst && grad_moments && grad_query, "null pointer");
+    GAOT_KLAUNCH(k_geo_moments_bwd, dim3((unsigned)ceil_div(num_queries * G, 256)), dim3(256), 0, (hipStream_t)stream,
+                 source_pos, query_pos, rowptr_dst, src_sorted, num_queries, grad_moments, grad_edge, grad_query);
     GAOT_LAUNCH_CHECK();
     return GAOT_OK;
 }

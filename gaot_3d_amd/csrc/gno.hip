@@ -272,13 +272,15 @@ __device__ __forceinline__ void load_wgroup(float (&w)[16], const WRsrc& rs, int
     }
 }
 
-template <int NH, int H>
+// CG: also the coordinate gradient of every edge, g_e = W_0^T dz_0[e] (6 fp32, source-sorted edge order) -> gcoord [E][6]
+// (the output pointer is a parameter pack: empty when CG is off, so those instantiations keep today's kernel arguments)
+template <int NH, int H, bool CG, class... CoordOut>
 __global__ __launch_bounds__(256, 1) void k_gno_bwd(
     MlpPtrs mlp, MlpPtrs mlp_t /* w = transposed copies [in][out] */, const float* __restrict__ y_pos,
     const float* __restrict__ x_pos, const float* __restrict__ f_y, const float* __restrict__ gs /* grad_out / deg */,
     const int* __restrict__ src_s, const int* __restrict__ dst_s,
     const int* __restrict__ rowptr_src, int64_t E, float* __restrict__ grad_f, float* __restrict__ part,
-    float* __restrict__ wpart /* [n_blocks][ParamLayout::total] */) {
+    float* __restrict__ wpart /* [n_blocks][ParamLayout::total] */, CoordOut... gcoord_) {
     // One workgroup = 4 waves = 4 tiles of 32 source-sorted edges per iteration.  Each wave runs the
     // data path (recompute, dk, data gradients) of its own tile in registers; the weight-gradient
     // MFMAs are split by OUTPUT tile across the four waves (each wave sweeps all four edge tiles
@@ -307,6 +309,8 @@ __global__ __launch_bounds__(256, 1) void k_gno_bwd(
     for (int l = 0; l < NH; ++l)
         for (int i = threadIdx.x; i < H; i += 256) bias_l[l * H + i] = mlp.b[l][i];
     for (int i = threadIdx.x; i < C; i += 256) bias_l[NH * H + i] = mlp.b[NH][i];
+    if constexpr (CG)   // W_0^T [IN0][H] behind the biases (bwd_lds_bytes(.., true))
+        for (int i = threadIdx.x; i < H * IN0; i += 256) bias_l[NH * H + C + (i % IN0) * H + i / IN0] = mlp.w[0][i];
     __syncthreads();
 
     WRsrc rs;
@@ -547,6 +551,30 @@ __global__ __launch_bounds__(256, 1) void k_gno_bwd(
                         dW0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, dW0, 0, 0, 0);
                     }
                 }
+                if constexpr (CG) {
+                    // own tile: g[e][k] = sum_j W_0[j][k] dz_0[j][e], lane (edge l31, half hf) -> inputs k = 3 hf .. 3 hf + 2
+                    // (y_pos[src] for hf = 0, x_pos[dst] for hf = 1); own buf holds dz_0 as [e][j], W_0^T is in LDS
+                    const float* wk = bias_l + NH * H + C + 3 * hf * H;
+                    const float* dr = buf + l31 * LDH;
+                    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+#pragma unroll 4
+                    for (int j = 0; j < H; j += 4) {
+                        const float4 c0 = *reinterpret_cast<const float4*>(wk + j);
+                        const float4 c1 = *reinterpret_cast<const float4*>(wk + H + j);
+                        const float4 c2 = *reinterpret_cast<const float4*>(wk + 2 * H + j);
+                        const float d0 = dr[j], d1 = dr[j + 1], d2 = dr[j + 2], d3 = dr[j + 3];
+                        a0 += d0 * c0.x + d1 * c0.y + d2 * c0.z + d3 * c0.w;
+                        a1 += d0 * c1.x + d1 * c1.y + d2 * c1.z + d3 * c1.w;
+                        a2 += d0 * c2.x + d1 * c2.y + d2 * c2.z + d3 * c2.w;
+                    }
+                    const int64_t e = base + l31;
+                    if (e < E) {
+                        float* o = first_arg(gcoord_...) + e * 6 + 3 * hf;
+                        o[0] = a0;
+                        o[1] = a1;
+                        o[2] = a2;
+                    }
+                }
             }
             __syncthreads();
         });
@@ -636,9 +664,9 @@ size_t fwd_lds_bytes(int nh, int h, int t) {
     const int weights = IN0P * h + h + (nh - 1) * (h * h + h) + h * 32 + 32;
     return sizeof(float) * (size_t)(weights + 4 * t * 32 * 32) + sizeof(int) * (size_t)(4 * t * 2 * 32);
 }
-size_t bwd_lds_bytes(int nh, int h) {
+size_t bwd_lds_bytes(int nh, int h, bool coords = false) {
     const int per_wave = nh * 32 * (h + 1) + 32 * (h + 1) + 32 * IN0P + 64;
-    return sizeof(float) * (size_t)(4 * per_wave + nh * h + 32);
+    return sizeof(float) * (size_t)(4 * per_wave + nh * h + 32 + (coords ? IN0 * h : 0));
 }
 
 template <int NH, int H>
@@ -658,19 +686,26 @@ int launch_fwd(const MlpPtrs& p, const float* y_pos, const float* x_pos, const f
     return GAOT_OK;
 }
 
-template <int NH, int H>
+template <int NH, int H, bool CG>
 int launch_bwd(const MlpPtrs& p, const MlpPtrs& pt, const float* y_pos, const float* x_pos, const float* f_y,
                const float* gs, const int* src_s, const int* dst_s, const int* rowptr_src,
-               int64_t E, float* grad_f, float* part, float* wpart, int grid, hipStream_t st) {
-    const size_t lds = bwd_lds_bytes(NH, H);
-    auto kern = k_gno_bwd<NH, H>;
+               int64_t E, float* grad_f, float* part, float* wpart, float* gcoord, int grid, hipStream_t st) {
+    const size_t lds = bwd_lds_bytes(NH, H, CG);
+    auto kern = [] {
+        if constexpr (CG) return k_gno_bwd<NH, H, true, float*>;
+        else return k_gno_bwd<NH, H, false>;
+    }();
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) {
         gaot_set_error("gno_bwd: cannot set dynamic LDS %zu: %s", lds, hipGetErrorString(e));
         return GAOT_ERR_LAUNCH;
     }
-    GAOT_KLAUNCH(kern, dim3(grid), dim3(256), lds, st, p, pt, y_pos, x_pos, f_y, gs, src_s, dst_s,
-                       rowptr_src, E, grad_f, part, wpart);
+    if constexpr (CG)
+        GAOT_KLAUNCH(kern, dim3(grid), dim3(256), lds, st, p, pt, y_pos, x_pos, f_y, gs, src_s, dst_s,
+                           rowptr_src, E, grad_f, part, wpart, gcoord);
+    else
+        GAOT_KLAUNCH(kern, dim3(grid), dim3(256), lds, st, p, pt, y_pos, x_pos, f_y, gs, src_s, dst_s,
+                           rowptr_src, E, grad_f, part, wpart);
     return GAOT_OK;
 }
 
@@ -696,7 +731,8 @@ size_t gaot_gno_bwd_bf16_image_bytes(int n_hidden);
 int gaot_gno_bwd_bf16_dispatch(int n_hidden, const float* const* w, const float* const* b, const float* w0t,
                                void* images, const float* y_pos, const float* x_pos, const float* f_y, const float* gs,
                                const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr_src,
-                               int64_t num_edges, float* grad_f, float* part, float* wpart, int grid, hipStream_t st);
+                               int64_t num_edges, float* grad_f, float* part, float* wpart, float* gcoord, int grid,
+                               hipStream_t st);
 
 extern "C" size_t gaot_gno_fwd_workspace_bytes(int64_t num_edges, int channels) {
     return sizeof(float) * (size_t)(ceil_div(num_edges, 32) * 2 * channels) + 64;
@@ -760,27 +796,36 @@ extern "C" size_t gaot_gno_bwd_workspace_bytes(const gaot_mlp_t* mlp, int64_t nu
     return sizeof(float) * fl + gaot_gno_bwd_bf16_image_bytes(mlp->n_hidden) + 512;
 }
 
-extern "C" int gaot_gno_bwd(const gaot_mlp_t* mlp, const float* y_pos, const float* x_pos, const float* f_y,
-                            const float* grad_out, const int32_t* rowptr_dst, const int32_t* src_sorted,
-                            const int32_t* dst_sorted, const int32_t* rowptr_src, int64_t num_edges,
-                            int64_t num_sources, int64_t num_queries, float* grad_f_y, const gaot_mlp_grad_t* grads,
-                            int precision, void* workspace, size_t workspace_bytes, gaot_stream_t stream) {
-    GAOT_ENTER();
-    GAOT_CHECK_ARG(mlp && grads, "null mlp");
+namespace {
+// gaot_gno_bwd (gcoord = null) and gaot_gno_bwd_coords (gcoord = [num_edges][6])
+// GAOT_CHECK_ARG with the name of the entry point that was called
+#define GNO_BWD_CHECK(cond, msg)                          \
+    do {                                                  \
+        if (!(cond)) {                                    \
+            gaot_set_error("%s: %s", fn, msg);            \
+            return GAOT_ERR_ARG;                          \
+        }                                                 \
+    } while (0)
+int gno_bwd_impl(const char* fn, const gaot_mlp_t* mlp, const float* y_pos, const float* x_pos, const float* f_y,
+                 const float* grad_out, const int32_t* rowptr_dst, const int32_t* src_sorted, const int32_t* dst_sorted,
+                 const int32_t* rowptr_src, int64_t num_edges, int64_t num_sources, int64_t num_queries, float* grad_f_y,
+                 const gaot_mlp_grad_t* grads, float* gcoord, int precision, void* workspace, size_t workspace_bytes,
+                 gaot_stream_t stream) {
+    GNO_BWD_CHECK(mlp && grads, "null mlp");
     if (!mlp_supported(mlp, true, precision)) {
-        gaot_set_error("gaot_gno_bwd: unsupported MLP shape (n_hidden=%d hidden=%d channels=%d; four hidden layers in bf16 mode only)", mlp->n_hidden,
-                       mlp->hidden, mlp->channels);
+        gaot_set_error("%s: unsupported MLP shape (n_hidden=%d hidden=%d channels=%d; four hidden layers in bf16 mode only)", fn,
+                       mlp->n_hidden, mlp->hidden, mlp->channels);
         return GAOT_ERR_UNSUPPORTED;
     }
-    GAOT_CHECK_ARG(num_edges >= 0 && num_sources >= 0 && num_queries >= 0, "negative size");
+    GNO_BWD_CHECK(num_edges >= 0 && num_sources >= 0 && num_queries >= 0, "negative size");
     // the bf16 kernel gathers its 128-byte rows through 2 GB buffer resources: 2^24 rows per table
-    GAOT_CHECK_ARG(precision != 1 || (num_sources <= (1 << 24) && num_queries <= (1 << 24)),
+    GNO_BWD_CHECK(precision != 1 || (num_sources <= (1 << 24) && num_queries <= (1 << 24)),
                    "bf16 GNO backward: more than 2^24 source or query rows (run the mesh point-sharded or in fp32 mode)");
     // ... and addresses the two 128-byte partial slots of a 16-edge tile with a 32-bit byte offset
-    GAOT_CHECK_ARG(precision != 1 || num_edges < ((int64_t)1 << 27),
+    GNO_BWD_CHECK(precision != 1 || num_edges < ((int64_t)1 << 27),
                    "bf16 GNO backward: 2^27 or more edges in one launch (run the mesh point-sharded or in fp32 mode)");
-    GAOT_CHECK_ARG(workspace_bytes >= gaot_gno_bwd_workspace_bytes(mlp, num_edges, num_queries), "workspace too small");
-    GAOT_CHECK_ARG(rowptr_src && rowptr_dst, "null rowptr");
+    GNO_BWD_CHECK(workspace_bytes >= gaot_gno_bwd_workspace_bytes(mlp, num_edges, num_queries), "workspace too small");
+    GNO_BWD_CHECK(rowptr_src && rowptr_dst, "null rowptr");
     hipStream_t st = (hipStream_t)stream;
     const int nh = mlp->n_hidden, h = mlp->hidden;
     const int total = param_total(nh, h);
@@ -792,14 +837,14 @@ extern "C" int gaot_gno_bwd(const gaot_mlp_t* mlp, const float* y_pos, const flo
     float* wpart = flat + total;
     float* gs = wpart + (size_t)grid * total;
     void* images = (void*)(((uintptr_t)(gs + (size_t)num_queries * 32) + 255) & ~(uintptr_t)255);
-    GAOT_CHECK_ARG(precision == 0 || precision == 1, "precision must be 0 (fp32) or 1 (bf16 matrix cores)");
+    GNO_BWD_CHECK(precision == 0 || precision == 1, "precision must be 0 (fp32) or 1 (bf16 matrix cores)");
 
     MlpPtrs p, pt;
     int off = 0;
     for (int l = 0; l <= nh; ++l) {
         p.w[l] = mlp->weight[l];
         p.b[l] = mlp->bias[l];
-        GAOT_CHECK_ARG(p.w[l] && p.b[l] && grads->weight[l] && grads->bias[l], "null MLP parameter / gradient");
+        GNO_BWD_CHECK(p.w[l] && p.b[l] && grads->weight[l] && grads->bias[l], "null MLP parameter / gradient");
         const int out_dim = (l == nh) ? 32 : h;
         const int in_dim = (l == 0) ? IN0 : h;
         pt.w[l] = wt + off;
@@ -828,18 +873,26 @@ extern "C" int gaot_gno_bwd(const gaot_mlp_t* mlp, const float* y_pos, const flo
     if (num_edges == 0) {
         hipMemsetAsync(flat, 0, sizeof(float) * total, st);
     } else {
-        GAOT_CHECK_ARG(y_pos && x_pos && f_y && grad_out && src_sorted && dst_sorted && grad_f_y, "null pointer");
+        GNO_BWD_CHECK(y_pos && x_pos && f_y && grad_out && src_sorted && dst_sorted && grad_f_y, "null pointer");
+        const bool cg = gcoord != nullptr;
         GAOT_KLAUNCH(k_scale_by_inv_deg, dim3((unsigned)ceil_div(num_queries * 8, 256)), dim3(256), 0, st, grad_out,
                            rowptr_dst, num_queries, gs);
         int rc = GAOT_OK;
         if (precision == 1) {
             rc = gaot_gno_bwd_bf16_dispatch(nh, p.w, p.b, pt.w[0], images, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted,
-                                            rowptr_src, num_edges, grad_f_y, part, wpart, grid, st);
-        } else
-        switch (nh) {
-            case 1: rc = launch_bwd<1, 64>(p, pt, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src, num_edges, grad_f_y, part, wpart, grid, st); break;
-            case 2: rc = launch_bwd<2, 64>(p, pt, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src, num_edges, grad_f_y, part, wpart, grid, st); break;
-            case 3: rc = launch_bwd<3, 64>(p, pt, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src, num_edges, grad_f_y, part, wpart, grid, st); break;
+                                            rowptr_src, num_edges, grad_f_y, part, wpart, gcoord, grid, st);
+        } else if (!cg) {
+            switch (nh) {
+                case 1: rc = launch_bwd<1, 64, false>(p, pt, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src, num_edges, grad_f_y, part, wpart, nullptr, grid, st); break;
+                case 2: rc = launch_bwd<2, 64, false>(p, pt, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src, num_edges, grad_f_y, part, wpart, nullptr, grid, st); break;
+                case 3: rc = launch_bwd<3, 64, false>(p, pt, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src, num_edges, grad_f_y, part, wpart, nullptr, grid, st); break;
+            }
+        } else {
+            switch (nh) {
+                case 1: rc = launch_bwd<1, 64, true>(p, pt, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src, num_edges, grad_f_y, part, wpart, gcoord, grid, st); break;
+                case 2: rc = launch_bwd<2, 64, true>(p, pt, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src, num_edges, grad_f_y, part, wpart, gcoord, grid, st); break;
+                case 3: rc = launch_bwd<3, 64, true>(p, pt, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src, num_edges, grad_f_y, part, wpart, gcoord, grid, st); break;
+            }
         }
         if (rc != GAOT_OK) return rc;
         GAOT_KLAUNCH(k_reduce_params, dim3((unsigned)ceil_div(total, 64)), dim3(256), 0, st, wpart, n_waves,
@@ -857,4 +910,30 @@ extern "C" int gaot_gno_bwd(const gaot_mlp_t* mlp, const float* y_pos, const flo
     }
     GAOT_LAUNCH_CHECK();
     return GAOT_OK;
+}
+#undef GNO_BWD_CHECK
+}  // namespace
+
+extern "C" int gaot_gno_bwd(const gaot_mlp_t* mlp, const float* y_pos, const float* x_pos, const float* f_y,
+                            const float* grad_out, const int32_t* rowptr_dst, const int32_t* src_sorted,
+                            const int32_t* dst_sorted, const int32_t* rowptr_src, int64_t num_edges,
+                            int64_t num_sources, int64_t num_queries, float* grad_f_y, const gaot_mlp_grad_t* grads,
+                            int precision, void* workspace, size_t workspace_bytes, gaot_stream_t stream) {
+    GAOT_ENTER();
+    return gno_bwd_impl("gaot_gno_bwd", mlp, y_pos, x_pos, f_y, grad_out, rowptr_dst, src_sorted, dst_sorted, rowptr_src,
+                        num_edges, num_sources, num_queries, grad_f_y, grads, nullptr, precision, workspace, workspace_bytes,
+                        stream);
+}
+
+extern "C" int gaot_gno_bwd_coords(const gaot_mlp_t* mlp, const float* y_pos, const float* x_pos, const float* f_y,
+                                   const float* grad_out, const int32_t* rowptr_dst, const int32_t* src_sorted,
+                                   const int32_t* dst_sorted, const int32_t* rowptr_src, int64_t num_edges,
+                                   int64_t num_sources, int64_t num_queries, float* grad_f_y, const gaot_mlp_grad_t* grads,
+                                   float* grad_edge_coords, int precision, void* workspace, size_t workspace_bytes,
+                                   gaot_stream_t stream) {
+    GAOT_ENTER();
+    GAOT_CHECK_ARG(num_edges == 0 || grad_edge_coords, "null grad_edge_coords");
+    return gno_bwd_impl("gaot_gno_bwd_coords", mlp, y_pos, x_pos, f_y, grad_out, rowptr_dst, src_sorted, dst_sorted,
+                        rowptr_src, num_edges, num_sources, num_queries, grad_f_y, grads, grad_edge_coords, precision,
+                        workspace, workspace_bytes, stream);
 }

@@ -339,7 +339,8 @@ int gaot_gno_fwd_bf16_dispatch(int n_hidden, const float* const* w, const float*
 int gaot_gno_bwd3_bf16_launch(int n_hidden, void* images, const float* w0t, const float* const* w, const float* const* b,
                               const float* y_pos, const float* x_pos, const float* f_y, const float* gs,
                               const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr_src,
-                              int64_t num_edges, float* grad_f, float* part, float* wpart, int grid, hipStream_t st);
+                              int64_t num_edges, float* grad_f, float* part, float* wpart, float* gcoord, int grid,
+                              hipStream_t st);
 
 // recompute and transposed data-gradient fragment images of the hidden layers (8 KB each) and of the last layer (4 KB each)
 size_t gaot_gno_bwd_bf16_image_bytes(int n_hidden) { return (size_t)(n_hidden - 1) * 2 * 8192 + 2 * 4096 + 256; }
@@ -349,7 +350,8 @@ size_t gaot_gno_bwd_bf16_image_bytes(int n_hidden) { return (size_t)(n_hidden - 
 int gaot_gno_bwd_bf16_dispatch(int n_hidden, const float* const* w, const float* const* b, const float* w0t,
                                void* images, const float* y_pos, const float* x_pos, const float* f_y, const float* gs,
                                const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr_src,
-                               int64_t num_edges, float* grad_f, float* part, float* wpart, int grid, hipStream_t st) {
+                               int64_t num_edges, float* grad_f, float* part, float* wpart, float* gcoord, int grid,
+                               hipStream_t st) {
     return gaot_gno_bwd3_bf16_launch(n_hidden, images, w0t, w, b, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src,
-                                     num_edges, grad_f, part, wpart, grid, st);
+                                     num_edges, grad_f, part, wpart, gcoord, grid, st);
 }

@@ -150,12 +150,14 @@ __global__ void k_prep_bwd3_images(MlpPtrs mlp, int nh, bf16_t* base) {
     }
 }
 
-template <int NH>
+// CG: also the coordinate gradient of every edge, g_e = W_0^T dz_0[e] (6 fp32, source-sorted edge order) -> gcoord [E][6]
+// (the output pointer is a parameter pack: empty when CG is off, so those instantiations keep today's kernel arguments)
+template <int NH, bool CG, class... CoordOut>
 __global__ __launch_bounds__(512, 1) void k_gno_bwd3_bf16(
     const uint4* __restrict__ images, const float* __restrict__ w0t_g, MlpPtrs mlp, const float* __restrict__ y_pos,
     const float* __restrict__ x_pos, const float* __restrict__ f_y, const float* __restrict__ gs,
     const int* __restrict__ src_s, const int* __restrict__ dst_s, const int* __restrict__ rowptr_src, int64_t E,
-    float* __restrict__ grad_f, float* __restrict__ part, float* __restrict__ wpart) {
+    float* __restrict__ grad_f, float* __restrict__ part, float* __restrict__ wpart, CoordOut... gcoord_) {
     constexpr int C = 32, H = 64;
     using L = Lds3<NH>;
     using PL = ParamLayout3<NH>;
@@ -455,6 +457,27 @@ __global__ __launch_bounds__(512, 1) void k_gno_bwd3_bf16(
                 }
             }
         }
+        if constexpr (CG) {
+            // g[k][e] = sum_j W_0[j][k] dz_0[j][e] from the fp32 dz_0 (before its bf16 rounding) and the fp32 layer-0 image:
+            // k-step (mb, i) contracts features j = 16 mb + 4 g + i -- dz[mb][i] as it stands is the B operand; A rows k >= 8
+            // read rows k & 7 (their outputs are never stored).  Lane (edge n, group g) ends with k = 4 g + i.
+            f32x4 gc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    gc = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[(n & 7) * L::W0S + 16 * mb + 4 * g + i], dz[mb][i], gc, 0, 0, 0);
+            const int64_t e = base + n;
+            if (e < E && g < 2) {
+                float* o = first_arg(gcoord_...) + e * 6 + 4 * g;
+                o[0] = gc[0];
+                o[1] = gc[1];
+                if (g == 0) {
+                    o[2] = gc[2];
+                    o[3] = gc[3];
+                }
+            }
+        }
 #pragma unroll
         for (int s = 0; s < 2; ++s) store_frag_rows(mine + L::dz(0), frag_of(dz[2 * s], dz[2 * s + 1]), s, n, g);
         __syncthreads();
@@ -553,13 +576,16 @@ __global__ __launch_bounds__(512, 1) void k_gno_bwd3_bf16(
     }
 }
 
-template <int NH>
+template <int NH, bool CG>
 int launch_bwd3(const void* images, const float* w0t, const MlpPtrs& p, const float* y_pos, const float* x_pos,
                 const float* f_y, const float* gs, const int* src_s, const int* dst_s, const int* rowptr_src, int64_t E,
-                float* grad_f, float* part, float* wpart, int grid, hipStream_t st) {
+                float* grad_f, float* part, float* wpart, float* gcoord, int grid, hipStream_t st) {
     constexpr int lds = Lds3<NH>::total;
     static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = k_gno_bwd3_bf16<NH>;
+    auto kern = [] {
+        if constexpr (CG) return k_gno_bwd3_bf16<NH, true, float*>;
+        else return k_gno_bwd3_bf16<NH, false>;
+    }();
     static bool attr_set = false;
     if (!attr_set) {
         const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -569,19 +595,25 @@ int launch_bwd3(const void* images, const float* w0t, const MlpPtrs& p, const fl
         }
         attr_set = true;
     }
-    GAOT_KLAUNCH(kern, dim3(grid), dim3(512), lds, st, (const uint4*)images, w0t, p, y_pos, x_pos, f_y, gs, src_s, dst_s,
-                 rowptr_src, E, grad_f, part, wpart);
+    if constexpr (CG)
+        GAOT_KLAUNCH(kern, dim3(grid), dim3(512), lds, st, (const uint4*)images, w0t, p, y_pos, x_pos, f_y, gs, src_s, dst_s,
+                     rowptr_src, E, grad_f, part, wpart, gcoord);
+    else
+        GAOT_KLAUNCH(kern, dim3(grid), dim3(512), lds, st, (const uint4*)images, w0t, p, y_pos, x_pos, f_y, gs, src_s, dst_s,
+                     rowptr_src, E, grad_f, part, wpart);
     return GAOT_OK;
 }
 
 }  // namespace
 
 // images: scratch of gaot_gno_bwd_bf16_image_bytes() (gno_bf16.hip); w0t = fp32 [6][64] transposed first-layer weight; part: two
-// 32-channel slots per 16-EDGE tile (k_segment_fixup<32, 4>); wpart: one flat parameter-gradient partial per workgroup
+// 32-channel slots per 16-EDGE tile (k_segment_fixup<32, 4>); wpart: one flat parameter-gradient partial per workgroup;
+// gcoord: null, or [num_edges][6] coordinate gradients per edge (source-sorted order)
 int gaot_gno_bwd3_bf16_launch(int n_hidden, void* images, const float* w0t, const float* const* w, const float* const* b,
                               const float* y_pos, const float* x_pos, const float* f_y, const float* gs,
                               const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr_src,
-                              int64_t num_edges, float* grad_f, float* part, float* wpart, int grid, hipStream_t st) {
+                              int64_t num_edges, float* grad_f, float* part, float* wpart, float* gcoord, int grid,
+                              hipStream_t st) {
     if (n_hidden < 1 || n_hidden > 4) {      // before anything indexes w / b / MlpPtrs with it
         gaot_set_error("gaot_gno_bwd (bf16): unsupported n_hidden %d", n_hidden);
         return GAOT_ERR_UNSUPPORTED;
@@ -589,10 +621,20 @@ int gaot_gno_bwd3_bf16_launch(int n_hidden, void* images, const float* w0t, cons
     MlpPtrs p;
     for (int l = 0; l <= n_hidden; ++l) { p.w[l] = w[l]; p.b[l] = b[l]; }
     GAOT_KLAUNCH(k_prep_bwd3_images, dim3(32), dim3(256), 0, st, p, n_hidden, (bf16_t*)images);
-    switch (n_hidden) {
-        case 1: return launch_bwd3<1>(images, w0t, p, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src, num_edges, grad_f, part, wpart, grid, st);
-        case 2: return launch_bwd3<2>(images, w0t, p, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src, num_edges, grad_f, part, wpart, grid, st);
-        case 3: return launch_bwd3<3>(images, w0t, p, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src, num_edges, grad_f, part, wpart, grid, st);
-        default: return launch_bwd3<4>(images, w0t, p, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src, num_edges, grad_f, part, wpart, grid, st);
+#define GNO_BWD3_ARGS images, w0t, p, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src, num_edges, grad_f, part, wpart, gcoord, grid, st
+    if (gcoord == nullptr) {
+        switch (n_hidden) {
+            case 1: return launch_bwd3<1, false>(GNO_BWD3_ARGS);
+            case 2: return launch_bwd3<2, false>(GNO_BWD3_ARGS);
+            case 3: return launch_bwd3<3, false>(GNO_BWD3_ARGS);
+            default: return launch_bwd3<4, false>(GNO_BWD3_ARGS);
+        }
     }
+    switch (n_hidden) {
+        case 1: return launch_bwd3<1, true>(GNO_BWD3_ARGS);
+        case 2: return launch_bwd3<2, true>(GNO_BWD3_ARGS);
+        case 3: return launch_bwd3<3, true>(GNO_BWD3_ARGS);
+        default: return launch_bwd3<4, true>(GNO_BWD3_ARGS);
+    }
+#undef GNO_BWD3_ARGS
 }

@@ -8,6 +8,11 @@ namespace gno {
 constexpr int IN0 = 6;      // [y_pos(3), x_pos(3)]
 constexpr int IN0P = 8;     // padded
 
+// the single argument of a (possibly empty) parameter pack: optional kernel outputs whose absence leaves the kernel's argument
+// list as it was
+template <class T>
+__device__ __forceinline__ T first_arg(T t) { return t; }
+
 __device__ __forceinline__ void wave_lds_fence() {
     // LDS ops of one wave execute in order; this only stops the compiler from reordering.
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");

@@ -38,6 +38,27 @@ def src_to_dst_map(g: BipartiteGraph) -> Tensor:
     return m
 
 
+def dst_to_src_map(g: BipartiteGraph) -> Tensor:
+    """position in the dst-sorted order -> position in the src-sorted order (int32 [E], the inverse of src_to_dst_map);
+    cached on the graph"""
+    m = g.__dict__.get("_dst2src")
+    if m is None:
+        s2d = src_to_dst_map(g)
+        m = torch.empty_like(s2d)
+        m[s2d.long()] = torch.arange(s2d.shape[0], dtype=torch.int32, device=s2d.device)
+        g.__dict__["_dst2src"] = m
+    return m
+
+
+def coord_grads_by_endpoint(d: Tensor, g: BipartiteGraph, col_src: int, col_dst: int, num_src: int, num_dst: int):
+    """per-edge coordinate gradients in the dst-sorted order -> (sum by source of columns col_src..+3, sum by query of
+    columns col_dst..+3); either column may be None (not needed)"""
+    d = d if d.is_contiguous() else d.contiguous()
+    gy = None if col_src is None else segment_reduce(d, g.by_src.rowptr, src_to_dst_map(g), num_src, SUM, col0=col_src, channels=3)
+    gx = None if col_dst is None else segment_reduce(d, g.by_dst.rowptr, None, num_dst, SUM, col0=col_dst, channels=3)
+    return gy, gx
+
+
 # ---- raw calls --------------------------------------------------------------------------------------------------
 def gather_rows(table: Tensor, idx: Tensor, out: Optional[Tensor] = None, col0: int = 0) -> Tensor:
     lib = _lib.load()
@@ -116,7 +137,8 @@ class GatherFn(Function):
 
 
 class EdgeInputFn(Function):
-    """agg = cat([y_pos[src], x_pos[dst], f_y[src] (optional)], -1)  (integral_transform.py:146-152); grad -> f_y only"""
+    """agg = cat([y_pos[src], x_pos[dst], f_y[src] (optional)], -1)  (integral_transform.py:146-152); grad -> f_y and the
+    coordinates (columns 0-2 summed by source, 3-5 by query)"""
 
     @staticmethod
     def forward(ctx, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], g: BipartiteGraph):
@@ -127,16 +149,35 @@ class EdgeInputFn(Function):
         if f_y is not None:
             gather_rows(f_y, g.by_dst.other, out, col0=6)
         ctx.g, ctx.c, ctx.rows = g, c, (0 if f_y is None else f_y.shape[0])
+        ctx.ny, ctx.nx = y_pos.shape[0], x_pos.shape[0]
         return out
 
     @staticmethod
     def backward(ctx, d: Tensor):
-        if ctx.c == 0:
-            return None, None, None, None
         g = ctx.g
         d = d if d.is_contiguous() else d.contiguous()
-        df = segment_reduce(d, g.by_src.rowptr, src_to_dst_map(g), ctx.rows, SUM, col0=6, channels=ctx.c)
-        return None, None, df, None
+        gy, gx = coord_grads_by_endpoint(d, g, 0 if ctx.needs_input_grad[0] else None, 3 if ctx.needs_input_grad[1] else None,
+                                         ctx.ny, ctx.nx)
+        df = None
+        if ctx.c > 0 and ctx.needs_input_grad[2]:
+            df = segment_reduce(d, g.by_src.rowptr, src_to_dst_map(g), ctx.rows, SUM, col0=6, channels=ctx.c)
+        return gy, gx, df, None
+
+
+class EdgeOffsetFn(Function):
+    """y_pos[src] - x_pos[dst] per edge (edge_coords mode 1, PointNet GeoEmbed geoembed.py:196-198); backward = the sum of the
+    rows by source, and minus their sum by query"""
+
+    @staticmethod
+    def forward(ctx, y_pos: Tensor, x_pos: Tensor, g: BipartiteGraph):
+        ctx.g, ctx.ny, ctx.nx = g, y_pos.shape[0], x_pos.shape[0]
+        return edge_coords(y_pos, x_pos, g, 1)
+
+    @staticmethod
+    def backward(ctx, d: Tensor):
+        gy, gx = coord_grads_by_endpoint(d, ctx.g, 0 if ctx.needs_input_grad[0] else None,
+                                         0 if ctx.needs_input_grad[1] else None, ctx.ny, ctx.nx)
+        return gy, (None if gx is None else -gx), None
 
 
 class SegmentReduceFn(Function):

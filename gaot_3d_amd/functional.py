@@ -265,8 +265,15 @@ class GnoFn(Function):
         ws = list(saved[3:3 + ctx.nl])
         bs = list(saved[3 + ctx.nl:])
         d = dout if dout.is_contiguous() else dout.contiguous()
+        need = ctx.needs_input_grad
+        if need[1] or need[2]:      # coordinates that require grad: the kernel also forms W_0^T dz_0 per edge
+            gf, gw, gb, gy, gx = ops.gno_backward(ws, bs, y_pos, x_pos, f, d, ctx.graph, coords=True)
+            grads: List[Optional[Tensor]] = []
+            for l in range(ctx.nl):
+                grads += [gw[l].view(ctx.wshapes[l]) if need[4 + 2 * l] else None, gb[l] if need[5 + 2 * l] else None]
+            return (gf if need[0] else None, gy if need[1] else None, gx if need[2] else None, None, *grads)
         gf, gw, gb = ops.gno_backward(ws, bs, y_pos, x_pos, f, d, ctx.graph)
-        grads: List[Optional[Tensor]] = []
+        grads = []
         for l in range(ctx.nl):
             grads += [gw[l].view(ctx.wshapes[l]), gb[l]]
         return (gf, None, None, None, *grads)

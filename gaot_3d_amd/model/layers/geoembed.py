@@ -11,7 +11,31 @@ import torch.nn as nn
 from ... import edgeops as EO
 from ... import functional as GF
 from ... import ops
-from .integral_transform import graph_for
+from .integral_transform import coords_need_grad, graph_for
+
+
+class GeoStatFn(torch.autograd.Function):
+    """statistical features (z-scored [Q, 9]) as a function of the coordinates: forward = gaot_geoembed_moments +
+    gaot_geoembed_from_moments (the values of the cached path), backward = the same two steps in reverse
+    (gaot_geoembed_from_moments_bwd, gaot_geoembed_moments_bwd), the per-edge source gradients summed by source"""
+
+    @staticmethod
+    def forward(ctx, source_pos, query_pos, g):
+        mom = ops.geoembed_moments(source_pos, query_pos, g)
+        ctx.g = g
+        ctx.save_for_backward(source_pos, query_pos, mom)
+        return ops.geoembed_from_moments(mom)
+
+    @staticmethod
+    def backward(ctx, d):
+        source_pos, query_pos, mom = ctx.saved_tensors
+        g = ctx.g
+        adj = ops.geoembed_from_moments_bwd(mom, d)
+        ge, gq = ops.geoembed_moments_bwd(source_pos, query_pos, g, adj)
+        gs = None
+        if ctx.needs_input_grad[0]:
+            gs, _ = EO.coord_grads_by_endpoint(ge, g, 0, None, source_pos.shape[0], query_pos.shape[0])
+        return gs, (gq if ctx.needs_input_grad[1] else None), None
 
 
 class GeometricEmbedding(nn.Module):
@@ -39,6 +63,10 @@ class GeometricEmbedding(nn.Module):
         the group; the per-row statistics are assembled from additive fp64 moments with one SUM all-reduce."""
         if graph is None:
             graph = graph_for(edge_index.to(query_pos.device), source_pos.shape[0], query_pos.shape[0])
+        coord_grad = coords_need_grad(source_pos, query_pos)
+        if shard_group is not None and coord_grad:
+            raise NotImplementedError("GeometricEmbedding: gradients with respect to the coordinates are not supported for "
+                                      "point-sharded samples (shard_group); detach the coordinates")
         if self.method == "pointnet":
             if shard_group is not None and sharded_queries_total is None:
                 # encoder side of a point-sharded sample: a token's edges are spread over the ranks
@@ -53,8 +81,12 @@ class GeometricEmbedding(nn.Module):
             from ... import comm
             comm.run(lambda: dist.all_reduce(mom, op=dist.ReduceOp.SUM, group=shard_group), (mom,), "all_reduce")
             feats = ops.geoembed_from_moments(mom)
+        elif coord_grad:
+            # coordinates that require grad: the features are a differentiable function of them (neither read from nor
+            # written to the per-sample cache below)
+            feats = GeoStatFn.apply(source_pos, query_pos, graph)
         else:
-            # geometry only: no autograd through it.  One sweep over the neighbour lists (additive fp64 moments about the
+            # geometry only, no coordinate requires grad.  One sweep over the neighbour lists (additive fp64 moments about the
             # query position, then centroid / covariance / eigenvalues per row): 0.22 ms at configs[1] against 0.37 ms
             # for the two-sweep kernel (gaot_geoembed_raw: centroid first, then centred second moments); same features.
             # A per-sample constant: kept on the neighbour-list object (which the batch caches per edge tensor) for as long
@@ -100,7 +132,7 @@ class GeometricEmbedding(nn.Module):
         nq = query_pos.shape[0]
         if g.by_dst.num_edges == 0:
             return torch.zeros(nq, self.output_dim, dtype=query_pos.dtype, device=query_pos.device)
-        c = EO.edge_coords(source_pos, query_pos, g, 1)                                    # :196-198
+        c = EO.EdgeOffsetFn.apply(source_pos, query_pos, g)                                # :196-198
         h = GF.linear(c, self.pointnet_mlp[0].weight, self.pointnet_mlp[0].bias, act="relu", precision=0)
         h = GF.linear(h, self.pointnet_mlp[2].weight, self.pointnet_mlp[2].bias, act="relu", precision=0)
         pooled = EO.SegmentReduceFn.apply(h, g, EO.MAX if self.pooling == "max" else EO.MEAN)   # :211-216

@@ -63,6 +63,11 @@ def graph_for(edge_index: torch.Tensor, num_src: int, num_dst: int, cache_owner=
     return ops.build_graph(edge_index, num_src, num_dst)
 
 
+def coords_need_grad(*pos) -> bool:
+    """does autograd want a gradient with respect to any of these coordinate tensors?"""
+    return torch.is_grad_enabled() and any(p is not None and p.requires_grad for p in pos)
+
+
 class IntegralTransform(nn.Module):
     def __init__(self, channel_mlp=None, channel_mlp_layers=None, channel_mlp_non_linearity="gelu",
                  transform_type="linear", use_attn=None, coord_dim=None, attention_type="cosine"):
@@ -97,14 +102,17 @@ class IntegralTransform(nn.Module):
         fcs = list(self.channel_mlp.fcs)
         if edge_index is not None and edge_index.shape[1] == 0 and graph is None:   # integral_transform.py:106-112
             return torch.zeros(x_pos.shape[0], fcs[-1].weight.shape[0], dtype=x_pos.dtype, device=x_pos.device)
+        if self.use_attn and coords_need_grad(y_pos, x_pos):
+            raise NotImplementedError("IntegralTransform: gradients with respect to the coordinates are not supported with "
+                                      "use_attn=True (cosine / dot-product edge scores); detach y_pos / x_pos")
         if graph is None:
             graph = graph_for(edge_index.to(x_pos.device), y_pos.shape[0], x_pos.shape[0])
-        plan = self._fused_plan(fcs, f_y, y_pos)
+        plan = self._fused_plan(fcs, f_y, y_pos, x_pos)
         if plan is not None:
             return self._forward_fused(fcs, y_pos, x_pos, f_y, graph, *plan)
         return self._forward_general(fcs, y_pos, x_pos, f_y, graph)
 
-    def _fused_plan(self, fcs, f_y, y_pos):
+    def _fused_plan(self, fcs, f_y, y_pos, x_pos=None):
         """(coord_dim, channels) when the fused kernels (csrc/gno*.hip: coordinates of dimension 3, hidden width 64, 32
         channels per pass) can evaluate this transform EXACTLY, possibly through zero padding; None -> general path.
         Kernel MLP coord-pair -> 64 (x 1..4; with gradients in fp32 mode: 1..3) -> C with GELU, 'linear' transform, mean reduction:
@@ -117,7 +125,8 @@ class IntegralTransform(nn.Module):
             return None
         # the exact-fp32 backward keeps the hidden activations of 128 edges in LDS: three hidden layers at most when gradients
         # are needed in fp32 mode; the bf16 backward takes four (its operand fragments then come from L2, gno_bwd3_bf16.hip)
-        need_grad = torch.is_grad_enabled() and (f_y.requires_grad or any(fc.weight.requires_grad for fc in fcs))
+        need_grad = torch.is_grad_enabled() and (f_y.requires_grad or any(fc.weight.requires_grad for fc in fcs)
+                                                 or y_pos.requires_grad or (x_pos is not None and x_pos.requires_grad))
         from ... import ops as _ops
         max_fcs = 4 if (need_grad and _ops.get_precision() != "bf16") else 5
         if activation_name(getattr(self.channel_mlp, "non_linearity", "gelu")) != "gelu" or not (2 <= len(fcs) <= max_fcs):

@@ -177,8 +177,10 @@ def gno_forward(weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Tensor, g: B
 
 
 def gno_backward(weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Tensor, grad_out: Tensor, g: BipartiteGraph,
-                 precision: Optional[int] = None):
-    """-> (grad_f_y, [grad_w...], [grad_b...])"""
+                 precision: Optional[int] = None, coords: bool = False):
+    """-> (grad_f_y, [grad_w...], [grad_b...]); with ``coords`` also (grad_y_pos, grad_x_pos) appended: the kernel writes
+    W_0^T dz_0 per edge (gaot_gno_bwd_coords, source-sorted order), summed here by source and by query with the fixed-order
+    segmented sums"""
     lib = _lib.load()
     prec = _PRECISION["mode"] if precision is None else precision
     m, keep = _mlp_struct(weights, biases)
@@ -196,6 +198,17 @@ def gno_backward(weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Tensor, gra
         gs.weight[l] = gw[l].data_ptr()
         gs.bias[l] = gb[l].data_ptr()
     ws = _ws(lib.gaot_gno_bwd_workspace_bytes(C.byref(m), e, g.num_dst), dev)
+    if coords:
+        gec = torch.empty(e, 6, dtype=torch.float32, device=dev)
+        with _timed(f"gno_bwd_coords_nh{m.n_hidden}"):
+            check(lib.gaot_gno_bwd_coords(C.byref(m), _ptr(y_pos), _ptr(x_pos), _ptr(f_y), _ptr(grad_out), _ptr(g.by_dst.rowptr),
+                                          _ptr(g.by_src.key), _ptr(g.by_src.other), _ptr(g.by_src.rowptr), e, g.num_src,
+                                          g.num_dst, _ptr(grad_f), C.byref(gs), _ptr(gec), prec, _ptr(ws), ws.numel(), _stream()),
+                  "gaot_gno_bwd_coords")
+        from . import edgeops as EO
+        gy = EO.segment_reduce(gec, g.by_src.rowptr, None, g.num_src, EO.SUM, col0=0, channels=3)
+        gx = EO.segment_reduce(gec, g.by_dst.rowptr, EO.dst_to_src_map(g), g.num_dst, EO.SUM, col0=3, channels=3)
+        return grad_f, gw, gb, gy, gx
     with _timed(f"gno_bwd_nh{m.n_hidden}"):
         check(lib.gaot_gno_bwd(C.byref(m), _ptr(y_pos), _ptr(x_pos), _ptr(f_y), _ptr(grad_out), _ptr(g.by_dst.rowptr),
                                _ptr(g.by_src.key), _ptr(g.by_src.other), _ptr(g.by_src.rowptr), e, g.num_src, g.num_dst,
@@ -1276,6 +1289,30 @@ def geoembed_from_moments(mom: Tensor) -> Tensor:
     ws = _ws(lib.gaot_geoembed_stats_workspace_bytes(), mom.device)
     check(lib.gaot_geoembed_from_moments(_ptr(mom), q, _ptr(feat), _ptr(ws), ws.numel(), _stream()), "gaot_geoembed_from_moments")
     return feat
+
+
+def geoembed_from_moments_bwd(mom: Tensor, grad_feat: Tensor) -> Tensor:
+    """dL/d features [Q, 9] -> dL/d moments [Q, 12] fp64 (include/gaot3d_hip.h: gaot_geoembed_from_moments_bwd)"""
+    lib = _lib.load()
+    q = mom.shape[0]
+    grad_feat = _req(grad_feat, torch.float32, "grad_features")
+    adj = torch.empty(q, 12, dtype=torch.float64, device=mom.device)
+    ws = _ws(lib.gaot_geoembed_from_moments_bwd_workspace_bytes(q), mom.device)
+    check(lib.gaot_geoembed_from_moments_bwd(_ptr(mom), _ptr(grad_feat), q, _ptr(adj), _ptr(ws), ws.numel(), _stream()),
+          "gaot_geoembed_from_moments_bwd")
+    return adj
+
+
+def geoembed_moments_bwd(source_pos: Tensor, query_pos: Tensor, g: BipartiteGraph, adj: Tensor):
+    """dL/d moments -> (dL/du per edge [E, 3] in the by-query edge order, dL/d query_pos [Q, 3])"""
+    lib = _lib.load()
+    source_pos = _req(source_pos, torch.float32, "source_pos")
+    query_pos = _req(query_pos, torch.float32, "query_pos")
+    ge = torch.empty(g.by_dst.num_edges, 3, dtype=torch.float32, device=query_pos.device)
+    gq = torch.empty(g.num_dst, 3, dtype=torch.float32, device=query_pos.device)
+    check(lib.gaot_geoembed_moments_bwd(_ptr(source_pos), _ptr(query_pos), _ptr(g.by_dst.rowptr), _ptr(g.by_dst.other),
+                                        g.num_dst, _ptr(adj), _ptr(ge), _ptr(gq), _stream()), "gaot_geoembed_moments_bwd")
+    return ge, gq
 
 
 def _ptr_array(ts):

@@ -756,6 +756,10 @@ class ShardedStep:
 
     def forward_backward(self, batch: MeshBatch, tokens_pos: Optional[Tensor]):
         from . import functional as GF
+        coords = [batch.pos, tokens_pos] + [getattr(batch, a, None) for a in ("query_coord_pos", "query_pos")]
+        if any(isinstance(c, Tensor) and c.requires_grad for c in coords):
+            raise NotImplementedError("ShardedStep: gradients with respect to the coordinates (batch.pos, tokens_pos, "
+                                      "query positions) are not supported for point-sharded samples; detach them")
         if self.buckets is not None:
             self.buckets.reset()
         pred = self.model(batch=batch, tokens_pos=tokens_pos)

@@ -79,7 +79,7 @@ int gaot_gno_fwd(const gaot_mlp_t* mlp /* host */, const float* y_pos, const flo
                  void* workspace, size_t workspace_bytes, gaot_stream_t stream);
 
 /* Backward of the above (autograd of the reference ops): grad wrt f_y and wrt every MLP
- * parameter; none wrt coordinates.  Edges are given sorted by SOURCE (gaot_csr_build with
+ * parameter; none wrt coordinates (gaot_gno_bwd_coords below adds them).  Edges are given sorted by SOURCE (gaot_csr_build with
  * sort_row=0) so that grad_f_y is again an atomics-free segmented sum; rowptr_dst (from the
  * by-query list) supplies the mean's 1/deg.  grad outputs are overwritten, not accumulated. */
 size_t gaot_gno_bwd_workspace_bytes(const gaot_mlp_t* mlp /* host */, int64_t num_edges, int64_t num_queries);
@@ -89,6 +89,14 @@ int gaot_gno_bwd(const gaot_mlp_t* mlp /* host */, const float* y_pos, const flo
                  const int32_t* rowptr_src, int64_t num_edges, int64_t num_sources, int64_t num_queries,
                  float* grad_f_y /* [num_sources, channels] */, const gaot_mlp_grad_t* grads /* host */,
                  int precision, void* workspace, size_t workspace_bytes, gaot_stream_t stream);
+/* The same, and the coordinate gradient of every edge: grad_edge_coords[e] = W_0^T dz_0[e] (6 fp32: d/d y_pos[src] (3),
+ * d/d x_pos[dst] (3)) in the SOURCE-sorted edge order of src_sorted.  Summing its rows by source / by query (fixed-order
+ * segmented sums, the caller's) gives the gradients wrt y_pos / x_pos.  Workspace: gaot_gno_bwd_workspace_bytes. */
+int gaot_gno_bwd_coords(const gaot_mlp_t* mlp /* host */, const float* y_pos, const float* x_pos, const float* f_y,
+                        const float* grad_out, const int32_t* rowptr_dst, const int32_t* src_sorted, const int32_t* dst_sorted,
+                        const int32_t* rowptr_src, int64_t num_edges, int64_t num_sources, int64_t num_queries,
+                        float* grad_f_y, const gaot_mlp_grad_t* grads /* host */, float* grad_edge_coords /* [num_edges, 6] */,
+                        int precision, void* workspace, size_t workspace_bytes, gaot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Statistical geometric-embedding features (reference GeometricEmbedding.
@@ -113,6 +121,17 @@ int gaot_geoembed_raw(const float* source_pos, const float* query_pos, const int
                       gaot_stream_t stream);
 int gaot_geoembed_finalize(float* features, int64_t num_queries, const double* colsums, int64_t num_queries_total,
                            void* workspace, size_t workspace_bytes, gaot_stream_t stream);
+/* Backward of moments -> features (autograd of geoembed.py:117-182 in the coordinates), in the same two steps:
+ * from_moments_bwd: dL/d features [Q, 9] (fp32) -> dL/d moments [Q, 12] (fp64; column z-score, clamp, centroid, covariance,
+ * eigvalsh adjoint V diag(dlambda) V^T); rows without neighbours and N get none.
+ * moments_bwd: one sweep over the by-query list: grad_edge[i] (3 fp32, by-query edge order) = dL/d u of edge i (d/d source
+ * position), grad_query[q] = -sum of its row (d/d query position). */
+size_t gaot_geoembed_from_moments_bwd_workspace_bytes(int64_t num_queries);
+int gaot_geoembed_from_moments_bwd(const double* moments, const float* grad_features, int64_t num_queries,
+                                   double* grad_moments, void* workspace, size_t workspace_bytes, gaot_stream_t stream);
+int gaot_geoembed_moments_bwd(const float* source_pos, const float* query_pos, const int32_t* rowptr_dst,
+                              const int32_t* src_sorted, int64_t num_queries, const double* grad_moments,
+                              float* grad_edge /* [E, 3] */, float* grad_query /* [Q, 3] */, gaot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Dense GEMM  C[m][n] = act(sum_k A(m,k) B(k,n) + bias[n]) + residual[m][n]   (row-major, fp32 I/O)

@@ -122,3 +122,59 @@ elif what == "gno":
         fl = e * {2: 13088, 3: 21280, 4: 29472}[nh]
         timeit(lambda: ops.gno_forward(ws, bs, yp, xp, f, g), f"gno_fwd nh={nh}", fl)
         timeit(lambda: ops.gno_backward(ws, bs, yp, xp, f, go, g), f"gno_bwd nh={nh}", 3 * fl)
+elif what == "coordgrad":
+    # cost of the gradients with respect to the coordinates at configs[1] (500K points, 64x64x32 tokens, knn k=8): the GNO
+    # backward with / without them (both precisions), the statistical GeoEmbed forward + backward, and a whole training step
+    # (forward + MSE + backward) with / without batch.pos.requires_grad_()
+    from gaot_3d_amd.data import make_synthetic_sample
+    from gaot_3d_amd.model.layers.geoembed import GeoStatFn
+    batch, tokens = make_synthetic_sample(500000, (64, 64, 32), k=8, seed=0, device=dev)
+    n, m = 500000, tokens.shape[0]
+    tokens = tokens.to(dev)
+    for prec in ("fp32", "bf16"):
+        gaot_3d_amd.set_precision(prec)
+        for nh, ei, ns, nd, yp, xp in ((3, batch.encoder_edge_index_s0, n, m, batch.pos, tokens),
+                                       (2, batch.decoder_edge_index_s0, m, n, tokens, batch.pos)):
+            ws = [torch.randn(64, 6, device=dev) * 0.3] + [torch.randn(64, 64, device=dev) * 0.1 for _ in range(nh - 1)] + [torch.randn(32, 64, device=dev) * 0.1]
+            bs = [torch.zeros(w.shape[0], device=dev) for w in ws]
+            g = ops.build_graph(ei, ns, nd)
+            f = torch.randn(ns, 32, device=dev); go = torch.randn(nd, 32, device=dev)
+            timeit(lambda: ops.gno_backward(ws, bs, yp, xp, f, go, g), f"{prec} gno_bwd nh={nh} (E={ei.shape[1]})")
+            timeit(lambda: ops.gno_backward(ws, bs, yp, xp, f, go, g, coords=True), f"{prec} gno_bwd nh={nh} + coordinate grads (kernel + 2 segment sums)")
+            ops.timing_reset(True)
+            for _ in range(reps):
+                ops.gno_backward(ws, bs, yp, xp, f, go, g)
+                ops.gno_backward(ws, bs, yp, xp, f, go, g, coords=True)
+            torch.cuda.synchronize()
+            for name, (calls, tot) in ops.timing_summary().items():
+                print(f"  {name}: {tot / calls:.4f} ms")
+            ops.timing_reset(False)
+    gaot_3d_amd.set_precision("fp32")
+    g = ops.build_graph(batch.encoder_edge_index_s0, n, m)
+    timeit(lambda: ops.geoembed_moments(batch.pos, tokens, g), "geoembed moments sweep (forward)")
+    timeit(lambda: ops.geoembed_from_moments(ops.geoembed_moments(batch.pos, tokens, g)), "geoembed forward (moments + finish)")
+    mom = ops.geoembed_moments(batch.pos, tokens, g)
+    gf = torch.randn(m, 9, device=dev)
+    timeit(lambda: ops.geoembed_from_moments_bwd(mom, gf), "geoembed from_moments_bwd")
+    adj = ops.geoembed_from_moments_bwd(mom, gf)
+    timeit(lambda: ops.geoembed_moments_bwd(batch.pos, tokens, g, adj), "geoembed moments_bwd sweep")
+    sp = batch.pos.clone().requires_grad_()
+    timeit(lambda: torch.autograd.grad((GeoStatFn.apply(sp, tokens, g) * gf).sum(), [sp]),
+           "geoembed forward + backward (autograd, incl. the source-side segment sum)")
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    from gaot_3d_amd.model import init_model
+    for prec in ("bf16", "fp32"):
+        gaot_3d_amd.set_precision(prec)
+        model = init_model(6, 1, "gaot_3d", bench.model_config((64, 64, 32), 10, 8, 0.0)).to(dev).train()
+        pos0 = batch.pos.detach()
+        for want in (False, True):
+            # the same tensor on every step (the per-sample caches see one sample): pos0 itself, or one leaf that requires grad
+            batch.pos = pos0.clone().requires_grad_() if want else pos0
+
+            def step():
+                model.zero_grad(set_to_none=True)
+                GF.mse_loss(model(batch=batch, tokens_pos=tokens), batch.x).backward()
+            timeit(step, f"{prec} train step fwd+bwd, batch.pos.requires_grad={want}")
+        batch.pos = pos0
+        del model
