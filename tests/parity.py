@@ -58,8 +58,11 @@ def grads_cosine(name, got: dict, ref: dict, bound, per_tensor=None, energy=1e-6
         total = float(r.norm() ** 2)
         for k in keys:
             x, y = _f(got[k]).flatten(), _f(ref[k]).flatten()
-            if float(y.norm() ** 2) > energy * total:
-                ck = float(x @ y / (x.norm() * y.norm() + 1e-300))
+            ck = float(x @ y / (x.norm() * y.norm() + 1e-300))
+            checked = float(y.norm() ** 2) > energy * total
+            print(f"[parity] {name}/{k}: cosine={ck:.6f} rel_l2={float((x - y).norm() / y.norm().clamp(min=1e-300)):.3e}"
+                  f"{f' (bound {per_tensor})' if checked else ' (below the energy filter)'}")
+            if checked:
                 assert ck >= per_tensor, (name, k, ck)
     return c
 

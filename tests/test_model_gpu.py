@@ -122,8 +122,10 @@ def test_cfg0_vs_oracle(precision):
         # reference's peak so that it scales with the signal: max|pred - oracle| <= 2e-2 * max|oracle|, relative L2 <= 1e-2
         PAR.close_peak("cfg0_bf16/pred", pred, pred_r, 2e-2, rel_l2=1e-2)
         PAR.close("cfg0_bf16/loss", loss, loss_r, 1e-2, 0.0)
+        # per tensor, every tensor (no energy filter): worst measured on the MI355X 0.999789 (decoder k_proj), the bound leaves
+        # 3 x its 1 - cosine (tests/test_block_bf16_fp64_gpu.py pins the Transformer's tensors one by one)
         PAR.grads_cosine("cfg0_bf16/grads", {k: p.grad for k, p in model.named_parameters() if p.requires_grad}, grads_r,
-                         0.999, per_tensor=0.99)
+                         0.999, per_tensor=0.9994, energy=0.0)
 
 
 def test_product_fails_loudly_without_gpu_tensors():

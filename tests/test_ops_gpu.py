@@ -123,11 +123,12 @@ def test_attention_fwd_bwd(b, s, h, hkv, rope):
 
 
 @pytest.mark.parametrize("b,s,h,hkv,p", [(1, 64, 2, 2, 0.0), (2, 100, 2, 1, 0.1), (1, 333, 8, 8, 0.0), (1, 1, 1, 1, 0.0), (1, 1000, 4, 2, 0.1),
-                                         (2, 777, 8, 4, 0.1), (1, 4096, 8, 8, 0.1)])
+                                         (2, 777, 8, 4, 0.1), (2, 4096, 8, 8, 0.1)])
 def test_attention_fp32_one_pass_backward_equals_two_pass(b, s, h, hkv, p):
     """fp32 mode: gaot_attn_bwd_fused_f32 (dK, dV, dQ from one pass, fp32 slab partials summed in slab order; reference attn.py:110-127
     autograd) against the two-pass kernels on the same inputs and the same dropout mask: dK / dV bit-identical (the same arithmetic),
-    dQ to fp32 summation order; a second run bit-identical"""
+    dQ to fp32 summation order; a second run bit-identical.  S = 4096 with two sequences: one sequence of 8 kv heads would be
+    `starved` (ops.attn_bwd: fewer than 256 workgroups of 256 keys) and go to the two-pass kernels"""
     from gaot_3d_amd import ops
     torch.manual_seed(s)
     n = (h + 2 * hkv) * 32
@@ -140,10 +141,13 @@ def test_attention_fp32_one_pass_backward_equals_two_pass(b, s, h, hkv, p):
     try:
         for fused in (False, True, True):
             ops._ATTN_F32_FUSED = fused
+            ops.timing_reset(True)
             g = ops.attn_bwd(qkv, o, d_o, lse, b, s, h, hkv, 1.0 / math.sqrt(32), p, seed)
             torch.cuda.synchronize()
+            assert ("attn_bwd_fused_f32" in ops.TIMING["events"]) == fused, sorted(ops.TIMING["events"])   # the kernel under test ran
             outs.setdefault(fused, []).append(g)
     finally:
+        ops.timing_reset(False)
         ops._ATTN_F32_FUSED = old
     two, one, again = outs[False][0], outs[True][0], outs[True][1]
     assert torch.equal(one, again)
@@ -159,6 +163,57 @@ def test_attention_fp32_one_pass_backward_equals_two_pass(b, s, h, hkv, p):
             assert torch.equal(ops.attn_bwd(qkv, o, d_o, lse, b, s, h, hkv, 1.0 / math.sqrt(32), p, seed), two)
         finally:
             ops._ATTN_F32_FUSED_CAP = cap
+
+
+@pytest.mark.parametrize("p", [0.0, 0.1])
+def test_attention_fp32_one_pass_backward_long_sequence(p):
+    """the fp32 one-pass backward at bench.py's fp32 shape (S = 16 384, 8 heads: 64 slabs of 256 keys, 1 GB of dQ slab partials)
+    against the two-pass kernels on all heads and against the oracle's SDPA in fp64 on one head (same dropout mask)"""
+    from gaot_3d_amd import ops
+    from test_fullsize_oracle_gpu import _attention_fp64
+    b, s, h, hkv, hd = 1, 16384, 8, 8, 5
+    g = torch.Generator().manual_seed(77 + int(p * 10))
+    qkv = torch.randn(b * s, (h + 2 * hkv) * 32, generator=g)
+    qkv[:, :2 * h * 32] *= 1.5                 # logits of spread ~2.2: a softmax that is neither flat nor one-hot
+    d_o = torch.randn(b * s, h * 32, generator=g)
+    word = 0x0F32_5EED_0000 + int(p * 100)
+    seed = torch.tensor([word], dtype=torch.int64, device=DEV) if p > 0 else None
+    scale = 1.0 / math.sqrt(32)
+    qd, dod = qkv.to(DEV), d_o.to(DEV)
+    o, lse = ops.attn_fwd(qd, b, s, h, hkv, scale, p, seed)
+    outs = {}
+    old = ops._ATTN_F32_FUSED
+    try:
+        for fused in (True, False):
+            ops._ATTN_F32_FUSED = fused
+            ops.timing_reset(True)
+            outs[fused] = ops.attn_bwd(qd, o, dod, lse, b, s, h, hkv, scale, p, seed)
+            torch.cuda.synchronize()
+            ran = sorted(ops.TIMING["events"])
+            assert ("attn_bwd_fused_f32" in ran) == fused, ran
+    finally:
+        ops.timing_reset(False)
+        ops._ATTN_F32_FUSED = old
+    one, two = outs[True], outs[False]
+    tag = f"attn_fp32_one_pass S={s} H={h}/{hkv} p={p}"
+    assert torch.equal(one[:, h * 32:], two[:, h * 32:]), "dK | dV differ from the two-pass kernels"
+    dq1, dq2 = one[:, :h * 32], two[:, :h * 32]
+    err = (dq1 - dq2).abs().max().item() / max(dq2.abs().max().item(), 1e-30)
+    print(f"[parity] {tag}: dK | dV bit-identical to two-pass, dQ max diff / peak {err:.2e} (bound 1.0e-05)")
+    assert err < 1e-5
+    keep, p_eff = None, 0.0
+    if p > 0.0:
+        p_eff = orc.dropout_threshold(p) / 65536.0
+        keep = ops.attn_dropout_mask(seed, p, b, h, s)[0, hd].cpu().bool()
+    cols = lambda blk: slice((blk * h + hd) * 32, (blk * h + hd + 1) * 32)
+    head = torch.cat([qkv[:, cols(0)], qkv[:, cols(1)], qkv[:, cols(2)]], dim=1)
+    ref, gref = _attention_fp64(head, d_o[:, hd * 32:(hd + 1) * 32], None, keep, p_eff)
+    close_peak(f"{tag}/out head {hd} vs fp64", o[:, hd * 32:(hd + 1) * 32], ref, FP32_ATTN_LONG_BOUND)
+    for blk, nm in ((0, "dq"), (1, "dk"), (2, "dv")):
+        close_peak(f"{tag}/{nm} head {hd} vs fp64", one[:, cols(blk)], gref[:, 32 * blk:32 * (blk + 1)], FP32_ATTN_LONG_BOUND)
+
+
+FP32_ATTN_LONG_BOUND = 1.2e-5    # max |err| / peak against fp64: 3 x the worst measured on the MI355X (4.2e-6, dk at p = 0.1)
 
 
 @pytest.mark.parametrize("b,s,h,hkv,rope", [(1, 64, 2, 2, False), (2, 100, 2, 1, True), (1, 333, 8, 8, True),
