@@ -44,6 +44,24 @@ class AdamW(torch.optim.Optimizer):
                 self._dev[gi][0].fill_(group["lr"])
                 self._host_lr[gi] = group["lr"]
 
+    def state_dict(self):
+        """torch.optim.AdamW's layout: every parameter gets a ``step`` tensor of its OWN (a 0-dim fp32 CPU tensor, as torch keeps
+        it).  The live state shares one device counter between all parameters; handed out as it is, torch.optim.AdamW would advance
+        that one tensor once per parameter and step."""
+        sd = super().state_dict()
+        host = {}    # id(shared counter) -> value, one device read per counter
+        state = {}
+        for k, st in sd["state"].items():
+            st = dict(st)
+            s = st.get("step")
+            if torch.is_tensor(s):
+                if id(s) not in host:
+                    host[id(s)] = float(s)
+                st["step"] = torch.tensor(host[id(s)], dtype=torch.float32)
+            state[k] = st
+        sd["state"] = state
+        return sd
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None

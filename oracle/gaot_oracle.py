@@ -344,7 +344,7 @@ def magno_decoder(sd: SD, cfg, rndata_flat: Tensor, phys_pos_query: Tensor, late
 # --------------------------------------------------------------------------------------
 def rmsnorm(x: Tensor, w: Tensor, eps: float) -> Tensor:
     """attn.py:167-178"""
-    xf = x.float()
+    xf = x if x.dtype == torch.float64 else x.float()   # an fp64 run of the oracle (tests/trajectory_ref.py) stays fp64
     return (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)).type_as(x) * w
 
 
