@@ -41,26 +41,11 @@ struct AttnBwdArgs {
     gdrop::Drop drop;
 };
 
-// dropout words (csrc/attn_dropout.h).  Lanes that hold ONE query and the 32 keys of a tile in runs of 4 (forward,
-// dQ) read their 8 key-pair words from bw_s, stored [hf][g][pair]; lanes that hold ONE key and runs of queries
-// (dK/dV) read the row words of the tile's queries, split into halfword copies [parity][32].
-__device__ __forceinline__ void stage_col_words(uint32_t* bw_s, uint32_t ck, int64_t k0) {
-    if (threadIdx.x < 16) {
-        const int jj = threadIdx.x;
-        bw_s[((jj >> 1) & 1) * 8 + (jj >> 2) * 2 + (jj & 1)] = gdrop::col_word(ck, (uint32_t)(k0 >> 1) + jj);
-    }
-}
-// keep flags of the lane's 16 rows (bit r = row r of the accumulator layout)
-__device__ __forceinline__ uint32_t keep_bits_cols(uint32_t aw, const uint32_t* bw_s, int hf, uint32_t thr) {
-    uint32_t bits = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const uint32_t x = aw ^ bw_s[hf * 8 + j];
-        bits |= ((x & 0xffffu) >= thr ? 1u : 0u) << (2 * j);
-        bits |= ((x >> 16) >= thr ? 1u : 0u) << (2 * j + 1);
-    }
-    return bits;
-}
+// dropout words (csrc/attn_dropout.h): lanes that hold ONE query and the 32 keys of a tile in runs of 4 (forward, dQ) read their 8
+// key-pair words from bw_s; lanes that hold ONE key and runs of queries (dK/dV) read the row words of the tile's queries, split
+// into halfword copies [parity][32].
+using gdrop::stage_col_words;
+using gdrop::keep_bits_cols;
 
 __device__ __forceinline__ float xhalf(float v) { return __shfl_xor(v, 32, 64); }
 

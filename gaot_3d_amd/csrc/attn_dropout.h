@@ -62,4 +62,24 @@ __host__ __device__ __forceinline__ bool keep_elem(uint32_t rk, uint32_t ck, uin
     return ((k & 1) ? (w >> 16) : (w & 0xffffu)) >= thr;
 }
 
+// The words of one 32-key tile for lanes that hold ONE query and, in the 32x32 MFMA accumulator layout, the tile's keys in runs of
+// 4 (register r of lane half hf = key (r & 3) + 8 (r >> 2) + 4 hf): the tile's 16 key-pair words staged [hf][g][pair] in bw_s
+// (threads 0..15 of the workgroup write, a barrier follows), then the keep flags of the lane's 16 registers (bit r = register r).
+__device__ __forceinline__ void stage_col_words(uint32_t* bw_s, uint32_t ck, int64_t k0) {
+    if (threadIdx.x < 16) {
+        const int jj = threadIdx.x;
+        bw_s[((jj >> 1) & 1) * 8 + (jj >> 2) * 2 + (jj & 1)] = col_word(ck, (uint32_t)(k0 >> 1) + jj);
+    }
+}
+__device__ __forceinline__ uint32_t keep_bits_cols(uint32_t aw, const uint32_t* bw_s, int hf, uint32_t thr) {
+    uint32_t bits = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const uint32_t x = aw ^ bw_s[hf * 8 + j];
+        bits |= ((x & 0xffffu) >= thr ? 1u : 0u) << (2 * j);
+        bits |= ((x >> 16) >= thr ? 1u : 0u) << (2 * j + 1);
+    }
+    return bits;
+}
+
 }  // namespace gdrop

@@ -579,11 +579,56 @@ class RopeFn(Function):
         return g, None, None, None, None, None
 
 
+class AttentionHdFn(Function):
+    """softmax(QK^T/sqrt(d))V for head sizes 64 and 128 in bf16 mode on the flash kernels of csrc/attn_hd.hip (reference
+    attn.py:110-127): q | k | v is the fused fp32 projection, already rotated (RopeFn outside); saves it with o, lse and the seed
+    word -- every saved tensor is O(S * d)."""
+
+    calls = {"fwd": 0, "bwd": 0}     # launches of this process (tests assert which path ran)
+
+    @staticmethod
+    def forward(ctx, qkv: Tensor, b: int, s: int, h: int, hkv: int, head_dim: int, dropout_p: float = 0.0, head0: int = 0,
+                heads_total: int = 0):
+        qkv = qkv if qkv.is_contiguous() else qkv.contiguous()
+        scale = 1.0 / (head_dim ** 0.5)
+        seed = next_dropout_seed(qkv.device) if dropout_p > 0.0 else None
+        o, lse = ops.attn_hd_fwd(qkv, b, s, h, hkv, head_dim, scale, dropout_p, seed, head0, heads_total)
+        AttentionHdFn.calls["fwd"] += 1
+        ctx.save_for_backward(qkv, o, lse, seed if seed is not None else torch.empty(0, device=qkv.device))
+        ctx.dims = (b, s, h, hkv, head_dim, scale, dropout_p, int(head0), int(heads_total))
+        return o
+
+    @staticmethod
+    def backward(ctx, d_o: Tensor):
+        qkv, o, lse, seed = ctx.saved_tensors
+        b, s, h, hkv, head_dim, scale, dropout_p, head0, heads_total = ctx.dims
+        d = d_o if d_o.is_contiguous() else d_o.contiguous()
+        dqkv = ops.attn_hd_bwd(qkv, o, d, lse, b, s, h, hkv, head_dim, scale, dropout_p, seed if dropout_p > 0.0 else None,
+                               head0, heads_total)
+        AttentionHdFn.calls["bwd"] += 1
+        return dqkv, None, None, None, None, None, None, None, None
+
+
+HD_FLASH_HEAD_DIMS = (64, 128)
+
+
 def attention_general(qkv: Tensor, freqs: Optional[Tensor], b: int, s: int, h: int, hkv: int, head_dim: int,
                       dropout_p: float = 0.0, head0: int = 0, heads_total: int = 0) -> Tensor:
-    """softmax(Q K^T / sqrt(d)) V for ANY head_dim (reference attn.py:110-127 accepts every hidden_size % num_heads == 0):
-    the unfused general path -- per (batch, head) an S x S score matrix in HBM, exact-fp32 MFMA GEMMs, the row softmax and
-    element dropout kernels, autograd by composition.  head_dim 32 (every shipped configuration) runs the flash kernels."""
+    """softmax(Q K^T / sqrt(d)) V for ANY head_dim other than 32 (reference attn.py:110-127 accepts every hidden_size % num_heads
+    == 0), the single dispatch point: head sizes 64 and 128 in bf16 mode on the GPU run the flash kernels of csrc/attn_hd.hip
+    (AttentionHdFn; RoPE outside through RopeFn); everything else -- fp32 mode, the other head sizes -- the unfused general path
+    (_attention_unfused).  head_dim 32 (every shipped configuration) runs AttentionFn."""
+    if ops.get_precision() == "bf16" and qkv.is_cuda and head_dim in HD_FLASH_HEAD_DIMS:
+        if freqs is not None:
+            qkv = RopeFn.apply(qkv, freqs, b * s, s, h + hkv, head_dim)
+        return AttentionHdFn.apply(qkv, b, s, h, hkv, head_dim, float(dropout_p), int(head0), int(heads_total))
+    return _attention_unfused(qkv, freqs, b, s, h, hkv, head_dim, dropout_p, head0, heads_total)
+
+
+def _attention_unfused(qkv: Tensor, freqs: Optional[Tensor], b: int, s: int, h: int, hkv: int, head_dim: int,
+                       dropout_p: float = 0.0, head0: int = 0, heads_total: int = 0) -> Tensor:
+    """the unfused general path -- per (batch, head) an S x S score matrix in HBM, exact-fp32 MFMA GEMMs, the row softmax and
+    element dropout kernels, autograd by composition"""
     from . import edgeops as EO
     rows = b * s
     if freqs is not None:

@@ -640,6 +640,61 @@ def attn_bwd(qkv: Tensor, o: Tensor, d_o: Tensor, lse: Tensor, b: int, s: int, h
     return dqkv
 
 
+def attn_hd_fwd(qkv: Tensor, b: int, s: int, h: int, hkv: int, head_dim: int, scale: float, dropout_p: float = 0.0,
+                seed: Optional[Tensor] = None, head0: int = 0, heads_total: int = 0):
+    """flash attention for head sizes 64 and 128 in bf16 mode (csrc/attn_hd.hip).  qkv: [B*S, (h + 2*hkv)*head_dim] fused fp32
+    projection output (q | k | v column blocks), already rotated; -> (o [B*S, h*head_dim], lse [b, h, s]).  ``head0`` /
+    ``heads_total`` as in attn_fwd"""
+    lib = _lib.load()
+    qkv = _req(qkv, torch.float32, "qkv")
+    if head_dim not in (64, 128):
+        raise GaotError(f"attn_hd_fwd: head_dim {head_dim} unsupported (only 64 and 128)")
+    if qkv.dim() != 2 or tuple(qkv.shape) != (b * s, (h + 2 * hkv) * head_dim):
+        raise GaotError(f"attn_hd_fwd: qkv must be [{b * s}, {(h + 2 * hkv) * head_dim}], got {tuple(qkv.shape)}")
+    ld = qkv.shape[1]
+    dev = qkv.device
+    o = torch.empty(b * s, h * head_dim, dtype=torch.float32, device=dev)
+    lse = torch.empty(b, h, s, dtype=torch.float32, device=dev)
+    base = qkv.data_ptr()
+    q, k, v = C.c_void_p(base), C.c_void_p(base + 4 * h * head_dim), C.c_void_p(base + 4 * (h + hkv) * head_dim)
+    with _timed("attn_hd_fwd"):
+        dp, sp = _drop_args(dropout_p, seed)
+        check(lib.gaot_attn_hd_fwd(q, k, v, _ptr(o), _ptr(lse), ld, ld, ld, h * head_dim, b, s, h, hkv, head_dim, float(scale),
+                                   dp, sp, int(head0), int(heads_total), _stream()), "gaot_attn_hd_fwd")
+    return o, lse
+
+
+def attn_hd_bwd(qkv: Tensor, o: Tensor, d_o: Tensor, lse: Tensor, b: int, s: int, h: int, hkv: int, head_dim: int,
+                scale: float, dropout_p: float = 0.0, seed: Optional[Tensor] = None, head0: int = 0,
+                heads_total: int = 0) -> Tensor:
+    """-> dqkv, the gradient w.r.t. the (rotated) fused projection, in its layout; delta, dK / dV and dQ are three launches"""
+    lib = _lib.load()
+    dp, sp = _drop_args(dropout_p, seed)
+    qkv = _req(qkv, torch.float32, "qkv")
+    o = _req(o, torch.float32, "o")
+    d_o = _req(d_o, torch.float32, "d_o")
+    lse = _req(lse, torch.float32, "lse")
+    if head_dim not in (64, 128):
+        raise GaotError(f"attn_hd_bwd: head_dim {head_dim} unsupported (only 64 and 128)")
+    if tuple(qkv.shape) != (b * s, (h + 2 * hkv) * head_dim) or tuple(o.shape) != (b * s, h * head_dim) or o.shape != d_o.shape \
+            or lse.numel() != b * h * s:
+        raise GaotError("attn_hd_bwd: qkv / o / d_o / lse do not match (b, s, h, hkv, head_dim)")
+    ld = qkv.shape[1]
+    dev = qkv.device
+    dqkv = torch.empty_like(qkv)
+    delta = torch.empty(b, h, s, dtype=torch.float32, device=dev)
+    base, gbase = qkv.data_ptr(), dqkv.data_ptr()
+    offk, offv = 4 * h * head_dim, 4 * (h + hkv) * head_dim
+    for name, mask in (("attn_hd_bwd_delta", 1), ("attn_hd_bwd_dkv", 2), ("attn_hd_bwd_dq", 4)):
+        with _timed(name):
+            check(lib.gaot_attn_hd_bwd(C.c_void_p(base), C.c_void_p(base + offk), C.c_void_p(base + offv), _ptr(o),
+                                       _ptr(d_o), _ptr(lse), _ptr(delta), C.c_void_p(gbase), C.c_void_p(gbase + offk),
+                                       C.c_void_p(gbase + offv), ld, ld, ld, h * head_dim, h * head_dim, ld, ld, ld, b, s, h, hkv,
+                                       head_dim, float(scale), dp, sp, int(head0), int(heads_total), mask, _stream()),
+                  "gaot_attn_hd_bwd")
+    return dqkv
+
+
 def attn_fwd_bf16(qkv: Optional[Tensor], freqs: Optional[Tensor], b: int, s: int, h: int, hkv: int, scale: float,
                   dropout_p: float = 0.0, seed: Optional[Tensor] = None, image: Optional[Tensor] = None, head0: int = 0,
                   heads_total: int = 0):

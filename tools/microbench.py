@@ -178,3 +178,65 @@ elif what == "coordgrad":
             timeit(step, f"{prec} train step fwd+bwd, batch.pos.requires_grad={want}")
         batch.pos = pos0
         del model
+elif what == "attn_headdim":
+    # head sizes 64 and 128 in bf16 mode at hidden 256, S = 16 384, b = 1, RoPE on, p = 0.1: forward + backward of (1) the unfused
+    # general path (functional._attention_unfused: the path every head size other than 32 took before the flash kernels), (2) the
+    # flash kernels of csrc/attn_hd.hip (functional.attention_general), and, FOR ORIENTATION ONLY -- hand-scheduled kernels, not a
+    # target -- (3) the head-size-32 kernels at the same hidden size (8 heads, equal FLOPs).  HIP events around each call, median
+    # of `reps` after one warm-up, the three alternating in one process.
+    gaot_3d_amd.set_precision("bf16")
+    s, hidden, pd = int(os.environ.get("MB_S", 16384)), 256, 0.1
+    GF.set_dropout_seed(2026, dev)
+
+    def fwd_bwd(path, qkv, freqs, h, d, w):
+        qkv.grad = None
+        if path == "unfused":
+            o = GF._attention_unfused(qkv, freqs, 1, s, h, h, d, pd)
+        elif path == "flash":
+            o = GF.attention_general(qkv, freqs, 1, s, h, h, d, pd)
+        else:
+            o = GF.AttentionFn.apply(qkv, freqs, 1, s, h, h, pd)
+        (o * w).sum().backward()
+
+    def median_ms(fn):
+        fn(); torch.cuda.synchronize()
+        ts = []
+        for _ in range(reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); fn(); e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        ts.sort()
+        return ts[len(ts) // 2], ts[0], ts[-1]
+
+    w = torch.randn(s, hidden, device=dev)
+    x32 = torch.randn(s, 3 * hidden, device=dev).requires_grad_(True)
+    f32_ = (1.0 / (10000 ** (torch.arange(0, 32, 2).float() / 32))).to(dev)
+    for d in (64, 128):
+        h = hidden // d
+        qkv = torch.randn(s, 3 * hidden, device=dev).requires_grad_(True)
+        freqs = (1.0 / (10000 ** (torch.arange(0, d, 2).float() / d))).to(dev)
+        flops = 18 * s * s * d * h          # forward 4, dK/dV 8, dQ 6 S^2 D per head
+        res = {}
+        for name, fn in (("unfused", lambda: fwd_bwd("unfused", qkv, freqs, h, d, w)),
+                         ("flash", lambda: fwd_bwd("flash", qkv, freqs, h, d, w)),
+                         ("hd32", lambda: fwd_bwd("hd32", x32, f32_, 8, 32, w))):
+            res[name] = median_ms(fn)
+        print(f"D={d} h={h} S={s} p={pd} rope: (1) _attention_unfused fwd+bwd: {res['unfused'][0]:.3f} ms (min {res['unfused'][1]:.3f}, max {res['unfused'][2]:.3f})")
+        print(f"D={d} h={h} S={s} p={pd} rope: (2) flash kernels (attn_hd) fwd+bwd: {res['flash'][0]:.3f} ms (min {res['flash'][1]:.3f}, max {res['flash'][2]:.3f})"
+              f"  = {res['flash'][0] / res['unfused'][0]:.3f} x (1);  {flops / res['flash'][0] / 1e9:.1f} TF/s of 18 S^2 D h, "
+              f"{100 * flops / res['flash'][0] / 1e9 / 2500:.1f} % of the 2.5 PF/s bf16 roof (whole call incl. RoPE and the loss product)")
+        print(f"D={d}: (3) orientation only, head size 32 x 8 heads (hand-scheduled kernels): {res['hd32'][0]:.3f} ms (min {res['hd32'][1]:.3f}, max {res['hd32'][2]:.3f})")
+    ops.timing_reset(True)
+    for d in (64, 128):
+        h = hidden // d
+        qkv = torch.randn(s, 3 * hidden, device=dev).requires_grad_(True)
+        freqs = (1.0 / (10000 ** (torch.arange(0, d, 2).float() / d))).to(dev)
+        ops.TIMING["events"] = {}
+        for _ in range(reps):
+            fwd_bwd("flash", qkv, freqs, h, d, w)
+        torch.cuda.synchronize()
+        for name, (calls, tot) in ops.timing_summary().items():
+            if name.startswith("attn_hd"):
+                print(f"  D={d} {name}: {tot / calls:.4f} ms")
+    ops.timing_reset(False)
