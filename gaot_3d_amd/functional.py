@@ -22,11 +22,6 @@ def _w2d(w: Tensor) -> Tensor:
     return w if w.is_contiguous() else w.contiguous()
 
 
-# bf16 weight copies made ahead of their use by ONE multi-tensor launch (precast_weights, called by Transformer.forward
-# for all of its matrices) and valid only until release_precast(): keyed by (address, shape) of the fp32 matrix
-_WB_CACHE: dict = {}
-
-
 def _wb_eligible(w: Tensor, prec: int) -> bool:
     n, k = w.shape
     return bool(prec == 1 and w.is_cuda and n > 64 and k > 64 and n % 8 == 0 and k % 8 == 0 and w.data_ptr() % 16 == 0)
@@ -39,34 +34,97 @@ def fused_view(ws) -> Tensor:
                                 (w0.shape[1], 1))
 
 
-_WBT_CACHE: dict = {}
+def _rows2d(x: Tensor, k: int, m: int = -1) -> Tensor:
+    """x as a contiguous [m, k] matrix of rows"""
+    x2 = x.reshape(m, k)
+    return x2 if x2.is_contiguous() else x2.contiguous()
+
+
+def _split_rows(dwcat: Tensor, shapes) -> List[Tensor]:
+    """the gradient of a co-located [sum(out_i), in] matrix, sliced back into its parameters' shapes"""
+    dws, row = [], 0
+    for shp in shapes:
+        dws.append(dwcat[row:row + shp[0]].view(shp))
+        row += shp[0]
+    return dws
+
+
+class _Images:
+    """The weight images prepared ahead of their use by ONE multi-tensor launch per kind (Transformer.forward: precast_weights,
+    prepack_ffn, prepack_qkv, prepack_skip) and valid only until release_precast(): per kind, (address, shape) of the fp32 matrix ->
+    image.  ``wb`` / ``wbt``: the bf16 copy / bf16 transpose; ``ffn``: (fragment-ordered image of the co-located [w1; w3] and w2 for
+    the fused FFN kernels (csrc/ffn_fused.hip), has the backward's images, address of the o_proj weight packed behind them or None);
+    ``qkv`` / ``skip``: the fragment image of the co-located q | k | v weight / of a decoder block's skip_proj weight.
+    The accessors return the prepared image, else pack it now with one launch."""
+
+    def __init__(self):
+        self.kinds = {kind: {} for kind in ("wb", "wbt", "ffn", "qkv", "skip")}
+
+    def clear(self, *kinds) -> None:
+        for kind in kinds or self.kinds:
+            self.kinds[kind].clear()
+
+    def __len__(self) -> int:
+        return sum(len(d) for d in self.kinds.values())
+
+    def put(self, kind: str, w: Tensor, image) -> None:
+        self.kinds[kind][(w.data_ptr(), tuple(w.shape))] = image
+
+    def get(self, kind: str, w: Tensor):
+        return self.kinds[kind].get((w.data_ptr(), tuple(w.shape)))
+
+    def wb(self, w: Tensor) -> Tensor:
+        c = self.get("wb", w)
+        return c if c is not None else ops.cast_bf16(w)
+
+    def ffn(self, w13: Tensor, w2: Tensor, f: int, need_bwd: bool) -> Tensor:
+        packed, has_bwd, _wo = self.get("ffn", w13) or (None, False, None)
+        if packed is None or (need_bwd and not has_bwd):
+            packed = ops.ffn_pack(w13, w2, f, need_bwd)
+        return packed
+
+    def block(self, w13: Tensor, w2: Tensor, wo: Tensor, f: int) -> Tensor:
+        packed, _has_bwd, wo_ptr = self.get("ffn", w13) or (None, False, None)
+        if packed is None or wo_ptr != wo.data_ptr():      # no image, or not one that carries THIS o_proj
+            packed = ops.block_pack_multi([(w13, w2, wo)], f)[0]
+        return packed
+
+    def qkv(self, wcat: Tensor) -> Tensor:
+        packed = self.get("qkv", wcat)
+        return packed if packed is not None else ops.qkv_pack_multi([wcat], True)[0]
+
+    def skip(self, w: Tensor) -> Tensor:
+        packed = self.get("skip", w)
+        return packed if packed is not None else ops.skip_pack_multi([w])[0]
+
+
+_IMAGES = _Images()
 
 
 def precast_weights(mats, transposed=()) -> None:
     """``transposed``: matrices whose bf16 TRANSPOSE is wanted as well (the FFN's w2 and w1|w3: their input-gradient GEMMs run
     as x W^T on it, see FFNFn.backward) -- one more launch for all of them"""
-    _WB_CACHE.clear()
-    _WBT_CACHE.clear()
+    _IMAGES.clear("wb", "wbt")
     if ops.get_precision() != "bf16":
         return
     todo = [m for m in (_w2d(m) for m in mats) if _wb_eligible(m, 1)]
     for m, c in zip(todo, ops.cast_bf16_multi(todo)):
-        _WB_CACHE[(m.data_ptr(), tuple(m.shape))] = c
+        _IMAGES.put("wb", m, c)
     if transposed and torch.is_grad_enabled():
         todo = [m for m in (_w2d(m) for m in transposed) if _wb_eligible(m, 1) and m.is_contiguous()]
         for m, c in zip(todo, ops.cast_bf16_transpose_multi(todo)):
-            _WBT_CACHE[(m.data_ptr(), tuple(m.shape))] = c
+            _IMAGES.put("wbt", m, c)
 
 
-# fragment-ordered images of FFN weights for the fused FFN kernels (csrc/ffn_fused.hip), made by ONE launch for all blocks of a
-# Transformer (prepack_ffn) and valid until release_precast(): keyed by (address, shape) of the co-located fp32 [w1; w3]
-_FFN_PACK_CACHE: dict = {}
-_WO_PACKED: dict = {}      # key of a block image that carries the o_proj fragment image -> address of that o_proj weight
 _FFN_FUSED = os.environ.get("GAOT_FFN_FUSED", "1") != "0"
 _BLOCK_TAIL = os.environ.get("GAOT_BLOCK_TAIL", "1") != "0"    # o_proj + residual + ffn_norm + FFN + residual in one forward launch (A/B switch)
 _OPROJ_BWD_IMAGE = os.environ.get("GAOT_OPROJ_BWD_IMAGE", "1") != "0"   # BlockTailFn.backward hands dO over as the flash backward's image (A/B switch)
 _NORM_FFN = os.environ.get("GAOT_NORM_FFN", "1") != "0"        # the block's ffn_norm inside the fused FFN forward (A/B switch)
 _FFN_BWD_DX = os.environ.get("GAOT_FFN_BWD_DX", "1") != "0"      # the input gradient inside the fused backward launch (A/B switch)
+_NORM_QKV = os.environ.get("GAOT_NORM_QKV", "1") != "0"      # attn_norm + q | k | v image in one launch (A/B switch)
+_NORM_BWD_FUSED = os.environ.get("GAOT_NORM_BWD_FUSED", "1") != "0"    # RMSNorm backward in the epilogue of the product in front of it (A/B switch)
+_CAT_QKV = os.environ.get("GAOT_CAT_QKV", "1") != "0"        # the decoder block's skip projection inside the head kernel (A/B switch)
+_CAT_BWD_DX = os.environ.get("GAOT_CAT_BWD_DX", "1") != "0"  # ... and its two input gradients inside the head's backward kernel (A/B switch)
 
 
 def _ffn_fusable(w13: Tensor, w2: Tensor) -> bool:
@@ -79,8 +137,7 @@ def prepack_ffn(pairs, with_backward: bool, wos=None) -> None:
     """``pairs``: (co-located [w1; w3] view, w2) of every FFN about to run; those the fused kernels take (d_model 256, F % 128 == 0,
     bf16 mode) are packed by one launch per distinct F; ``with_backward``: the images the fused backward reads as well; ``wos``
     (with the backward images): the o_proj weight of each pair's block -- packed behind them for the block-tail kernel (BlockTailFn)"""
-    _FFN_PACK_CACHE.clear()
-    _WO_PACKED.clear()
+    _IMAGES.clear("ffn")
     by_f: dict = {}
     pairs = list(pairs)
     wos = list(wos) if (wos is not None and with_backward and _BLOCK_TAIL) else [None] * len(pairs)
@@ -98,20 +155,13 @@ def prepack_ffn(pairs, with_backward: bool, wos=None) -> None:
         else:
             outs = ops.ffn_pack_multi([(a, b) for a, b, _ in items], f, with_backward)
         for (w13, _w2, wo), packed in zip(items, outs):
-            _FFN_PACK_CACHE[(w13.data_ptr(), tuple(w13.shape))] = (packed, bool(with_backward))
-            if has_wo:
-                _WO_PACKED[(w13.data_ptr(), tuple(w13.shape))] = wo.data_ptr()
-
-
-_QKV_PACK_CACHE: dict = {}       # (address, shape) of the co-located fp32 q | k | v weight -> its fragment image (prepack_qkv)
-_NORM_QKV = os.environ.get("GAOT_NORM_QKV", "1") != "0"      # attn_norm + q | k | v image in one launch (A/B switch)
-_NORM_BWD_FUSED = os.environ.get("GAOT_NORM_BWD_FUSED", "1") != "0"    # RMSNorm backward in the epilogue of the product in front of it (A/B switch)
+            _IMAGES.put("ffn", w13, (packed, bool(with_backward), wo.data_ptr() if has_wo else None))
 
 
 def prepack_qkv(wcats) -> None:
     """``wcats``: the co-located [q; k; v] weight views of the blocks about to run; those the fused head kernel takes (bf16 mode,
     [N, 256] with N a multiple of 256) are packed by one launch"""
-    _QKV_PACK_CACHE.clear()
+    _IMAGES.clear("qkv")
     if not (_NORM_QKV and ops.get_precision() == "bf16"):
         return
     by_n: dict = {}
@@ -121,34 +171,25 @@ def prepack_qkv(wcats) -> None:
             by_n.setdefault(w.shape[0], []).append(w)
     for _n, ws in by_n.items():
         for w, packed in zip(ws, ops.qkv_pack_multi(ws, True)):
-            _QKV_PACK_CACHE[(w.data_ptr(), tuple(w.shape))] = packed
-
-
-_SKIP_PACK_CACHE: dict = {}      # (address, shape) of a decoder block's fp32 skip_proj weight -> its fragment image (prepack_skip)
-_CAT_BWD_DX = os.environ.get("GAOT_CAT_BWD_DX", "1") != "0"  # ... and its two input gradients inside the head's backward kernel (A/B switch)
-_CAT_QKV = os.environ.get("GAOT_CAT_QKV", "1") != "0"        # the decoder block's skip projection inside the head kernel (A/B switch)
+            _IMAGES.put("qkv", w, packed)
 
 
 def prepack_skip(ws) -> None:
-    _SKIP_PACK_CACHE.clear()
+    _IMAGES.clear("skip")
     if not (_CAT_QKV and _NORM_QKV and ops.get_precision() == "bf16"):
         return
     ok = [w for w in (_w2d(w) for w in ws) if w.is_cuda and w.dtype == torch.float32 and w.is_contiguous() and tuple(w.shape) == (256, 512)]
     for w, packed in zip(ok, ops.skip_pack_multi(ok)):
-        _SKIP_PACK_CACHE[(w.data_ptr(), tuple(w.shape))] = packed
+        _IMAGES.put("skip", w, packed)
 
 
 def release_precast() -> None:
-    _WB_CACHE.clear()
-    _WBT_CACHE.clear()
-    _FFN_PACK_CACHE.clear()
-    _QKV_PACK_CACHE.clear()
-    _SKIP_PACK_CACHE.clear()
+    _IMAGES.clear()
 
 
 def _wbt(w: Tensor) -> Optional[Tensor]:
     """the bf16 transpose of a weight prepared by precast_weights, if any"""
-    return _WBT_CACHE.get((w.data_ptr(), tuple(w.shape)))
+    return _IMAGES.get("wbt", w)
 
 
 def _wb(w: Tensor, precision: Optional[int]) -> Tensor:
@@ -156,10 +197,27 @@ def _wb(w: Tensor, precision: Optional[int]) -> Tensor:
     to bf16 ONCE per use instead of once per workgroup that streams it (a 64-row tile re-reads the whole matrix: at
     M = 16 384 that is 256 x); everything else stays fp32"""
     prec = (1 if ops.get_precision() == "bf16" else 0) if precision is None else precision
-    if _wb_eligible(w, prec):
-        c = _WB_CACHE.get((w.data_ptr(), tuple(w.shape)))
-        return c if c is not None else ops.cast_bf16(w)
-    return w
+    return _IMAGES.wb(w) if _wb_eligible(w, prec) else w
+
+
+def _placeholder(shape, device, **payload) -> Tensor:
+    """a storage-less fp32 tensor of ``shape`` (ONE element, expanded: the [rows, n] buffer never exists) that carries the real data
+    -- a kernels' image -- as Python attributes to the next autograd node"""
+    t = torch.empty(1, dtype=torch.float32, device=device).expand(*shape)
+    for name, value in payload.items():
+        setattr(t, name, value)
+    return t
+
+
+def _payload(t: Tensor, name: str):
+    """what _placeholder attached to ``t`` under ``name``, or None for a real tensor.  A tensor that owns fewer bytes than its shape
+    needs and carries no ``name`` is a placeholder whose image was lost on the way (a hook or the engine delivered another tensor
+    object): its one element is uninitialised -- an error, not garbage"""
+    v = getattr(t, name, None)
+    if v is None and t.untyped_storage().nbytes() < t.numel() * t.element_size():
+        raise GaotError(f"a shape-only placeholder arrived without its image ({name}): the tensor was replaced on its way (a hook, "
+                        "a view); it has no values of its own")
+    return v
 
 
 def _dw_gemm(a: Tensor, b: Tensor, m: int, n: int, k: int, lda: int, ldb: int, precision, params=None) -> Tensor:
@@ -187,15 +245,9 @@ class LinearFn(Function):
         n, k = w.shape
         if x.shape[-1] != k:
             raise GaotError(f"linear: input has {x.shape[-1]} features, weight expects {k}")
-        x2 = x.reshape(-1, k)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
+        x2 = _rows2d(x, k)
         m = x2.shape[0]
-        res = None
-        if residual is not None:
-            res = residual.reshape(m, n)
-            if not res.is_contiguous():
-                res = res.contiguous()
+        res = None if residual is None else _rows2d(residual, n, m)
         w = _wb(w, precision)
         if act > 3:     # outside the GEMM epilogue's set (ops.ACT): pre-activation from the GEMM, activation as its own pass
             if res is not None:
@@ -219,9 +271,7 @@ class LinearFn(Function):
         x2, w, z = ctx.saved_tensors
         n, k = w.shape
         m = x2.shape[0]
-        dy2 = dy.reshape(m, n)
-        if not dy2.is_contiguous():
-            dy2 = dy2.contiguous()
+        dy2 = _rows2d(dy, n, m)
         dz = ops.act_bwd(z, dy2, ctx.act) if ctx.act else dy2
         dx = dw = db = dres = None
         if ctx.needs_input_grad[0]:
@@ -425,7 +475,7 @@ class AttentionFn(Function):
         all-gathered, so the attention work -- 60 % of a 500 K-point step -- is divided by G instead of repeated G times."""
         scale = 1.0 / (32 ** 0.5)
         bf16 = ops.get_precision() == "bf16"
-        pre_img = getattr(qkv, "_gaot_qkv_image", None)   # MultiLinearFn wrote the projection as the kernels' image
+        pre_img = _payload(qkv, "_gaot_qkv_image")        # its producer wrote the projection as the kernels' image
         if pre_img is not None and not (bf16 and head_group is None):
             raise GaotError("a q|k|v image placeholder reached an attention path that needs the fp32 projection")
         if pre_img is None:
@@ -472,7 +522,9 @@ class AttentionFn(Function):
         if ctx.hp is not None:       # this rank's heads of the (replicated) output gradient
             grk = ctx.hp[2]
             d_o = d_o[:, grk * h * 32:(grk + 1) * h * 32]
-        pre = getattr(d_o, "_gaot_do_image", None)     # BlockTailFn.backward: dO already is the kernels' bf16 image, delta is formed
+        # BlockTailFn.backward: dO already is the kernels' bf16 image, delta is formed.  (It sends one to the unsharded bf16 kernels
+        # only: everywhere else a gradient that owns less than its shape -- the expanded one of ``o.sum()`` -- is a real tensor)
+        pre = _payload(d_o, "_gaot_do_image") if (bf16 and ctx.hp is None) else getattr(d_o, "_gaot_do_image", None)
         if pre is not None and not (bf16 and ctx.hp is None):
             raise GaotError("a dO image placeholder reached an attention backward that needs the fp32 gradient")
         if pre is not None:
@@ -669,9 +721,6 @@ class SwiGLUFn(Function):
         return ops.swiglu_bwd(ag, d, ctx.f), None
 
 
-_FFN_BWD_FUSED = os.environ.get("GAOT_FFN_BWD_FUSED", "0") == "1"
-
-
 class FFNFn(Function):
     """w2(silu(w1 x) * w3 x) [+ residual] (reference FFN.forward, attn.py:150-157) for the bf16 path with the
     intermediates kept as bf16 in memory: [rows, 2F] = w1 x | w3 x, silu(a)*g and both of their gradients are written
@@ -691,11 +740,9 @@ class FFNFn(Function):
         """``res_is_x``: the residual IS the input (the block's ``h + ffn(h)``, attn.py:229): its gradient is folded into the
         dx GEMM's epilogue instead of meeting dx in a separate accumulation pass"""
         f, d = w1.shape
-        x2 = x.reshape(-1, d)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
+        x2 = _rows2d(x, d)
         m = x2.shape[0]
-        wcat32 = w1.new_empty(0).set_(w1.untyped_storage(), w1.storage_offset(), (2 * f, d), (d, 1))
+        wcat32 = fused_view((w1, w3))
         wcat = _wb(wcat32, 1)
         w2c = _wb(_w2d(w2), 1)
         wcat_t, w2t = _wbt(wcat32), _wbt(_w2d(w2))   # bf16 transposes from the per-forward cast pass, or None
@@ -705,28 +752,18 @@ class FFNFn(Function):
         if res_is_x:
             res = x2
         elif residual is not None:
-            res = residual.reshape(m, d)
-            if not res.is_contiguous():
-                res = res.contiguous()
+            res = _rows2d(residual, d, m)
         w2f = _w2d(w2)
         if xa.dtype == torch.bfloat16 and _ffn_fusable(wcat32, w2f) and (res is None or res.dtype == torch.float32):
             # the whole FFN in ONE launch over 64-row blocks (csrc/ffn_fused.hip): u never returns from HBM; a | g and u are still
             # written for the backward below; bit-identical to the two launches of the other branch
             # Nothing is saved for the backward but the (bf16) input: FFNFn.backward recomputes a | g inside gaot_ffn_bwd_dag -- the 96 MB
             # of a | g and u per layer at S = 16 384 cross HBM once (backward) instead of three times.  Bit-identical to the other branch.
-            need_bwd = any(ctx.needs_input_grad[:4])
-            packed, has_bwd = _FFN_PACK_CACHE.get((wcat32.data_ptr(), tuple(wcat32.shape)), (None, False))
-            if packed is None or (need_bwd and not has_bwd):
-                packed = ops.ffn_pack(wcat32, w2f, f, need_bwd)
+            packed = _IMAGES.ffn(wcat32, w2f, f, any(ctx.needs_input_grad[:4]))
             y, _ag, _u = ops.ffn_fwd(xa, packed, f, res, save=False)
-            empty = w2c.new_empty(0)
-            ctx.save_for_backward(xa, wcat, w2c, packed, empty, wcat_t if wcat_t is not None else empty, w2t if w2t is not None else empty)
-            ctx.fused = True
-            ctx.res_is_x = res_is_x
-            ctx.wparams = (w1, w3, w2)
-            ctx.meta = (f, d, x.shape, residual.shape if (residual is not None and not res_is_x) else None, w1.shape, w2.shape)
-            return y.view(*x.shape[:-1], d)
+            ag, u, ctx.fused = packed, w2c.new_empty(0), True      # (saved in the places of a | g and u)
         else:
+            ctx.fused = False
             if xa.dtype == torch.bfloat16 and wcat.dtype == torch.bfloat16 and d == 256 and f % 32 == 0:
                 ag, u = ops.ffn_w13_swiglu(xa, wcat, f)     # projection + SwiGLU in one launch (csrc/gemm_k256.hip, OUT_SWIGLU)
             else:
@@ -735,7 +772,6 @@ class FFNFn(Function):
             y = ops.gemm(u, w2c, m, d, f, f, f, False, True, residual=res, ldr=d, precision=1)
         empty = w2c.new_empty(0)
         ctx.save_for_backward(xa, wcat, w2c, ag, u, wcat_t if wcat_t is not None else empty, w2t if w2t is not None else empty)
-        ctx.fused = False
         ctx.res_is_x = res_is_x
         ctx.wparams = (w1, w3, w2)
         ctx.meta = (f, d, x.shape, residual.shape if (residual is not None and not res_is_x) else None, w1.shape, w2.shape)
@@ -746,9 +782,7 @@ class FFNFn(Function):
         x2, wcat, w2c, ag, u, wcat_t, w2t = ctx.saved_tensors
         f, d, xshape, rshape, w1shape, w2shape = ctx.meta
         m = x2.shape[0]
-        dy2 = dy.reshape(m, d)
-        if not dy2.is_contiguous():
-            dy2 = dy2.contiguous()
+        dy2 = _rows2d(dy, d, m)
         if ctx.fused:
             # (x2, wcat, w2c, packed, -, wcat_t, w2t): a | g recomputed, du = dy W2, the SwiGLU derivative and the bf16 copy of dy in ONE
             # launch (csrc/ffn_fused.hip: k_ffn_bwd); the three products that follow read its outputs
@@ -759,7 +793,7 @@ class FFNFn(Function):
                 dw2 = _dw_gemm(dyb, u, d, f, m, d, f, 1, ctx.wparams[2:]).view(w2shape)
                 dwcat = _dw_gemm(dag, x2, 2 * f, d, m, 2 * f, d, 1, ctx.wparams[:2])
                 dres = dy2.view(rshape) if (rshape is not None and ctx.needs_input_grad[4]) else None
-                return dx.view(xshape), dwcat[:f].view(w1shape), dwcat[f:].view(w1shape), dw2, dres, None
+                return (dx.view(xshape), *_split_rows(dwcat, (w1shape, w1shape)), dw2, dres, None)
             dag, u, dyb = ops.ffn_bwd_dag(x2, dy2, packed, f)
             dw2 = _dw_gemm(dyb, u, d, f, m, d, f, 1, ctx.wparams[2:]).view(w2shape)
         elif d == 256 and w2c.dtype == torch.bfloat16 and f % 64 == 0:
@@ -767,16 +801,9 @@ class FFNFn(Function):
             # (csrc/gemm_k256.hip: 41 -> 18 us at configs[1]) for one rounding pass over dy and a 0.5 MB weight transpose;
             # the weight-gradient GEMM reads the same bf16 rows (half the A traffic)
             dyb = ops.cast_bf16(dy2)
-            if _FFN_BWD_FUSED:
-                # measurement only (GAOT_FFN_BWD_FUSED=1): the SwiGLU backward in that product's epilogue (gaot_ffn_w2_bwd_swiglu: du
-                # never reaches HBM).  Built, bit-compatible, and SLOWER: 54.9 us against 22.8 + 24.8 us at [16 384, 1024] -- a lane
-                # of the transposed product owns a row, so the epilogue's reads of a | g touch 32 rows per instruction where the
-                # stand-alone pass streams at 6.7 TB/s (profiles/archive/r5_t_ffn_bwd_fusion_lab.txt); the step: 21.98 against 21.93 ms
-                dag = ops.ffn_w2_bwd_swiglu(dyb, w2t if w2t.numel() else w2c.t().contiguous(), ag, f)
-            else:
-                du = ops.gemm(dyb, w2t if w2t.numel() else w2c.t().contiguous(), m, f, d, d, d, False, True, precision=1,
-                              out_dtype=torch.bfloat16)
-                dag = ops.swiglu_bwd_bf16(ag, du, f)
+            du = ops.gemm(dyb, w2t if w2t.numel() else w2c.t().contiguous(), m, f, d, d, d, False, True, precision=1,
+                          out_dtype=torch.bfloat16)
+            dag = ops.swiglu_bwd_bf16(ag, du, f)
             dw2 = _dw_gemm(dyb, u, d, f, m, d, f, 1, ctx.wparams[2:]).view(w2shape)
         else:
             du = ops.gemm(dy2, w2c, m, f, d, d, f, False, False, precision=1, out_dtype=torch.bfloat16)
@@ -794,7 +821,40 @@ class FFNFn(Function):
                               precision=1).view(xshape)
         dwcat = _dw_gemm(dag, x2, 2 * f, d, m, 2 * f, d, 1, ctx.wparams[:2])
         dres = dy2.view(rshape) if (rshape is not None and ctx.needs_input_grad[4]) else None
-        return dx, dwcat[:f].view(w1shape), dwcat[f:].view(w1shape), dw2, dres, None
+        return (dx, *_split_rows(dwcat, (w1shape, w1shape)), dw2, dres, None)
+
+
+def _norm_ffn_bwd(yb: Tensor, dy2: Tensor, packed: Tensor, f: int, h: Tensor, norm_w: Tensor, rstd: Tensor, nparam, wparams):
+    """the backward of ``n = ffn_norm(h); y = n + ffn(n)`` (yb = bf16(n)) shared by NormFFNFn and BlockTailFn: the fused FFN backward
+    with the norm's in its epilogue (or behind it), then the two weight-gradient products -> (dh, dnw, dw1, dw3, dw2)"""
+    m, d = yb.shape
+    if _NORM_BWD_FUSED:
+        dh, dag, u, dyb, dnw = ops.ffn_bwd_norm(yb, dy2, packed, f, h, norm_w, rstd, defer=ops.defer_ok((nparam,)))
+    else:
+        dn, dag, u, dyb = ops.ffn_bwd(yb, dy2, packed, f, True)       # dn: gradient w.r.t. the normalised rows (FFN input + residual)
+        dh, dnw = ops.rmsnorm_bwd(h, norm_w, dn, rstd, defer=ops.defer_ok((nparam,)))
+    dw2 = _dw_gemm(dyb, u, d, f, m, d, f, 1, wparams[2:]).view(wparams[2].shape)
+    dwcat = _dw_gemm(dag, yb, 2 * f, d, m, 2 * f, d, 1, wparams[:2])
+    return (dh, dnw, *_split_rows(dwcat, (wparams[0].shape, wparams[1].shape)), dw2)
+
+
+def _norm_qkv_bwd(d: Tensor, yb: Tensor, packed: Tensor, wcat: Tensor, x: Tensor, norm_w: Tensor, rstd: Tensor, dres: Optional[Tensor],
+                  dtap: Optional[Tensor], nparam, wparams, cat=None):
+    """the backward of ``q | k | v = attn_norm(x) Wqkv^T`` (yb = bf16(attn_norm(x))) shared by NormQKVFn and CatNormQKVFn: the
+    weight-gradient product, then d(norm x) = dqkv Wqkv with attn_norm's backward (and the residual's / the skip's addends) in its
+    epilogue, or behind it -> (dwcat, dx, dnw, dxa, dxb); ``cat`` = (skip image, same): the skip projection's two input gradients
+    leave the same launch (k_qkv_bwd_norm<CATB>), else dxa = dxb = None"""
+    m, ntot = d.shape
+    dwcat = _dw_gemm(d, yb, ntot, 256, m, ntot, 256, 1, wparams)
+    dxa = dxb = None
+    if cat is not None:
+        dx, dxa, dxb, dnw = ops.qkv_bwd_norm_cat(d, packed, x, norm_w, rstd, dres, cat[0], cat[1], defer=ops.defer_ok((nparam,)))
+    elif _NORM_BWD_FUSED:
+        dx, dnw = ops.qkv_bwd_norm(d, packed, x, norm_w, rstd, dres, dtap, defer=ops.defer_ok((nparam,)))
+    else:
+        dn = ops.gemm(d, wcat, m, 256, ntot, ntot, 256, False, False, precision=1)
+        dx, dnw = ops.rmsnorm_bwd(x, norm_w, dn, rstd, dres, defer=ops.defer_ok((nparam,)), dx_add2=dtap)
+    return dwcat, dx, dnw, dxa, dxb
 
 
 class NormFFNFn(Function):
@@ -808,43 +868,26 @@ class NormFFNFn(Function):
         if not (_FFN_FUSED and _NORM_FFN and h.is_cuda and h.dtype == torch.float32 and h.shape[-1] == 256 and norm_w.numel() == 256
                 and _adjacent([_w2d(w1), _w2d(w3)]) and all(t.requires_grad for t in (w1, w3, w2)) and torch.is_grad_enabled()):
             return False
-        f = w1.shape[0]
-        wcat32 = w1.new_empty(0).set_(w1.untyped_storage(), w1.storage_offset(), (2 * f, 256), (256, 1))
-        return _ffn_fusable(wcat32, _w2d(w2))
+        return _ffn_fusable(fused_view((w1, w3)), _w2d(w2))
 
     @staticmethod
     def forward(ctx, h: Tensor, norm_w: Tensor, eps: float, w1: Tensor, w3: Tensor, w2: Tensor):
         f, d = w1.shape
-        h2 = h.reshape(-1, d)
-        if not h2.is_contiguous():
-            h2 = h2.contiguous()
-        wcat32 = w1.new_empty(0).set_(w1.untyped_storage(), w1.storage_offset(), (2 * f, d), (d, 1))
-        packed, has_bwd = _FFN_PACK_CACHE.get((wcat32.data_ptr(), tuple(wcat32.shape)), (None, False))
-        if packed is None or not has_bwd:
-            packed = ops.ffn_pack(wcat32, _w2d(w2), f, True)
+        h2 = _rows2d(h, d)
+        packed = _IMAGES.ffn(fused_view((w1, w3)), _w2d(w2), f, True)
         y, yb, rstd = ops.norm_ffn_fwd(h2, norm_w, eps, packed, f)
         ctx.save_for_backward(h2, norm_w, rstd, yb, packed)
         ctx.wparams = (w1, w3, w2)
         ctx.nparam = norm_w
-        ctx.meta = (f, d, h.shape, w1.shape, w2.shape)
+        ctx.meta = (f, d, h.shape)
         return y.view(*h.shape[:-1], d)
 
     @staticmethod
     def backward(ctx, dy: Tensor):
         h2, norm_w, rstd, yb, packed = ctx.saved_tensors
-        f, d, hshape, w1shape, w2shape = ctx.meta
-        m = h2.shape[0]
-        dy2 = dy.reshape(m, d)
-        if not dy2.is_contiguous():
-            dy2 = dy2.contiguous()
-        if _NORM_BWD_FUSED:
-            dh, dag, u, dyb, dnw = ops.ffn_bwd_norm(yb, dy2, packed, f, h2, norm_w, rstd, defer=ops.defer_ok((ctx.nparam,)))
-        else:
-            dn, dag, u, dyb = ops.ffn_bwd(yb, dy2, packed, f, True)       # dn: gradient w.r.t. the normalised rows (FFN input + residual)
-            dh, dnw = ops.rmsnorm_bwd(h2, norm_w, dn, rstd, defer=ops.defer_ok((ctx.nparam,)))
-        dw2 = _dw_gemm(dyb, u, d, f, m, d, f, 1, ctx.wparams[2:]).view(w2shape)
-        dwcat = _dw_gemm(dag, yb, 2 * f, d, m, 2 * f, d, 1, ctx.wparams[:2])
-        return dh.view(hshape), dnw, None, dwcat[:f].view(w1shape), dwcat[f:].view(w1shape), dw2
+        f, d, hshape = ctx.meta
+        dh, dnw, dw1, dw3, dw2 = _norm_ffn_bwd(yb, _rows2d(dy, d, h2.shape[0]), packed, f, h2, norm_w, rstd, ctx.nparam, ctx.wparams)
+        return dh.view(hshape), dnw, None, dw1, dw3, dw2
 
 
 class NormQKVFn(Function):
@@ -867,15 +910,11 @@ class NormQKVFn(Function):
         ntot = sum(w.shape[0] for w in ws)
         xc = x if x.is_contiguous() else x.contiguous()
         x2 = xc.reshape(-1, 256)
-        m = x2.shape[0]
-        wcat32 = ws[0].new_empty(0).set_(ws[0].untyped_storage(), ws[0].storage_offset(), (ntot, 256), (256, 1))
-        packed = _QKV_PACK_CACHE.get((wcat32.data_ptr(), tuple(wcat32.shape)))
-        if packed is None:
-            packed = ops.qkv_pack_multi([wcat32], True)[0]
+        wcat32 = fused_view(ws)
+        packed = _IMAGES.qkv(wcat32)
         freqs, b, s, h, hkv, scale = image_spec
         img, yb, rstd = ops.norm_qkv_image(x2, norm_w, eps, packed, b, s, h, hkv, freqs, scale)
-        out = torch.empty(1, dtype=torch.float32, device=x.device).expand(m, ntot)   # shape only: no [m, ntot] buffer
-        out._gaot_qkv_image = img
+        out = _placeholder((x2.shape[0], ntot), x.device, _gaot_qkv_image=img)
         ctx.save_for_backward(x2, norm_w, rstd, yb, _wb(wcat32, 1), packed)
         ctx.wparams, ctx.nparam = tuple(weights), norm_w
         ctx.meta = (x.shape, [w.shape for w in weights], ntot)
@@ -886,23 +925,12 @@ class NormQKVFn(Function):
     @staticmethod
     def backward(ctx, dqkv: Tensor, dres: Optional[Tensor] = None, dtap: Optional[Tensor] = None):
         x2, norm_w, rstd, yb, wcat, packed = ctx.saved_tensors
-        xshape, wshapes, ntot = ctx.meta
-        m = x2.shape[0]
+        xshape, wshapes, _ntot = ctx.meta
         d = dqkv if dqkv.is_contiguous() else dqkv.contiguous()
-        dwcat = _dw_gemm(d, yb, ntot, 256, m, ntot, 256, 1, ctx.wparams)
         dres2 = None if dres is None else dres.reshape(x2.shape)
         dtap2 = None if dtap is None else dtap.reshape(x2.shape)
-        if _NORM_BWD_FUSED:
-            # d(norm x) = dqkv Wqkv with attn_norm's backward (and the residual's / the skip's addends) in its epilogue: one launch
-            dx, dnw = ops.qkv_bwd_norm(d, packed, x2, norm_w, rstd, dres2, dtap2, defer=ops.defer_ok((ctx.nparam,)))
-        else:
-            dn = ops.gemm(d, wcat, m, 256, ntot, ntot, 256, False, False, precision=1)
-            dx, dnw = ops.rmsnorm_bwd(x2, norm_w, dn, rstd, dres2, defer=ops.defer_ok((ctx.nparam,)), dx_add2=dtap2)
-        dws, col = [], 0
-        for shp in wshapes:
-            dws.append(dwcat[col:col + shp[0]].view(shp))
-            col += shp[0]
-        return (dx.view(xshape), dnw, None, None, None, *dws)
+        dwcat, dx, dnw, _, _ = _norm_qkv_bwd(d, yb, packed, wcat, x2, norm_w, rstd, dres2, dtap2, ctx.nparam, ctx.wparams)
+        return (dx.view(xshape), dnw, None, None, None, *_split_rows(dwcat, wshapes))
 
 
 class CatNormQKVFn(Function):
@@ -921,23 +949,14 @@ class CatNormQKVFn(Function):
         ws = [_w2d(w) for w in weights]
         ntot = sum(w.shape[0] for w in ws)
         ctx.same = _same_view(x, skip)
-        xa = x.reshape(-1, 256)
-        xb = skip.reshape(-1, 256)
-        xa = xa if xa.is_contiguous() else xa.contiguous()
-        xb = xb if xb.is_contiguous() else xb.contiguous()
-        m = xa.shape[0]
+        xa, xb = _rows2d(x, 256), _rows2d(skip, 256)
         wsk = _w2d(wskip)
-        wcat32 = ws[0].new_empty(0).set_(ws[0].untyped_storage(), ws[0].storage_offset(), (ntot, 256), (256, 1))
-        packed = _QKV_PACK_CACHE.get((wcat32.data_ptr(), tuple(wcat32.shape)))
-        if packed is None:
-            packed = ops.qkv_pack_multi([wcat32], True)[0]
-        spk = _SKIP_PACK_CACHE.get((wsk.data_ptr(), tuple(wsk.shape)))
-        if spk is None:
-            spk = ops.skip_pack_multi([wsk])[0]
+        wcat32 = fused_view(ws)
+        packed = _IMAGES.qkv(wcat32)
+        spk = _IMAGES.skip(wsk)
         freqs, b, s, h, hkv, scale = image_spec
         img, xo, yb, rstd = ops.cat_norm_qkv_image(xa, xb, spk, bskip, norm_w, eps, packed, b, s, h, hkv, freqs, scale)
-        out = torch.empty(1, dtype=torch.float32, device=x.device).expand(m, ntot)   # shape only
-        out._gaot_qkv_image = img
+        out = _placeholder((xa.shape[0], ntot), x.device, _gaot_qkv_image=img)
         ctx.save_for_backward(xa, xb, xo, norm_w, rstd, yb, _wb(wcat32, 1), packed, _wb(wsk, 1), spk)
         ctx.wparams, ctx.nparam, ctx.sparams = tuple(weights), norm_w, (wskip, bskip)
         ctx.meta = (x.shape, skip.shape, [w.shape for w in weights], ntot, wskip.shape)
@@ -947,20 +966,13 @@ class CatNormQKVFn(Function):
     @staticmethod
     def backward(ctx, dqkv: Tensor, dres: Optional[Tensor] = None):
         xa, xb, xo, norm_w, rstd, yb, wcat, packed, wskb, spk = ctx.saved_tensors
-        xshape, sshape, wshapes, ntot, wsshape = ctx.meta
+        xshape, sshape, wshapes, _ntot, wsshape = ctx.meta
         m = xa.shape[0]
         d = dqkv if dqkv.is_contiguous() else dqkv.contiguous()
-        dwcat = _dw_gemm(d, yb, ntot, 256, m, ntot, 256, 1, ctx.wparams)
         dres2 = None if dres is None else dres.reshape(m, 256)
-        dxa = dxb = None
         fused_dx = _NORM_BWD_FUSED and _CAT_BWD_DX and ctx.needs_input_grad[0] and (ctx.same or ctx.needs_input_grad[1])
-        if fused_dx:    # the projection's two input gradients leave the same launch (k_qkv_bwd_norm<CATB>)
-            dxo, dxa, dxb, dnw = ops.qkv_bwd_norm_cat(d, packed, xo, norm_w, rstd, dres2, spk, ctx.same, defer=ops.defer_ok((ctx.nparam,)))
-        elif _NORM_BWD_FUSED:
-            dxo, dnw = ops.qkv_bwd_norm(d, packed, xo, norm_w, rstd, dres2, None, defer=ops.defer_ok((ctx.nparam,)))
-        else:
-            dn = ops.gemm(d, wcat, m, 256, ntot, ntot, 256, False, False, precision=1)
-            dxo, dnw = ops.rmsnorm_bwd(xo, norm_w, dn, rstd, dres2, defer=ops.defer_ok((ctx.nparam,)))
+        dwcat, dxo, dnw, dxa, dxb = _norm_qkv_bwd(d, yb, packed, wcat, xo, norm_w, rstd, dres2, None, ctx.nparam, ctx.wparams,
+                                                  cat=(spk, ctx.same) if fused_dx else None)
         # the skip projection's backward (CatLinearFn.backward on [xa | xb] W^T + b)
         n, k = 256, 512
         wsk, bsk = ctx.sparams
@@ -974,11 +986,8 @@ class CatNormQKVFn(Function):
         ops.gemm(dxo, xa, n, 256, m, n, 256, True, False, out=dws, ldc=k, precision=1)
         ops.gemm(dxo, xb, n, 256, m, n, 256, True, False, out=dws[:, 256:], ldc=k, precision=1)
         dbs = ops.colsum(dxo, m, n, n) if (bsk is not None and ctx.needs_input_grad[3]) else None
-        dwl, col = [], 0
-        for shp in wshapes:
-            dwl.append(dwcat[col:col + shp[0]].view(shp))
-            col += shp[0]
-        return (None if dxa is None else dxa.view(xshape), None if dxb is None else dxb.view(sshape), dws.view(wsshape), dbs, dnw, None, None, *dwl)
+        return (None if dxa is None else dxa.view(xshape), None if dxb is None else dxb.view(sshape), dws.view(wsshape), dbs, dnw, None, None,
+                *_split_rows(dwcat, wshapes))
 
 
 class BlockTailFn(Function):
@@ -1007,42 +1016,31 @@ class BlockTailFn(Function):
         o2 = o if o.is_contiguous() else o.contiguous()
         x2 = x if x.is_contiguous() else x.contiguous()
         wo2 = _w2d(wo)
-        wcat32 = w1.new_empty(0).set_(w1.untyped_storage(), w1.storage_offset(), (2 * f, d), (d, 1))
-        key = (wcat32.data_ptr(), tuple(wcat32.shape))
-        packed, _has_bwd = _FFN_PACK_CACHE.get(key, (None, False))
-        if packed is None or _WO_PACKED.get(key) != wo2.data_ptr():
-            packed = ops.block_pack_multi([(wcat32, _w2d(w2), wo2)], f)[0]
+        packed = _IMAGES.block(fused_view((w1, w3)), _w2d(w2), wo2, f)
         y, h, yb, rstd = ops.block_tail_fwd(o2, x2, norm_w, eps, packed, f)
         ctx.save_for_backward(o2, _wb(wo2, 1), h, norm_w, rstd, yb, packed)
         ctx.wparams = (w1, w3, w2)
         ctx.nparam, ctx.oparam = norm_w, wo
-        ctx.meta = (f, d, w1.shape, w2.shape, wo.shape)
+        ctx.meta = (f, d, wo.shape)
         return y
 
     @staticmethod
     def backward(ctx, dy: Tensor):
         o2, wob, h, norm_w, rstd, yb, packed = ctx.saved_tensors
-        f, d, w1shape, w2shape, woshape = ctx.meta
+        f, d, woshape = ctx.meta
         m = h.shape[0]
         dy2 = dy if dy.is_contiguous() else dy.contiguous()
-        if _NORM_BWD_FUSED:
-            dh, dag, u, dyb, dnw = ops.ffn_bwd_norm(yb, dy2, packed, f, h, norm_w, rstd, defer=ops.defer_ok((ctx.nparam,)))
-        else:
-            dn, dag, u, dyb = ops.ffn_bwd(yb, dy2, packed, f, True)
-            dh, dnw = ops.rmsnorm_bwd(h, norm_w, dn, rstd, defer=ops.defer_ok((ctx.nparam,)))
-        dw2 = _dw_gemm(dyb, u, d, f, m, d, f, 1, ctx.wparams[2:]).view(w2shape)
-        dwcat = _dw_gemm(dag, yb, 2 * f, d, m, 2 * f, d, 1, ctx.wparams[:2])
+        dh, dnw, dw1, dw3, dw2 = _norm_ffn_bwd(yb, dy2, packed, f, h, norm_w, rstd, ctx.nparam, ctx.wparams)
         d_o = None
         if ctx.needs_input_grad[0]:
             if ctx.attn_dims is not None:
                 b_, s_, h_, hkv_ = ctx.attn_dims
                 img, delta = ops.oproj_bwd_image(dh, o2, packed, f, b_, s_, h_, hkv_)
-                d_o = torch.empty(1, dtype=torch.float32, device=dh.device).expand(m, d)      # shape only
-                d_o._gaot_do_image = (img, delta)
+                d_o = _placeholder((m, d), dh.device, _gaot_do_image=(img, delta))
             else:
                 d_o = ops.gemm(dh, wob, m, d, d, d, d, False, False, precision=1)
         dwo = _dw_gemm(dh, o2, d, d, m, d, d, 1, (ctx.oparam,)).view(woshape)
-        return d_o, (dh if ctx.needs_input_grad[1] else None), dwo, dnw, None, dwcat[:f].view(w1shape), dwcat[f:].view(w1shape), dw2, None
+        return d_o, (dh if ctx.needs_input_grad[1] else None), dwo, dnw, None, dw1, dw3, dw2, None
 
 
 class Mlp2Fn(Function):
@@ -1060,9 +1058,7 @@ class Mlp2Fn(Function):
 
     @staticmethod
     def forward(ctx, x: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Optional[Tensor]):
-        x2 = x.reshape(-1, x.shape[-1])
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
+        x2 = _rows2d(x, x.shape[-1])
         w1c, w2c = _w2d(w1), _w2d(w2)
         out = ops.mlp2_forward(x2, w1c, b1, w2c, b2)
         ctx.save_for_backward(x2, w1c, b1, w2c)
@@ -1073,9 +1069,7 @@ class Mlp2Fn(Function):
     def backward(ctx, dout: Tensor):
         x2, w1c, b1, w2c = ctx.saved_tensors
         xshape, w1shape, w2shape, has_b2 = ctx.meta
-        d = dout.reshape(x2.shape[0], w2c.shape[0])
-        if not d.is_contiguous():
-            d = d.contiguous()
+        d = _rows2d(dout, w2c.shape[0], x2.shape[0])
         dx, dw1, db1, dw2 = ops.mlp2_backward(x2, w1c, b1, w2c, d)
         db2 = ops.colsum(d, d.shape[0], d.shape[1], d.shape[1]) if has_b2 else None
         return dx.view(xshape), dw1.view(w1shape), db1, dw2.view(w2shape), db2
@@ -1183,22 +1177,19 @@ class MultiLinearFn(Function):
         right shape that carries the image (``_gaot_qkv_image``): the fp32 q|k|v never exists in HBM."""
         ws = [_w2d(w) for w in weights]
         k = ws[0].shape[1]
-        x2 = x.reshape(-1, k)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
+        x2 = _rows2d(x, k)
         m = x2.shape[0]
         ntot = sum(w.shape[0] for w in ws)
         ctx.fused = len(ws) > 1 and _adjacent(ws) and all(ctx.needs_input_grad[3 + i] for i in range(len(ws)))
         ctx.wparams = tuple(weights)
         if ctx.fused:   # the weights are slices of one buffer (colocate): one [ntot, k] matrix, one GEMM
-            wcat = _wb(ws[0].new_empty(0).set_(ws[0].untyped_storage(), ws[0].storage_offset(), (ntot, k), (k, 1)), precision)
+            wcat = _wb(fused_view(ws), precision)
             xb = bf16_copy_of(x, (m, k)) if wcat.dtype == torch.bfloat16 else None
             xa = xb if xb is not None else x2      # bf16 image written by the producing RMSNorm: half the A traffic
             if image_spec is not None and xb is not None and k == 256 and ntot % 64 == 0:
                 freqs, b, s, h, hkv, scale = image_spec
                 img = ops.qkv_image(xb, wcat, m, b, s, h, hkv, freqs, scale)
-                out = torch.empty(1, dtype=torch.float32, device=x.device).expand(m, ntot)   # shape only: no [m, ntot] buffer
-                out._gaot_qkv_image = img
+                out = _placeholder((m, ntot), x.device, _gaot_qkv_image=img)
                 ctx.save_for_backward(xa, wcat)
                 ctx.precision, ctx.xshape, ctx.wshapes = precision, x.shape, [w.shape for w in weights]
                 return out
@@ -1230,11 +1221,7 @@ class MultiLinearFn(Function):
             if ctx.needs_input_grad[0]:
                 dx = ops.gemm(d, wcat, m, k, ntot, ntot, k, False, False, precision=ctx.precision)
             dwcat = _dw_gemm(d, x2, ntot, k, m, ntot, k, ctx.precision, ctx.wparams)
-            for shp in ctx.wshapes:
-                n = shp[0]
-                dws.append(dwcat[col:col + n].view(shp))
-                col += n
-            return (dx.view(ctx.xshape) if dx is not None else None, None, None, *dws)
+            return (dx.view(ctx.xshape) if dx is not None else None, None, None, *_split_rows(dwcat, ctx.wshapes))
         for i, w in enumerate(ws):
             n = w.shape[0]
             blk = d[:, col:]

@@ -42,8 +42,30 @@ def _req(t: Tensor, dtype, name: str) -> Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _req_rows(t: Tensor, dtype, cols: int, name: str, dense: bool = True, rows: Optional[int] = None) -> int:
+    """a row operand of the fused kernels: a 2-D ``dtype`` matrix [rows, cols], contiguous (``dense``) or with unit column stride
+    and any row stride; -> its number of rows"""
+    if t.dtype != dtype or t.dim() != 2 or t.shape[1] != cols or (rows is not None and t.shape[0] != rows) \
+            or not (t.is_contiguous() if dense else t.stride(1) == 1):
+        raise GaotError(f"{name}: {'contiguous ' if dense else ''}{dtype} [{'rows' if rows is None else rows}, {cols}] expected, "
+                        f"got {t.dtype} {tuple(t.shape)} with strides {tuple(t.stride())}")
+    return int(t.shape[0])
+
+
 def _ws(nbytes: int, device) -> Tensor:
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
+
+
+def _slices_of_one_buffer(n: int, sizes, dtype, device, align: int = 1) -> List[Tensor]:
+    """n flat tensors that are slices of ONE buffer (the outputs of a multi-tensor launch): ``sizes`` elements each (one int for
+    all, or one per slice), every slice starting at a multiple of ``align`` elements"""
+    sizes = [int(sizes)] * n if isinstance(sizes, int) else [int(sz) for sz in sizes]
+    offs, total = [], 0
+    for sz in sizes:
+        offs.append(total)
+        total += (sz + align - 1) // align * align
+    buf = torch.empty(total, dtype=dtype, device=device)
+    return [buf[o:o + sz] for o, sz in zip(offs, sizes)]
 
 
 # Optional per-call device timing (bench.py): HIP events recorded on the stream the kernels are launched on.
@@ -581,20 +603,30 @@ def attn_dropout_mask(seed: Tensor, p: float, b: int, h: int, s: int) -> Tensor:
     return keep
 
 
+def _qkv_args(qkv: Tensor, h: int, hkv: int, head_dim: int, dqkv: Optional[Tensor] = None):
+    """the q | k | v column blocks of a fused fp32 [rows, (h + 2 hkv) * head_dim] projection as the attention entry points take them:
+    -> ((q, k, v), (ldq, ldk, ldv, ldo)); with the gradient buffer ``dqkv`` of the same layout
+    -> ((q, k, v), (dq, dk, dv), (ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv))"""
+    ld = qkv.shape[1]
+    offs = (0, 4 * h * head_dim, 4 * (h + hkv) * head_dim)      # bytes
+    q3 = tuple(C.c_void_p(qkv.data_ptr() + o) for o in offs)
+    if dqkv is None:
+        return q3, (ld, ld, ld, h * head_dim)
+    return q3, tuple(C.c_void_p(dqkv.data_ptr() + o) for o in offs), (ld, ld, ld, h * head_dim, h * head_dim, ld, ld, ld)
+
+
 def attn_fwd(qkv: Tensor, b: int, s: int, h: int, hkv: int, scale: float, dropout_p: float = 0.0,
              seed: Optional[Tensor] = None, head0: int = 0, heads_total: int = 0):
     """qkv: [B*S, (h + 2*hkv)*32] fused projection output (q | k | v column blocks).  ``head0`` / ``heads_total``: the h heads
     are heads head0 .. of heads_total (a rank's slice): the dropout mask is keyed by the global head index"""
     lib = _lib.load()
-    ld = qkv.shape[1]
     dev = qkv.device
     o = torch.empty(b * s, h * 32, dtype=torch.float32, device=dev)
     lse = torch.empty(b, h, s, dtype=torch.float32, device=dev)
-    base = qkv.data_ptr()
-    q, k, v = C.c_void_p(base), C.c_void_p(base + 4 * h * 32), C.c_void_p(base + 4 * (h + hkv) * 32)
+    q3, lds = _qkv_args(qkv, h, hkv, 32)
     with _timed("attn_fwd"):
         dp, sp = _drop_args(dropout_p, seed)
-        check(lib.gaot_attn_fwd(q, k, v, _ptr(o), _ptr(lse), ld, ld, ld, h * 32, b, s, h, hkv, 32, float(scale), dp, sp,
+        check(lib.gaot_attn_fwd(*q3, _ptr(o), _ptr(lse), *lds, b, s, h, hkv, 32, float(scale), dp, sp,
                                 int(head0), int(heads_total), _PRECISION["mode"], _stream()), "gaot_attn_fwd")
     return o, lse
 
@@ -603,40 +635,28 @@ def attn_bwd(qkv: Tensor, o: Tensor, d_o: Tensor, lse: Tensor, b: int, s: int, h
              dropout_p: float = 0.0, seed: Optional[Tensor] = None, head0: int = 0, heads_total: int = 0) -> Tensor:
     lib = _lib.load()
     dp, sp = _drop_args(dropout_p, seed)
-    ld = qkv.shape[1]
     dev = qkv.device
     dqkv = torch.empty_like(qkv)
     delta = torch.empty(b, h, s, dtype=torch.float32, device=dev)
-    base, gbase = qkv.data_ptr(), dqkv.data_ptr()
-    offk, offv = 4 * h * 32, 4 * (h + hkv) * 32
+    q3, g3, lds = _qkv_args(qkv, h, hkv, 32, dqkv)
     # dK, dV and dQ from one pass (5 S^2 d products instead of 7); its fp32 dQ slab partials live in a buffer of this call -- b * h *
     # ceil(s / 256) * s * 128 bytes (1.07 GB at S = 16 384, 8 heads; quadratic in S): past the cap the two-pass kernels run
     nb = int(lib.gaot_attn_bwd_fused_f32_scratch_bytes(b, s, h)) if _ATTN_F32_FUSED else 0
     # (a long sequence with few kv heads per launch -- one rank's share of a sharded step -- leaves the one-pass kernel fewer than one
     # workgroup per CU, 256 keys each; the two-pass kernels split twice as fine)
     starved = s >= 4096 and b * hkv * ((s + 255) // 256) < 256
-    if _ATTN_F32_FUSED and nb <= _ATTN_F32_FUSED_CAP and not starved:
-        scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
-        with _timed("attn_bwd_delta"):
-            check(lib.gaot_attn_bwd(C.c_void_p(base), C.c_void_p(base + offk), C.c_void_p(base + offv), _ptr(o),
-                                    _ptr(d_o), _ptr(lse), _ptr(delta), C.c_void_p(gbase), C.c_void_p(gbase + offk),
-                                    C.c_void_p(gbase + offv), ld, ld, ld, h * 32, h * 32, ld, ld, ld, b, s, h, hkv, 32,
-                                    float(scale), dp, sp, int(head0), int(heads_total), _PRECISION["mode"], 1, _stream()),
-                  "gaot_attn_bwd")
-        with _timed("attn_bwd_fused_f32"):
-            check(lib.gaot_attn_bwd_fused_f32(C.c_void_p(base), C.c_void_p(base + offk), C.c_void_p(base + offv), _ptr(o),
-                                              _ptr(d_o), _ptr(lse), _ptr(delta), C.c_void_p(gbase), C.c_void_p(gbase + offk),
-                                              C.c_void_p(gbase + offv), ld, ld, ld, h * 32, h * 32, ld, ld, ld, b, s, h, hkv, 32,
-                                              float(scale), dp, sp, int(head0), int(heads_total), 0, _ptr(scratch), nb, _stream()),
-                  "gaot_attn_bwd_fused_f32")
-        return dqkv
-    for name, mask in (("attn_bwd_delta", 1), ("attn_bwd_dkv", 2), ("attn_bwd_dq", 4)):
+    one_pass = _ATTN_F32_FUSED and nb <= _ATTN_F32_FUSED_CAP and not starved
+    scratch = torch.empty(nb, dtype=torch.uint8, device=dev) if one_pass else None
+    for name, mask in (("attn_bwd_delta", 1),) if one_pass else (("attn_bwd_delta", 1), ("attn_bwd_dkv", 2), ("attn_bwd_dq", 4)):
         with _timed(name):
-            check(lib.gaot_attn_bwd(C.c_void_p(base), C.c_void_p(base + offk), C.c_void_p(base + offv), _ptr(o),
-                                    _ptr(d_o), _ptr(lse), _ptr(delta), C.c_void_p(gbase), C.c_void_p(gbase + offk),
-                                    C.c_void_p(gbase + offv), ld, ld, ld, h * 32, h * 32, ld, ld, ld, b, s, h, hkv, 32,
+            check(lib.gaot_attn_bwd(*q3, _ptr(o), _ptr(d_o), _ptr(lse), _ptr(delta), *g3, *lds, b, s, h, hkv, 32,
                                     float(scale), dp, sp, int(head0), int(heads_total), _PRECISION["mode"], mask, _stream()),
                   "gaot_attn_bwd")
+    if one_pass:
+        with _timed("attn_bwd_fused_f32"):
+            check(lib.gaot_attn_bwd_fused_f32(*q3, _ptr(o), _ptr(d_o), _ptr(lse), _ptr(delta), *g3, *lds, b, s, h, hkv, 32,
+                                              float(scale), dp, sp, int(head0), int(heads_total), 0, _ptr(scratch), nb, _stream()),
+                  "gaot_attn_bwd_fused_f32")
     return dqkv
 
 
@@ -651,15 +671,13 @@ def attn_hd_fwd(qkv: Tensor, b: int, s: int, h: int, hkv: int, head_dim: int, sc
         raise GaotError(f"attn_hd_fwd: head_dim {head_dim} unsupported (only 64 and 128)")
     if qkv.dim() != 2 or tuple(qkv.shape) != (b * s, (h + 2 * hkv) * head_dim):
         raise GaotError(f"attn_hd_fwd: qkv must be [{b * s}, {(h + 2 * hkv) * head_dim}], got {tuple(qkv.shape)}")
-    ld = qkv.shape[1]
     dev = qkv.device
     o = torch.empty(b * s, h * head_dim, dtype=torch.float32, device=dev)
     lse = torch.empty(b, h, s, dtype=torch.float32, device=dev)
-    base = qkv.data_ptr()
-    q, k, v = C.c_void_p(base), C.c_void_p(base + 4 * h * head_dim), C.c_void_p(base + 4 * (h + hkv) * head_dim)
+    q3, lds = _qkv_args(qkv, h, hkv, head_dim)
     with _timed("attn_hd_fwd"):
         dp, sp = _drop_args(dropout_p, seed)
-        check(lib.gaot_attn_hd_fwd(q, k, v, _ptr(o), _ptr(lse), ld, ld, ld, h * head_dim, b, s, h, hkv, head_dim, float(scale),
+        check(lib.gaot_attn_hd_fwd(*q3, _ptr(o), _ptr(lse), *lds, b, s, h, hkv, head_dim, float(scale),
                                    dp, sp, int(head0), int(heads_total), _stream()), "gaot_attn_hd_fwd")
     return o, lse
 
@@ -679,17 +697,12 @@ def attn_hd_bwd(qkv: Tensor, o: Tensor, d_o: Tensor, lse: Tensor, b: int, s: int
     if tuple(qkv.shape) != (b * s, (h + 2 * hkv) * head_dim) or tuple(o.shape) != (b * s, h * head_dim) or o.shape != d_o.shape \
             or lse.numel() != b * h * s:
         raise GaotError("attn_hd_bwd: qkv / o / d_o / lse do not match (b, s, h, hkv, head_dim)")
-    ld = qkv.shape[1]
-    dev = qkv.device
     dqkv = torch.empty_like(qkv)
-    delta = torch.empty(b, h, s, dtype=torch.float32, device=dev)
-    base, gbase = qkv.data_ptr(), dqkv.data_ptr()
-    offk, offv = 4 * h * head_dim, 4 * (h + hkv) * head_dim
+    delta = torch.empty(b, h, s, dtype=torch.float32, device=qkv.device)
+    q3, g3, lds = _qkv_args(qkv, h, hkv, head_dim, dqkv)
     for name, mask in (("attn_hd_bwd_delta", 1), ("attn_hd_bwd_dkv", 2), ("attn_hd_bwd_dq", 4)):
         with _timed(name):
-            check(lib.gaot_attn_hd_bwd(C.c_void_p(base), C.c_void_p(base + offk), C.c_void_p(base + offv), _ptr(o),
-                                       _ptr(d_o), _ptr(lse), _ptr(delta), C.c_void_p(gbase), C.c_void_p(gbase + offk),
-                                       C.c_void_p(gbase + offv), ld, ld, ld, h * head_dim, h * head_dim, ld, ld, ld, b, s, h, hkv,
+            check(lib.gaot_attn_hd_bwd(*q3, _ptr(o), _ptr(d_o), _ptr(lse), _ptr(delta), *g3, *lds, b, s, h, hkv,
                                        head_dim, float(scale), dp, sp, int(head0), int(heads_total), mask, _stream()),
                   "gaot_attn_hd_bwd")
     return dqkv
@@ -862,12 +875,8 @@ def cast_bf16_multi(xs: Sequence[Tensor]) -> List[Tensor]:
     lib = _lib.load()
     if not xs:
         return []
-    offs, total = [], 0
-    for x in xs:
-        offs.append(total)
-        total += (x.numel() + 7) // 8 * 8
-    buf = torch.empty(total, dtype=torch.bfloat16, device=xs[0].device)
-    outs = [buf[o:o + x.numel()].view(x.shape) for o, x in zip(offs, xs)]
+    flat = _slices_of_one_buffer(len(xs), [x.numel() for x in xs], torch.bfloat16, xs[0].device, align=8)
+    outs = [o.view(x.shape) for o, x in zip(flat, xs)]
     entries = (_CastEntry * len(xs))()
     for i, (x, o) in enumerate(zip(xs, outs)):
         x = _req(x, torch.float32, "x")
@@ -881,12 +890,8 @@ def cast_bf16_transpose_multi(xs: Sequence[Tensor]) -> List[Tensor]:
     lib = _lib.load()
     if not xs:
         return []
-    offs, total = [], 0
-    for x in xs:
-        offs.append(total)
-        total += (x.numel() + 7) // 8 * 8
-    buf = torch.empty(total, dtype=torch.bfloat16, device=xs[0].device)
-    outs = [buf[o:o + x.numel()].view(x.shape[1], x.shape[0]) for o, x in zip(offs, xs)]
+    flat = _slices_of_one_buffer(len(xs), [x.numel() for x in xs], torch.bfloat16, xs[0].device, align=8)
+    outs = [o.view(x.shape[1], x.shape[0]) for o, x in zip(flat, xs)]
     entries = (_CastEntry * len(xs))()
     rows, cols = (C.c_int * len(xs))(), (C.c_int * len(xs))()
     for i, (x, o) in enumerate(zip(xs, outs)):
@@ -926,10 +931,8 @@ def ffn_pack(w13: Tensor, w2: Tensor, f: int, with_backward: bool) -> Tensor:
     """the fp32 co-located [w1; w3] ([2F, 256]) and w2 ([256, F]) as the fragment-ordered bf16 images the fused FFN kernels stream
     (include/gaot3d_hip.h: gaot_ffn_pack); one uint8 buffer"""
     lib = _lib.load()
-    if w13.dtype != torch.float32 or w2.dtype != torch.float32 or not (w13.is_contiguous() and w2.is_contiguous()):
-        raise GaotError("ffn_pack: contiguous fp32 weights expected")
-    if tuple(w13.shape) != (2 * f, 256) or tuple(w2.shape) != (256, f):
-        raise GaotError(f"ffn_pack: expected [2F, 256] and [256, F] with F = {f}, got {tuple(w13.shape)} and {tuple(w2.shape)}")
+    _req_rows(w13, torch.float32, 256, "ffn_pack: [w1; w3]", rows=2 * f)
+    _req_rows(w2, torch.float32, f, "ffn_pack: w2", rows=256)
     packed = torch.empty(lib.gaot_ffn_packed_bytes(int(f), int(with_backward)), dtype=torch.uint8, device=w13.device)
     check(lib.gaot_ffn_pack(_ptr(w13), _ptr(w2), int(f), _ptr(packed), int(with_backward), _stream()), "gaot_ffn_pack")
     return packed
@@ -945,14 +948,12 @@ def ffn_pack_multi(pairs, f: int, with_backward: bool) -> List[Tensor]:
     pairs = list(pairs)
     if not pairs:
         return []
-    nb = int(lib.gaot_ffn_packed_bytes(int(f), int(with_backward)))
-    buf = torch.empty(len(pairs) * nb, dtype=torch.uint8, device=pairs[0][0].device)
-    outs = [buf[i * nb:(i + 1) * nb] for i in range(len(pairs))]
+    for w13, w2 in pairs:
+        _req_rows(w13, torch.float32, 256, "ffn_pack_multi: [w1; w3]", rows=2 * f)
+        _req_rows(w2, torch.float32, f, "ffn_pack_multi: w2", rows=256)
+    outs = _slices_of_one_buffer(len(pairs), int(lib.gaot_ffn_packed_bytes(int(f), int(with_backward))), torch.uint8, pairs[0][0].device)
     items = (_FfnPackItem * len(pairs))()
     for i, ((w13, w2), o) in enumerate(zip(pairs, outs)):
-        if w13.dtype != torch.float32 or w2.dtype != torch.float32 or not (w13.is_contiguous() and w2.is_contiguous()) \
-                or tuple(w13.shape) != (2 * f, 256) or tuple(w2.shape) != (256, f):
-            raise GaotError("ffn_pack_multi: contiguous fp32 [2F, 256] / [256, F] weights expected")
         items[i] = _FfnPackItem(w13.data_ptr(), w2.data_ptr(), o.data_ptr())
     check(lib.gaot_ffn_pack_multi(items, len(pairs), int(f), int(with_backward), _stream()), "gaot_ffn_pack_multi")
     return outs
@@ -962,11 +963,9 @@ def ffn_fwd(xb: Tensor, packed: Tensor, f: int, residual: Optional[Tensor] = Non
     """y = w2(silu(w1 x) * w3 x) + residual in one launch (include/gaot3d_hip.h: gaot_ffn_fwd): x [rows, 256] bf16, ``packed`` from
     ffn_pack -> (y fp32 [rows, 256], a | g bf16 [rows, 2F] or None, u bf16 [rows, F] or None)"""
     lib = _lib.load()
-    if xb.dtype != torch.bfloat16 or not xb.is_contiguous() or xb.shape[1] != 256:
-        raise GaotError("ffn_fwd: contiguous bf16 [rows, 256] input expected")
-    rows = xb.shape[0]
-    if residual is not None and (residual.dtype != torch.float32 or residual.stride(-1) != 1 or tuple(residual.shape) != (rows, 256)):
-        raise GaotError("ffn_fwd: fp32 [rows, 256] residual expected")
+    rows = _req_rows(xb, torch.bfloat16, 256, "ffn_fwd: input")
+    if residual is not None:
+        _req_rows(residual, torch.float32, 256, "ffn_fwd: residual", dense=False, rows=rows)
     y = torch.empty(rows, 256, dtype=torch.float32, device=xb.device)
     ag = torch.empty(rows, 2 * f, dtype=torch.bfloat16, device=xb.device) if save else None
     u = torch.empty(rows, f, dtype=torch.bfloat16, device=xb.device) if save else None
@@ -987,14 +986,13 @@ def block_pack_multi(triples, f: int) -> List[Tensor]:
     triples = list(triples)
     if not triples:
         return []
-    nb = int(lib.gaot_block_packed_bytes(int(f)))
-    buf = torch.empty(len(triples) * nb, dtype=torch.uint8, device=triples[0][0].device)
-    outs = [buf[i * nb:(i + 1) * nb] for i in range(len(triples))]
+    for w13, w2, wo in triples:
+        _req_rows(w13, torch.float32, 256, "block_pack_multi: [w1; w3]", rows=2 * f)
+        _req_rows(w2, torch.float32, f, "block_pack_multi: w2", rows=256)
+        _req_rows(wo, torch.float32, 256, "block_pack_multi: o_proj", rows=256)
+    outs = _slices_of_one_buffer(len(triples), int(lib.gaot_block_packed_bytes(int(f))), torch.uint8, triples[0][0].device)
     items = (_BlockPackItem * len(triples))()
     for i, ((w13, w2, wo), o) in enumerate(zip(triples, outs)):
-        for t, shp in ((w13, (2 * f, 256)), (w2, (256, f)), (wo, (256, 256))):
-            if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shp:
-                raise GaotError("block_pack_multi: contiguous fp32 [2F, 256] / [256, F] / [256, 256] weights expected")
         items[i] = _BlockPackItem(w13.data_ptr(), w2.data_ptr(), wo.data_ptr(), o.data_ptr())
     check(lib.gaot_block_pack_multi(items, len(triples), int(f), _stream()), "gaot_block_pack_multi")
     return outs
@@ -1006,8 +1004,7 @@ def block_tail_fwd(attn_out: Tensor, x: Tensor, norm_weight: Tensor, eps: float,
     lib = _lib.load()
     rows = attn_out.shape[0]
     for t, nm in ((attn_out, "attn_out"), (x, "x")):
-        if t.dtype != torch.float32 or t.dim() != 2 or tuple(t.shape) != (rows, 256) or t.stride(1) != 1:
-            raise GaotError(f"block_tail_fwd: fp32 [rows, 256] {nm} expected")
+        _req_rows(t, torch.float32, 256, f"block_tail_fwd: {nm}", dense=False, rows=rows)
     nw = _req(norm_weight, torch.float32, "norm_weight")
     dev = attn_out.device
     y = torch.empty(rows, 256, dtype=torch.float32, device=dev)
@@ -1031,13 +1028,11 @@ def qkv_pack_multi(ws, with_backward: bool) -> List[Tensor]:
     if not ws:
         return []
     n = ws[0].shape[0]
-    nb = int(lib.gaot_qkv_packed_bytes(n, int(with_backward)))
-    buf = torch.empty(len(ws) * nb, dtype=torch.uint8, device=ws[0].device)
-    outs = [buf[i * nb:(i + 1) * nb] for i in range(len(ws))]
+    for w in ws:
+        _req_rows(w, torch.float32, 256, "qkv_pack_multi: q | k | v weight", rows=n)
+    outs = _slices_of_one_buffer(len(ws), int(lib.gaot_qkv_packed_bytes(n, int(with_backward))), torch.uint8, ws[0].device)
     items = (_QkvPackItem * len(ws))()
     for i, (w, o) in enumerate(zip(ws, outs)):
-        if w.dtype != torch.float32 or not w.is_contiguous() or tuple(w.shape) != (n, 256):
-            raise GaotError("qkv_pack_multi: contiguous fp32 [N, 256] weights of one N expected")
         items[i] = _QkvPackItem(w.data_ptr(), o.data_ptr())
     check(lib.gaot_qkv_pack_multi(items, len(ws), n, int(with_backward), _stream()), "gaot_qkv_pack_multi")
     return outs
@@ -1049,13 +1044,11 @@ def skip_pack_multi(ws) -> List[Tensor]:
     ws = list(ws)
     if not ws:
         return []
-    nb = int(lib.gaot_skip_packed_bytes())
-    buf = torch.empty(len(ws) * nb, dtype=torch.uint8, device=ws[0].device)
-    outs = [buf[i * nb:(i + 1) * nb] for i in range(len(ws))]
+    for w in ws:
+        _req_rows(w, torch.float32, 512, "skip_pack_multi: skip_proj weight", rows=256)
+    outs = _slices_of_one_buffer(len(ws), int(lib.gaot_skip_packed_bytes()), torch.uint8, ws[0].device)
     items = (_QkvPackItem * len(ws))()
     for i, (w, o) in enumerate(zip(ws, outs)):
-        if w.dtype != torch.float32 or not w.is_contiguous() or tuple(w.shape) != (256, 512):
-            raise GaotError("skip_pack_multi: contiguous fp32 [256, 512] weights expected")
         items[i] = _QkvPackItem(w.data_ptr(), o.data_ptr())
     check(lib.gaot_skip_pack_multi(items, len(ws), _stream()), "gaot_skip_pack_multi")
     return outs
@@ -1066,10 +1059,9 @@ def cat_norm_qkv_image(xa: Tensor, xb: Tensor, skip_packed: Tensor, skip_bias: O
     """skip_proj(cat([xa, xb])) + attn_norm + q | k | v image in one launch (gaot_cat_norm_qkv_image) ->
     (image, x_out fp32 [rows, 256], yb, rstd)"""
     lib = _lib.load()
-    rows = xa.shape[0]
+    rows = b * s
     for t in (xa, xb):
-        if t.dtype != torch.float32 or t.dim() != 2 or tuple(t.shape) != (rows, 256) or t.stride(1) != 1 or rows != b * s:
-            raise GaotError("cat_norm_qkv_image: fp32 [b * s, 256] inputs expected")
+        _req_rows(t, torch.float32, 256, "cat_norm_qkv_image: input", dense=False, rows=rows)
     nw = _req(norm_weight, torch.float32, "norm_weight")
     bs = None if skip_bias is None else _req(skip_bias, torch.float32, "skip_bias")
     img = _ws(lib.gaot_attn_bf16_image_bytes(b, s, h, hkv), xa.device)
@@ -1089,9 +1081,7 @@ def norm_qkv_image(x: Tensor, norm_weight: Tensor, eps: float, packed: Tensor, b
     """attn_norm + q | k | v projection written as the attention kernels' bf16 image in one launch (gaot_norm_qkv_image) ->
     (image, yb = bf16(norm(x)) [rows, 256], rstd [rows])"""
     lib = _lib.load()
-    rows = x.shape[0]
-    if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != 256 or x.stride(1) != 1 or rows != b * s:
-        raise GaotError("norm_qkv_image: fp32 [b * s, 256] input expected")
+    rows = _req_rows(x, torch.float32, 256, "norm_qkv_image: input", dense=False, rows=b * s)
     nw = _req(norm_weight, torch.float32, "norm_weight")
     img = _ws(lib.gaot_attn_bf16_image_bytes(b, s, h, hkv), x.device)
     yb = torch.empty(rows, 256, dtype=torch.bfloat16, device=x.device)
@@ -1119,13 +1109,9 @@ def ffn_bwd_norm(yb: Tensor, dy: Tensor, packed: Tensor, f: int, h: Tensor, norm
     """ffn_bwd with ffn_norm's backward in its epilogue (include/gaot3d_hip.h: gaot_ffn_bwd_norm) -> (dh fp32 [rows, 256], dag, u, dyb,
     d(norm weight) [256])"""
     lib = _lib.load()
-    rows = yb.shape[0]
-    if yb.dtype != torch.bfloat16 or not yb.is_contiguous() or yb.shape[1] != 256:
-        raise GaotError("ffn_bwd_norm: contiguous bf16 [rows, 256] input expected")
-    if dy.dtype != torch.float32 or not dy.is_contiguous() or tuple(dy.shape) != (rows, 256):
-        raise GaotError("ffn_bwd_norm: contiguous fp32 [rows, 256] gradient expected")
-    if h.dtype != torch.float32 or tuple(h.shape) != (rows, 256) or h.stride(1) != 1:
-        raise GaotError("ffn_bwd_norm: fp32 [rows, 256] norm input expected")
+    rows = _req_rows(yb, torch.bfloat16, 256, "ffn_bwd_norm: input")
+    _req_rows(dy, torch.float32, 256, "ffn_bwd_norm: gradient", rows=rows)
+    _req_rows(h, torch.float32, 256, "ffn_bwd_norm: norm input", dense=False, rows=rows)
     nw = _req(norm_weight, torch.float32, "norm_weight")
     dev = yb.device
     dag = torch.empty(rows, 2 * f, dtype=torch.bfloat16, device=dev)
@@ -1148,8 +1134,7 @@ def qkv_bwd_norm(dqkv: Tensor, packed: Tensor, x: Tensor, norm_weight: Tensor, r
     rows, n = dqkv.shape
     if dqkv.dtype != torch.float32 or not dqkv.is_contiguous() or n % 256:
         raise GaotError("qkv_bwd_norm: contiguous fp32 [rows, N] gradient with N a multiple of 256 expected")
-    if x.dtype != torch.float32 or tuple(x.shape) != (rows, 256) or x.stride(1) != 1:
-        raise GaotError("qkv_bwd_norm: fp32 [rows, 256] norm input expected")
+    _req_rows(x, torch.float32, 256, "qkv_bwd_norm: norm input", dense=False, rows=rows)
     nw = _req(norm_weight, torch.float32, "norm_weight")
     dres = None if dres is None else _req(dres, torch.float32, "dres")
     dtap = None if dtap is None else _req(dtap, torch.float32, "dtap")
@@ -1171,8 +1156,7 @@ def qkv_bwd_norm_cat(dqkv: Tensor, packed: Tensor, x: Tensor, norm_weight: Tenso
     rows, n = dqkv.shape
     if dqkv.dtype != torch.float32 or not dqkv.is_contiguous() or n % 256:
         raise GaotError("qkv_bwd_norm_cat: contiguous fp32 [rows, N] gradient with N a multiple of 256 expected")
-    if x.dtype != torch.float32 or tuple(x.shape) != (rows, 256) or x.stride(1) != 1:
-        raise GaotError("qkv_bwd_norm_cat: fp32 [rows, 256] norm input expected")
+    _req_rows(x, torch.float32, 256, "qkv_bwd_norm_cat: norm input", dense=False, rows=rows)
     if skip_packed.numel() != int(lib.gaot_skip_packed_bytes()):
         raise GaotError("qkv_bwd_norm_cat: skip_packed is not a skip_pack_multi image")
     nw = _req(norm_weight, torch.float32, "norm_weight")
@@ -1193,9 +1177,11 @@ def oproj_bwd_image(dh: Tensor, attn_out: Tensor, packed: Tensor, f: int, b: int
     """d_o = dh Wo as the flash backward's operands (include/gaot3d_hip.h: gaot_oproj_bwd_image): -> (an attn_bwd_scratch buffer whose head
     holds the bf16 dO image, delta fp32 [b, h, s]) for attn_bwd_bf16(do_image=..., delta=...)"""
     lib = _lib.load()
-    rows = dh.shape[0]
-    if h != 8 or rows != b * s or any(t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (rows, 256) for t in (dh, attn_out)):
-        raise GaotError("oproj_bwd_image: contiguous fp32 [b * s, 256] tensors and 8 heads of 32 expected")
+    if h != 8:
+        raise GaotError("oproj_bwd_image: 8 heads of 32 expected")
+    rows = b * s
+    for t, nm in ((dh, "dh"), (attn_out, "attn_out")):
+        _req_rows(t, torch.float32, 256, f"oproj_bwd_image: {nm}", rows=rows)
     scratch = attn_bwd_scratch(b, s, h, hkv, dh.device)
     delta = torch.empty(b, h, s, dtype=torch.float32, device=dh.device)
     with _timed("oproj_bwd_image"):
@@ -1208,10 +1194,8 @@ def norm_ffn_fwd(h: Tensor, norm_weight: Tensor, eps: float, packed: Tensor, f: 
     """RMSNorm + FFN + residual in one launch (include/gaot3d_hip.h: gaot_norm_ffn_fwd): h fp32 [rows, 256] ->
     (y fp32 [rows, 256] = n + ffn(n), yb = bf16(n) [rows, 256], rstd [rows]) with n = RMSNorm(h)"""
     lib = _lib.load()
-    if h.dtype != torch.float32 or h.dim() != 2 or h.shape[1] != 256 or h.stride(1) != 1:
-        raise GaotError("norm_ffn_fwd: fp32 [rows, 256] input expected")
+    rows = _req_rows(h, torch.float32, 256, "norm_ffn_fwd: input", dense=False)
     nw = _req(norm_weight, torch.float32, "norm_weight")
-    rows = h.shape[0]
     y = torch.empty(rows, 256, dtype=torch.float32, device=h.device)
     yb = torch.empty(rows, 256, dtype=torch.bfloat16, device=h.device)
     rstd = torch.empty(rows, dtype=torch.float32, device=h.device)
@@ -1225,11 +1209,8 @@ def ffn_bwd_dag(xb: Tensor, dy: Tensor, packed: Tensor, f: int, want_dyb: bool =
     """the first half of the FFN backward for a forward that saved nothing (include/gaot3d_hip.h: gaot_ffn_bwd_dag): x [rows, 256] bf16,
     dy fp32 [rows, 256], ``packed`` from ffn_pack(..., with_backward=True) -> (dag bf16 [rows, 2F], u bf16 [rows, F], dyb bf16 or None)"""
     lib = _lib.load()
-    if xb.dtype != torch.bfloat16 or not xb.is_contiguous() or xb.shape[1] != 256:
-        raise GaotError("ffn_bwd_dag: contiguous bf16 [rows, 256] input expected")
-    rows = xb.shape[0]
-    if dy.dtype != torch.float32 or not dy.is_contiguous() or tuple(dy.shape) != (rows, 256):
-        raise GaotError("ffn_bwd_dag: contiguous fp32 [rows, 256] gradient expected")
+    rows = _req_rows(xb, torch.bfloat16, 256, "ffn_bwd_dag: input")
+    _req_rows(dy, torch.float32, 256, "ffn_bwd_dag: gradient", rows=rows)
     dag = torch.empty(rows, 2 * f, dtype=torch.bfloat16, device=xb.device)
     u = torch.empty(rows, f, dtype=torch.bfloat16, device=xb.device)
     dyb = torch.empty(rows, 256, dtype=torch.bfloat16, device=xb.device) if want_dyb else None
@@ -1242,11 +1223,8 @@ def ffn_bwd(xb: Tensor, dy: Tensor, packed: Tensor, f: int, add_dy: bool, want_d
     """ffn_bwd_dag with the input gradient in the same launch (include/gaot3d_hip.h: gaot_ffn_bwd) ->
     (dx fp32 [rows, 256] = dag W13 (+ dy), dag, u, dyb)"""
     lib = _lib.load()
-    if xb.dtype != torch.bfloat16 or not xb.is_contiguous() or xb.shape[1] != 256:
-        raise GaotError("ffn_bwd: contiguous bf16 [rows, 256] input expected")
-    rows = xb.shape[0]
-    if dy.dtype != torch.float32 or not dy.is_contiguous() or tuple(dy.shape) != (rows, 256):
-        raise GaotError("ffn_bwd: contiguous fp32 [rows, 256] gradient expected")
+    rows = _req_rows(xb, torch.bfloat16, 256, "ffn_bwd: input")
+    _req_rows(dy, torch.float32, 256, "ffn_bwd: gradient", rows=rows)
     dag = torch.empty(rows, 2 * f, dtype=torch.bfloat16, device=xb.device)
     u = torch.empty(rows, f, dtype=torch.bfloat16, device=xb.device)
     dyb = torch.empty(rows, 256, dtype=torch.bfloat16, device=xb.device) if want_dyb else None

@@ -406,9 +406,7 @@ class SeqAttnFn(torch.autograd.Function):
         world, rank = dist.get_world_size(group), dist.get_rank(group)
         r, k = x.shape[-2], x.shape[-1]
         xb = GF.bf16_copy_of(x, (r, k))
-        ws = [GF._w2d(w) for w in (wq, wk, wv)]
-        ntot = (h + 2 * hkv) * 32
-        wcat = GF._wb(ws[0].new_empty(0).set_(ws[0].untyped_storage(), ws[0].storage_offset(), (ntot, k), (k, 1)), 1)
+        wcat = GF._wb(GF.fused_view((wq, wk, wv)), 1)
         s_total = r * world
         scale = 1.0 / (32 ** 0.5)
         hl, kl = h // world, hkv // world

@@ -450,3 +450,109 @@ def test_host_graph_helper_matches_graph_oracle(strategy, is_decoder):
         assert set(map(tuple, got.t().tolist())) == set(map(tuple, ref.t().tolist()))
     else:
         assert torch.equal(got.long(), ref)
+
+
+# ---- the Transformer host layer (gaot_3d_amd/functional.py, gaot_3d_amd/ops.py): what needs no device ----
+def test_placeholder_payload_is_loud_when_lost():
+    """a real tensor carries nothing; a placeholder hands its payload on; the same one-element storage under another tensor object
+    (what a hook or the engine may deliver) is an error, never a read of that element"""
+    from gaot_3d_amd import functional as GF
+    from gaot_3d_amd._lib import GaotError
+    assert GF._payload(torch.zeros(3, 4), "_gaot_qkv_image") is None
+    assert GF._payload(torch.zeros(6, 4)[::2], "_gaot_qkv_image") is None       # strided, but it owns what its shape needs
+    img = torch.arange(6)
+    p = GF._placeholder((5, 7), "cpu", _gaot_qkv_image=img)
+    assert tuple(p.shape) == (5, 7) and p.dtype == torch.float32 and p.untyped_storage().nbytes() == 4
+    assert GF._payload(p, "_gaot_qkv_image") is img
+    both = GF._placeholder((2, 3), "cpu", _gaot_do_image=(img, img))
+    assert GF._payload(both, "_gaot_do_image") == (img, img)
+    lost = p.view_as(p)
+    assert lost.untyped_storage().nbytes() == 4 and not hasattr(lost, "_gaot_qkv_image")
+    with pytest.raises(GaotError):
+        GF._payload(lost, "_gaot_qkv_image")
+
+
+def test_release_precast_empties_the_image_store():
+    from gaot_3d_amd import functional as GF
+    store = GF._IMAGES
+    GF.release_precast()
+    assert len(store) == 0
+    w = torch.zeros(4, 8)
+    for kind in store.kinds:
+        store.put(kind, w, (torch.zeros(1), True, None) if kind == "ffn" else torch.zeros(1))
+    assert sorted(store.kinds) == ["ffn", "qkv", "skip", "wb", "wbt"] and len(store) == 5
+    assert all(store.get(kind, w) is not None for kind in store.kinds)
+    assert store.get("wb", torch.zeros(8, 4)) is None       # same size, another shape (and address)
+    GF.release_precast()
+    assert len(store) == 0 and all(store.get(kind, w) is None for kind in store.kinds)
+
+
+def test_fused_view_and_split_rows_round_trip():
+    """three co-located parameters: fused_view is the [sum rows, k] matrix over their storage, _split_rows cuts a matrix of that
+    shape back into views of the parameters' shapes at the parameters' rows"""
+    from gaot_3d_amd import functional as GF
+    g = torch.Generator().manual_seed(3)
+    ps = [torch.nn.Parameter(torch.randn(n, 6, generator=g)) for n in (4, 2, 3)]
+    vals = [p.detach().clone() for p in ps]
+    GF.colocate(ps)
+    assert GF._adjacent([p.data for p in ps])
+    cat = GF.fused_view(ps)
+    assert tuple(cat.shape) == (9, 6) and cat.is_contiguous() and cat.data_ptr() == ps[0].data_ptr()
+    assert torch.equal(cat, torch.cat(vals))
+    parts = GF._split_rows(cat, [p.shape for p in ps])
+    row = 0
+    for part, p, v in zip(parts, ps, vals):
+        assert part.shape == p.shape and torch.equal(part, v)
+        assert part.data_ptr() == p.data_ptr() == cat.data_ptr() + row * 6 * 4
+        row += p.shape[0]
+    conv = GF._split_rows(cat, [(4, 6, 1), (5, 6, 1)])        # Conv1d(k = 1) storage of a weight
+    assert [tuple(c.shape) for c in conv] == [(4, 6, 1), (5, 6, 1)] and conv[1].data_ptr() == cat.data_ptr() + 4 * 6 * 4
+
+
+def _bad_operand_calls():
+    from gaot_3d_amd import ops
+    f32, b16 = torch.float32, torch.bfloat16
+    z = lambda *shape, dtype=f32: torch.zeros(*shape, dtype=dtype)
+    packed, nw, rstd = torch.zeros(16, dtype=torch.uint8), torch.ones(256), torch.ones(64)
+    return {
+        "ffn_fwd fp32 input": lambda: ops.ffn_fwd(z(64, 256), packed, 128),
+        "ffn_fwd narrow input": lambda: ops.ffn_fwd(z(64, 128, dtype=b16), packed, 128),
+        "ffn_fwd strided input": lambda: ops.ffn_fwd(z(64, 512, dtype=b16)[:, ::2], packed, 128),
+        "ffn_fwd short residual": lambda: ops.ffn_fwd(z(64, 256, dtype=b16), packed, 128, z(32, 256)),
+        "ffn_fwd bf16 residual": lambda: ops.ffn_fwd(z(64, 256, dtype=b16), packed, 128, z(64, 256, dtype=b16)),
+        "ffn_bwd fp32 input": lambda: ops.ffn_bwd(z(64, 256), z(64, 256), packed, 128, True),
+        "ffn_bwd short gradient": lambda: ops.ffn_bwd(z(64, 256, dtype=b16), z(63, 256), packed, 128, True),
+        "ffn_bwd_dag strided gradient": lambda: ops.ffn_bwd_dag(z(64, 256, dtype=b16), z(64, 512)[:, :256], packed, 128),
+        "ffn_bwd_norm wide norm input": lambda: ops.ffn_bwd_norm(z(64, 256, dtype=b16), z(64, 256), packed, 128, z(64, 512), nw, rstd),
+        "norm_ffn_fwd bf16 input": lambda: ops.norm_ffn_fwd(z(64, 256, dtype=b16), nw, 1e-6, packed, 128),
+        "norm_ffn_fwd 3-D input": lambda: ops.norm_ffn_fwd(z(1, 64, 256), nw, 1e-6, packed, 128),
+        "norm_qkv_image rows != b * s": lambda: ops.norm_qkv_image(z(64, 256), nw, 1e-6, packed, 1, 128, 8, 4, None, 1.0),
+        "cat_norm_qkv_image short skip": lambda: ops.cat_norm_qkv_image(z(64, 256), z(32, 256), packed, None, nw, 1e-6, packed, 1, 64, 8, 4, None, 1.0),
+        "block_tail_fwd narrow x": lambda: ops.block_tail_fwd(z(64, 256), z(64, 128), nw, 1e-6, packed, 128),
+        "qkv_bwd_norm N % 256": lambda: ops.qkv_bwd_norm(z(64, 384), packed, z(64, 256), nw, rstd),
+        "qkv_bwd_norm short norm input": lambda: ops.qkv_bwd_norm(z(64, 512), packed, z(32, 256), nw, rstd),
+        "oproj_bwd_image 4 heads": lambda: ops.oproj_bwd_image(z(64, 256), z(64, 256), packed, 128, 1, 64, 4, 4),
+        "oproj_bwd_image strided dh": lambda: ops.oproj_bwd_image(z(64, 512)[:, :256], z(64, 256), packed, 128, 1, 64, 8, 4),
+        "ffn_pack wrong F": lambda: ops.ffn_pack(z(256, 256), z(256, 64), 128, True),
+        "ffn_pack_multi bf16 weight": lambda: ops.ffn_pack_multi([(z(256, 256, dtype=b16), z(256, 128))], 128, True),
+        "block_pack_multi wrong o_proj": lambda: ops.block_pack_multi([(z(256, 256), z(256, 128), z(256, 128))], 128),
+        "qkv_pack_multi wrong shape": lambda: ops.qkv_pack_multi([z(512, 128)], True),
+        "qkv_pack_multi two N": lambda: ops.qkv_pack_multi([z(512, 256), z(256, 256)], True),
+        "skip_pack_multi wrong shape": lambda: ops.skip_pack_multi([z(256, 256)]),
+    }
+
+
+@pytest.mark.parametrize("case", sorted(_bad_operand_calls()))
+def test_ops_reject_bad_row_operands_before_any_library_call(case, monkeypatch):
+    """the operand checks of the fused Transformer-block entry points: a wrong dtype, shape or layout is a GaotError raised on the
+    host (CPU tensors here), ahead of every call into the library -- its size queries included"""
+    from gaot_3d_amd import _lib
+    from gaot_3d_amd._lib import GaotError
+
+    class NoLibrary:
+        def __getattr__(self, name):
+            raise AssertionError(f"{name} called before the operands were checked")
+
+    monkeypatch.setattr(_lib, "load", lambda: NoLibrary())
+    with pytest.raises(GaotError):
+        _bad_operand_calls()[case]()
