@@ -222,5 +222,28 @@ class Report:
         self.achieved[name] = rel
         return self._out(name, finite and rel <= bound, f"max |err_j| / sum|term_ij| = {rel:.3e} (bound {bound:.1e})")
 
+    def model(self, name, got, r, e, rms_factor=0.25, max_factor=2.0):
+        """a result against a rounding model R and the exact form E (tests/gno_ref.py): rms(got - R) <= rms_factor x rms(R - E) and
+        max|got - R| <= max_factor x max|R - E| -- the yardstick R - E is the model's own bf16 error, nothing of it comes from ``got`` --
+        and exactly 0 wherever R = E = 0 (no edges, rows without edges)"""
+        got, r, e = _d(got), _d(r), _d(e)
+        if got.shape != r.shape:
+            return self._out(name, False, f"shape {tuple(got.shape)} != {tuple(r.shape)}")
+        if not bool(torch.isfinite(got).all()):
+            self.achieved[name] = (float("inf"), float("inf"))
+            return self._out(name, False, "not finite")
+        n = max(r.numel(), 1)
+        yard, err = r - e, got - r
+        yrms, ymax = (yard.square().sum().item() / n) ** 0.5, yard.abs().max().item() if r.numel() else 0.0
+        erms, emax = (err.square().sum().item() / n) ** 0.5, err.abs().max().item() if r.numel() else 0.0
+        rr = 0.0 if erms == 0.0 else (erms / yrms if yrms > 0.0 else float("inf"))
+        rm = 0.0 if emax == 0.0 else (emax / ymax if ymax > 0.0 else float("inf"))
+        zero = (r == 0) & (e == 0)
+        nz = int((got[zero] != 0).sum())
+        self.achieved[name] = (rr, rm)
+        ok = rr <= rms_factor and rm <= max_factor and nz == 0
+        return self._out(name, ok, f"rms(got-R)/rms(R-E)={rr:.3e} (bound {rms_factor:.3g}) max|got-R|/max|R-E|={rm:.3e} (bound {max_factor:.3g}) "
+                                   f"rms(R-E)={yrms:.3e} max|R-E|={ymax:.3e}" + (f" NONZERO where R = E = 0: {nz}" if nz else ""))
+
     def done(self):
         assert not self.failures, f"{len(self.failures)} check(s) missed:\n" + "\n".join(self.failures)
