@@ -263,9 +263,7 @@ __device__ __forceinline__ void drop_packed(bf16x8& f0, bf16x8& f1, uint32_t awf
 // grows" ~40 % of the tiles of a wave went through the rescale path at S = 16 384 on random scores; now a handful do.
 // o = acc / l and lse = m ln2 + log l do not depend on where m sits.
 constexpr float RESCALE_SUM = 64.0f;
-// FSB: schedule pins of the bound-based (FAST) tile, bit i = __builtin_amdgcn_sched_barrier(0) at 1: the start of a tile,
-// 2: after the exp stream (before packing / row sums / mask), 4: before the P V products
-template <int OCC, int TPM, bool DROP, bool FAST, int FSB = 0>
+template <int OCC, int TPM, bool DROP, bool FAST>
 __global__ __launch_bounds__(256, OCC) void k_attn_fwd_bf16(FwdArgs a) {
     __shared__ __attribute__((aligned(16))) char lds[2 * TPM * TILE_BYTES];  // K tiles, then V tiles
     __shared__ __attribute__((aligned(16))) uint32_t bw_s[DROP ? 16 * TPM : 4];
@@ -367,7 +365,6 @@ __global__ __launch_bounds__(256, OCC) void k_attn_fwd_bf16(FwdArgs a) {
                 }
             };
             if constexpr (FAST) {
-                if constexpr ((FSB & 1) != 0) __builtin_amdgcn_sched_barrier(0);
                 f32x16 zero;
     #pragma unroll
                 for (int r = 0; r < 16; ++r) zero[r] = 0.f;
@@ -381,10 +378,9 @@ __global__ __launch_bounds__(256, OCC) void k_attn_fwd_bf16(FwdArgs a) {
                 }
     #pragma unroll
                 for (int r = 0; r < 16; ++r) sc[r] = __builtin_amdgcn_exp2f(sc[r]);
-                if constexpr ((FSB & 2) != 0) __builtin_amdgcn_sched_barrier(0);
                 bf16x8 p0, p1;
                 acc_to_frags(sc, p0, p1);
-                if constexpr ((FSB & 8) != 0) {   // row sums of the PACKED (bf16-rounded, undropped) p -- the values the P V product uses: one v_dot2c_f32_bf16 per pair
+                if constexpr (DROP) {   // row sums of the PACKED (bf16-rounded, undropped) p -- the values the P V product uses: one v_dot2c_f32_bf16 per pair
                     typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
                     const bf16x2_t ones = {(__bf16)1.0f, (__bf16)1.0f};
                     const uint4 ua = __builtin_bit_cast(uint4, p0), ub = __builtin_bit_cast(uint4, p1);
@@ -403,7 +399,6 @@ __global__ __launch_bounds__(256, OCC) void k_attn_fwd_bf16(FwdArgs a) {
                     l += q0 + q1;
                 }
                 if constexpr (DROP) drop_packed(p0, p1, aw, bw_s + 16 * t, hf, tpk);
-                if constexpr ((FSB & 4) != 0) __builtin_amdgcn_sched_barrier(0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols(vt, lane, 0), p0, acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols(vt, lane, 1), p1, acc, 0, 0, 0);
                 return;
@@ -1090,10 +1085,9 @@ __global__ __launch_bounds__(256, OCC) void k_attn_bwd_dq_kb(BwdArgs a) {
 // LDS: stage tiles 8 KB + row constants + K tiles 32 KB + dS tiles 32 KB + dQ slots 64 KB = 137 KB -> one workgroup per CU,
 // two waves per SIMD (256 registers), grid = (S/512) * HKV workgroups: at S = 16 384, 8 heads exactly one per CU.
 // ------------------------------------------------------------------------------------------------
-// LDS layout of k_attn_bwd_fused<DROP, W waves, KB key blocks per wave, NT query tiles per stage>
-template <int W, int KB, int NT>
+// LDS layout of k_attn_bwd_fused: 8 waves x 2 key blocks per wave, 2 query tiles (64 queries) per stage
 struct FusedLds {
-    static constexpr int QS = 32 * NT;
+    static constexpr int W = 8, KB = 2, NT = 2, QS = 32 * NT;
     static constexpr int STAGE = 0;                                  // Q tiles, then dO tiles
     static constexpr int LSE = STAGE + 2 * NT * TILE_BYTES;          // float[QS]
     static constexpr int DEL = LSE + QS * 4;                         // float[QS]
@@ -1109,27 +1103,29 @@ struct FusedArgs {
     BwdArgs a;
     bf16_t* dqpart;       // [B][H][nslab][S][32] bf16 (fp32 sums over the slab's keys, rounded once: see k_attn_dq_reduce)
     int nslab;
-    int lab;              // measurement switch (GAOT_ATTN_BWD_LAB): selects the SB instantiation on the host side
-    unsigned long long* stamps;   // ORD == 2 (diagnostic build, GAOT_ATTN_BWD_STAMPS=1): 16 cycle sums per wave, else NULL
 };
 
-// FB_WAVES x FB_KB = 16 key blocks (512 keys) per workgroup either way: 8 waves x 2 blocks run two waves per SIMD in 256
-// registers each; 4 waves x 4 blocks run ONE wave per SIMD with the whole 512-register file (K^T fragments of the dQ product
-// kept in registers, one read of a Q / dO fragment or row constant serves four units, four slots to reduce instead of eight).
-// PK (dropout only): the row words arrive packed per PAIR of queries (the two consecutive queries of an accumulator register
+// 8 waves x 2 key blocks = 16 key blocks (512 keys) per workgroup: two waves per SIMD in 256 registers each.
+// With dropout the row words arrive packed per PAIR of queries (the two consecutive queries of an accumulator register
 // pair), so one xor makes the uniform 16-bit values of both and the two compares read its halves directly (SDWA): 2.5
-// mask-generation instructions per pair instead of 4, and half the row-word reads.
-// ORD (with PK): 0 = all of a tile's exp / mask work, then all of its dV / dK products; 1 = key block by key block (block 0's
-// dV / dK MFMAs are in flight under block 1's exp / mask stream)
-// TT (round 5): the dS tile reaches the dQ product's "query on the lane" orientation on the MATRIX pipe -- the accumulator as the
-// A operand [key][query] times a permutation fragment I[query][query'] (two MFMAs, exact: products with 1.0 / 0.0), packed again --
-// instead of through the wave-private LDS tile (4 ds_write_b64 + 4 ds_read_b64_tr_b16 per unit on an issue port that is 89 % busy)
-template <bool DROP, int FB_WAVES, int FB_KB, int FB_NT, bool PK = false, int ORD = 0, int SB = 0, bool TT = false>
-__global__ __launch_bounds__(64 * FB_WAVES, FB_WAVES == 8 ? 1 : (FB_KB >= 4 ? 1 : 2)) void k_attn_bwd_fused(FusedArgs fa) {
-    using L = FusedLds<FB_WAVES, FB_KB, FB_NT>;
+// mask-generation instructions per pair instead of 4, and half the row-word reads.  All of a tile's exp / mask work comes
+// first, then all of its dV / dK products.
+// (measured and removed: 4 waves x 4 key blocks, ONE wave per SIMD with the whole 512-register file -- K^T fragments of the dQ
+// product kept in registers, one read of a Q / dO fragment or row constant serves four units, four slots to reduce instead of
+// eight: 1.9 / 1.27 ms, profiles/archive/r4_b_attn_bwd_lab.txt; the hand-scheduled k_attn_bwd_asm below is that shape done right)
+// (measured and removed: the round-3 mask arithmetic -- row words per query, xor + compare per element)
+// (measured and removed: key block by key block order -- block 0's dV / dK MFMAs in flight under block 1's exp / mask stream)
+// (measured and removed, round 5: the dS tile brought to the dQ product's "query on the lane" orientation on the MATRIX pipe --
+// the accumulator as the A operand [key][query] times a permutation fragment I[query][query'], two exact MFMAs, packed again --
+// instead of through the wave-private LDS tile, 4 ds_write_b64 + 4 ds_read_b64_tr_b16 per unit on an issue port that is 89 % busy)
+// (measured and removed: in-kernel cycle stamps per phase, a diagnostic build: profiles/archive/r4_d_attn_stamps_microbench.txt,
+// profiles/archive/r4_h_attn_bwd_prio_stamps.txt)
+template <bool DROP>
+__global__ __launch_bounds__(512, 1) void k_attn_bwd_fused(FusedArgs fa) {
+    using L = FusedLds;
+    constexpr int FB_WAVES = L::W, FB_KB = L::KB, FB_NT = L::NT;
     constexpr int FB_QS = L::QS, FB_OFF_STAGE = L::STAGE, FB_OFF_LSE = L::LSE, FB_OFF_DEL = L::DEL, FB_OFF_AW = L::AW, FB_OFF_K = L::K;
     constexpr int FB_KEYS = L::KEYS, FB_OFF_DS = L::DS, FB_OFF_SLOT = L::SLOT;
-    constexpr bool KT_REGS = FB_KB >= 4;          // the wave's K^T fragments (A operand of the dQ product) live in registers
     constexpr int NTHR = 64 * FB_WAVES;
     const BwdArgs& a = fa.a;
     extern __shared__ __attribute__((aligned(1024))) char lds[];
@@ -1144,30 +1140,14 @@ __global__ __launch_bounds__(64 * FB_WAVES, FB_WAVES == 8 ? 1 : (FB_KB >= 4 ? 1 
     // stage), every part keeps dK / dV partials of its own (dqkv + part * dqkv_part, summed in part order by k_sum_cols) and
     // writes the slab partials of ITS queries
     const int64_t q_lo = (int64_t)blockIdx.y * a.chunk, q_hi = min((int64_t)a.S, q_lo + a.chunk);
-    // in-kernel stamps (ORD == 2 only: a diagnostic instantiation, never the product's): cycles between consecutive stamp
-    // points, summed per wave; index = the stamp that CLOSES the interval
-    unsigned long long st_acc[16], st_last = 0;
-    if constexpr (ORD == 2) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) st_acc[i] = 0;
-        st_last = __builtin_amdgcn_s_memtime();
-    }
-    auto STAMP = [&](int i) {
-        if constexpr (ORD == 2) {
-            __builtin_amdgcn_sched_barrier(0);
-            const unsigned long long t = __builtin_amdgcn_s_memtime();
-            st_acc[i] += t - st_last;
-            st_last = t;
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
     // priority between the two waves of a SIMD: s_setprio flips around the S / dP MFMA cluster of every tile, both waves alike
     // (measured and removed, profiles/archive/r4_b / r4_e / r4_h: static priority for either half of the waves, priority for one half
     // inside its MFMA clusters only, one half a level higher throughout, no priority at all: within +-1.5 % at compile time;
     // RUN-TIME-conditional s_setprio splits the basic blocks around the clusters and changed the dropout kernel's schedule by
     // +30 %: the flips around the S / dP cluster are unconditional)
-    // SB: bit i = __builtin_amdgcn_sched_barrier(0) at phase boundary i (1: after the S / dP cluster, 2: after the exp / mask
-    // stream, 4: after the dV / dK products, 8: after the dQ products) -- pins the compiler's schedule at those points
+    // __builtin_amdgcn_sched_barrier(0) pins the compiler's schedule at the top of a tile, after the exp / mask stream and after
+    // the dQ products (pins after the S / dP cluster and after the dV / dK products, and no pins at all, were measured:
+    // profiles/archive/r4_f_attn_bwd_sched_barrier_lab.txt)
     const int64_t key0 = (int64_t)slab * FB_KEYS + wave * (32 * FB_KB);
     const int64_t rowbase = (int64_t)b * a.S;
     char* ktile = lds + FB_OFF_K + wave * FB_KB * TILE_BYTES;
@@ -1196,24 +1176,6 @@ __global__ __launch_bounds__(64 * FB_WAVES, FB_WAVES == 8 ? 1 : (FB_KB >= 4 ? 1 
     for (int kb = 0; kb < FB_KB; ++kb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) { dkt[kb][r] = 0.f; dvt[kb][r] = 0.f; }
-    // TT: permutation fragments, B operand [k = query][n = query'], element j of k-step s stands for query 16 s + 8 (j >> 2) +
-    // 4 hf + (j & 3) (the k order of an accumulator used as an operand): 1.0 where that query is the lane's own
-    bf16x8 idf[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) idf[s][j] = (TT && (16 * s + 8 * (j >> 2) + 4 * hf + (j & 3)) == l31) ? (short)0x3F80 : (short)0;
-    // loop-invariant K^T fragments (the A operand of dQ^T = K^T dS^T): read back once from the wave's own tile when the
-    // register file has room for them (one wave per SIMD), else re-read per tile (two waves per SIMD, 256 registers)
-    bf16x8 ktf[KT_REGS ? FB_KB : 1][2];
-    if constexpr (KT_REGS) {
-#pragma unroll
-        for (int kb = 0; kb < FB_KB; ++kb) {
-            ktf[kb][0] = frag_cols(ktile + kb * TILE_BYTES, lane, 0);
-            ktf[kb][1] = frag_cols(ktile + kb * TILE_BYTES, lane, 1);
-        }
-    }
-
     // staging: 2 NT 128 16-byte chunks per stage (tile t of Q0.. dO0.., row r, chunk c), NST per thread
     constexpr int NSTG = NTHR;
     constexpr int NST = 2 * FB_NT * 128 / NSTG;
@@ -1302,7 +1264,7 @@ __global__ __launch_bounds__(64 * FB_WAVES, FB_WAVES == 8 ? 1 : (FB_KB >= 4 ? 1 
                 const int64_t ki = key0 + 32 * kb + l31;
                 const uint32_t bw = gdrop::col_word(ck, (uint32_t)(ki >> 1));
                 bsel[kb] = (ki & 1) ? (bw >> 16) : (bw & 0xffffu);
-                if constexpr (PK) bsel[kb] |= bsel[kb] << 16;
+                bsel[kb] |= bsel[kb] << 16;
             }
         }
         const uint32_t thr_v = a.drop.thr;
@@ -1317,8 +1279,7 @@ __global__ __launch_bounds__(64 * FB_WAVES, FB_WAVES == 8 ? 1 : (FB_KB >= 4 ? 1 
                 lse_w[threadIdx.x] = in ? -lt * LOG2E : -INFINITY;
                 del_w[threadIdx.x] = in ? -et * dscale : 0.f;
             }
-            if constexpr (DROP && !PK) stage_row_words<FB_QS>(aw_w, rk, q0);
-            if constexpr (DROP && PK) {
+            if constexpr (DROP) {
                 // packed form: copy c (key parity), word ((t 2 + hf) 4 + g4) 2 + j = halfword c of the row words of queries
                 // 32 t + 8 g4 + 4 hf + 2 j (low half) and + 1 (high half): a lane's 8 words of a tile are 32 contiguous bytes
                 if (threadIdx.x < FB_QS / 2) {
@@ -1335,28 +1296,21 @@ __global__ __launch_bounds__(64 * FB_WAVES, FB_WAVES == 8 ? 1 : (FB_KB >= 4 ? 1 
         const float* del_s = reinterpret_cast<const float*>(sbuf + FB_OFF_DEL);
         const uint32_t* aw_s = reinterpret_cast<const uint32_t*>(sbuf + FB_OFF_AW);
         for (int64_t q0 = q_lo; q0 < q_hi; q0 += FB_QS) {
-            {
-                STAMP(0);            // end of the previous stage's tiles (incl. its slot stores)
-                __syncthreads();     // A: every wave is done with the staged tiles and has written its slots of the previous stage
-                STAMP(1);            // wait at barrier A
-                // the tile loads issued a stage ago are waited for HERE, before this section's slab-partial store is issued (vmcnt
-                // counts stores too: behind the store the wait would cover its whole round trip)
-                stage_store(regs, sbuf);
-                stage_consts(sbuf, q0);
-                if (q0 > q_lo) reduce_slots(q0 - FB_QS);
-                STAMP(2);            // staging stores + slot reduction
-                __syncthreads();     // B
-                STAMP(3);            // wait at barrier B
-                if (q0 + FB_QS < q_hi) {
-                    stage_load(regs, q0 + FB_QS);
-                    load_consts(q0 + FB_QS);
-                }
+            __syncthreads();     // A: every wave is done with the staged tiles and has written its slots of the previous stage
+            // the tile loads issued a stage ago are waited for HERE, before this section's slab-partial store is issued (vmcnt
+            // counts stores too: behind the store the wait would cover its whole round trip)
+            stage_store(regs, sbuf);
+            stage_consts(sbuf, q0);
+            if (q0 > q_lo) reduce_slots(q0 - FB_QS);
+            __syncthreads();     // B
+            if (q0 + FB_QS < q_hi) {
+                stage_load(regs, q0 + FB_QS);
+                load_consts(q0 + FB_QS);
             }
-            STAMP(4);            // issue of the next stage's global loads
 #pragma unroll
             for (int t = 0; t < FB_NT; ++t) {
                 if (q0 + 32 * t >= q_hi) break;
-                if constexpr ((SB & 16) != 0) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);
                 const char* qt = sbuf + FB_OFF_STAGE + t * TILE_BYTES;
                 const char* dt = sbuf + FB_OFF_STAGE + (FB_NT + t) * TILE_BYTES;
                 f32x16 lc, dc;
@@ -1374,12 +1328,10 @@ __global__ __launch_bounds__(64 * FB_WAVES, FB_WAVES == 8 ? 1 : (FB_KB >= 4 ? 1 
                     dp[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da1, vf[kb][1], dp[kb], 0, 0, 0);
                 }
                 __builtin_amdgcn_s_setprio(0);
-                if constexpr ((SB & 1) != 0) __builtin_amdgcn_sched_barrier(0);
-                STAMP(5);        // row constants + row fragments read, S / dP MFMAs issued
                 const bf16x8 dc0 = frag_cols(dt, lane, 0), dc1 = frag_cols(dt, lane, 1);
                 const bf16x8 qc0 = frag_cols(qt, lane, 0), qc1 = frag_cols(qt, lane, 1);
                 uint32_t w8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                if constexpr (DROP && PK) {
+                if constexpr (DROP) {
                     const uint4* awp = reinterpret_cast<const uint4*>(aw_s + (l31 & 1) * (FB_QS / 2 + 4) + (t * 2 + hf) * 8);
                     const uint4 wa = awp[0], wb = awp[1];
                     w8[0] = wa.x; w8[1] = wa.y; w8[2] = wa.z; w8[3] = wa.w; w8[4] = wb.x; w8[5] = wb.y; w8[6] = wb.z; w8[7] = wb.w;
@@ -1401,7 +1353,7 @@ __global__ __launch_bounds__(64 * FB_WAVES, FB_WAVES == 8 ? 1 : (FB_KB >= 4 ? 1 
                     sc[kb][r0] = pm0; sc[kb][r1] = pm1;
                     dp[kb][r0] = p0 * t0; dp[kb][r1] = p1 * t1;
                 };
-                if constexpr (DROP && PK && ORD != 1) {
+                if constexpr (DROP) {
 #pragma unroll
                     for (int g4 = 0; g4 < 4; ++g4)
 #pragma unroll
@@ -1409,46 +1361,9 @@ __global__ __launch_bounds__(64 * FB_WAVES, FB_WAVES == 8 ? 1 : (FB_KB >= 4 ? 1 
 #pragma unroll
                             for (int j = 0; j < 2; ++j) mask_pair(kb, g4, j);
                 }
-                if constexpr ((SB & 2) != 0) __builtin_amdgcn_sched_barrier(0);
-                STAMP(6);        // wait for the MFMA results + exp / mask stream (PK)
-                if constexpr (DROP && !PK) {   // row words read 4 at a time: the two key blocks share them (measured: key-block-outer order,
-                    // which would put block 0's MFMAs under block 1's mask work, is 7 % slower)
-                    const uint32_t* awp = aw_s + (l31 & 1) * (FB_QS + 4) + 32 * t + 4 * hf;
-                    // the row words of group g4 + 1 are requested before group g4 is worked on (left alone the compiler loads
-                    // each group right before its first use and the wave sits out the LDS round trip four times per tile)
-                    uint4 wv = *reinterpret_cast<const uint4*>(awp);
-#pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4) {
-                        uint4 nxt = wv;
-                        if (g4 < 3) {
-                            nxt = *reinterpret_cast<const uint4*>(awp + 8 * (g4 + 1));
-                            asm volatile("" : "+v"(nxt.x), "+v"(nxt.y), "+v"(nxt.z), "+v"(nxt.w));   // keep the load here
-                        }
-                        const uint32_t ww[4] = {wv.x, wv.y, wv.z, wv.w};
-#pragma unroll
-                        for (int kb = 0; kb < FB_KB; ++kb)
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                const int r = 4 * g4 + i;
-                                const float p = __builtin_amdgcn_exp2f(sc[kb][r]);
-                                const bool keep = (ww[i] ^ bsel[kb]) >= a.drop.thr;
-                                float pm = keep ? p : 0.f;
-                                asm volatile("" : "+v"(pm));   // select on fp32, then ONE cvt_pk per pair (see k_attn_bwd_dkv_kb)
-                                sc[kb][r] = pm;
-                                dp[kb][r] = p * (keep ? dp[kb][r] : dc[r]);
-                            }
-                        wv = nxt;
-                    }
-                }
-                bf16x8 tsf[FB_KB][2];     // TT: the unit's dS^T fragments (query on the lane)
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int kb = 0; kb < FB_KB; ++kb) {
-                    if constexpr (DROP && PK && ORD == 1) {
-#pragma unroll
-                        for (int g4 = 0; g4 < 4; ++g4)
-#pragma unroll
-                            for (int j = 0; j < 2; ++j) mask_pair(kb, g4, j);
-                    }
                     if constexpr (!DROP) {
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
@@ -1464,14 +1379,6 @@ __global__ __launch_bounds__(64 * FB_WAVES, FB_WAVES == 8 ? 1 : (FB_KB >= 4 ? 1 
                     dkt[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qc0, d0, dkt[kb], 0, 0, 0);
                     dvt[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dc1, p1, dvt[kb], 0, 0, 0);
                     dkt[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qc1, d1, dkt[kb], 0, 0, 0);
-                    if constexpr (TT) {
-                        f32x16 tr;
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) tr[r] = 0.f;
-                        tr = __builtin_amdgcn_mfma_f32_32x32x16_bf16(d0, idf[0], tr, 0, 0, 0);
-                        tr = __builtin_amdgcn_mfma_f32_32x32x16_bf16(d1, idf[1], tr, 0, 0, 0);
-                        acc_to_frags(tr, tsf[kb][0], tsf[kb][1]);
-                    } else {
                     // dS tile [key = l31][query]: the lane's 4 runs of 4 consecutive queries (8 g + 4 hf + 0..3) = 8-byte stores
                     const uint4 lo = __builtin_bit_cast(uint4, d0), hi = __builtin_bit_cast(uint4, d1);
                     char* dst = dstile + kb * TILE_BYTES;
@@ -1479,10 +1386,7 @@ __global__ __launch_bounds__(64 * FB_WAVES, FB_WAVES == 8 ? 1 : (FB_KB >= 4 ? 1 
                     *reinterpret_cast<uint2*>(dst + tile_off(l31, 1) + 8 * hf) = make_uint2(lo.z, lo.w);
                     *reinterpret_cast<uint2*>(dst + tile_off(l31, 2) + 8 * hf) = make_uint2(hi.x, hi.y);
                     *reinterpret_cast<uint2*>(dst + tile_off(l31, 3) + 8 * hf) = make_uint2(hi.z, hi.w);
-                    }
                 }
-                if constexpr ((SB & 4) != 0) __builtin_amdgcn_sched_barrier(0);
-                STAMP(7);        // conversions, dV / dK MFMAs issued, dS tile stored
                 // dQ^T[d][q] of this wave's 64 keys: K^T (A, transposed read of the K tile) x dS^T (B, transposed read of
                 // the tile just written: same LDS object, so the compiler keeps the order, and LDS operations of one wave
                 // complete in order)
@@ -1491,38 +1395,22 @@ __global__ __launch_bounds__(64 * FB_WAVES, FB_WAVES == 8 ? 1 : (FB_KB >= 4 ? 1 
                 for (int r = 0; r < 16; ++r) dq[r] = 0.f;
 #pragma unroll
                 for (int kb = 0; kb < FB_KB; ++kb) {
-                    if constexpr (TT) {
-                        dq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(KT_REGS ? ktf[kb][0] : frag_cols(ktile + kb * TILE_BYTES, lane, 0), tsf[kb][0], dq, 0, 0, 0);
-                        dq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(KT_REGS ? ktf[kb][1] : frag_cols(ktile + kb * TILE_BYTES, lane, 1), tsf[kb][1], dq, 0, 0, 0);
-                    } else if constexpr (KT_REGS) {
-                        dq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ktf[kb][0], frag_cols(dstile + kb * TILE_BYTES, lane, 0), dq, 0, 0, 0);
-                        dq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ktf[kb][1], frag_cols(dstile + kb * TILE_BYTES, lane, 1), dq, 0, 0, 0);
-                    } else {
-                        dq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols(ktile + kb * TILE_BYTES, lane, 0),
-                                                                     frag_cols(dstile + kb * TILE_BYTES, lane, 0), dq, 0, 0, 0);
-                        dq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols(ktile + kb * TILE_BYTES, lane, 1),
-                                                                     frag_cols(dstile + kb * TILE_BYTES, lane, 1), dq, 0, 0, 0);
-                    }
+                    dq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols(ktile + kb * TILE_BYTES, lane, 0),
+                                                                 frag_cols(dstile + kb * TILE_BYTES, lane, 0), dq, 0, 0, 0);
+                    dq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols(ktile + kb * TILE_BYTES, lane, 1),
+                                                                 frag_cols(dstile + kb * TILE_BYTES, lane, 1), dq, 0, 0, 0);
                 }
                 // slot [q = l31][32 d] fp32, 16-byte chunk index (2 g + hf) XOR (q & 7): conflict-free stores and reduction reads
-                if constexpr ((SB & 8) != 0) __builtin_amdgcn_sched_barrier(0);
-                STAMP(8);        // dS round trip through LDS + dQ MFMAs issued
+                __builtin_amdgcn_sched_barrier(0);
                 char* slot = lds + FB_OFF_SLOT + (t * FB_WAVES + wave) * 4096 + l31 * 128;
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
                     *reinterpret_cast<float4*>(slot + (((2 * g + hf) ^ (l31 & 7)) << 4)) =
                         make_float4(dq[4 * g], dq[4 * g + 1], dq[4 * g + 2], dq[4 * g + 3]);
-                STAMP(9);        // wait for the dQ MFMAs + slot stores
             }
         }
         __syncthreads();
         reduce_slots(q_lo + ((q_hi - 1 - q_lo) / FB_QS) * (int64_t)FB_QS);
-    }
-    if constexpr (ORD == 2) {
-        if (fa.stamps && lane == 0) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) fa.stamps[((int64_t)((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * FB_WAVES + wave) * 16 + i] = st_acc[i];
-        }
     }
     const float vsc = DROP ? a.drop.inv_keep : 1.f;
     const float ksc = vsc / LOG2E;
@@ -1590,9 +1478,7 @@ using AsmLds = AsmLdsT<DROP ? (GAOT_ATTN_BWD_ASM_MFMA_T_DROP != 0) : (GAOT_ATTN_
 static_assert(AsmLds<false>::TOTAL <= 160 * 1024 && AsmLds<true>::SLOT % 128 == 0 && AsmLds<false>::SLOT % 128 == 0 &&
               AsmLds<true>::NT * 4 * 4096 >= 4 * 4 * TILE_BYTES, "LDS layout");
 
-// LAB (measurement only, results invalid): 1 = the stage code without the tile loop, 2 = the tile loop without slot reduction /
-// row-word hashing (barriers and tile staging kept), 3 = no barriers either
-template <bool DROP, int LAB = 0>
+template <bool DROP>
 __global__ __launch_bounds__(256, 1) void k_attn_bwd_asm(FusedArgs fa) {
     using L = AsmLds<DROP>;
     constexpr bool MT = DROP ? (GAOT_ATTN_BWD_ASM_MFMA_T_DROP != 0) : (GAOT_ATTN_BWD_ASM_MFMA_T_NODROP != 0);
@@ -1756,14 +1642,14 @@ __global__ __launch_bounds__(256, 1) void k_attn_bwd_asm(FusedArgs fa) {
         float* del_w = reinterpret_cast<float*>(lds + L::DEL);
         uint32_t* aw_w = reinterpret_cast<uint32_t*>(lds + L::AW);
         for (int64_t q0 = q_lo; q0 < q_hi; q0 += QS) {
-            if constexpr (LAB != 3) __syncthreads();     // A: every wave is done with the staged tiles and has written its slots of the previous stage
+            __syncthreads();     // A: every wave is done with the staged tiles and has written its slots of the previous stage
             stage_store(regs);
             if (threadIdx.x < QS) {
                 const bool in = q0 + threadIdx.x < a.S;
                 lse_w[threadIdx.x] = in ? -lt * LOG2E : -INFINITY;
                 del_w[threadIdx.x] = in ? -et * dscale : 0.f;
             }
-            if constexpr (DROP && LAB < 2) {
+            if constexpr (DROP) {
                 if (threadIdx.x < QS / 2) {   // packed row words: see k_attn_bwd_fused (PK)
                     const int u = threadIdx.x, st = u >> 4, sh = (u >> 3) & 1, sg = (u >> 1) & 3, sj = u & 1;
                     const uint32_t qe = (uint32_t)q0 + 32 * st + 8 * sg + 4 * sh + 2 * sj;
@@ -1772,13 +1658,12 @@ __global__ __launch_bounds__(256, 1) void k_attn_bwd_asm(FusedArgs fa) {
                     aw_w[QS / 2 + 4 + u] = (w0 >> 16) | (w1 & 0xffff0000u);
                 }
             }
-            if (q0 > q_lo && LAB < 2) reduce_slots(q0 - QS);
-            if constexpr (LAB != 3) __syncthreads();     // B
+            if (q0 > q_lo) reduce_slots(q0 - QS);
+            __syncthreads();     // B
             if (q0 + QS < q_hi) {
                 stage_load(regs, q0 + QS);
                 load_consts(q0 + QS);
             }
-            if constexpr (LAB == 1) continue;
             if constexpr (DROP)
                 asm volatile(GAOT_ATTN_BWD_STAGE_ASM_DROP
                              :: [a_const] "v"(a_const), [a_r0] "v"(a_r0), [a_r1] "v"(a_r1), [a_c0] "v"(a_c0), [a_c1] "v"(a_c1), [a_w] "v"(a_w),
@@ -1826,7 +1711,7 @@ __global__ __launch_bounds__(256, 1) void k_attn_bwd_asm(FusedArgs fa) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_attn_fwd_asm: the bound-based forward tile (k_attn_fwd_bf16<4, 4, DROP, true, 8>) with ONE wave per SIMD and a hand-scheduled
+// k_attn_fwd_asm: the bound-based forward tile (k_attn_fwd_bf16<4, 4, DROP, true>, row sums of the packed p) with ONE wave per SIMD and a hand-scheduled
 // tile loop (gen_attn_fwd_asm.py -> attn_fwd_asm.inc).  Workgroup = 4 waves x 4 query tiles = 512 queries of one head; the keys
 // stream through LDS in stages of 128 (the compiled kernel's staging, two barriers per stage), and the tile loop of a stage --
 // 16 (key tile, query tile) units = 64 MFMAs, 1 024 vector instructions with dropout -- is ONE asm statement.  It owns v48-v152 and
@@ -1844,7 +1729,7 @@ struct FwdAsmLds {
     static constexpr int TOTAL = BW + 16 * KT * 4;
     static constexpr int QUERIES = 4 * QT * 32, KEYS = KT * 32;
 };
-template <bool DROP, int LAB = 0>     // LAB 1 (measurement only, results invalid): the stage code without the tile loop
+template <bool DROP>
 __global__ __launch_bounds__(256, 1) void k_attn_fwd_asm(FwdArgs a) {
     using L = FwdAsmLds;
     constexpr int QT = L::QT, KT = L::KT;
@@ -1927,7 +1812,6 @@ __global__ __launch_bounds__(256, 1) void k_attn_fwd_asm(FwdArgs a) {
         if constexpr (DROP) stage_col_words<KT>(bw_s, ck, k0);
         __syncthreads();
         if (k0 + L::KEYS < hi) stage_loadN<KT>(regs, kp, a.ld, vp, a.ld, k0 + L::KEYS, a.S);
-        if constexpr (LAB == 1) continue;
 #if GAOT_ATTN_FWD_ASM_LSUM_MFMA
         // (the row sums accumulate in a96-a159 through two MFMAs per unit against a fragment of ones)
         if constexpr (DROP)
@@ -2169,8 +2053,8 @@ extern "C" int gaot_attn_fwd_bf16(const float* qkv, const float* rope_freqs, voi
     // with the maximum-free tile path the kernels need ~150 registers: three waves per SIMD without scratch beat four with it
     // (dropout, S = 16 384, 8 heads: <3,4> 0.550 ms, <4,4> 0.66 ms with 144 B of scratch; before that path <4,4> 0.577 ms)
     // bound-based kernel (128 registers: 4 workgroups per CU), then the adaptive one for the workgroups it flagged
-    // (schedule pins inside the forward's tile -- start of tile / after the exp stream / before the P V products -- were
-    // measured: +-0.5 %, profiles/archive/r4_g_attn_lab.txt; the template parameter stays at 0)
+    // (measured and removed: schedule pins inside the forward's tile -- start of tile / after the exp stream / before the P V
+    // products: +-0.5 %, profiles/archive/r4_g_attn_lab.txt)
     // (a keep-bit image -- the forward also writing one 32-bit word of keep bits per (query, 32-key tile) for the backward to read
     // through scalar loads -- measured as its two halves, profiles/archive/r4_w_keep_bit_image_lab.txt: WRITING the words (8 and-or steps,
     // one cross-half combine, one 128-byte store per wave and tile) costs the forward 0.516 -> 0.599 ms; the backward with its masks
@@ -2180,20 +2064,13 @@ extern "C" int gaot_attn_fwd_bf16(const float* qkv, const float* rope_freqs, voi
     // forward waits on; profiles/archive/r4_t_attn_fwd_dma_lab.txt; removed)
     // row sums of the bound-based tile: with dropout one v_dot2c_f32_bf16 per pair of the packed p (-2 %: 0.524 -> 0.514 ms per layer,
     // profiles/archive/r5_l_attn_fwd_rowsum_lab.txt), without dropout the 16 fp32 adds (no difference measured there).
-    // GAOT_ATTN_FWD_LAB = 1 / 8 forces the adds / the dot products for both (measurement only).
-    static const int fwd_lab = [] { const char* e = getenv("GAOT_ATTN_FWD_LAB"); return e ? atoi(e) : 0; }();
-    const bool dot2 = fwd_lab == 8 || (fwd_lab != 1 && a.drop.thr);
     // launches with S a multiple of 512 and at least half a workgroup per CU (key-range parts included): the one-wave-per-SIMD kernel
     // with the generated tile loop (k_attn_fwd_asm) does the bound-based pass; GAOT_ATTN_FWD_ASM=0 keeps the compiled kernel (measurement)
     const bool fwd_asm = [] { const char* e = getenv("GAOT_ATTN_FWD_ASM"); return !e || atoi(e) != 0; }();   // read per call: tests switch it
-    if (fwd_asm && fwd_lab == 0 && S % FwdAsmLds::QUERIES == 0 && (P == 1 || a.chunk % FwdAsmLds::KEYS == 0) &&
+    if (fwd_asm && S % FwdAsmLds::QUERIES == 0 && (P == 1 || a.chunk % FwdAsmLds::KEYS == 0) &&
         (int64_t)(S / FwdAsmLds::QUERIES) * H * B * fgrid.y >= 128) {
         const dim3 agrid((unsigned)((S / FwdAsmLds::QUERIES) * H), fgrid.y, (unsigned)B);
-        static const int asm_lab = [] { const char* e = getenv("GAOT_ATTN_FWD_ASM_LAB"); return e ? atoi(e) : 0; }();
-        if (asm_lab == 1) {
-            if (a.drop.thr) GAOT_KLAUNCH((k_attn_fwd_asm<true, 1>), agrid, dim3(256), 0, st, a);
-            else GAOT_KLAUNCH((k_attn_fwd_asm<false, 1>), agrid, dim3(256), 0, st, a);
-        } else if (a.drop.thr) {
+        if (a.drop.thr) {
             GAOT_KLAUNCH((k_attn_fwd_asm<true>), agrid, dim3(256), 0, st, a);
             GAOT_KLAUNCH((k_attn_fwd_bf16<3, 4, true, false>), fgrid, dim3(256), 0, st, a);
         } else {
@@ -2201,12 +2078,10 @@ extern "C" int gaot_attn_fwd_bf16(const float* qkv, const float* rope_freqs, voi
             GAOT_KLAUNCH((k_attn_fwd_bf16<3, 4, false, false>), fgrid, dim3(256), 0, st, a);
         }
     } else if (a.drop.thr) {
-        if (dot2) GAOT_KLAUNCH((k_attn_fwd_bf16<4, 4, true, true, 8>), fgrid, dim3(256), 0, st, a);
-        else GAOT_KLAUNCH((k_attn_fwd_bf16<4, 4, true, true>), fgrid, dim3(256), 0, st, a);
+        GAOT_KLAUNCH((k_attn_fwd_bf16<4, 4, true, true>), fgrid, dim3(256), 0, st, a);
         GAOT_KLAUNCH((k_attn_fwd_bf16<3, 4, true, false>), fgrid, dim3(256), 0, st, a);
     } else {
-        if (dot2) GAOT_KLAUNCH((k_attn_fwd_bf16<4, 4, false, true, 8>), fgrid, dim3(256), 0, st, a);
-        else GAOT_KLAUNCH((k_attn_fwd_bf16<4, 4, false, true>), fgrid, dim3(256), 0, st, a);
+        GAOT_KLAUNCH((k_attn_fwd_bf16<4, 4, false, true>), fgrid, dim3(256), 0, st, a);
         GAOT_KLAUNCH((k_attn_fwd_bf16<3, 4, false, false>), fgrid, dim3(256), 0, st, a);
     }
     if (P > 1)
@@ -2263,11 +2138,7 @@ extern "C" int gaot_attn_bwd_bf16(const void* qkv_image, const float* o, const f
         af.dqkv = Pf > 1 ? parts : dqkv;      // dK / dV of a query part go to its own copy, summed below
         af.chunk = chunk_f;
         af.dqkv_part = dqkv_part;
-        static const int lab = [] { const char* e = getenv("GAOT_ATTN_BWD_LAB"); return e ? atoi(e) : 0; }();   // lab: schedule pins
-        FusedArgs fa{af, dqpart, nslab, lab, nullptr};
-        static const bool want_stamps = [] { const char* e = getenv("GAOT_ATTN_BWD_STAMPS"); return e && atoi(e) != 0; }();
-        static unsigned long long* stamp_buf = nullptr;
-        const size_t stamp_n = (size_t)nslab * HKV * B * nyf * 8 * 16;
+        FusedArgs fa{af, dqpart, nslab};
         const dim3 gf((unsigned)(nslab * HKV), nyf, (unsigned)B);
         auto go = [&](auto kern, int lds_bytes, int nthr) -> int {
             hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
@@ -2279,53 +2150,23 @@ extern "C" int gaot_attn_bwd_bf16(const void* qkv_image, const float* o, const f
             return GAOT_OK;
         };
         if (phase_mask & 16) {
-            // lab switch (measurement only): GAOT_ATTN_BWD_VARIANT = 0 (the shipped form: 8 waves x 2 key blocks, 64-query stages,
-            // packed row words + SDWA compares), 1 (4 waves x 4 key blocks, one wave per SIMD), 7 (round-3 mask arithmetic);
-            // GAOT_ATTN_BWD_STAMPS=1: the diagnostic instantiation with in-kernel cycle stamps (results unchanged, slower)
-            static const int variant = [] { const char* e = getenv("GAOT_ATTN_BWD_VARIANT"); return e ? atoi(e) : 0; }();
-            int rc;
             // k_attn_bwd_asm (one wave per SIMD, hand-scheduled tile loop, dS transposed on the matrix pipe with dropout / through LDS
             // without) is the default for whole-sequence launches: same box, S = 16 384, H = 8 (profiles/archive/r5_d_attn_bwd_asm_mfma_t2.txt):
-            // 0.798 against 0.836 ms with dropout (-4.5 %), 0.669 against 0.717 ms without (-6.7 %); dK / dV bit-identical to the compiled
-            // kernel, dQ within 5e-5 of peak (four slots of four key blocks instead of eight of two).  Few heads per launch: query-range
-            // parts as in the compiled kernel (ranges that are multiples of 128 queries; others keep the compiled kernel).  GAOT_ATTN_BWD_VARIANT=2 forces the asm kernel, =3 the compiled one.
-            if ((variant == 2 || (variant == 0 && lab == 0 && !want_stamps)) && (nyf == 1 || chunk_f % AsmLds<true>::QS == 0)) {
-                if (lab == 1) rc = drop ? go(k_attn_bwd_asm<true, 1>, AsmLds<true>::TOTAL, 256) : go(k_attn_bwd_asm<false, 1>, AsmLds<false>::TOTAL, 256);
-                else if (lab == 2) rc = drop ? go(k_attn_bwd_asm<true, 2>, AsmLds<true>::TOTAL, 256) : go(k_attn_bwd_asm<false, 2>, AsmLds<false>::TOTAL, 256);
-                else if (lab == 3) rc = drop ? go(k_attn_bwd_asm<true, 3>, AsmLds<true>::TOTAL, 256) : go(k_attn_bwd_asm<false, 3>, AsmLds<false>::TOTAL, 256);
-                else rc = drop ? go(k_attn_bwd_asm<true>, AsmLds<true>::TOTAL, 256) : go(k_attn_bwd_asm<false>, AsmLds<false>::TOTAL, 256);
-            }
-            else if (variant == 1)       // one wave per SIMD, compiler-managed 512 registers: 1.9 / 1.27 ms (profiles/archive/r4_b_attn_bwd_lab.txt)
-                rc = drop ? go(k_attn_bwd_fused<true, 4, 4, 2>, FusedLds<4, 4, 2>::TOTAL, 256) : go(k_attn_bwd_fused<false, 4, 4, 2>, FusedLds<4, 4, 2>::TOTAL, 256);
-            // (128-query stages with bf16 slots -- FB_NT = 4 -- measured 1.07 / 0.81 ms against 0.90 / 0.76: spills in the
-            // dropout variant, profiles/archive/r4_g_attn_lab.txt; removed)
-            else if (variant == 7 && drop)   // round-3 mask arithmetic (row words per query, xor + compare per element)
-                rc = go(k_attn_bwd_fused<true, 8, 2, 2, false, 0, 26>, FusedLds<8, 2, 2>::TOTAL, 512);
-            else if (want_stamps && drop) {    // diagnostic build: cycles per phase of the PK kernel, printed to stderr
-                if (!stamp_buf) (void)hipMalloc((void**)&stamp_buf, stamp_n * 8);
-                fa.stamps = stamp_buf;
-                rc = go(k_attn_bwd_fused<true, 8, 2, 2, true, 2, 26>, FusedLds<8, 2, 2>::TOTAL, 512);
-                if (rc == GAOT_OK && stamp_buf) {
-                    (void)hipStreamSynchronize(st);
-                    unsigned long long* h = (unsigned long long*)malloc(stamp_n * 8);
-                    (void)hipMemcpy(h, stamp_buf, stamp_n * 8, hipMemcpyDeviceToHost);
-                    double sum[16] = {0}, lo[16] = {0}, hi[16] = {0};   // all waves / waves 0-3 / waves 4-7
-                    const size_t nw = stamp_n / 16;
-                    for (size_t w = 0; w < nw; ++w)
-                        for (int i = 0; i < 16; ++i) { sum[i] += (double)h[w * 16 + i]; ((w & 7) < 4 ? lo : hi)[i] += (double)h[w * 16 + i]; }
-                    double tot = 0;
-                    for (int i = 0; i < 16; ++i) tot += sum[i];
-                    fprintf(stderr, "[attn_bwd stamps] mean cycles per wave %.0f;", tot / nw);
-                    for (int i = 0; i < 10; ++i) fprintf(stderr, " s%d %.1f%% (w0-3 %.1f%% w4-7 %.1f%%)", i, 100 * sum[i] / tot, 200 * lo[i] / tot, 200 * hi[i] / tot);
-                    fprintf(stderr, "\n");
-                    free(h);
-                }
-            }
-
-            else if (lab == 200)      // TT: dS transposed on the matrix pipe
-                rc = drop ? go(k_attn_bwd_fused<true, 8, 2, 2, true, 0, 26, true>, FusedLds<8, 2, 2>::TOTAL, 512) : go(k_attn_bwd_fused<false, 8, 2, 2, false, 0, 26, true>, FusedLds<8, 2, 2>::TOTAL, 512);
-            else if (lab == 100)      // no schedule pins (the round-3 / r4_d schedule)
-                rc = drop ? go(k_attn_bwd_fused<true, 8, 2, 2, true, 0, 0>, FusedLds<8, 2, 2>::TOTAL, 512) : go(k_attn_bwd_fused<false, 8, 2, 2, false, 0, 0>, FusedLds<8, 2, 2>::TOTAL, 512);
+            // 0.798 against 0.836 ms with dropout (-4.5 %), 0.669 against 0.717 ms without (-6.7 %); without dropout dK / dV are bit-identical
+            // to the compiled kernel's (with dropout its dS = p (-delta') + (keep p) dP' form rounds differently), dQ within 5e-5 of peak at
+            // S = 16 384 (four slots of four key blocks instead of eight of two; at S = 1024 one flipped bf16 rounding of a slab partial
+            // is 2e-3 of peak: test_attention_backward_asm_kernel_equals_compiled_kernel).  Few heads per launch: query-range
+            // parts as in the compiled kernel (ranges that are multiples of 128 queries; others keep the compiled kernel).
+            // GAOT_ATTN_BWD_ASM=0 keeps the compiled kernel (k_attn_bwd_fused: 8 waves x 2 key blocks, 64-query stages, schedule pinned
+            // at the top of a tile, after the exp / mask stream and after the dQ products)
+            const bool bwd_asm = [] { const char* e = getenv("GAOT_ATTN_BWD_ASM"); return !e || atoi(e) != 0; }();   // read per call: tests switch it
+            int rc;
+            if (bwd_asm && (nyf == 1 || chunk_f % AsmLds<true>::QS == 0))
+                rc = drop ? go(k_attn_bwd_asm<true>, AsmLds<true>::TOTAL, 256) : go(k_attn_bwd_asm<false>, AsmLds<false>::TOTAL, 256);
+            else
+                rc = drop ? go(k_attn_bwd_fused<true>, FusedLds::TOTAL, 512) : go(k_attn_bwd_fused<false>, FusedLds::TOTAL, 512);
+            // (measured and removed: 128-query stages with bf16 slots -- four query tiles per stage -- 1.07 / 0.81 ms against 0.90 / 0.76:
+            // spills in the dropout variant, profiles/archive/r4_g_attn_lab.txt)
             // (compile-time priority variants on the pinned schedule -- waves >= W/2 one level higher, static priority without
             // flips, no priority at all -- measured within +-1.5 % of the flips: profiles/archive/r4_h_attn_bwd_prio_stamps.txt)
             // (double-buffered stage tiles filled by the first half of the waves before the stage barrier -- to use their 17 % of
@@ -2335,8 +2176,6 @@ extern "C" int gaot_attn_bwd_bf16(const void* qkv_image, const float* o, const f
             // not; the nops are not what the stream waits on -- profiles/archive/r4_o_attn_bwd_asm_group_lab.txt; removed)
             // (all S products before the dP products, with and without a pin behind the cluster, and a pin after the dV / dK block:
             // within +-1 % -- profiles/archive/r4_k_attn_bwd_cluster_order_lab.txt)
-            else                      // shipped: schedule pinned at the top of a tile, after the exp / mask stream and after the dQ products
-                rc = drop ? go(k_attn_bwd_fused<true, 8, 2, 2, true, 0, 26>, FusedLds<8, 2, 2>::TOTAL, 512) : go(k_attn_bwd_fused<false, 8, 2, 2, false, 0, 26>, FusedLds<8, 2, 2>::TOTAL, 512);
             if (rc != GAOT_OK) return rc;
         }
         if ((phase_mask & 16) && Pf > 1)   // dK / dV columns: sum of the query parts, part order

@@ -21,17 +21,6 @@ namespace {
 typedef unsigned short bf16_t;
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-// lab only (tools/lab/ffn_fwd_lab.hip): ablation bits -- 1: the weight ring is loaded once and never refilled; 4: u = a (no SwiGLU
-// arithmetic); 8: the activation / u fragments are read from LDS once per chunk phase; 16: no barrier in the chunk loop
-#ifndef GAOT_FFN_ABL
-#define GAOT_FFN_ABL 0
-#endif
-#ifdef GAOT_FFN_TIMING      // lab only: s_memtime stamps of workgroup 0 / wave 0 at the phase boundaries
-__device__ unsigned long long g_ffn_t[64];
-#define FFN_STAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) g_ffn_t[i] = __builtin_readcyclecounter(); } while (0)
-#else
-#define FFN_STAMP(i) do { } while (0)
-#endif
 constexpr int D = 256, RB = 64, FC = 128;          // d_model, rows per workgroup, F columns per chunk
 constexpr int H_BYTES = RB * D * 2;                // activation tile: 64 rows x 512 B
 constexpr int U_BYTES = RB * FC * 2;               // one u chunk: 64 rows x 256 B
@@ -150,7 +139,6 @@ __global__ __launch_bounds__(256, 1) void k_ffn_fwd(const bf16_t* __restrict__ X
     const int t = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
     if ((int)(blockIdx.x >> 3) >= per || t >= nblk) return;
     const int m0 = t * RB, NC = F / FC;
-    FFN_STAMP(0);
     constexpr int LA = RD - 1;
     static_assert(6 % RD == 0, "the ring is indexed by the position within the loop body");
 
@@ -173,9 +161,7 @@ __global__ __launch_bounds__(256, 1) void k_ffn_fwd(const bf16_t* __restrict__ X
     const int wv = __builtin_amdgcn_readfirstlane(wave);
     const __amdgpu_buffer_rsrc_t w13rs = __builtin_amdgcn_make_buffer_rsrc((void*)W13p, 0, 2 * F * D * 2, 0x00020000);
     const __amdgpu_buffer_rsrc_t w2rs = __builtin_amdgcn_make_buffer_rsrc((void*)W2p, 0, D * F * 2, 0x00020000);
-    bool wfirst = true;
     auto wload = [&](u32x4 (&dst)[8], int c, int st) {
-        if ((GAOT_FFN_ABL & 1) && !wfirst) return;
         if (st < 4) {
 #pragma unroll
             for (int jt = 0; jt < 2; ++jt)
@@ -204,7 +190,6 @@ __global__ __launch_bounds__(256, 1) void k_ffn_fwd(const bf16_t* __restrict__ X
         if (p < 4) wload(wr[p % RD], 0, p);
         else prefetch_body(0, p - 4);
     }
-    if (GAOT_FFN_ABL & 1) { wload(wr[LA % RD], 0, 0); wfirst = false; }
 
     float* rstd_l = reinterpret_cast<float*>(lds + H_BYTES + 2 * U_BYTES + (SAVE ? 2 * AG_BYTES : 0));      // NORM: 64 floats (+ OPROJ: 4 x 64)
     if constexpr (OPROJ) {
@@ -371,7 +356,6 @@ __global__ __launch_bounds__(256, 1) void k_ffn_fwd(const bf16_t* __restrict__ X
                                                                 // drain here would sit out the round trip of their h / yb stores to HBM)
     }
     __builtin_amdgcn_s_barrier();
-    FFN_STAMP(1);
 
     f32x16 y[2][2], agc[2][2], agn[2][2];
 #pragma unroll
@@ -387,11 +371,9 @@ __global__ __launch_bounds__(256, 1) void k_ffn_fwd(const bf16_t* __restrict__ X
     // one 16-deep k-step (ks = 0..15) of the a | g product into acc, with the NEXT k-step's activation fragments requested first
     auto ag_kstep = [&](f32x16 (&acc)[2][2], const u32x4 (&w)[8], int ks) {
         const bf16x8 h0 = hn0, h1 = hn1;
-        if (!(GAOT_FFN_ABL & 8) || ks == 15) {
-            const int slot = ((2 * ((ks + 1) & 15) + hf) ^ sw) << 4;
-            hn0 = *reinterpret_cast<const bf16x8*>(hb + slot);
-            hn1 = *reinterpret_cast<const bf16x8*>(hb + 32 * 512 + slot);
-        }
+        const int slot = ((2 * ((ks + 1) & 15) + hf) ^ sw) << 4;
+        hn0 = *reinterpret_cast<const bf16x8*>(hb + slot);
+        hn1 = *reinterpret_cast<const bf16x8*>(hb + 32 * 512 + slot);
         const bf16x8 wa = __builtin_bit_cast(bf16x8, w[ks & 3]), wg = __builtin_bit_cast(bf16x8, w[4 + (ks & 3)]);
         acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa, h0, acc[0][0], 0, 0, 0);
         acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wg, h0, acc[1][0], 0, 0, 0);
@@ -409,7 +391,6 @@ __global__ __launch_bounds__(256, 1) void k_ffn_fwd(const bf16_t* __restrict__ X
         for (int s = 0; s < 4; ++s) ag_kstep(agc, wr[st % RD], 4 * st + s);
     }
 
-    FFN_STAMP(2);
     for (int c = 0; c < NC; ++c) {
         char* ub = lds + H_BYTES + (c & 1) * U_BYTES;
         char* agb = lds + H_BYTES + 2 * U_BYTES + (c & 1) * AG_BYTES;
@@ -442,22 +423,18 @@ __global__ __launch_bounds__(256, 1) void k_ffn_fwd(const bf16_t* __restrict__ X
             // breadth first: no instruction reads its predecessor's result (a dependent v_exp_f32 / v_rcp_f32 chain stalls the wave's
             // one issue port for the latency of each link, and with it the MFMAs queued behind)
             float o[2], t[2];
-            if (GAOT_FFN_ABL & 4) {
-                o[0] = av[0]; o[1] = av[1];
-            } else {
 #pragma unroll
-                for (int e = 0; e < 2; ++e) t[e] = -1.4426950408889634f * av[e];
+            for (int e = 0; e < 2; ++e) t[e] = -1.4426950408889634f * av[e];
 #pragma unroll
-                for (int e = 0; e < 2; ++e) t[e] = __builtin_amdgcn_exp2f(t[e]);
+            for (int e = 0; e < 2; ++e) t[e] = __builtin_amdgcn_exp2f(t[e]);
 #pragma unroll
-                for (int e = 0; e < 2; ++e) t[e] = 1.0f + t[e];
+            for (int e = 0; e < 2; ++e) t[e] = 1.0f + t[e];
 #pragma unroll
-                for (int e = 0; e < 2; ++e) t[e] = __builtin_amdgcn_rcpf(t[e]);
+            for (int e = 0; e < 2; ++e) t[e] = __builtin_amdgcn_rcpf(t[e]);
 #pragma unroll
-                for (int e = 0; e < 2; ++e) o[e] = av[e] * t[e];
+            for (int e = 0; e < 2; ++e) o[e] = av[e] * t[e];
 #pragma unroll
-                for (int e = 0; e < 2; ++e) o[e] = o[e] * gv[e];
-            }
+            for (int e = 0; e < 2; ++e) o[e] = o[e] * gv[e];
             pu[ps][pw][h] = pack2(o[0], o[1]);
         };
         auto finish = [&](int i, int q, int ps) {       // units (i, q) [pw 0] and (i, q + 2) [pw 1]
@@ -515,9 +492,7 @@ __global__ __launch_bounds__(256, 1) void k_ffn_fwd(const bf16_t* __restrict__ X
             }
         }
         __builtin_amdgcn_sched_barrier(0);
-        FFN_STAMP(3 + 3 * c);
-        if (!(GAOT_FFN_ABL & 16)) __builtin_amdgcn_s_barrier();
-        FFN_STAMP(4 + 3 * c);     // the chunk's u is complete; the other buffer's readers (chunk c - 1) are all past their reads
+        __builtin_amdgcn_s_barrier();     // the chunk's u is complete; the other buffer's readers (chunk c - 1) are all past their reads
         // ---- y += u chunk W2c^T: two 64-deep steps ----
         bf16x8 un0 = *reinterpret_cast<const bf16x8*>(ub + l31 * 256 + ((hf ^ sw) << 4)), un1 = *reinterpret_cast<const bf16x8*>(ub + (32 + l31) * 256 + ((hf ^ sw) << 4));
 #pragma unroll
@@ -526,7 +501,7 @@ __global__ __launch_bounds__(256, 1) void k_ffn_fwd(const bf16_t* __restrict__ X
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 const bf16x8 u0 = un0, u1 = un1;
-                if (4 * (st - 4) + s + 1 < 8 && !(GAOT_FFN_ABL & 8)) {
+                if (4 * (st - 4) + s + 1 < 8) {
                     const int slot = ((2 * (4 * (st - 4) + s + 1) + hf) ^ sw) << 4;
                     un0 = *reinterpret_cast<const bf16x8*>(ub + l31 * 256 + slot);
                     un1 = *reinterpret_cast<const bf16x8*>(ub + (32 + l31) * 256 + slot);
@@ -564,7 +539,6 @@ __global__ __launch_bounds__(256, 1) void k_ffn_fwd(const bf16_t* __restrict__ X
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int jt = 0; jt < 2; ++jt) agc[jt][i] = agn[jt][i];
-        FFN_STAMP(5 + 3 * c);
     }
     // ---- y (+ residual): column 64 wave + 32 jt + mfma32_row(r, hf), row m0 + 32 i + l31 ----
 #pragma unroll
@@ -587,14 +561,10 @@ __global__ __launch_bounds__(256, 1) void k_ffn_fwd(const bf16_t* __restrict__ X
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), yrs, rowoff + (wave * 64 + 32 * jt + 8 * q + 4 * hf) * 4, 0, 0);
             }
     }
-    FFN_STAMP(40);
 }
 
 constexpr int FWD_LDS = H_BYTES + 2 * U_BYTES, FWD_LDS_SAVE = FWD_LDS + 2 * AG_BYTES;
-#ifndef GAOT_FFN_FWD_RING
-#define GAOT_FFN_FWD_RING 3
-#endif
-constexpr int FWD_RING = GAOT_FFN_FWD_RING;
+constexpr int FWD_RING = 3;
 
 template <bool SAVE, bool NORM, bool OPROJ = false>
 int launch_ffn_fwd(const void* x, const void* w13p, const void* w2p, const float* r, float* y, void* ag, void* u, int M, int F, int ldr,

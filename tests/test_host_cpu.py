@@ -60,7 +60,7 @@ def test_attn_bwd_asm_include_is_current_and_owns_its_agprs(tmp_path):
                     if int(m.group(1)) < 224:
                         bad.append(ln.strip())
         assert not bad, f"{name}: compiler-generated code touches the asm's AGPRs: {bad[:5]}"
-        assert re.search(r"\.amdhsa_private_segment_fixed_size 0\b", body) or "LAB" in name, f"{name} needs scratch"
+        assert re.search(r"\.amdhsa_private_segment_fixed_size 0\b", body), f"{name} needs scratch"
     # the forward's generated tile loop (k_attn_fwd_asm): same contract for its include and its a0-a95 (Q fragments, O^T accumulators)
     gen = subprocess.run([sys.executable, os.path.join(csrc, "gen_attn_fwd_asm.py")], capture_output=True, text=True, check=True,
                          env={k: v for k, v in os.environ.items() if not k.startswith("GEN_")}).stdout
@@ -84,7 +84,7 @@ def test_attn_bwd_asm_include_is_current_and_owns_its_agprs(tmp_path):
 
 def test_hot_path_kernels_need_no_scratch(tmp_path):
     """No kernel of the shipped path may need scratch memory (spilled registers / private arrays): the code objects' metadata is
-    read from the built library.  Known exceptions are variants off the default path (lab / fallback instantiations)."""
+    read from the built library.  Known exceptions are variants off the default path (fallback instantiations)."""
     import re, shutil, subprocess
     from gaot_3d_amd import _lib
     objdump, readelf = "/opt/rocm/lib/llvm/bin/llvm-objdump", "/opt/rocm/lib/llvm/bin/llvm-readelf"
@@ -98,8 +98,7 @@ def test_hot_path_kernels_need_no_scratch(tmp_path):
     subprocess.run([objdump, "--offloading", str(work / "lib.so")], check=True, capture_output=True, cwd=work)
     objs = sorted(f for f in os.listdir(work) if "gfx950" in f)
     assert objs, "no gfx950 code object found in the library"
-    allowed = ("k_attn_bwd_fusedILb1ELi4ELi4E",          # one-wave-per-SIMD lab variant (GAOT_ATTN_BWD_VARIANT=1)
-               "k_attn_bwd_dkv_bf16ILi4E", "k_attn_bwd_dq_bf16ILi4E",   # two-pass fallback, four workgroups per CU
+    allowed = ("k_attn_bwd_dkv_bf16ILi4E", "k_attn_bwd_dq_bf16ILi4E",   # two-pass fallback, four workgroups per CU
                "k_gno_bwdILi3ELi64E",                      # fp32-mode GNO backward, three hidden layers
                "k_gno_bwd3_bf16ILi4E")                      # four hidden layers: fragments from L2, 85 spilled registers
     seen, offenders = 0, []

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Run the bf16 attention backward on fixed inputs and save d(q|k|v): two runs with different GAOT_ATTN_BWD_VARIANT values are
-compared with `cmp` mode.  usage: attn_bwd_variant_check.py run <out.pt> | cmp <a.pt> <b.pt>"""
+"""Run the bf16 attention backward on fixed inputs (full-size sequences) and save d(q|k|v): a run with GAOT_ATTN_BWD_ASM unset (the
+hand-scheduled kernel where eligible) and one with GAOT_ATTN_BWD_ASM=0 (the compiled kernel) are compared with `cmp` mode.  usage: attn_bwd_variant_check.py run <out.pt> | cmp <a.pt> <b.pt>"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
