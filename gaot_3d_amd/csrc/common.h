@@ -46,6 +46,10 @@ extern long long g_gaot_launches;
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// gemm.hip: the split-K plan gaot_gemm takes for the weight-gradient product dW[m][n] = sum over k rows -- `splits` ranges of kps
+// rows, completed with `lanes` part-lanes (rowlinear.hip walks the same ranges in the same order)
+void gaot_gemm_dw_plan(int64_t m, int64_t n, int64_t k, int* splits, int64_t* kps, int* lanes);
+
 // Row of a 32x32 MFMA C/D tile held in register r (0..15) of a lane in half h (lane>>5):
 // row = (r&3) + 8*(r>>2) + 4*h ; column = lane&31.   (dtype independent on gfx950)
 __device__ __forceinline__ constexpr int mfma32_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }

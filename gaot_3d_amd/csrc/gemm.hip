@@ -349,6 +349,16 @@ static GemmPlan plan_gemm(int64_t M, int64_t N, int64_t K, int bk = BK) {
     return p;
 }
 
+// part-lanes of the split-K completion (k_splitk_reduce<16> / <64>, gaot_reduce_multi): 16 for the small per-point weight gradients
+// cut into many splits, else 4 -- the ONE place that decides it
+static int splitk_lanes(int splits, int64_t mn) { return (splits >= 64 && mn <= 32768) ? 16 : 4; }
+
+// the split-K plan of a weight-gradient product for kernels that walk the same row ranges in the same order (rowlinear.hip)
+void gaot_gemm_dw_plan(int64_t m, int64_t n, int64_t k, int* splits, int64_t* kps, int* lanes) {
+    const GemmPlan p = plan_gemm(m, n, k);
+    *splits = p.splits; *kps = p.kps; *lanes = splitk_lanes(p.splits, m * n);
+}
+
 extern "C" size_t gaot_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K) {
     const GemmPlan p = plan_gemm(M, N, K);   // the 64-deep bf16 tiling never needs more splits than this
     return p.splits > 1 ? sizeof(float) * (size_t)(p.splits * M * N) + 64 : 0;
@@ -396,9 +406,9 @@ static int gemm_impl(const void* A, const void* B, void* C, int64_t M, int64_t N
     else launch_cfg<2, 2, 2, 2>(gk, a_trans, b_trans, precision, a_vec, b_vec, gk.splits, st);
     if (gk.splits > 1 && defer_splits) {      // the caller sums the partials later (gaot_reduce_multi), in the order k_splitk_reduce would
         *defer_splits = gk.splits;
-        *defer_lanes = (gk.splits >= 64 && M * N <= 32768) ? 16 : 4;
+        *defer_lanes = splitk_lanes(gk.splits, M * N);
     } else if (gk.splits > 1) {
-        if (gk.splits >= 64 && M * N <= 32768)
+        if (splitk_lanes(gk.splits, M * N) == 16)
             GAOT_KLAUNCH(k_splitk_reduce<16>, dim3((unsigned)ceil_div(M * N, 16)), dim3(256), 0, st, part, gk.splits, g);
         else
             GAOT_KLAUNCH(k_splitk_reduce<64>, dim3((unsigned)ceil_div(M * N, 64)), dim3(256), 0, st, part, gk.splits, g);

@@ -131,7 +131,8 @@ __global__ __launch_bounds__(256, 2) void k_mlp2_fwd(Mlp2Args a, float* __restri
     }
 }
 
-// per-workgroup partial layout: dW1^T? no -- dW1 [H][32], then db1 [H], then dW2 [OC][H]
+// weight-gradient partials: three tables [workgroup][H * 32] (dW1), [workgroup][H] (db1), [workgroup][OC * H] (dW2), one behind the
+// other for gridDim.x workgroups -- each the [parts][n] table gaot_reduce_multi sums
 template <int NOB, int OC>
 __global__ __launch_bounds__(256, 1) void k_mlp2_bwd(Mlp2Args a, const float* __restrict__ dout, float* __restrict__ dx,
                                                      float* __restrict__ wpart) {
@@ -273,37 +274,23 @@ __global__ __launch_bounds__(256, 1) void k_mlp2_bwd(Mlp2Args a, const float* __
             }
         }
     }
-    // workgroup partial: dW1 [H][32] | db1 [H] | dW2 [OC][H]
-    float* wp = wpart + (int64_t)blockIdx.x * (H * MLP_IN + H + OC * H);
+    float* wp1 = wpart + (int64_t)blockIdx.x * (H * MLP_IN);
+    float* wpb = wpart + (int64_t)gridDim.x * (H * MLP_IN) + (int64_t)blockIdx.x * H;
+    float* wp2 = wpart + (int64_t)gridDim.x * (H * MLP_IN + H) + (int64_t)blockIdx.x * (OC * H);
 #pragma unroll
     for (int o = 0; o < OBW; ++o) {
         const int ob = wave * OBW + o;
         if (ob >= NOB) continue;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) wp[(int64_t)(32 * ob + l31) * MLP_IN + mfma32_row(r, hf)] = dw1t[o][r];   // [j][k]
+        for (int r = 0; r < 16; ++r) wp1[(int64_t)(32 * ob + l31) * MLP_IN + mfma32_row(r, hf)] = dw1t[o][r];   // [j][k]
         const float d1 = db1[o] + __shfl_xor(db1[o], 32, 64);
-        if (hf == 0) wp[H * MLP_IN + 32 * ob + l31] = d1;
+        if (hf == 0) wpb[32 * ob + l31] = d1;
 #pragma unroll
         for (int c = 0; c < OC; ++c) {
             const float d2 = dw2[o][c] + __shfl_xor(dw2[o][c], 32, 64);
-            if (hf == 0) wp[H * MLP_IN + H + c * H + 32 * ob + l31] = d2;
+            if (hf == 0) wp2[c * H + 32 * ob + l31] = d2;
         }
     }
-}
-
-// out[i] = sum over workgroups of part[g * stride + i], i < count: a workgroup owns 64 outputs, its 4 waves each sum
-// every 4th partial, the 4 sums are added in wave order (fixed order -> bit-reproducible)
-__global__ __launch_bounds__(256) void k_mlp2_reduce(const float* __restrict__ part, int groups, int64_t stride, int64_t count,
-                                                     float* __restrict__ out) {
-    __shared__ float red[4][64];
-    const int o = threadIdx.x & 63, sl = threadIdx.x >> 6;
-    const int64_t i = (int64_t)blockIdx.x * 64 + o;
-    float s = 0.f;
-    if (i < count)
-        for (int g = sl; g < groups; g += 4) s += part[(int64_t)g * stride + i];
-    red[sl][o] = s;
-    __syncthreads();
-    if (sl == 0 && i < count) out[i] = ((red[0][o] + red[1][o]) + red[2][o]) + red[3][o];
 }
 
 constexpr size_t bwd_lds_bytes(int nob, int oc) {
@@ -382,17 +369,20 @@ extern "C" size_t gaot_mlp2_bwd_workspace_bytes(int hidden, int out_dim) {
     return sizeof(float) * (size_t)MLP_BWD_GRID * (hidden * MLP_IN + hidden + out_dim * hidden) + 64;
 }
 
+extern "C" int64_t gaot_mlp2_bwd_parts(int64_t num_rows) {
+    return std::max<int64_t>(1, std::min<int64_t>(ceil_div(num_rows, MLP_ROWS), MLP_BWD_GRID));
+}
+
 extern "C" int gaot_mlp2_bwd(const float* x, int64_t num_rows, int in_dim, int hidden, int out_dim, const float* w1,
                              const float* b1, const float* w2, const float* d_out, float* d_x, float* d_w1, float* d_b1,
                              float* d_w2, void* workspace, size_t workspace_bytes, gaot_stream_t stream) {
     GAOT_ENTER();
     GAOT_CHECK_ARG(num_rows >= 0, "negative size");
     if (int rc = check_shape(in_dim, hidden, out_dim)) return rc;
-    GAOT_CHECK_ARG(w1 && b1 && w2 && d_w1 && d_b1 && d_w2, "null pointer");
+    GAOT_CHECK_ARG(w1 && b1 && w2 && ((d_w1 && d_b1 && d_w2) || (!d_w1 && !d_b1 && !d_w2)), "null pointer");
     GAOT_CHECK_ARG(workspace && workspace_bytes >= gaot_mlp2_bwd_workspace_bytes(hidden, out_dim), "workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    const int64_t np = (int64_t)hidden * MLP_IN + hidden + (int64_t)out_dim * hidden;
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(num_rows, MLP_ROWS), MLP_BWD_GRID));
+    const int grid = (int)gaot_mlp2_bwd_parts(num_rows);
     float* wpart = (float*)workspace;
     if (num_rows > 0) {
         GAOT_CHECK_ARG(x && d_out && d_x, "null pointer");
@@ -402,11 +392,11 @@ extern "C" int gaot_mlp2_bwd(const float* x, int64_t num_rows, int in_dim, int h
     int rc = hidden == 64 ? bwd_oc<2>(a, out_dim, d_out, d_x, wpart, grid, st)
                           : (hidden == 128 ? bwd_oc<4>(a, out_dim, d_out, d_x, wpart, grid, st) : bwd_oc<8>(a, out_dim, d_out, d_x, wpart, grid, st));
     if (rc != GAOT_OK) return rc;
-    // partial layout [dW1 | db1 | dW2] -> the three outputs (contiguous pieces of one reduction)
-    const int64_t n1 = (int64_t)hidden * MLP_IN, n2 = hidden, n3 = (int64_t)out_dim * hidden;
-    GAOT_KLAUNCH(k_mlp2_reduce, dim3((unsigned)ceil_div(n1, 64)), dim3(256), 0, st, wpart, grid, np, n1, d_w1);
-    GAOT_KLAUNCH(k_mlp2_reduce, dim3((unsigned)ceil_div(n2, 64)), dim3(256), 0, st, wpart + n1, grid, np, n2, d_b1);
-    GAOT_KLAUNCH(k_mlp2_reduce, dim3((unsigned)ceil_div(n3, 64)), dim3(256), 0, st, wpart + n1 + n2, grid, np, n3, d_w2);
     GAOT_LAUNCH_CHECK();
-    return GAOT_OK;
+    if (!d_w1) return GAOT_OK;      // the three tables stay in the workspace for gaot_reduce_multi (lanes = 4)
+    // ONE launch sums the three tables: 4 part-lanes each take every 4th workgroup, then ((l0 + l1) + l2) + l3
+    const int64_t n1 = (int64_t)hidden * MLP_IN, n2 = hidden, n3 = (int64_t)out_dim * hidden;
+    const gaot_reduce_desc_t descs[3] = {{wpart, d_w1, n1, grid, 4}, {wpart + grid * n1, d_b1, n2, grid, 4},
+                                         {wpart + grid * (n1 + n2), d_w2, n3, grid, 4}};
+    return gaot_reduce_multi(descs, 3, stream);
 }

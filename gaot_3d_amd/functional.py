@@ -248,6 +248,14 @@ class LinearFn(Function):
         x2 = _rows2d(x, k)
         m = x2.shape[0]
         res = None if residual is None else _rows2d(residual, n, m)
+        ctx.rowlin = res is None and ops.rowlin_ok((x2,), w, bias, act, precision)
+        if ctx.rowlin:      # thin fp32 linear: one pass (csrc/rowlinear.hip); ReLU's backward reads the saved OUTPUT, no pre-activation
+            y = ops.rowlin_forward((x2,), w, bias, act == 2)
+            ctx.save_for_backward(x2, w, y if act else None)
+            ctx.act, ctx.has_bias, ctx.precision = act, bias is not None, precision
+            ctx.wshape, ctx.xshape, ctx.res_shape = weight.shape, x.shape, None
+            ctx.wparam, ctx.bparam = weight, bias
+            return y.view(*x.shape[:-1], n)
         w = _wb(w, precision)
         if act > 3:     # outside the GEMM epilogue's set (ops.ACT): pre-activation from the GEMM, activation as its own pass
             if res is not None:
@@ -272,6 +280,12 @@ class LinearFn(Function):
         n, k = w.shape
         m = x2.shape[0]
         dy2 = _rows2d(dy, n, m)
+        if ctx.rowlin:
+            want_w, want_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+            params = tuple(p for p, want in ((ctx.wparam, want_w), (ctx.bparam, want_b)) if want)
+            (dx,), dw, db = ops.rowlin_backward((x2,), w, dy2, z, ctx.act == 2, (ctx.needs_input_grad[0],),
+                                                defer=bool(params) and ops.defer_ok(params), want_w=want_w, want_b=want_b)
+            return (dx.view(ctx.xshape) if dx is not None else None, dw.view(ctx.wshape) if want_w else None, db, None, None, None)
         dz = ops.act_bwd(z, dy2, ctx.act) if ctx.act else dy2
         dx = dw = db = dres = None
         if ctx.needs_input_grad[0]:
@@ -1063,6 +1077,7 @@ class Mlp2Fn(Function):
         out = ops.mlp2_forward(x2, w1c, b1, w2c, b2)
         ctx.save_for_backward(x2, w1c, b1, w2c)
         ctx.meta = (x.shape, w1.shape, w2.shape, b2 is not None)
+        ctx.params = (w1, b1, w2)       # the parameters themselves: ops.defer_ok
         return out.view(*x.shape[:-1], w2c.shape[0])
 
     @staticmethod
@@ -1070,7 +1085,8 @@ class Mlp2Fn(Function):
         x2, w1c, b1, w2c = ctx.saved_tensors
         xshape, w1shape, w2shape, has_b2 = ctx.meta
         d = _rows2d(dout, w2c.shape[0], x2.shape[0])
-        dx, dw1, db1, dw2 = ops.mlp2_backward(x2, w1c, b1, w2c, d)
+        params = tuple(p for p, want in zip(ctx.params, ctx.needs_input_grad[1:4]) if want)
+        dx, dw1, db1, dw2 = ops.mlp2_backward(x2, w1c, b1, w2c, d, defer=bool(params) and ops.defer_ok(params))
         db2 = ops.colsum(d, d.shape[0], d.shape[1], d.shape[1]) if has_b2 else None
         return dx.view(xshape), dw1.view(w1shape), db1, dw2.view(w2shape), db2
 
@@ -1259,6 +1275,14 @@ class CatLinearFn(Function):
         if sum(x.shape[1] for x in xs2) != k:
             raise GaotError(f"cat_linear: inputs have {sum(x.shape[1] for x in xs2)} features, weight expects {k}")
         m = xs2[0].shape[0]
+        # were two of the inputs the same autograd tensor?  (then a None for the later one is "no further contribution")
+        ctx.dups = any(_same_view(xs[i], xs[j]) for i in range(len(xs)) for j in range(i))
+        ctx.meta = (precision, weight.shape, bias is not None)
+        ctx.wparam, ctx.bparam = weight, bias
+        ctx.rowlin = not ctx.dups and all(x.dim() == 2 for x in xs2) and ops.rowlin_ok(xs2, w, bias, 0, precision)
+        if ctx.rowlin:      # thin fp32 linear: every input row read once, the output written once (csrc/rowlinear.hip)
+            ctx.save_for_backward(w, *xs2)
+            return ops.rowlin_forward(xs2, w, bias, False)
         if all(x.shape[1] > 64 and x.shape[1] % 8 == 0 for x in xs2):
             w = _wb(w, precision)
         y = None
@@ -1269,9 +1293,6 @@ class CatLinearFn(Function):
                          precision=precision)
             col += ki
         ctx.save_for_backward(w, *xs2)
-        ctx.meta = (precision, weight.shape, bias is not None)
-        # were two of the inputs the same autograd tensor?  (then a None for the later one is "no further contribution")
-        ctx.dups = any(_same_view(xs[i], xs[j]) for i in range(len(xs)) for j in range(i))
         return y
 
     @staticmethod
@@ -1281,6 +1302,12 @@ class CatLinearFn(Function):
         n, k = w.shape
         d = dy if dy.is_contiguous() else dy.contiguous()
         m = d.shape[0]
+        if ctx.rowlin:
+            want_w, want_b = ctx.needs_input_grad[0], has_bias and ctx.needs_input_grad[1]
+            params = tuple(p for p, want in ((ctx.wparam, want_w), (ctx.bparam, want_b)) if want)
+            dxs, dw, db = ops.rowlin_backward(xs, w, d, None, False, ctx.needs_input_grad[3:], defer=bool(params) and ops.defer_ok(params),
+                                              want_w=want_w, want_b=want_b)
+            return (dw.view(wshape) if want_w else None, db, None, *dxs)
         dw = torch.empty(n, k, dtype=torch.float32, device=d.device) if ctx.needs_input_grad[0] else None
         dxs = []
         col = 0

@@ -1385,15 +1385,98 @@ def mlp2_forward(x: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Optional[Ten
     return out
 
 
-def mlp2_backward(x: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, dout: Tensor):
+def _finish_tables(ws: Tensor, outs, parts, lanes, defer: bool) -> None:
+    """the fixed-order sums of the [parts][n] partial tables that lie one behind the other in ``ws`` (fp32) into ``outs``: left
+    to flush_deferred (defer) or ONE gaot_reduce_multi launch now -- the same kernel, the same order, the same bits.  ``parts`` /
+    ``lanes``: one int for all tables or one per table"""
+    tab = ws.view(torch.float32)
+    arr = (_ReduceDesc * len(outs))()
+    parts_of = [parts] * len(outs) if isinstance(parts, int) else list(parts)
+    lanes_of = [lanes] * len(outs) if isinstance(lanes, int) else list(lanes)
+    off = 0
+    for j, out in enumerate(outs):
+        n, parts, lanes = out.numel(), parts_of[j], lanes_of[j]
+        if defer:
+            _defer(tab[off:off + parts * n], out, n, parts, lanes)
+        else:
+            arr[j].part, arr[j].out, arr[j].n, arr[j].parts, arr[j].lanes = tab.data_ptr() + 4 * off, out.data_ptr(), n, parts, lanes
+        off += parts * n
+    if not defer:
+        check(_lib.load().gaot_reduce_multi(arr, len(outs), _stream()), "gaot_reduce_multi")
+
+
+def mlp2_backward(x: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, dout: Tensor, defer: bool = False):
+    """-> (dx, dw1, db1, dw2); the three weight gradients are completed by one launch, or (``defer``, see defer_ok) by
+    flush_deferred"""
     lib = _lib.load()
     rows, hid, oc = x.shape[0], w1.shape[0], w2.shape[0]
     dx = torch.empty_like(x)
     dw1, db1, dw2 = torch.empty_like(w1), torch.empty_like(b1), torch.empty_like(w2)
     ws = _ws(lib.gaot_mlp2_bwd_workspace_bytes(hid, oc), x.device)
-    check(lib.gaot_mlp2_bwd(_ptr(x), rows, x.shape[1], hid, oc, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(dout), _ptr(dx), _ptr(dw1),
-                            _ptr(db1), _ptr(dw2), _ptr(ws), ws.numel(), _stream()), "gaot_mlp2_bwd")
+    check(lib.gaot_mlp2_bwd(_ptr(x), rows, x.shape[1], hid, oc, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(dout), _ptr(dx), None, None, None,
+                            _ptr(ws), ws.numel(), _stream()), "gaot_mlp2_bwd")
+    _finish_tables(ws, (dw1, db1, dw2), int(lib.gaot_mlp2_bwd_parts(rows)), 4, defer)
     return dx, dw1, db1, dw2
+
+
+# single-pass thin fp32 linears (csrc/rowlinear.hip).  ROWLIN counts the calls that took them (tests assert the route)
+ROWLIN = {"enabled": True, "fwd": 0, "bwd": 0}
+
+
+def rowlin_ok(xs: Sequence[Tensor], w: Tensor, bias: Optional[Tensor], act: int, precision: Optional[int]) -> bool:
+    """may y = act([xs] w^T + bias) run on the single-pass kernels?  fp32 mode, dense fp32 operands on the GPU, act none / ReLU,
+    a shape inside gaot_rowlin_supported, and no side stream for the weight gradients (comm.set_side_stream)"""
+    from . import comm
+    prec = _PRECISION["mode"] if precision is None else precision
+    if not ROWLIN["enabled"] or prec != 0 or act not in (0, 2) or comm.side_stream() is not None or not 1 <= len(xs) <= 4:
+        return False
+    m = xs[0].shape[0]
+    for t in (*xs, w) + (() if bias is None else (bias,)):
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+            return False
+    if any(x.dim() != 2 or x.shape[0] != m for x in xs) or w.dim() != 2 or w.shape[1] != sum(x.shape[1] for x in xs):
+        return False
+    ks = (C.c_int * len(xs))(*[int(x.shape[1]) for x in xs])
+    return bool(_lib.load().gaot_rowlin_supported(ks, len(xs), int(w.shape[0])))
+
+
+def rowlin_forward(xs: Sequence[Tensor], w: Tensor, bias: Optional[Tensor], relu: bool) -> Tensor:
+    """y [M, N] = act([x_0 | x_1 | ...] w^T + bias) in one launch (include/gaot3d_hip.h: gaot_rowlin_fwd)"""
+    lib = _lib.load()
+    m, n = xs[0].shape[0], w.shape[0]
+    y = torch.empty(m, n, dtype=torch.float32, device=w.device)
+    ks = (C.c_int * len(xs))(*[int(x.shape[1]) for x in xs])
+    check(lib.gaot_rowlin_fwd(_ptr_array(xs), ks, len(xs), _ptr(w), _ptr(bias), m, n, int(relu), _ptr(y), _stream()), "gaot_rowlin_fwd")
+    ROWLIN["fwd"] += 1
+    return y
+
+
+def rowlin_backward(xs: Sequence[Tensor], w: Tensor, dy: Tensor, y: Optional[Tensor], relu: bool, need_dx: Sequence[bool],
+                    defer: bool = False, want_w: bool = True, want_b: bool = True):
+    """-> ([dx_i or None], dw [N, Ktot] or None, db [N] or None) from one walk over the rows of dy (and of the saved output ``y``
+    with ReLU); the wanted ones of dw and db are completed by one launch, or (``defer``, see defer_ok) by flush_deferred -- the
+    same sums either way; the partial rows of an unwanted one are simply dropped"""
+    lib = _lib.load()
+    m, n, dev = xs[0].shape[0], w.shape[0], w.device
+    dxs = [torch.empty_like(x) if need else None for x, need in zip(xs, need_dx)]
+    ROWLIN["bwd"] += 1
+    if m == 0:
+        return (dxs, torch.zeros_like(w) if want_w else None,
+                torch.zeros(n, dtype=torch.float32, device=dev) if want_b else None)
+    dw = torch.empty_like(w) if want_w else None
+    db = torch.empty(n, dtype=torch.float32, device=dev) if want_b else None
+    wp, wl, bp = C.c_int(0), C.c_int(0), C.c_int(0)
+    check(lib.gaot_rowlin_plan(m, n, C.byref(wp), C.byref(wl), C.byref(bp)), "gaot_rowlin_plan")
+    ws = _ws(4 * (wp.value * w.numel() + bp.value * n), dev)
+    tab = ws.view(torch.float32)
+    ks = (C.c_int * len(xs))(*[int(x.shape[1]) for x in xs])
+    check(lib.gaot_rowlin_bwd(_ptr_array(xs), ks, len(xs), _ptr(w), _ptr(dy), _ptr(y) if relu else None, m, n, int(relu), _ptr_array(dxs),
+                              _ptr(tab), C.c_void_p(tab.data_ptr() + 4 * wp.value * w.numel()), _stream()), "gaot_rowlin_bwd")
+    if want_w:
+        _finish_tables(ws, (dw,) + ((db,) if want_b else ()), (wp.value, bp.value), (wl.value, 32), defer)
+    elif want_b:
+        _finish_tables(ws[4 * wp.value * w.numel():], (db,), bp.value, 32, defer)
+    return dxs, dw, db
 
 
 def launch_count_reset() -> None:

@@ -541,14 +541,40 @@ int gaot_compact_pairs(const int32_t* a, const int32_t* b, const int32_t* flags,
  * mlp.py:227-335), bf16 operands / fp32 accumulation.  x [rows, 32], w1 [hidden, 32], w2 [out, hidden]
  * row-major fp32; hidden in {64, 128, 256}, out in 1..4.  The [rows, hidden] activations never reach
  * HBM; backward recomputes them and reduces the weight gradients in a fixed order.  d_b2 is the
- * column sum of d_out (gaot_colsum).
+ * column sum of d_out (gaot_colsum).  gaot_mlp2_bwd with d_w1 == d_b1 == d_w2 == NULL leaves the
+ * weight-gradient partials in the workspace as three tables of P = gaot_mlp2_bwd_parts(num_rows) rows,
+ * [P][hidden * 32] | [P][hidden] | [P][out * hidden], for gaot_reduce_multi with lanes = 4 -- the order of
+ * the in-call completion (ONE gaot_reduce_multi launch), bit-identical.
  * ------------------------------------------------------------------------------------------- */
 int gaot_mlp2_fwd(const float* x, int64_t num_rows, int in_dim, int hidden, int out_dim, const float* w1, const float* b1,
                   const float* w2, const float* b2, float* out, gaot_stream_t stream);
 size_t gaot_mlp2_bwd_workspace_bytes(int hidden, int out_dim);
+int64_t gaot_mlp2_bwd_parts(int64_t num_rows);
 int gaot_mlp2_bwd(const float* x, int64_t num_rows, int in_dim, int hidden, int out_dim, const float* w1, const float* b1,
                   const float* w2, const float* d_out, float* d_x, float* d_w1, float* d_b1, float* d_w2, void* workspace,
                   size_t workspace_bytes, gaot_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Thin fp32 linears over many rows in one pass (csrc/rowlinear.hip):  y = act([x_0 | x_1 | ...] W^T + b),
+ * act none or ReLU (ReLU: one input only) -- the per-point / per-token linears around the GNOs (reference magno.py:494,571-575,
+ * 771-775: torch.cat + nn.Linear; geoembed.py: the statistics MLP).  nin = 1..4 dense row-major inputs
+ * x_i [M, ks[i]] with ks[i] <= 64, W [N, sum ks] row-major, N <= 64, and at most four 32 x 32 blocks of
+ * weights (ceil(N / 32) * sum ceil(ks[i] / 32) <= 4): gaot_rowlin_supported says whether a shape is in.
+ * Exact fp32 (v_mfma_f32_32x32x2_f32) in the summation order of the gaot_gemm / gaot_colsum launches they replace (the results are
+ * those launches' bit for bit); a row's result depends on that row alone.
+ *   gaot_rowlin_fwd : every input row read once, every output row written once
+ *   gaot_rowlin_bwd : one pass over dy (and, relu != 0, over the saved OUTPUT y: dz = dy * (y > 0));
+ *                     dxs[i] = dz W[:, block i] for the inputs whose dxs[i] is not NULL (dxs may be NULL);
+ *                     dW and db leave as partial rows, dw_part [w_parts][N * sum ks] for gaot_reduce_multi with w_lanes
+ *                     and db_part [b_parts][N] for lanes = 32 (gaot_rowlin_plan: the split-K plan of gaot_gemm's weight
+ *                     gradients and the row chunks of gaot_colsum).  M >= 1.
+ * ------------------------------------------------------------------------------------------- */
+int gaot_rowlin_supported(const int* ks, int nin, int N);
+int gaot_rowlin_plan(int64_t M, int N, int* w_parts, int* w_lanes, int* b_parts);
+int gaot_rowlin_fwd(const float* const* xs, const int* ks, int nin, const float* W, const float* b, int64_t M, int N, int relu,
+                    float* y, gaot_stream_t stream);
+int gaot_rowlin_bwd(const float* const* xs, const int* ks, int nin, const float* W, const float* dy, const float* y, int64_t M,
+                    int N, int relu, float* const* dxs, float* dw_part, float* db_part, gaot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * General (unfused) per-edge operators: the glue around the GEMM-run edge MLP for the GNO variants the
