@@ -47,6 +47,10 @@ SIGNATURES = {
                           C.POINTER(MlpGradT), _i, _p, _sz, _p]),
     "gaot_gno_bwd_coords": (_i, [C.POINTER(MlpT), _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p,
                                  C.POINTER(MlpGradT), _p, _i, _p, _sz, _p]),
+    "gaot_gno_fwd_nl": (_i, [C.POINTER(MlpT), _i, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _i, _p, _sz, _p]),
+    "gaot_gno_bwd_nl_workspace_bytes": (_sz, [C.POINTER(MlpT), _i64, _i64]),
+    "gaot_gno_bwd_nl": (_i, [C.POINTER(MlpT), _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p,
+                             C.POINTER(MlpGradT), _p, _i, _p, _sz, _p]),
     "gaot_geoembed_stats_workspace_bytes": (_sz, []),
     "gaot_geoembed_moments": (_i, [_p, _p, _p, _p, _i64, _p, _p]),
     "gaot_geoembed_from_moments": (_i, [_p, _i64, _p, _p, _sz, _p]),

@@ -41,12 +41,14 @@ struct FwdLds {
     static constexpr int weights_end = bL + 32;
 };
 
-template <int NH, int H, int T>
+// MODE (gno_common.h): in the nonlinear / kernel-only modes `nl_` is one NlFwd and layer 0 starts from b_0 + t[src]
+template <int NH, int H, int T, int MODE, class... Nl>
 __global__ __launch_bounds__(256, 2) void k_gno_fwd(MlpPtrs mlp, const float* __restrict__ y_pos,
                                                     const float* __restrict__ x_pos, const float* __restrict__ f_y,
                                                     const int* __restrict__ src_s, const int* __restrict__ dst_s,
                                                     const int* __restrict__ rowptr, int64_t E, float* __restrict__ out,
-                                                    float* __restrict__ part) {
+                                                    float* __restrict__ part, Nl... nl_) {
+    static_assert(MODE == MODE_LINEAR || H == NLH, "t rows are 64 wide");
     constexpr int C = 32;
     constexpr int KB = H / 32;
     using L = FwdLds<NH, H>;
@@ -87,6 +89,7 @@ __global__ __launch_bounds__(256, 2) void k_gno_fwd(MlpPtrs mlp, const float* __
         const int64_t base = mt * 32 * T;
         // MLP input k = 2i+hf of this lane's edge: [y.x y.y y.z x.x x.y x.z][2i+hf], i = 0..2
         float bin[T][3];
+        [[maybe_unused]] int sid[T];   // source of this lane's edge (edges past E: row 0, a valid row)
 #pragma unroll
         for (int t = 0; t < T; ++t) {
             const int64_t e = base + 32 * t + l31;
@@ -98,6 +101,7 @@ __global__ __launch_bounds__(256, 2) void k_gno_fwd(MlpPtrs mlp, const float* __
             bin[t][0] = ys[hf];
             bin[t][1] = hf ? xq[0] : ys[2];
             bin[t][2] = xq[1 + hf];
+            if constexpr (MODE != MODE_LINEAR) sid[t] = s;
             if (hf == 0) {
                 ids[(t * 2 + 0) * 32 + l31] = s;
                 ids[(t * 2 + 1) * 32 + l31] = valid ? q : -1;
@@ -112,6 +116,21 @@ __global__ __launch_bounds__(256, 2) void k_gno_fwd(MlpPtrs mlp, const float* __
             for (int r = 0; r < 16; ++r) bias[r] = lds[L::b0 + 32 * ob + mfma32_row(r, hf)];
 #pragma unroll
             for (int t = 0; t < T; ++t) h[t][ob] = bias;
+            if constexpr (MODE != MODE_LINEAR) {
+                // + t[src]: the lane's 16 features of this 32-block are four runs of four (mfma32_row): four 16-byte loads
+#pragma unroll
+                for (int t = 0; t < T; ++t) {
+                    const float* tr = first_arg(nl_...).t + (int64_t)sid[t] * NLH + 32 * ob + 4 * hf;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const float4 v = *reinterpret_cast<const float4*>(tr + 8 * j);
+                        h[t][ob][4 * j + 0] += v.x;
+                        h[t][ob][4 * j + 1] += v.y;
+                        h[t][ob][4 * j + 2] += v.z;
+                        h[t][ob][4 * j + 3] += v.w;
+                    }
+                }
+            }
 #pragma unroll
             for (int i = 0; i < IN0 / 2; ++i) {
                 const float a = lds[L::w0 + (2 * i + hf) * H + 32 * ob + l31];
@@ -168,13 +187,17 @@ __global__ __launch_bounds__(256, 2) void k_gno_fwd(MlpPtrs mlp, const float* __
                     const float b = lds[L::wL + (32 * kb + mfma32_row(r, hf)) * C + l31];
                     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(h[t][kb][r], b, acc, 0, 0, 0);
                 }
-            // multiply by the gathered feature row and stage [e][c]
+            // multiply by the gathered feature row and stage [e][c]  (kernel-only mode: the kernel value itself)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int el = mfma32_row(r, hf);
-                const int s = ids[(t * 2 + 0) * 32 + el];
-                const float fv = f_y[(int64_t)s * C + l31];
-                stage[(t * 32 + el) * C + l31] = acc[r] * fv;
+                if constexpr (MODE == MODE_KERNELONLY) {
+                    stage[(t * 32 + el) * C + l31] = acc[r];
+                } else {
+                    const int s = ids[(t * 2 + 0) * 32 + el];
+                    const float fv = f_y[(int64_t)s * C + l31];
+                    stage[(t * 32 + el) * C + l31] = acc[r] * fv;
+                }
             }
         }
         wave_lds_fence();
@@ -274,7 +297,10 @@ __device__ __forceinline__ void load_wgroup(float (&w)[16], const WRsrc& rs, int
 
 // CG: also the coordinate gradient of every edge, g_e = W_0^T dz_0[e] (6 fp32, source-sorted edge order) -> gcoord [E][6]
 // (the output pointer is a parameter pack: empty when CG is off, so those instantiations keep today's kernel arguments)
-template <int NH, int H, bool CG, class... CoordOut>
+// MODE (gno_common.h): the nonlinear / kernel-only modes append one NlBwd to the pack: layer 0 is recomputed from b_0 + t[src], and
+// dt[s] = sum of dz_0 over the edges of source s is written beside grad_f (64 lanes = 64 features walk the wave's dz_0 tile).
+// Kernel-only mode: dk = gs (no f), and grad_f is not written (its only term, dt W_0f, is a per-node product of the caller's).
+template <int NH, int H, bool CG, int MODE, class... CoordOut>
 __global__ __launch_bounds__(256, 1) void k_gno_bwd(
     MlpPtrs mlp, MlpPtrs mlp_t /* w = transposed copies [in][out] */, const float* __restrict__ y_pos,
     const float* __restrict__ x_pos, const float* __restrict__ f_y, const float* __restrict__ gs /* grad_out / deg */,
@@ -344,11 +370,13 @@ __global__ __launch_bounds__(256, 1) void k_gno_bwd(
         load_wgroup<0, NH, H>(wA, rs, vo_row4, vo_row4c, vo_row1);
         // ---- gather -------------------------------------------------------------------------------
         float bin[3];  // MLP input k = 2i+hf of this lane's edge
+        [[maybe_unused]] int sid = 0;
         {
             const int64_t e = base + l31;
             const bool valid = e < E;
             const int s = valid ? src_s[e] : 0;
             const int q = valid ? dst_s[e] : 0;
+            if constexpr (MODE != MODE_LINEAR) sid = s;
             const float* ys = y_pos + (int64_t)s * 3;
             const float* xq = x_pos + (int64_t)q * 3;
             bin[0] = ys[hf];
@@ -370,6 +398,17 @@ __global__ __launch_bounds__(256, 1) void k_gno_bwd(
             f32x16 z;
 #pragma unroll
             for (int r = 0; r < 16; ++r) z[r] = bias_l[32 * ob + mfma32_row(r, hf)];
+            if constexpr (MODE != MODE_LINEAR) {
+                const float* tr = last_arg(gcoord_...).t + (int64_t)sid * NLH + 32 * ob + 4 * hf;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float4 v = *reinterpret_cast<const float4*>(tr + 8 * j);
+                    z[4 * j + 0] += v.x;
+                    z[4 * j + 1] += v.y;
+                    z[4 * j + 2] += v.z;
+                    z[4 * j + 3] += v.w;
+                }
+            }
 #pragma unroll
             for (int i = 0; i < IN0 / 2; ++i) {
                 const float a = bload(rs.wt[0], vo_row1, (2 * i * H + 32 * ob) * 4);
@@ -423,7 +462,8 @@ __global__ __launch_bounds__(256, 1) void k_gno_bwd(
             const int s_ = ids[el], q_ = ids[32 + el];
             const bool ok = q_ >= 0;
             gv[r] = ok ? gs[(int64_t)q_ * C + l31] : 0.f;
-            fv[r] = ok ? f_y[(int64_t)s_ * C + l31] : 0.f;
+            if constexpr (MODE == MODE_KERNELONLY) fv[r] = 1.f;
+            else fv[r] = ok ? f_y[(int64_t)s_ * C + l31] : 0.f;
         }
         // ---- last layer transposed: K'[e][c] -------------------------------------------------------
         f32x16 kp;
@@ -445,15 +485,20 @@ __global__ __launch_bounds__(256, 1) void k_gno_bwd(
         });
         // ---- per edge: g = grad_out[dst]/deg (pre-scaled) ; m' = g*k' (-> grad_f) ; dk' = g*f --------------
         f32x16 dkp;
+        if constexpr (MODE == MODE_KERNELONLY) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int el = mfma32_row(r, hf);
-            buf[el * LDH + l31] = gv[r] * kp[r];
-            dkp[r] = gv[r] * fv[r];
+            for (int r = 0; r < 16; ++r) dkp[r] = gv[r];
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int el = mfma32_row(r, hf);
+                buf[el * LDH + l31] = gv[r] * kp[r];
+                dkp[r] = gv[r] * fv[r];
+            }
+            wave_lds_fence();
+            if (hf == 0) segment_walk<C>(buf, LDH, ids, l31, base, rowptr_src, grad_f, part, false);
+            wave_lds_fence();
         }
-        wave_lds_fence();
-        if (hf == 0) segment_walk<C>(buf, LDH, ids, l31, base, rowptr_src, grad_f, part, false);
-        wave_lds_fence();
         // ---- dk' -> LDS [e][c] (own buf) ------------------------------------------------------------
 #pragma unroll
         for (int r = 0; r < 16; ++r) buf[mfma32_row(r, hf) * LDH + l31] = dkp[r];
@@ -538,6 +583,11 @@ __global__ __launch_bounds__(256, 1) void k_gno_bwd(
 #pragma unroll
                     for (int r = 0; r < 16; ++r) dz[kb][r] = dn[kb][r] * gp[l - 1][kb][r];
             } else {
+                if constexpr (MODE != MODE_LINEAR) {
+                    // dt[s][j] = sum of dz_0[j][e] over the edges of s: own buf holds the tile's dz_0 as [e][j]; lane = feature j
+                    const NlBwd nl = last_arg(gcoord_...);
+                    segment_walk<NLH>(buf, LDH, ids, lane, base, rowptr_src, nl.dt, nl.part_dt, false);
+                }
                 // dW_0[j][k<6] += sum_e dz[j][e] in[k][e] : this wave = j-block (wave&1), edge tiles of its pair
 #pragma unroll 1
                 for (int tt = 0; tt < 2; ++tt) {
@@ -669,12 +719,15 @@ size_t bwd_lds_bytes(int nh, int h, bool coords = false) {
     return sizeof(float) * (size_t)(4 * per_wave + nh * h + 32 + (coords ? IN0 * h : 0));
 }
 
-template <int NH, int H>
-int launch_fwd(const MlpPtrs& p, const float* y_pos, const float* x_pos, const float* f_y, const int* src_s,
+template <int NH, int H, int MODE>
+int launch_fwd(const MlpPtrs& p, const float* y_pos, const float* x_pos, const float* f_y, const float* ttab, const int* src_s,
                const int* dst_s, const int* rowptr, int64_t E, float* out, float* part, hipStream_t st) {
     constexpr int T = 2;
     const size_t lds = fwd_lds_bytes(NH, H, T);
-    auto kern = k_gno_fwd<NH, H, T>;
+    auto kern = [] {
+        if constexpr (MODE == MODE_LINEAR) return k_gno_fwd<NH, H, T, MODE>;
+        else return k_gno_fwd<NH, H, T, MODE, NlFwd>;
+    }();
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) {
         gaot_set_error("gno_fwd: cannot set dynamic LDS %zu: %s", lds, hipGetErrorString(e));
@@ -682,30 +735,47 @@ int launch_fwd(const MlpPtrs& p, const float* y_pos, const float* x_pos, const f
     }
     const int64_t n_macro = ceil_div(E, 32 * T);
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n_macro, 4), 256 * 2));
-    GAOT_KLAUNCH(kern, dim3(grid), dim3(256), lds, st, p, y_pos, x_pos, f_y, src_s, dst_s, rowptr, E, out, part);
+    if constexpr (MODE == MODE_LINEAR)
+        GAOT_KLAUNCH(kern, dim3(grid), dim3(256), lds, st, p, y_pos, x_pos, f_y, src_s, dst_s, rowptr, E, out, part);
+    else
+        GAOT_KLAUNCH(kern, dim3(grid), dim3(256), lds, st, p, y_pos, x_pos, f_y, src_s, dst_s, rowptr, E, out, part, NlFwd{ttab});
     return GAOT_OK;
 }
 
-template <int NH, int H, bool CG>
+template <int NH, int H, bool CG, int MODE>
 int launch_bwd(const MlpPtrs& p, const MlpPtrs& pt, const float* y_pos, const float* x_pos, const float* f_y,
                const float* gs, const int* src_s, const int* dst_s, const int* rowptr_src,
-               int64_t E, float* grad_f, float* part, float* wpart, float* gcoord, int grid, hipStream_t st) {
+               int64_t E, float* grad_f, float* part, float* wpart, float* gcoord, const NlBwd& nl, int grid, hipStream_t st) {
     const size_t lds = bwd_lds_bytes(NH, H, CG);
     auto kern = [] {
-        if constexpr (CG) return k_gno_bwd<NH, H, true, float*>;
-        else return k_gno_bwd<NH, H, false>;
+        if constexpr (MODE == MODE_LINEAR) {
+            if constexpr (CG) return k_gno_bwd<NH, H, true, MODE, float*>;
+            else return k_gno_bwd<NH, H, false, MODE>;
+        } else {
+            if constexpr (CG) return k_gno_bwd<NH, H, true, MODE, float*, NlBwd>;
+            else return k_gno_bwd<NH, H, false, MODE, NlBwd>;
+        }
     }();
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) {
         gaot_set_error("gno_bwd: cannot set dynamic LDS %zu: %s", lds, hipGetErrorString(e));
         return GAOT_ERR_LAUNCH;
     }
-    if constexpr (CG)
-        GAOT_KLAUNCH(kern, dim3(grid), dim3(256), lds, st, p, pt, y_pos, x_pos, f_y, gs, src_s, dst_s,
-                           rowptr_src, E, grad_f, part, wpart, gcoord);
-    else
-        GAOT_KLAUNCH(kern, dim3(grid), dim3(256), lds, st, p, pt, y_pos, x_pos, f_y, gs, src_s, dst_s,
-                           rowptr_src, E, grad_f, part, wpart);
+    if constexpr (MODE == MODE_LINEAR) {
+        if constexpr (CG)
+            GAOT_KLAUNCH(kern, dim3(grid), dim3(256), lds, st, p, pt, y_pos, x_pos, f_y, gs, src_s, dst_s,
+                               rowptr_src, E, grad_f, part, wpart, gcoord);
+        else
+            GAOT_KLAUNCH(kern, dim3(grid), dim3(256), lds, st, p, pt, y_pos, x_pos, f_y, gs, src_s, dst_s,
+                               rowptr_src, E, grad_f, part, wpart);
+    } else {
+        if constexpr (CG)
+            GAOT_KLAUNCH(kern, dim3(grid), dim3(256), lds, st, p, pt, y_pos, x_pos, f_y, gs, src_s, dst_s,
+                               rowptr_src, E, grad_f, part, wpart, gcoord, nl);
+        else
+            GAOT_KLAUNCH(kern, dim3(grid), dim3(256), lds, st, p, pt, y_pos, x_pos, f_y, gs, src_s, dst_s,
+                               rowptr_src, E, grad_f, part, wpart, nl);
+    }
     return GAOT_OK;
 }
 
@@ -723,57 +793,73 @@ bool mlp_supported(const gaot_mlp_t* m, bool backward, int precision = 0) {
 
 }  // namespace
 
-int gaot_gno_fwd_bf16_dispatch(int n_hidden, const float* const* w, const float* const* b, const float* y_pos,
-                               const float* x_pos, const float* f_y, const int32_t* src_sorted, const int32_t* dst_sorted,
-                               const int32_t* rowptr_dst, int64_t num_edges, float* out, float* part, hipStream_t st);
+int gaot_gno_fwd_bf16_dispatch(int n_hidden, int mode, const float* const* w, const float* const* b, const float* y_pos,
+                               const float* x_pos, const float* f_y, const float* ttab, const int32_t* src_sorted,
+                               const int32_t* dst_sorted, const int32_t* rowptr_dst, int64_t num_edges, float* out, float* part,
+                               hipStream_t st);
 
 size_t gaot_gno_bwd_bf16_image_bytes(int n_hidden);
-int gaot_gno_bwd_bf16_dispatch(int n_hidden, const float* const* w, const float* const* b, const float* w0t,
+int gaot_gno_bwd_bf16_dispatch(int n_hidden, int mode, const float* const* w, const float* const* b, const float* w0t,
                                void* images, const float* y_pos, const float* x_pos, const float* f_y, const float* gs,
                                const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr_src,
-                               int64_t num_edges, float* grad_f, float* part, float* wpart, float* gcoord, int grid,
-                               hipStream_t st);
+                               int64_t num_edges, float* grad_f, float* part, float* wpart, float* gcoord, const float* ttab,
+                               float* dt, float* part_dt, int grid, hipStream_t st);
 
 extern "C" size_t gaot_gno_fwd_workspace_bytes(int64_t num_edges, int channels) {
     return sizeof(float) * (size_t)(ceil_div(num_edges, 32) * 2 * channels) + 64;
 }
 
-extern "C" int gaot_gno_fwd(const gaot_mlp_t* mlp, const float* y_pos, const float* x_pos, const float* f_y,
-                            const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr_dst,
-                            int64_t num_edges, int64_t num_queries, float* out, int precision, void* workspace,
-                            size_t workspace_bytes, gaot_stream_t stream) {
-    GAOT_ENTER();
-    GAOT_CHECK_ARG(mlp, "null mlp");
+namespace {
+// GAOT_CHECK_ARG with the name of the entry point that was called
+#define GNO_CHECK(cond, msg)                              \
+    do {                                                  \
+        if (!(cond)) {                                    \
+            gaot_set_error("%s: %s", fn, msg);            \
+            return GAOT_ERR_ARG;                          \
+        }                                                 \
+    } while (0)
+// gaot_gno_fwd (mode = linear, ttab = null) and gaot_gno_fwd_nl
+int gno_fwd_impl(const char* fn, const gaot_mlp_t* mlp, const float* y_pos, const float* x_pos, const float* f_y,
+                 const float* ttab, int mode, const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr_dst,
+                 int64_t num_edges, int64_t num_queries, float* out, int precision, void* workspace, size_t workspace_bytes,
+                 gaot_stream_t stream) {
+    GNO_CHECK(mlp, "null mlp");
     if (!mlp_supported(mlp, false)) {
-        gaot_set_error("gaot_gno_fwd: unsupported MLP shape (n_hidden=%d hidden=%d channels=%d)", mlp->n_hidden,
+        gaot_set_error("%s: unsupported MLP shape (n_hidden=%d hidden=%d channels=%d)", fn, mlp->n_hidden,
                        mlp->hidden, mlp->channels);
         return GAOT_ERR_UNSUPPORTED;
     }
-    GAOT_CHECK_ARG(num_edges >= 0 && num_queries >= 0, "negative size");
-    GAOT_CHECK_ARG(rowptr_dst && (num_queries == 0 || out), "null pointer");
-    GAOT_CHECK_ARG(workspace_bytes >= gaot_gno_fwd_workspace_bytes(num_edges, mlp->channels), "workspace too small");
+    GNO_CHECK(num_edges >= 0 && num_queries >= 0, "negative size");
+    GNO_CHECK(rowptr_dst && (num_queries == 0 || out), "null pointer");
+    GNO_CHECK(workspace_bytes >= gaot_gno_fwd_workspace_bytes(num_edges, mlp->channels), "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     if (num_queries == 0) return GAOT_OK;
     MlpPtrs p;
     for (int l = 0; l <= mlp->n_hidden; ++l) {
         p.w[l] = mlp->weight[l];
         p.b[l] = mlp->bias[l];
-        GAOT_CHECK_ARG(p.w[l] && p.b[l], "null MLP parameter");
+        GNO_CHECK(p.w[l] && p.b[l], "null MLP parameter");
     }
     float* part = (float*)workspace;
     int rc = GAOT_OK;
     if (num_edges > 0) {
-        GAOT_CHECK_ARG(y_pos && x_pos && f_y && src_sorted && dst_sorted, "null pointer");
-        GAOT_CHECK_ARG(precision == 0 || precision == 1, "precision must be 0 (fp32) or 1 (bf16 matrix cores)");
+        GNO_CHECK(y_pos && x_pos && (f_y || mode == MODE_KERNELONLY) && src_sorted && dst_sorted, "null pointer");
+        GNO_CHECK(mode == MODE_LINEAR || ttab, "null t");
+        GNO_CHECK(precision == 0 || precision == 1, "precision must be 0 (fp32) or 1 (bf16 matrix cores)");
         if (precision == 1) {
-            rc = gaot_gno_fwd_bf16_dispatch(mlp->n_hidden, p.w, p.b, y_pos, x_pos, f_y, src_sorted, dst_sorted, rowptr_dst,
-                                            num_edges, out, part, st);
-        } else
-        switch (mlp->n_hidden) {
-            case 1: rc = launch_fwd<1, 64>(p, y_pos, x_pos, f_y, src_sorted, dst_sorted, rowptr_dst, num_edges, out, part, st); break;
-            case 2: rc = launch_fwd<2, 64>(p, y_pos, x_pos, f_y, src_sorted, dst_sorted, rowptr_dst, num_edges, out, part, st); break;
-            case 3: rc = launch_fwd<3, 64>(p, y_pos, x_pos, f_y, src_sorted, dst_sorted, rowptr_dst, num_edges, out, part, st); break;
-            case 4: rc = launch_fwd<4, 64>(p, y_pos, x_pos, f_y, src_sorted, dst_sorted, rowptr_dst, num_edges, out, part, st); break;
+            rc = gaot_gno_fwd_bf16_dispatch(mlp->n_hidden, mode, p.w, p.b, y_pos, x_pos, f_y, ttab, src_sorted, dst_sorted,
+                                            rowptr_dst, num_edges, out, part, st);
+        } else {
+#define GNO_FWD_CASE(NH_, MODE_)                                                                                          \
+    case NH_ * 3 + MODE_:                                                                                                 \
+        rc = launch_fwd<NH_, 64, MODE_>(p, y_pos, x_pos, f_y, ttab, src_sorted, dst_sorted, rowptr_dst, num_edges, out, part, st); \
+        break;
+#define GNO_FWD_CASES(NH_) GNO_FWD_CASE(NH_, MODE_LINEAR) GNO_FWD_CASE(NH_, MODE_NONLINEAR) GNO_FWD_CASE(NH_, MODE_KERNELONLY)
+            switch (mlp->n_hidden * 3 + mode) {
+                GNO_FWD_CASES(1) GNO_FWD_CASES(2) GNO_FWD_CASES(3) GNO_FWD_CASES(4)
+            }
+#undef GNO_FWD_CASES
+#undef GNO_FWD_CASE
         }
         if (rc != GAOT_OK) return rc;
     }
@@ -782,6 +868,26 @@ extern "C" int gaot_gno_fwd(const gaot_mlp_t* mlp, const float* y_pos, const flo
                        num_queries, part, out, 1);
     GAOT_LAUNCH_CHECK();
     return GAOT_OK;
+}
+}  // namespace
+
+extern "C" int gaot_gno_fwd(const gaot_mlp_t* mlp, const float* y_pos, const float* x_pos, const float* f_y,
+                            const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr_dst,
+                            int64_t num_edges, int64_t num_queries, float* out, int precision, void* workspace,
+                            size_t workspace_bytes, gaot_stream_t stream) {
+    GAOT_ENTER();
+    return gno_fwd_impl("gaot_gno_fwd", mlp, y_pos, x_pos, f_y, nullptr, MODE_LINEAR, src_sorted, dst_sorted, rowptr_dst,
+                        num_edges, num_queries, out, precision, workspace, workspace_bytes, stream);
+}
+
+extern "C" int gaot_gno_fwd_nl(const gaot_mlp_t* mlp, int mode, const float* y_pos, const float* x_pos, const float* f_y,
+                               const float* src_table, const int32_t* src_sorted, const int32_t* dst_sorted,
+                               const int32_t* rowptr_dst, int64_t num_edges, int64_t num_queries, float* out, int precision,
+                               void* workspace, size_t workspace_bytes, gaot_stream_t stream) {
+    GAOT_ENTER();
+    GAOT_CHECK_ARG(mode == MODE_NONLINEAR || mode == MODE_KERNELONLY, "mode must be 1 (nonlinear) or 2 (nonlinear_kernelonly)");
+    return gno_fwd_impl("gaot_gno_fwd_nl", mlp, y_pos, x_pos, f_y, src_table, mode, src_sorted, dst_sorted, rowptr_dst,
+                        num_edges, num_queries, out, precision, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t gaot_gno_bwd_workspace_bytes(const gaot_mlp_t* mlp, int64_t num_edges, int64_t num_queries) {
@@ -796,36 +902,37 @@ extern "C" size_t gaot_gno_bwd_workspace_bytes(const gaot_mlp_t* mlp, int64_t nu
     return sizeof(float) * fl + gaot_gno_bwd_bf16_image_bytes(mlp->n_hidden) + 512;
 }
 
+// ... and behind it the tile partials of dt: two 64-float slots per 16-edge tile
+extern "C" size_t gaot_gno_bwd_nl_workspace_bytes(const gaot_mlp_t* mlp, int64_t num_edges, int64_t num_queries) {
+    if (!mlp) return 0;
+    return gaot_gno_bwd_workspace_bytes(mlp, num_edges, num_queries) + sizeof(float) * (size_t)(ceil_div(num_edges, 16) * 2 * NLH) + 512;
+}
+
 namespace {
-// gaot_gno_bwd (gcoord = null) and gaot_gno_bwd_coords (gcoord = [num_edges][6])
-// GAOT_CHECK_ARG with the name of the entry point that was called
-#define GNO_BWD_CHECK(cond, msg)                          \
-    do {                                                  \
-        if (!(cond)) {                                    \
-            gaot_set_error("%s: %s", fn, msg);            \
-            return GAOT_ERR_ARG;                          \
-        }                                                 \
-    } while (0)
+// gaot_gno_bwd (gcoord = null), gaot_gno_bwd_coords (gcoord = [num_edges][6]) and gaot_gno_bwd_nl (mode != linear: ttab, dt)
 int gno_bwd_impl(const char* fn, const gaot_mlp_t* mlp, const float* y_pos, const float* x_pos, const float* f_y,
                  const float* grad_out, const int32_t* rowptr_dst, const int32_t* src_sorted, const int32_t* dst_sorted,
                  const int32_t* rowptr_src, int64_t num_edges, int64_t num_sources, int64_t num_queries, float* grad_f_y,
-                 const gaot_mlp_grad_t* grads, float* gcoord, int precision, void* workspace, size_t workspace_bytes,
-                 gaot_stream_t stream) {
-    GNO_BWD_CHECK(mlp && grads, "null mlp");
+                 const gaot_mlp_grad_t* grads, float* gcoord, int mode, const float* ttab, float* dt, int precision,
+                 void* workspace, size_t workspace_bytes, gaot_stream_t stream) {
+    GNO_CHECK(mlp && grads, "null mlp");
     if (!mlp_supported(mlp, true, precision)) {
         gaot_set_error("%s: unsupported MLP shape (n_hidden=%d hidden=%d channels=%d; four hidden layers in bf16 mode only)", fn,
                        mlp->n_hidden, mlp->hidden, mlp->channels);
         return GAOT_ERR_UNSUPPORTED;
     }
-    GNO_BWD_CHECK(num_edges >= 0 && num_sources >= 0 && num_queries >= 0, "negative size");
-    // the bf16 kernel gathers its 128-byte rows through 2 GB buffer resources: 2^24 rows per table
-    GNO_BWD_CHECK(precision != 1 || (num_sources <= (1 << 24) && num_queries <= (1 << 24)),
+    GNO_CHECK(num_edges >= 0 && num_sources >= 0 && num_queries >= 0, "negative size");
+    // the bf16 kernel gathers its 128-byte rows through 2 GB buffer resources: 2^24 rows per table (t / dt go through plain pointers)
+    GNO_CHECK(precision != 1 || (num_sources <= (1 << 24) && num_queries <= (1 << 24)),
                    "bf16 GNO backward: more than 2^24 source or query rows (run the mesh point-sharded or in fp32 mode)");
     // ... and addresses the two 128-byte partial slots of a 16-edge tile with a 32-bit byte offset
-    GNO_BWD_CHECK(precision != 1 || num_edges < ((int64_t)1 << 27),
+    GNO_CHECK(precision != 1 || num_edges < ((int64_t)1 << 27),
                    "bf16 GNO backward: 2^27 or more edges in one launch (run the mesh point-sharded or in fp32 mode)");
-    GNO_BWD_CHECK(workspace_bytes >= gaot_gno_bwd_workspace_bytes(mlp, num_edges, num_queries), "workspace too small");
-    GNO_BWD_CHECK(rowptr_src && rowptr_dst, "null rowptr");
+    const bool nlm = mode != MODE_LINEAR;
+    GNO_CHECK(workspace_bytes >= (nlm ? gaot_gno_bwd_nl_workspace_bytes(mlp, num_edges, num_queries)
+                                      : gaot_gno_bwd_workspace_bytes(mlp, num_edges, num_queries)), "workspace too small");
+    GNO_CHECK(rowptr_src && rowptr_dst, "null rowptr");
+    GNO_CHECK(!nlm || num_sources == 0 || dt, "null grad_src_table");
     hipStream_t st = (hipStream_t)stream;
     const int nh = mlp->n_hidden, h = mlp->hidden;
     const int total = param_total(nh, h);
@@ -837,14 +944,15 @@ int gno_bwd_impl(const char* fn, const gaot_mlp_t* mlp, const float* y_pos, cons
     float* wpart = flat + total;
     float* gs = wpart + (size_t)grid * total;
     void* images = (void*)(((uintptr_t)(gs + (size_t)num_queries * 32) + 255) & ~(uintptr_t)255);
-    GNO_BWD_CHECK(precision == 0 || precision == 1, "precision must be 0 (fp32) or 1 (bf16 matrix cores)");
+    float* part_dt = (float*)(((uintptr_t)images + gaot_gno_bwd_bf16_image_bytes(nh) + 255) & ~(uintptr_t)255);
+    GNO_CHECK(precision == 0 || precision == 1, "precision must be 0 (fp32) or 1 (bf16 matrix cores)");
 
     MlpPtrs p, pt;
     int off = 0;
     for (int l = 0; l <= nh; ++l) {
         p.w[l] = mlp->weight[l];
         p.b[l] = mlp->bias[l];
-        GNO_BWD_CHECK(p.w[l] && p.b[l] && grads->weight[l] && grads->bias[l], "null MLP parameter / gradient");
+        GNO_CHECK(p.w[l] && p.b[l] && grads->weight[l] && grads->bias[l], "null MLP parameter / gradient");
         const int out_dim = (l == nh) ? 32 : h;
         const int in_dim = (l == 0) ? IN0 : h;
         pt.w[l] = wt + off;
@@ -870,29 +978,32 @@ int gno_bwd_impl(const char* fn, const gaot_mlp_t* mlp, const float* y_pos, cons
         }
         sd.off[sd.n] = o;
     }
+    const bool want_gf = mode != MODE_KERNELONLY;   // kernel-only: no gs k term, grad_f_y is not written
     if (num_edges == 0) {
         hipMemsetAsync(flat, 0, sizeof(float) * total, st);
     } else {
-        GNO_BWD_CHECK(y_pos && x_pos && f_y && grad_out && src_sorted && dst_sorted && grad_f_y, "null pointer");
+        GNO_CHECK(y_pos && x_pos && grad_out && src_sorted && dst_sorted && (!want_gf || (f_y && grad_f_y)), "null pointer");
+        GNO_CHECK(!nlm || ttab, "null src_table");
         const bool cg = gcoord != nullptr;
         GAOT_KLAUNCH(k_scale_by_inv_deg, dim3((unsigned)ceil_div(num_queries * 8, 256)), dim3(256), 0, st, grad_out,
                            rowptr_dst, num_queries, gs);
         int rc = GAOT_OK;
+        const NlBwd nl{ttab, dt, part_dt};
         if (precision == 1) {
-            rc = gaot_gno_bwd_bf16_dispatch(nh, p.w, p.b, pt.w[0], images, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted,
-                                            rowptr_src, num_edges, grad_f_y, part, wpart, gcoord, grid, st);
-        } else if (!cg) {
-            switch (nh) {
-                case 1: rc = launch_bwd<1, 64, false>(p, pt, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src, num_edges, grad_f_y, part, wpart, nullptr, grid, st); break;
-                case 2: rc = launch_bwd<2, 64, false>(p, pt, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src, num_edges, grad_f_y, part, wpart, nullptr, grid, st); break;
-                case 3: rc = launch_bwd<3, 64, false>(p, pt, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src, num_edges, grad_f_y, part, wpart, nullptr, grid, st); break;
-            }
+            rc = gaot_gno_bwd_bf16_dispatch(nh, mode, p.w, p.b, pt.w[0], images, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted,
+                                            rowptr_src, num_edges, grad_f_y, part, wpart, gcoord, ttab, dt, part_dt, grid, st);
         } else {
-            switch (nh) {
-                case 1: rc = launch_bwd<1, 64, true>(p, pt, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src, num_edges, grad_f_y, part, wpart, gcoord, grid, st); break;
-                case 2: rc = launch_bwd<2, 64, true>(p, pt, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src, num_edges, grad_f_y, part, wpart, gcoord, grid, st); break;
-                case 3: rc = launch_bwd<3, 64, true>(p, pt, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src, num_edges, grad_f_y, part, wpart, gcoord, grid, st); break;
+#define GNO_BWD_CASE(NH_, CG_, MODE_)                                                                                       \
+    case (NH_ * 2 + CG_) * 3 + MODE_:                                                                                       \
+        rc = launch_bwd<NH_, 64, CG_ != 0, MODE_>(p, pt, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src, num_edges, \
+                                                  grad_f_y, part, wpart, gcoord, nl, grid, st);                            \
+        break;
+#define GNO_BWD_CASES(NH_, CG_) GNO_BWD_CASE(NH_, CG_, MODE_LINEAR) GNO_BWD_CASE(NH_, CG_, MODE_NONLINEAR) GNO_BWD_CASE(NH_, CG_, MODE_KERNELONLY)
+            switch ((nh * 2 + (cg ? 1 : 0)) * 3 + mode) {
+                GNO_BWD_CASES(1, 0) GNO_BWD_CASES(1, 1) GNO_BWD_CASES(2, 0) GNO_BWD_CASES(2, 1) GNO_BWD_CASES(3, 0) GNO_BWD_CASES(3, 1)
             }
+#undef GNO_BWD_CASES
+#undef GNO_BWD_CASE
         }
         if (rc != GAOT_OK) return rc;
         GAOT_KLAUNCH(k_reduce_params, dim3((unsigned)ceil_div(total, 64)), dim3(256), 0, st, wpart, n_waves,
@@ -901,17 +1012,27 @@ int gno_bwd_impl(const char* fn, const gaot_mlp_t* mlp, const float* y_pos, cons
     GAOT_KLAUNCH(k_scatter_params, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, st, flat, sd);
     if (num_sources > 0) {
         const int64_t n = num_sources * 8;   // four channels per thread
-        if (precision == 1)
-            GAOT_KLAUNCH((k_segment_fixup<32, 4>), dim3(segment_fixup_grid(n)), dim3(256), 0, st, rowptr_src,
-                               num_sources, part, grad_f_y, 0);
-        else
-            GAOT_KLAUNCH((k_segment_fixup<32, 5>), dim3(segment_fixup_grid(n)), dim3(256), 0, st, rowptr_src,
-                               num_sources, part, grad_f_y, 0);
+        if (want_gf) {
+            if (precision == 1)
+                GAOT_KLAUNCH((k_segment_fixup<32, 4>), dim3(segment_fixup_grid(n)), dim3(256), 0, st, rowptr_src,
+                                   num_sources, part, grad_f_y, 0);
+            else
+                GAOT_KLAUNCH((k_segment_fixup<32, 5>), dim3(segment_fixup_grid(n)), dim3(256), 0, st, rowptr_src,
+                                   num_sources, part, grad_f_y, 0);
+        }
+        if (nlm) {
+            if (precision == 1)
+                GAOT_KLAUNCH((k_segment_fixup<NLH, 4>), dim3(segment_fixup_grid(2 * n)), dim3(256), 0, st, rowptr_src,
+                                   num_sources, part_dt, dt, 0);
+            else
+                GAOT_KLAUNCH((k_segment_fixup<NLH, 5>), dim3(segment_fixup_grid(2 * n)), dim3(256), 0, st, rowptr_src,
+                                   num_sources, part_dt, dt, 0);
+        }
     }
     GAOT_LAUNCH_CHECK();
     return GAOT_OK;
 }
-#undef GNO_BWD_CHECK
+#undef GNO_CHECK
 }  // namespace
 
 extern "C" int gaot_gno_bwd(const gaot_mlp_t* mlp, const float* y_pos, const float* x_pos, const float* f_y,
@@ -921,8 +1042,8 @@ extern "C" int gaot_gno_bwd(const gaot_mlp_t* mlp, const float* y_pos, const flo
                             int precision, void* workspace, size_t workspace_bytes, gaot_stream_t stream) {
     GAOT_ENTER();
     return gno_bwd_impl("gaot_gno_bwd", mlp, y_pos, x_pos, f_y, grad_out, rowptr_dst, src_sorted, dst_sorted, rowptr_src,
-                        num_edges, num_sources, num_queries, grad_f_y, grads, nullptr, precision, workspace, workspace_bytes,
-                        stream);
+                        num_edges, num_sources, num_queries, grad_f_y, grads, nullptr, MODE_LINEAR, nullptr, nullptr, precision,
+                        workspace, workspace_bytes, stream);
 }
 
 extern "C" int gaot_gno_bwd_coords(const gaot_mlp_t* mlp, const float* y_pos, const float* x_pos, const float* f_y,
@@ -934,6 +1055,19 @@ extern "C" int gaot_gno_bwd_coords(const gaot_mlp_t* mlp, const float* y_pos, co
     GAOT_ENTER();
     GAOT_CHECK_ARG(num_edges == 0 || grad_edge_coords, "null grad_edge_coords");
     return gno_bwd_impl("gaot_gno_bwd_coords", mlp, y_pos, x_pos, f_y, grad_out, rowptr_dst, src_sorted, dst_sorted,
-                        rowptr_src, num_edges, num_sources, num_queries, grad_f_y, grads, grad_edge_coords, precision,
-                        workspace, workspace_bytes, stream);
+                        rowptr_src, num_edges, num_sources, num_queries, grad_f_y, grads, grad_edge_coords, MODE_LINEAR, nullptr,
+                        nullptr, precision, workspace, workspace_bytes, stream);
+}
+
+extern "C" int gaot_gno_bwd_nl(const gaot_mlp_t* mlp, int mode, const float* y_pos, const float* x_pos, const float* f_y,
+                               const float* src_table, const float* grad_out, const int32_t* rowptr_dst,
+                               const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr_src, int64_t num_edges,
+                               int64_t num_sources, int64_t num_queries, float* grad_f_y, float* grad_src_table,
+                               const gaot_mlp_grad_t* grads, float* grad_edge_coords, int precision, void* workspace,
+                               size_t workspace_bytes, gaot_stream_t stream) {
+    GAOT_ENTER();
+    GAOT_CHECK_ARG(mode == MODE_NONLINEAR || mode == MODE_KERNELONLY, "mode must be 1 (nonlinear) or 2 (nonlinear_kernelonly)");
+    return gno_bwd_impl("gaot_gno_bwd_nl", mlp, y_pos, x_pos, f_y, grad_out, rowptr_dst, src_sorted, dst_sorted, rowptr_src,
+                        num_edges, num_sources, num_queries, grad_f_y, grads, grad_edge_coords, mode, src_table, grad_src_table,
+                        precision, workspace, workspace_bytes, stream);
 }

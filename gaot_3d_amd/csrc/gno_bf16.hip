@@ -49,12 +49,13 @@ struct FwdLdsB {
 
 // The 12 waves of the one workgroup per CU (THREE waves per SIMD) share one copy of the weight images.
 constexpr int FWD_NW = 12;
-template <int NH, int T>
+// MODE (gno_common.h): in the nonlinear / kernel-only modes `nl_` is one NlFwd and layer 0 starts from b_0 + t[src]
+template <int NH, int T, int MODE, class... Nl>
 __global__ __launch_bounds__(FWD_NW * 64, 1) void k_gno_fwd_bf16(MlpPtrs mlp, const float* __restrict__ y_pos,
                                                          const float* __restrict__ x_pos, const float* __restrict__ f_y,
                                                          const int* __restrict__ src_s, const int* __restrict__ dst_s,
                                                          const int* __restrict__ rowptr, int64_t E, float* __restrict__ out,
-                                                         float* __restrict__ part) {
+                                                         float* __restrict__ part, Nl... nl_) {
     constexpr int C = 32, H = 64, KB = 2, NW = FWD_NW;
     using L = FwdLdsB<NH>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -132,9 +133,11 @@ __global__ __launch_bounds__(FWD_NW * 64, 1) void k_gno_fwd_bf16(MlpPtrs mlp, co
     for (int64_t mt = mt0; mt < n_macro; mt += mstep) {
         const int64_t base = mt * 32 * T;
         float bin[T][3];
+        [[maybe_unused]] int sid[T];   // source of this lane's edge (edges past E: row 0, a valid row)
 #pragma unroll
         for (int t = 0; t < T; ++t) {
             bin[t][0] = pbin[t][0]; bin[t][1] = pbin[t][1]; bin[t][2] = pbin[t][2];
+            if constexpr (MODE != MODE_LINEAR) sid[t] = cs[t];
             if (hf == 0) {
                 ids[(t * 2 + 0) * 32 + l31] = cs[t];
                 ids[(t * 2 + 1) * 32 + l31] = cq[t];
@@ -153,6 +156,21 @@ __global__ __launch_bounds__(FWD_NW * 64, 1) void k_gno_fwd_bf16(MlpPtrs mlp, co
             for (int r = 0; r < 16; ++r) bias[r] = lds[L::b0 + 32 * ob + mfma32_row(r, hf)];
 #pragma unroll
             for (int t = 0; t < T; ++t) z[t] = bias;
+            if constexpr (MODE != MODE_LINEAR) {
+                // + t[src] in fp32: the lane's 16 features of this 32-block are four runs of four (mfma32_row): four 16-byte loads
+#pragma unroll
+                for (int t = 0; t < T; ++t) {
+                    const float* tr = first_arg(nl_...).t + (int64_t)sid[t] * NLH + 32 * ob + 4 * hf;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const float4 v = *reinterpret_cast<const float4*>(tr + 8 * j);
+                        z[t][4 * j + 0] += v.x;
+                        z[t][4 * j + 1] += v.y;
+                        z[t][4 * j + 2] += v.z;
+                        z[t][4 * j + 3] += v.w;
+                    }
+                }
+            }
 #pragma unroll
             for (int i = 0; i < IN0 / 2; ++i) {
                 const float a = lds[L::w0 + (2 * i + hf) * H + 32 * ob + l31];
@@ -220,9 +238,13 @@ __global__ __launch_bounds__(FWD_NW * 64, 1) void k_gno_fwd_bf16(MlpPtrs mlp, co
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int el = mfma32_row(r, hf);
-                const int s = ids[(t * 2 + 0) * 32 + el];
-                const float fval = f_y[(int64_t)s * C + l31];
-                stage[(t * 32 + el) * C + l31] = acc[r] * fval;
+                if constexpr (MODE == MODE_KERNELONLY) {   // the kernel value itself
+                    stage[(t * 32 + el) * C + l31] = acc[r];
+                } else {
+                    const int s = ids[(t * 2 + 0) * 32 + el];
+                    const float fval = f_y[(int64_t)s * C + l31];
+                    stage[(t * 32 + el) * C + l31] = acc[r] * fval;
+                }
             }
         }
         wave_lds_fence();
@@ -238,8 +260,8 @@ size_t fwd_lds_bytes_b(int nh, int t, int nw) {
     return sizeof(float) * (size_t)(weights + nw * t * 32 * 32) + sizeof(int) * (size_t)(nw * t * 2 * 32);
 }
 
-template <int NH>
-int launch_fwd_b(const MlpPtrs& p, const float* y_pos, const float* x_pos, const float* f_y, const int* src_s,
+template <int NH, int MODE>
+int launch_fwd_b(const MlpPtrs& p, const float* y_pos, const float* x_pos, const float* f_y, const float* ttab, const int* src_s,
                  const int* dst_s, const int* rowptr, int64_t E, float* out, float* part, hipStream_t st) {
     // 12 waves per workgroup (one weight image per CU, THREE waves per SIMD; 127 KB of LDS at three hidden layers) with the
     // id / coordinate loads pipelined.  Measured at E = 4 M (profiles/archive/r5_w_gno_fwd_variants_lab.txt; nh = 3 / 2 / 4): round-4 form
@@ -248,7 +270,10 @@ int launch_fwd_b(const MlpPtrs& p, const float* y_pos, const float* x_pos, const
     // 12 waves alone 0.377 / 0.279 / 0.427.  (measured and removed: the other three forms)
     constexpr int T = 2, NW = FWD_NW;
     const size_t lds = fwd_lds_bytes_b(NH, T, NW);
-    auto kern = k_gno_fwd_bf16<NH, T>;
+    auto kern = [] {
+        if constexpr (MODE == MODE_LINEAR) return k_gno_fwd_bf16<NH, T, MODE>;
+        else return k_gno_fwd_bf16<NH, T, MODE, NlFwd>;
+    }();
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -260,47 +285,53 @@ int launch_fwd_b(const MlpPtrs& p, const float* y_pos, const float* x_pos, const
     }
     const int64_t n_macro = ceil_div(E, 32 * T);
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n_macro, NW), 256));
-    GAOT_KLAUNCH(kern, dim3(grid), dim3(NW * 64), lds, st, p, y_pos, x_pos, f_y, src_s, dst_s, rowptr, E, out, part);
+    if constexpr (MODE == MODE_LINEAR)
+        GAOT_KLAUNCH(kern, dim3(grid), dim3(NW * 64), lds, st, p, y_pos, x_pos, f_y, src_s, dst_s, rowptr, E, out, part);
+    else
+        GAOT_KLAUNCH(kern, dim3(grid), dim3(NW * 64), lds, st, p, y_pos, x_pos, f_y, src_s, dst_s, rowptr, E, out, part, NlFwd{ttab});
     return GAOT_OK;
 }
 
 }  // namespace
 
-// called from gaot_gno_fwd (gno.hip) when precision == 1; num_edges > 0, shapes already validated
-int gaot_gno_fwd_bf16_dispatch(int n_hidden, const float* const* w, const float* const* b, const float* y_pos,
-                               const float* x_pos, const float* f_y, const int32_t* src_sorted, const int32_t* dst_sorted,
-                               const int32_t* rowptr_dst, int64_t num_edges, float* out, float* part, hipStream_t st) {
+// called from gaot_gno_fwd / gaot_gno_fwd_nl (gno.hip) when precision == 1; num_edges > 0, shapes already validated
+int gaot_gno_fwd_bf16_dispatch(int n_hidden, int mode, const float* const* w, const float* const* b, const float* y_pos,
+                               const float* x_pos, const float* f_y, const float* ttab, const int32_t* src_sorted,
+                               const int32_t* dst_sorted, const int32_t* rowptr_dst, int64_t num_edges, float* out, float* part,
+                               hipStream_t st) {
     MlpPtrs p;
     for (int l = 0; l <= n_hidden; ++l) { p.w[l] = w[l]; p.b[l] = b[l]; }
-    switch (n_hidden) {
-        case 1: return launch_fwd_b<1>(p, y_pos, x_pos, f_y, src_sorted, dst_sorted, rowptr_dst, num_edges, out, part, st);
-        case 2: return launch_fwd_b<2>(p, y_pos, x_pos, f_y, src_sorted, dst_sorted, rowptr_dst, num_edges, out, part, st);
-        case 3: return launch_fwd_b<3>(p, y_pos, x_pos, f_y, src_sorted, dst_sorted, rowptr_dst, num_edges, out, part, st);
-        case 4: return launch_fwd_b<4>(p, y_pos, x_pos, f_y, src_sorted, dst_sorted, rowptr_dst, num_edges, out, part, st);
+#define GNO_FWDB_CASE(NH_, MODE_) \
+    case NH_ * 3 + MODE_: return launch_fwd_b<NH_, MODE_>(p, y_pos, x_pos, f_y, ttab, src_sorted, dst_sorted, rowptr_dst, num_edges, out, part, st);
+#define GNO_FWDB_CASES(NH_) GNO_FWDB_CASE(NH_, MODE_LINEAR) GNO_FWDB_CASE(NH_, MODE_NONLINEAR) GNO_FWDB_CASE(NH_, MODE_KERNELONLY)
+    if (n_hidden >= 1 && n_hidden <= 4 && mode >= 0 && mode <= 2) switch (n_hidden * 3 + mode) {
+        GNO_FWDB_CASES(1) GNO_FWDB_CASES(2) GNO_FWDB_CASES(3) GNO_FWDB_CASES(4)
     }
-    gaot_set_error("gaot_gno_fwd (bf16): unsupported n_hidden %d", n_hidden);
+#undef GNO_FWDB_CASES
+#undef GNO_FWDB_CASE
+    gaot_set_error("gaot_gno_fwd (bf16): unsupported n_hidden %d / mode %d", n_hidden, mode);
     return GAOT_ERR_UNSUPPORTED;
 }
 
 // =================================================================================================
 // Backward (bf16 matrix cores): k_gno_bwd3_bf16 (gno_bwd3_bf16.hip)
 // =================================================================================================
-int gaot_gno_bwd3_bf16_launch(int n_hidden, void* images, const float* w0t, const float* const* w, const float* const* b,
+int gaot_gno_bwd3_bf16_launch(int n_hidden, int mode, void* images, const float* w0t, const float* const* w, const float* const* b,
                               const float* y_pos, const float* x_pos, const float* f_y, const float* gs,
                               const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr_src,
-                              int64_t num_edges, float* grad_f, float* part, float* wpart, float* gcoord, int grid,
-                              hipStream_t st);
+                              int64_t num_edges, float* grad_f, float* part, float* wpart, float* gcoord, const float* ttab,
+                              float* dt, float* part_dt, int grid, hipStream_t st);
 
 // recompute and transposed data-gradient fragment images of the hidden layers (8 KB each) and of the last layer (4 KB each)
 size_t gaot_gno_bwd_bf16_image_bytes(int n_hidden) { return (size_t)(n_hidden - 1) * 2 * 8192 + 2 * 4096 + 256; }
 
-// called from gaot_gno_bwd (gno.hip) for precision == 1.  `images` = scratch of gaot_gno_bwd_bf16_image_bytes();
+// called from gaot_gno_bwd / _coords / _nl (gno.hip) for precision == 1.  `images` = scratch of gaot_gno_bwd_bf16_image_bytes();
 // w0t = fp32 [6][64] transposed first-layer weight (prepared by the caller, shared with the fp32 path).
-int gaot_gno_bwd_bf16_dispatch(int n_hidden, const float* const* w, const float* const* b, const float* w0t,
+int gaot_gno_bwd_bf16_dispatch(int n_hidden, int mode, const float* const* w, const float* const* b, const float* w0t,
                                void* images, const float* y_pos, const float* x_pos, const float* f_y, const float* gs,
                                const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr_src,
-                               int64_t num_edges, float* grad_f, float* part, float* wpart, float* gcoord, int grid,
-                               hipStream_t st) {
-    return gaot_gno_bwd3_bf16_launch(n_hidden, images, w0t, w, b, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src,
-                                     num_edges, grad_f, part, wpart, gcoord, grid, st);
+                               int64_t num_edges, float* grad_f, float* part, float* wpart, float* gcoord, const float* ttab,
+                               float* dt, float* part_dt, int grid, hipStream_t st) {
+    return gaot_gno_bwd3_bf16_launch(n_hidden, mode, images, w0t, w, b, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src,
+                                     num_edges, grad_f, part, wpart, gcoord, ttab, dt, part_dt, grid, st);
 }

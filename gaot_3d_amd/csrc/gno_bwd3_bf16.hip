@@ -89,6 +89,21 @@ __device__ __forceinline__ bf16x8 frag_rows8(const char* tile, int n, int g) {
 __device__ __forceinline__ float mul_f16lo(float a, unsigned g) { return __builtin_fmaf(a, (float)__builtin_bit_cast(h16x2, g)[0], 0.0f); }
 __device__ __forceinline__ float mul_f16hi(float a, unsigned g) { return __builtin_fmaf(a, (float)__builtin_bit_cast(h16x2, g)[1], 0.0f); }
 
+// one stride of the inclusive segmented scan along a 16-lane DPP row: lane n takes the value of lane n - D unless one of the rows
+// (bits of `mfirst`: lanes that start a row) begins in (n - D, n]
+template <int D>
+__device__ __forceinline__ void seg_scan_step(f32x4 (&v)[4], unsigned mfirst, int n) {
+    const bool take = n >= D && ((mfirst >> (n >= D ? n - D + 1 : 0)) & ((1u << D) - 1u)) == 0u;
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float x = v[mb][i];   // (a scalar copy: __builtin_bit_cast of a vector ELEMENT reads element 0)
+            const float up = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x110 + D, 0xf, 0xf, false));
+            v[mb][i] = x + (take ? up : 0.f);
+        }
+}
+
 template <int NH>
 struct Lds3 {
     static constexpr int H = 64, C = 32, WAVES = 8;
@@ -152,7 +167,12 @@ __global__ void k_prep_bwd3_images(MlpPtrs mlp, int nh, bf16_t* base) {
 
 // CG: also the coordinate gradient of every edge, g_e = W_0^T dz_0[e] (6 fp32, source-sorted edge order) -> gcoord [E][6]
 // (the output pointer is a parameter pack: empty when CG is off, so those instantiations keep today's kernel arguments)
-template <int NH, bool CG, class... CoordOut>
+// MODE (gno_common.h): the nonlinear / kernel-only modes append one NlBwd to the pack.  Layer 0 is recomputed from b_0 + t[src]
+// (the lane's four 16-byte pieces of the t row are requested one tile ahead, with the coordinates), and dt[s] = the sum of the fp32
+// dz_0 over the edges of source s is formed in registers by a segmented scan along the 16 edge lanes (seg_scan_step): direct
+// stores for rows that end inside the tile, the tile-ordered partial buffer for the rest.  Kernel-only mode: dk = bf16(gs), no f
+// gather, grad_f is not written.
+template <int NH, bool CG, int MODE, class... CoordOut>
 __global__ __launch_bounds__(512, 1) void k_gno_bwd3_bf16(
     const uint4* __restrict__ images, const float* __restrict__ w0t_g, MlpPtrs mlp, const float* __restrict__ y_pos,
     const float* __restrict__ x_pos, const float* __restrict__ f_y, const float* __restrict__ gs,
@@ -223,6 +243,7 @@ __global__ __launch_bounds__(512, 1) void k_gno_bwd3_bf16(
     int s_nx = 0, q_nx = 0;
     bool v_nx = false;
     float bin_nx[2] = {0.f, 0.f};
+    [[maybe_unused]] f32x4 t_nx[4];   // t[src] of the next tile: features 16 mb + 4 g .. + 3
     auto fetch_ids = [&](int64_t tb_) {
         const int64_t e = (tb_ + wave) * 16 + n;
         v_nx = tb_ < n_tiles && e < E;
@@ -234,6 +255,11 @@ __global__ __launch_bounds__(512, 1) void k_gno_bwd3_bf16(
         const float* xq = x_pos + (int64_t)q_nx * 3;
         bin_nx[0] = g < 3 ? ys[g] : xq[0];
         bin_nx[1] = g < 2 ? xq[1 + g] : 0.f;
+        if constexpr (MODE != MODE_LINEAR) {
+            const float* tr = last_arg(gcoord_...).t + (int64_t)s_nx * NLH + 4 * g;
+#pragma unroll
+            for (int mb = 0; mb < 4; ++mb) t_nx[mb] = *reinterpret_cast<const f32x4*>(tr + 16 * mb);
+        }
     };
     fetch_ids((int64_t)blockIdx.x * 8);
     fetch_pos();
@@ -243,6 +269,11 @@ __global__ __launch_bounds__(512, 1) void k_gno_bwd3_bf16(
         // tile loop into (and beyond) the whole register file
         asm volatile("" ::: "memory");
         float bin0, bin1;
+        [[maybe_unused]] f32x4 tcur[4];
+        if constexpr (MODE != MODE_LINEAR) {
+#pragma unroll
+            for (int mb = 0; mb < 4; ++mb) tcur[mb] = t_nx[mb];
+        }
         int idv, rbv = 0, rev = 0;   // per edge (lane n, all groups alike): source row or -1, and its [rb, re) edge range
         int s_raw, q_raw;            // endpoints as fetched (0 for edges past E)
         {
@@ -277,6 +308,8 @@ __global__ __launch_bounds__(512, 1) void k_gno_bwd3_bf16(
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb) {
                 gv[nb][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rg, q_ * (C * 4) + (16 * nb + n) * 4, 0, 0));
+                if constexpr (MODE == MODE_KERNELONLY) fv[nb][r] = 1.f;
+                else
                 fv[nb][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rf, s_ * (C * 4) + (16 * nb + n) * 4, 0, 0));
             }
         }
@@ -329,6 +362,7 @@ __global__ __launch_bounds__(512, 1) void k_gno_bwd3_bf16(
 #pragma unroll
             for (int mb = 0; mb < 4; ++mb) {
                 z[mb] = *reinterpret_cast<const f32x4*>(bias_l + 16 * mb + 4 * g);
+                if constexpr (MODE != MODE_LINEAR) z[mb] += tcur[mb];
                 z[mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[g * L::W0S + 16 * mb + n], bin0, z[mb], 0, 0, 0);
                 z[mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[(4 + g) * L::W0S + 16 * mb + n], bin1, z[mb], 0, 0, 0);
             }
@@ -365,7 +399,7 @@ __global__ __launch_bounds__(512, 1) void k_gno_bwd3_bf16(
             for (int r = 0; r < 4; ++r)
                 if (4 * g + r >= nvalid) { gv[0][r] = 0.f; gv[1][r] = 0.f; }
         }
-        {
+        if constexpr (MODE != MODE_KERNELONLY) {
             // the rows of the tile are runs of equal source ids; a run ends where the edge is the last of its row or of the
             // tile.  m'[e][c] goes through a [16 e][32 c] fp32 scratch (the dz_0 slot, written later): every lane (channel
             // l31, half hf) turns the 8 edges of its half into running sums, restarted at the first edge of every row;
@@ -413,7 +447,9 @@ __global__ __launch_bounds__(512, 1) void k_gno_bwd3_bf16(
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb)
             *reinterpret_cast<uint2*>(dkT + tile_off(16 * nb + n, g >> 1) + 8 * (g & 1)) =
-                make_uint2(pk_bf16(gv[nb][0] * fv[nb][0], gv[nb][1] * fv[nb][1]), pk_bf16(gv[nb][2] * fv[nb][2], gv[nb][3] * fv[nb][3]));
+                MODE == MODE_KERNELONLY
+                    ? make_uint2(pk_bf16(gv[nb][0], gv[nb][1]), pk_bf16(gv[nb][2], gv[nb][3]))
+                    : make_uint2(pk_bf16(gv[nb][0] * fv[nb][0], gv[nb][1] * fv[nb][1]), pk_bf16(gv[nb][2] * fv[nb][2], gv[nb][3] * fv[nb][3]));
         wave_lds_fence();
         // ---- data gradients, top down: dh_l[k][e] = sum_j W_{l+1}[j][k] dz_{l+1}[j][e] ; dz_l = dh_l * gelu'(z_l) ---------
         __builtin_amdgcn_sched_barrier(0);
@@ -480,6 +516,29 @@ __global__ __launch_bounds__(512, 1) void k_gno_bwd3_bf16(
         }
 #pragma unroll
         for (int s = 0; s < 2; ++s) store_frag_rows(mine + L::dz(0), frag_of(dz[2 * s], dz[2 * s + 1]), s, n, g);
+        if constexpr (MODE != MODE_LINEAR) {
+            // dt[s][j] = sum of the fp32 dz_0[j][e] over the edges of s.  A lane group g holds features 16 mb + 4 g + i of the 16
+            // edges n = its 16 lanes -- one DPP row -- so the segmented sum over the source-sorted tile is an inclusive segmented scan
+            // along the row (strides 1, 2, 4, 8 with row_shr; a lane takes the value d lanes down unless a row of the tile starts in
+            // between: a fixed order, bit-reproducible), in place in dz (its fragments are stored).  The lane of a row's last edge
+            // then holds the row's sum of its 16 features: four 16-byte stores, to dt for a row that lies inside the tile, else to
+            // the tile's partial slot (0: open to the left, 1: open to the right only; k_segment_fixup<64, 4> adds them in tile order).
+            const NlBwd nl = last_arg(gcoord_...);
+            const int64_t pos = base + n;
+            const bool ok = idv >= 0;
+            const unsigned mfirst = (unsigned)__ballot(ok && (pos == (int64_t)rbv || n == 0)) & 0xffffu;
+            const bool last = ok && (pos == (int64_t)rev - 1 || n == 15 || pos + 1 >= E);
+            const bool ol = (int64_t)rbv < base, orr = (int64_t)rev > base + 16;
+            seg_scan_step<1>(dz, mfirst, n);
+            seg_scan_step<2>(dz, mfirst, n);
+            seg_scan_step<4>(dz, mfirst, n);
+            seg_scan_step<8>(dz, mfirst, n);
+            if (last) {
+                float* o = (!ol && !orr) ? nl.dt + (int64_t)idv * NLH : nl.part_dt + ((base >> 4) * 2 + (ol ? 0 : 1)) * NLH;
+#pragma unroll
+                for (int mb = 0; mb < 4; ++mb) *reinterpret_cast<f32x4*>(o + 16 * mb + 4 * g) = dz[mb];
+            }
+        }
         __syncthreads();
         // ---- weight gradients of the eight tiles: dW_l[j][k] += sum_e dz_l[j][e] h_{l-1}[k][e]  (K = the 16 edges) ---------
 #pragma unroll 1
@@ -576,15 +635,20 @@ __global__ __launch_bounds__(512, 1) void k_gno_bwd3_bf16(
     }
 }
 
-template <int NH, bool CG>
+template <int NH, bool CG, int MODE>
 int launch_bwd3(const void* images, const float* w0t, const MlpPtrs& p, const float* y_pos, const float* x_pos,
                 const float* f_y, const float* gs, const int* src_s, const int* dst_s, const int* rowptr_src, int64_t E,
-                float* grad_f, float* part, float* wpart, float* gcoord, int grid, hipStream_t st) {
+                float* grad_f, float* part, float* wpart, float* gcoord, const NlBwd& nl, int grid, hipStream_t st) {
     constexpr int lds = Lds3<NH>::total;
     static_assert(lds <= 160 * 1024, "LDS budget");
     auto kern = [] {
-        if constexpr (CG) return k_gno_bwd3_bf16<NH, true, float*>;
-        else return k_gno_bwd3_bf16<NH, false>;
+        if constexpr (MODE == MODE_LINEAR) {
+            if constexpr (CG) return k_gno_bwd3_bf16<NH, true, MODE, float*>;
+            else return k_gno_bwd3_bf16<NH, false, MODE>;
+        } else {
+            if constexpr (CG) return k_gno_bwd3_bf16<NH, true, MODE, float*, NlBwd>;
+            else return k_gno_bwd3_bf16<NH, false, MODE, NlBwd>;
+        }
     }();
     static bool attr_set = false;
     if (!attr_set) {
@@ -595,12 +659,21 @@ int launch_bwd3(const void* images, const float* w0t, const MlpPtrs& p, const fl
         }
         attr_set = true;
     }
-    if constexpr (CG)
-        GAOT_KLAUNCH(kern, dim3(grid), dim3(512), lds, st, (const uint4*)images, w0t, p, y_pos, x_pos, f_y, gs, src_s, dst_s,
-                     rowptr_src, E, grad_f, part, wpart, gcoord);
-    else
-        GAOT_KLAUNCH(kern, dim3(grid), dim3(512), lds, st, (const uint4*)images, w0t, p, y_pos, x_pos, f_y, gs, src_s, dst_s,
-                     rowptr_src, E, grad_f, part, wpart);
+    if constexpr (MODE == MODE_LINEAR) {
+        if constexpr (CG)
+            GAOT_KLAUNCH(kern, dim3(grid), dim3(512), lds, st, (const uint4*)images, w0t, p, y_pos, x_pos, f_y, gs, src_s, dst_s,
+                         rowptr_src, E, grad_f, part, wpart, gcoord);
+        else
+            GAOT_KLAUNCH(kern, dim3(grid), dim3(512), lds, st, (const uint4*)images, w0t, p, y_pos, x_pos, f_y, gs, src_s, dst_s,
+                         rowptr_src, E, grad_f, part, wpart);
+    } else {
+        if constexpr (CG)
+            GAOT_KLAUNCH(kern, dim3(grid), dim3(512), lds, st, (const uint4*)images, w0t, p, y_pos, x_pos, f_y, gs, src_s, dst_s,
+                         rowptr_src, E, grad_f, part, wpart, gcoord, nl);
+        else
+            GAOT_KLAUNCH(kern, dim3(grid), dim3(512), lds, st, (const uint4*)images, w0t, p, y_pos, x_pos, f_y, gs, src_s, dst_s,
+                         rowptr_src, E, grad_f, part, wpart, nl);
+    }
     return GAOT_OK;
 }
 
@@ -608,33 +681,31 @@ int launch_bwd3(const void* images, const float* w0t, const MlpPtrs& p, const fl
 
 // images: scratch of gaot_gno_bwd_bf16_image_bytes() (gno_bf16.hip); w0t = fp32 [6][64] transposed first-layer weight; part: two
 // 32-channel slots per 16-EDGE tile (k_segment_fixup<32, 4>); wpart: one flat parameter-gradient partial per workgroup;
-// gcoord: null, or [num_edges][6] coordinate gradients per edge (source-sorted order)
-int gaot_gno_bwd3_bf16_launch(int n_hidden, void* images, const float* w0t, const float* const* w, const float* const* b,
+// gcoord: null, or [num_edges][6] coordinate gradients per edge (source-sorted order); mode != linear: ttab / dt [N_y][64] and
+// part_dt, two 64-float slots per 16-edge tile (k_segment_fixup<64, 4>)
+int gaot_gno_bwd3_bf16_launch(int n_hidden, int mode, void* images, const float* w0t, const float* const* w, const float* const* b,
                               const float* y_pos, const float* x_pos, const float* f_y, const float* gs,
                               const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr_src,
-                              int64_t num_edges, float* grad_f, float* part, float* wpart, float* gcoord, int grid,
-                              hipStream_t st) {
-    if (n_hidden < 1 || n_hidden > 4) {      // before anything indexes w / b / MlpPtrs with it
-        gaot_set_error("gaot_gno_bwd (bf16): unsupported n_hidden %d", n_hidden);
+                              int64_t num_edges, float* grad_f, float* part, float* wpart, float* gcoord, const float* ttab,
+                              float* dt, float* part_dt, int grid, hipStream_t st) {
+    if (n_hidden < 1 || n_hidden > 4 || mode < 0 || mode > 2) {      // before anything indexes w / b / MlpPtrs with it
+        gaot_set_error("gaot_gno_bwd (bf16): unsupported n_hidden %d / mode %d", n_hidden, mode);
         return GAOT_ERR_UNSUPPORTED;
     }
     MlpPtrs p;
     for (int l = 0; l <= n_hidden; ++l) { p.w[l] = w[l]; p.b[l] = b[l]; }
     GAOT_KLAUNCH(k_prep_bwd3_images, dim3(32), dim3(256), 0, st, p, n_hidden, (bf16_t*)images);
-#define GNO_BWD3_ARGS images, w0t, p, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src, num_edges, grad_f, part, wpart, gcoord, grid, st
-    if (gcoord == nullptr) {
-        switch (n_hidden) {
-            case 1: return launch_bwd3<1, false>(GNO_BWD3_ARGS);
-            case 2: return launch_bwd3<2, false>(GNO_BWD3_ARGS);
-            case 3: return launch_bwd3<3, false>(GNO_BWD3_ARGS);
-            default: return launch_bwd3<4, false>(GNO_BWD3_ARGS);
-        }
+    const NlBwd nl{ttab, dt, part_dt};
+#define GNO_BWD3_CASE(NH_, CG_, MODE_)                                                                                      \
+    case (NH_ * 2 + CG_) * 3 + MODE_:                                                                                       \
+        return launch_bwd3<NH_, CG_ != 0, MODE_>(images, w0t, p, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src,   \
+                                                 num_edges, grad_f, part, wpart, gcoord, nl, grid, st);
+#define GNO_BWD3_CASES(NH_, CG_) GNO_BWD3_CASE(NH_, CG_, MODE_LINEAR) GNO_BWD3_CASE(NH_, CG_, MODE_NONLINEAR) GNO_BWD3_CASE(NH_, CG_, MODE_KERNELONLY)
+    switch ((n_hidden * 2 + (gcoord ? 1 : 0)) * 3 + mode) {
+        GNO_BWD3_CASES(1, 0) GNO_BWD3_CASES(1, 1) GNO_BWD3_CASES(2, 0) GNO_BWD3_CASES(2, 1)
+        GNO_BWD3_CASES(3, 0) GNO_BWD3_CASES(3, 1) GNO_BWD3_CASES(4, 0) GNO_BWD3_CASES(4, 1)
     }
-    switch (n_hidden) {
-        case 1: return launch_bwd3<1, true>(GNO_BWD3_ARGS);
-        case 2: return launch_bwd3<2, true>(GNO_BWD3_ARGS);
-        case 3: return launch_bwd3<3, true>(GNO_BWD3_ARGS);
-        default: return launch_bwd3<4, true>(GNO_BWD3_ARGS);
-    }
-#undef GNO_BWD3_ARGS
+#undef GNO_BWD3_CASES
+#undef GNO_BWD3_CASE
+    return GAOT_ERR_UNSUPPORTED;
 }

@@ -10,8 +10,33 @@ constexpr int IN0P = 8;     // padded
 
 // the single argument of a (possibly empty) parameter pack: optional kernel outputs whose absence leaves the kernel's argument
 // list as it was
+template <class T, class... R>
+__device__ __forceinline__ T first_arg(T t, R...) { return t; }
 template <class T>
-__device__ __forceinline__ T first_arg(T t) { return t; }
+__device__ __forceinline__ T last_arg(T t) { return t; }
+template <class T, class U, class... R>
+__device__ __forceinline__ auto last_arg(T, U u, R... r) { return last_arg(u, r...); }
+
+// transform_type of the integral transform (reference integral_transform.py:146-157), a compile-time mode of the kernels:
+//   LINEAR      k = MLP([y_s, x_q]),         out_q = mean k * f_y[s]
+//   NONLINEAR   k = MLP([y_s, x_q, f_y[s]]), out_q = mean k * f_y[s]
+//   KERNELONLY  k = MLP([y_s, x_q, f_y[s]]), out_q = mean k
+// In the two new modes layer 0 is z_0 = W_0c [y_s, x_q] + b_0 + t[s] with the per-NODE product t = W_0f f_y ([N_y][64] fp32,
+// formed once on the row-linear kernels): an edge's layer-0 accumulator starts from b_0 + t[src] instead of b_0.  The backward
+// also returns dt[s] = sum_{e: src = s} dz_0[e] ([N_y][64] fp32, from the unrounded dz_0), a segmented sum over the source-sorted
+// edge list like grad f_y; dW_0f = dt^T f_y and grad f_y += dt W_0f are the caller's per-node products.
+enum { MODE_LINEAR = 0, MODE_NONLINEAR = 1, MODE_KERNELONLY = 2 };
+constexpr int NLH = 64;     // row width of t / dt
+// the extra operands of the two new modes, passed as the last kernel argument (a parameter pack that is empty in linear mode, so
+// those instantiations keep today's kernel arguments)
+struct NlFwd {
+    const float* t;         // [N_y][64]
+};
+struct NlBwd {
+    const float* t;         // [N_y][64]
+    float* dt;              // [N_y][64]
+    float* part_dt;         // two 64-float slots per tile: rows of dt that straddle tiles (k_segment_fixup<64, ..>)
+};
 
 __device__ __forceinline__ void wave_lds_fence() {
     // LDS ops of one wave execute in order; this only stops the compiler from reordering.

@@ -343,6 +343,46 @@ class GnoFn(Function):
         return (gf, None, None, None, *grads)
 
 
+class GnoNlFn(Function):
+    """Fused IntegralTransform for transform_type 'nonlinear' / 'nonlinear_kernelonly' (mean reduction), one 32-channel pass.
+    ``t`` = f_y W_0f^T [N_y, 64]: the feature term of the kernel MLP's first layer, a per-node product formed by the caller (shared
+    by the passes); ``params`` = (W_0c, b_0, W_1, b_1, ...) with the coordinate block W_0c [64, 6] of the first layer.  ``f_y`` = the
+    pass's 32 channels ('nonlinear') or None ('nonlinear_kernelonly').  Returns the gradient of ``t`` (autograd adds the passes' and
+    carries it into dW_0f and grad f_y through the caller's linear) beside those of f_y, the coordinates and the parameters."""
+
+    @staticmethod
+    def forward(ctx, mode: str, f_y: Optional[Tensor], t: Tensor, y_pos: Tensor, x_pos: Tensor, graph, *params):
+        nl = len(params) // 2
+        ws = [_w2d(p) for p in params[0::2]]
+        bs = list(params[1::2])
+        f = f_y if (f_y is None or f_y.is_contiguous()) else f_y.contiguous()
+        tc = t if t.is_contiguous() else t.contiguous()
+        out = ops.gno_nl_forward(mode, ws, bs, y_pos, x_pos, f, tc, graph)
+        ctx.graph, ctx.nl, ctx.mode, ctx.has_f = graph, nl, mode, f is not None
+        ctx.wshapes = [p.shape for p in params[0::2]]
+        ctx.save_for_backward(*([f] if f is not None else []), tc, y_pos, x_pos, *ws, *bs)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout: Tensor):
+        saved = list(ctx.saved_tensors)
+        f = saved.pop(0) if ctx.has_f else None
+        tc, y_pos, x_pos = saved[:3]
+        ws = list(saved[3:3 + ctx.nl])
+        bs = list(saved[3 + ctx.nl:])
+        d = dout if dout.is_contiguous() else dout.contiguous()
+        need = ctx.needs_input_grad
+        coords = need[3] or need[4]     # coordinates that require grad: the kernel also forms W_0c^T dz_0 per edge
+        res = ops.gno_nl_backward(ctx.mode, ws, bs, y_pos, x_pos, f, tc, d, ctx.graph, coords=coords)
+        gf, gt, gw, gb = res[:4]
+        gy, gx = (res[4], res[5]) if coords else (None, None)
+        grads: List[Optional[Tensor]] = []
+        for l in range(ctx.nl):
+            grads += [gw[l].view(ctx.wshapes[l]) if need[6 + 2 * l] else None, gb[l] if need[7 + 2 * l] else None]
+        return (None, gf if (ctx.has_f and need[1]) else None, gt if need[2] else None, gy if need[3] else None,
+                gx if need[4] else None, None, *grads)
+
+
 def _want_bf16_copy(x: Tensor) -> bool:
     return ops.get_precision() == "bf16" and x.is_cuda and x.shape[-1] % 8 == 0
 

@@ -2,8 +2,12 @@
 (src/model/layers/integral_transform.py:31-40, 80-87).
 
 Default configuration -- transform_type='linear', no attention weights, kernel MLP 6 -> 64 (x1..4) -> 32 -- runs the
-fused HIP kernels (csrc/gno.hip, gno_bf16.hip: no per-edge tensor ever reaches HBM).  Every other variant the
-reference offers ('nonlinear', 'nonlinear_kernelonly', use_attn cosine / dot_product, other MLP shapes, f_y=None)
+fused HIP kernels (csrc/gno.hip, gno_bf16.hip, gno_bwd3_bf16.hip: no per-edge tensor ever reaches HBM).  So do
+transform_type='nonlinear' and 'nonlinear_kernelonly' (kernel MLP 6 + C_in -> 64 (x1..4) -> C): the feature columns of the
+first layer act on the SOURCE node only, so t = W_0f f_y is one per-node product ([N_y, 64], fp32) and the kernels start every
+edge's first-layer accumulator from b_0 + t[src]; the backward returns dt[s] = sum of dz_0 over the edges of s, from which
+dW_0f = dt^T f_y and grad f_y += dt W_0f follow as per-node products (the autograd of the linear that formed t).
+Every other variant the reference offers (use_attn cosine / dot_product, other MLP shapes, f_y=None)
 runs the general path: per-edge tensors in dst-sorted order, the MLP on the GEMM kernels, gather / segment /
 element-wise glue and its autograd in csrc/edgeops.hip (gaot_3d_amd/edgeops.py).  HIP only, no CPU fallback."""
 from typing import Optional
@@ -115,14 +119,17 @@ class IntegralTransform(nn.Module):
     def _fused_plan(self, fcs, f_y, y_pos, x_pos=None):
         """(coord_dim, channels) when the fused kernels (csrc/gno*.hip: coordinates of dimension 3, hidden width 64, 32
         channels per pass) can evaluate this transform EXACTLY, possibly through zero padding; None -> general path.
-        Kernel MLP coord-pair -> 64 (x 1..4; with gradients in fp32 mode: 1..3) -> C with GELU, 'linear' transform, mean reduction:
+        Kernel MLP coord-pair -> 64 (x 1..4; with gradients in fp32 mode: 1..3) -> C with GELU, mean reduction; 'linear' transform, or
+        'nonlinear' / 'nonlinear_kernelonly' with the kernel MLP's input widened by f_y's channels (their term of the first layer is
+        the per-node product t = W_0f f_y, see ``_forward_fused``; 'nonlinear' needs as many input as output channels):
           * coord_dim 1 / 2 (the reference's default is 2, magno.py:28): coordinates padded with zeros to 3-D and the first
             layer's weight given zero columns for them -- the products that are added are exactly 0;
           * C != 32 (the reference's default is 16, magno.py:25): the last layer / f_y / the output are cut into blocks of 32
             channels (the last one zero-padded); every block is one pass of the 32-channel kernels, so C = 16 costs what
             C = 32 costs and C = 64 two passes (the hidden layers are recomputed), still without a per-edge tensor in HBM."""
-        if self.use_attn or self.transform_type != "linear" or f_y is None:
+        if self.use_attn or self.transform_type not in ("linear", "nonlinear", "nonlinear_kernelonly") or f_y is None:
             return None
+        cin = 0 if self.transform_type == "linear" else f_y.shape[1]      # feature columns of the first layer
         # the exact-fp32 backward keeps the hidden activations of 128 edges in LDS: three hidden layers at most when gradients
         # are needed in fp32 mode; the bf16 backward takes four (its operand fragments then come from L2, gno_bwd3_bf16.hip)
         need_grad = torch.is_grad_enabled() and (f_y.requires_grad or any(fc.weight.requires_grad for fc in fcs)
@@ -140,8 +147,9 @@ class IntegralTransform(nn.Module):
         # magno.py:32,36) is zero-padded to it -- gelu(0) = 0 and the padded rows / columns of the neighbouring weights are 0,
         # so every added product is exactly 0 (a width of 32 then costs what 64 costs; wider layers take the general path)
         chain = all(dims[i][1] == dims[i - 1][0] for i in range(1, len(dims)))
-        ok = (cd in (1, 2, 3) and dims[0][1] == 2 * cd and chain and all(1 <= d[0] <= 64 for d in dims[:-1])
-              and 1 <= c <= 256 and f_y.shape[1] == c and all(fc.bias is not None for fc in fcs))
+        ok = (cd in (1, 2, 3) and dims[0][1] == 2 * cd + cin and chain and all(1 <= d[0] <= 64 for d in dims[:-1])
+              and 1 <= c <= 256 and (f_y.shape[1] == c or self.transform_type == "nonlinear_kernelonly")
+              and all(fc.bias is not None for fc in fcs))
         return (cd, c) if ok else None
 
     def _fused_eligible(self, fcs, f_y) -> bool:
@@ -153,12 +161,23 @@ class IntegralTransform(nn.Module):
     def _forward_fused(self, fcs, y_pos, x_pos, f_y, graph, cd: int, c: int):
         w2 = lambda fc: fc.weight[:, :, 0] if fc.weight.dim() == 3 else fc.weight    # Conv1d(k=1) storage of mlp_type='channel'
         pad_hidden = any(fc.weight.shape[0] != 64 for fc in fcs[:-1])
-        if cd == 3 and c == 32 and not pad_hidden:                                    # the shipped shape: straight through
+        tt = self.transform_type
+        if tt == "linear" and cd == 3 and c == 32 and not pad_hidden:                 # the shipped shape: straight through
             params = []
             for fc in fcs:
                 params += [fc.weight, fc.bias]
             return GF.GnoFn.apply(f_y, y_pos, x_pos, graph, *params)
         y3, x3, w0 = y_pos, x_pos, w2(fcs[0])
+        t = None
+        if tt != "linear":
+            # W_0 = [W_0c | W_0f]: the feature term of the first layer, t = f_y W_0f^T [N_y, 64] (rows of W_0f zero-padded to the
+            # kernels' hidden width), is formed ONCE in fp32 (layer 0 is fp32 in both precision modes) and shared by the passes;
+            # its autograd turns the passes' summed dt into dW_0f = dt^T f_y and grad f_y += dt W_0f
+            w0f = w0[:, 2 * cd:]
+            if w0f.shape[0] != 64:
+                w0f = torch.nn.functional.pad(w0f, (0, 0, 0, 64 - w0f.shape[0]))
+            t = GF.linear(f_y, w0f.contiguous(), None, precision=0)
+            w0 = w0[:, :2 * cd]
         if cd < 3:
             y3 = torch.nn.functional.pad(y_pos, (0, 3 - cd))
             x3 = torch.nn.functional.pad(x_pos, (0, 3 - cd))
@@ -178,12 +197,17 @@ class IntegralTransform(nn.Module):
         outs = []
         for c0 in range(0, c, 32):
             n = min(32, c - c0)
-            wb, bb, fb = wl[c0:c0 + n], bl[c0:c0 + n], f_y[:, c0:c0 + n]
+            wb, bb = wl[c0:c0 + n], bl[c0:c0 + n]
+            fb = None if tt == "nonlinear_kernelonly" else f_y[:, c0:c0 + n]
             if n < 32:
                 wb = torch.nn.functional.pad(wb, (0, 0, 0, 32 - n))
                 bb = torch.nn.functional.pad(bb, (0, 32 - n))
-                fb = torch.nn.functional.pad(fb, (0, 32 - n))
-            o = GF.GnoFn.apply(fb.contiguous(), y3, x3, graph, w0, b0, *mid, wb.contiguous(), bb.contiguous())
+                fb = None if fb is None else torch.nn.functional.pad(fb, (0, 32 - n))
+            if tt == "linear":
+                o = GF.GnoFn.apply(fb.contiguous(), y3, x3, graph, w0, b0, *mid, wb.contiguous(), bb.contiguous())
+            else:
+                o = GF.GnoNlFn.apply(tt, None if fb is None else fb.contiguous(), t, y3, x3, graph, w0.contiguous(), b0, *mid,
+                                     wb.contiguous(), bb.contiguous())
             outs.append(o[:, :n] if n < 32 else o)
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
 

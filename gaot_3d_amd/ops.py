@@ -238,6 +238,85 @@ def gno_backward(weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Tensor, gra
     return grad_f, gw, gb
 
 
+GNO_MODES = {"nonlinear": 1, "nonlinear_kernelonly": 2}      # csrc/gno_common.h MODE_*
+
+
+def _gno_nl_args(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], src_table: Tensor, g: BipartiteGraph):
+    md = GNO_MODES.get(mode, mode)
+    if md not in (1, 2):
+        raise GaotError(f"gno (nonlinear): mode must be one of {tuple(GNO_MODES)}, got {mode!r}")
+    m, keep = _mlp_struct(weights, biases)
+    y_pos = _req(y_pos, torch.float32, "y_pos")
+    x_pos = _req(x_pos, torch.float32, "x_pos")
+    src_table = _req(src_table, torch.float32, "src_table")
+    if tuple(src_table.shape) != (g.num_src, 64) or m.hidden != 64:
+        raise GaotError(f"src_table must be [{g.num_src}, 64] (hidden width 64), got {tuple(src_table.shape)}, hidden {m.hidden}")
+    if y_pos.shape[0] != g.num_src or x_pos.shape[0] != g.num_dst:
+        raise GaotError(f"y_pos / x_pos have {y_pos.shape[0]} / {x_pos.shape[0]} rows, the graph {g.num_src} / {g.num_dst}")
+    if md == 1:
+        f_y = _req(f_y, torch.float32, "f_y")
+        if tuple(f_y.shape) != (g.num_src, m.channels):
+            raise GaotError(f"f_y must be [{g.num_src}, {m.channels}], got {tuple(f_y.shape)}")
+    else:
+        f_y = None
+    return md, m, keep, y_pos, x_pos, f_y, src_table
+
+
+def gno_nl_forward(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], src_table: Tensor,
+                   g: BipartiteGraph, precision: Optional[int] = None) -> Tensor:
+    """the fused transform for transform_type 'nonlinear' / 'nonlinear_kernelonly' (``mode``): ``weights[0]`` is the coordinate block
+    W_0c [64, 6] of the first layer, ``src_table`` = f_y W_0f^T [n_src, 64] its per-node feature term.  'nonlinear': f_y [n_src, 32]
+    multiplies the kernel; 'nonlinear_kernelonly': f_y is not used (pass None)."""
+    lib = _lib.load()
+    prec = _PRECISION["mode"] if precision is None else precision
+    md, m, keep, y_pos, x_pos, f_y, src_table = _gno_nl_args(mode, weights, biases, y_pos, x_pos, f_y, src_table, g)
+    q, e = g.num_dst, g.by_dst.num_edges
+    out = torch.empty(q, m.channels, dtype=torch.float32, device=x_pos.device)
+    ws = _ws(lib.gaot_gno_fwd_workspace_bytes(e, m.channels), x_pos.device)
+    with _timed(f"gno_fwd_nl{md}_nh{m.n_hidden}"):
+        check(lib.gaot_gno_fwd_nl(C.byref(m), md, _ptr(y_pos), _ptr(x_pos), _ptr(f_y), _ptr(src_table), _ptr(g.by_dst.other),
+                                  _ptr(g.by_dst.key), _ptr(g.by_dst.rowptr), e, q, _ptr(out), prec, _ptr(ws), ws.numel(), _stream()),
+              "gaot_gno_fwd_nl")
+    return out
+
+
+def gno_nl_backward(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], src_table: Tensor, grad_out: Tensor,
+                    g: BipartiteGraph, precision: Optional[int] = None, coords: bool = False):
+    """-> (grad_f_y, grad_src_table, [grad_w...], [grad_b...]); with ``coords`` also (grad_y_pos, grad_x_pos) appended.
+    grad_src_table[s] = the sum of dz_0 over the edges of source s ([n_src, 64]); grad_f_y is the gs * k term of 'nonlinear' alone
+    (None for 'nonlinear_kernelonly'): the terms through src_table -- dW_0f = grad_src_table^T f_y, grad f_y += grad_src_table W_0f --
+    are per-node products of the caller's."""
+    lib = _lib.load()
+    prec = _PRECISION["mode"] if precision is None else precision
+    md, m, keep, y_pos, x_pos, f_y, src_table = _gno_nl_args(mode, weights, biases, y_pos, x_pos, f_y, src_table, g)
+    grad_out = _req(grad_out, torch.float32, "grad_out")
+    if tuple(grad_out.shape) != (g.num_dst, m.channels):
+        raise GaotError(f"grad_out must be [{g.num_dst}, {m.channels}], got {tuple(grad_out.shape)}")
+    e = g.by_src.num_edges
+    dev = x_pos.device
+    grad_f = torch.empty(g.num_src, m.channels, dtype=torch.float32, device=dev) if md == 1 else None
+    grad_t = torch.empty(g.num_src, 64, dtype=torch.float32, device=dev)
+    gw = [torch.empty(tuple(w.shape[:2]), dtype=torch.float32, device=dev) for w in weights]
+    gb = [torch.empty(tuple(b.shape), dtype=torch.float32, device=dev) for b in biases]
+    gs = MlpGradT()
+    for l in range(len(weights)):
+        gs.weight[l] = gw[l].data_ptr()
+        gs.bias[l] = gb[l].data_ptr()
+    ws = _ws(lib.gaot_gno_bwd_nl_workspace_bytes(C.byref(m), e, g.num_dst), dev)
+    gec = torch.empty(e, 6, dtype=torch.float32, device=dev) if coords else None
+    with _timed(f"gno_bwd_nl{md}{'_coords' if coords else ''}_nh{m.n_hidden}"):
+        check(lib.gaot_gno_bwd_nl(C.byref(m), md, _ptr(y_pos), _ptr(x_pos), _ptr(f_y), _ptr(src_table), _ptr(grad_out),
+                                  _ptr(g.by_dst.rowptr), _ptr(g.by_src.key), _ptr(g.by_src.other), _ptr(g.by_src.rowptr), e,
+                                  g.num_src, g.num_dst, _ptr(grad_f), _ptr(grad_t), C.byref(gs), _ptr(gec), prec, _ptr(ws),
+                                  ws.numel(), _stream()), "gaot_gno_bwd_nl")
+    if coords:
+        from . import edgeops as EO
+        gy = EO.segment_reduce(gec, g.by_src.rowptr, None, g.num_src, EO.SUM, col0=0, channels=3)
+        gx = EO.segment_reduce(gec, g.by_dst.rowptr, EO.dst_to_src_map(g), g.num_dst, EO.SUM, col0=3, channels=3)
+        return grad_f, grad_t, gw, gb, gy, gx
+    return grad_f, grad_t, gw, gb
+
+
 # ------------------------------------------------------------------------------------------------
 # precision switch: "fp32" = exact-fp32 MFMA everywhere (parity mode); "bf16" = bf16 operands with
 # fp32 accumulation for the dense GEMMs / attention (BASELINE config 1)

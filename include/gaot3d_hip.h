@@ -98,6 +98,28 @@ int gaot_gno_bwd_coords(const gaot_mlp_t* mlp /* host */, const float* y_pos, co
                         float* grad_f_y, const gaot_mlp_grad_t* grads /* host */, float* grad_edge_coords /* [num_edges, 6] */,
                         int precision, void* workspace, size_t workspace_bytes, gaot_stream_t stream);
 
+/* transform_type 'nonlinear' (mode 1) and 'nonlinear_kernelonly' (mode 2) of the same transform (reference
+ * integral_transform.py:146-157): the kernel MLP sees [y_s, x_q, f_y[s]].  With W_0 = [W_0c | W_0f] the feature term of layer 0
+ * depends on the source node only: the caller forms src_table = f_y W_0f^T ([num_sources, 64] fp32, hidden widths below 64
+ * zero-padded) and the kernels start every edge's layer-0 accumulator from b_0 + src_table[src]; mlp->weight[0] is W_0c
+ * ([64][6], dense).  mode 1: out_q = mean k_e * f_y[src_e] (f_y [num_sources, 32]); mode 2: out_q = mean k_e (f_y unused, may
+ * be null).  Workspace of the forward: gaot_gno_fwd_workspace_bytes.
+ * Backward: as gaot_gno_bwd / gaot_gno_bwd_coords (grad_edge_coords may be null: no coordinate gradients), and
+ * grad_src_table[s] = sum over the edges of source s of dz_0[e] ([num_sources, 64] fp32, a fixed-order segmented sum: no atomics,
+ * bit-reproducible), from which the caller forms dW_0f = grad_src_table^T f_y and adds grad_src_table W_0f to grad f_y.
+ * mode 1: grad_f_y receives the gs * k term as in gaot_gno_bwd; mode 2: grad_f_y is not written (may be null). */
+int gaot_gno_fwd_nl(const gaot_mlp_t* mlp /* host */, int mode, const float* y_pos, const float* x_pos, const float* f_y,
+                    const float* src_table, const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr_dst,
+                    int64_t num_edges, int64_t num_queries, float* out, int precision, void* workspace, size_t workspace_bytes,
+                    gaot_stream_t stream);
+size_t gaot_gno_bwd_nl_workspace_bytes(const gaot_mlp_t* mlp /* host */, int64_t num_edges, int64_t num_queries);
+int gaot_gno_bwd_nl(const gaot_mlp_t* mlp /* host */, int mode, const float* y_pos, const float* x_pos, const float* f_y,
+                    const float* src_table, const float* grad_out, const int32_t* rowptr_dst, const int32_t* src_sorted,
+                    const int32_t* dst_sorted, const int32_t* rowptr_src, int64_t num_edges, int64_t num_sources,
+                    int64_t num_queries, float* grad_f_y, float* grad_src_table, const gaot_mlp_grad_t* grads /* host */,
+                    float* grad_edge_coords /* [num_edges, 6] or null */, int precision, void* workspace, size_t workspace_bytes,
+                    gaot_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Statistical geometric-embedding features (reference GeometricEmbedding.
  * _compute_statistical_features_pyg, src/model/layers/geoembed.py:99-182): z-scored

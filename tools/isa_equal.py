@@ -3,8 +3,10 @@
 SAME / DIFF / GONE, then the kernels only the NEW file has and the counts.  A kernel's body runs from its symbol line to
 .end_amdhsa_kernel (instruction text and the .amdhsa_* resource lines); before comparing, the kernel's own mangled name is
 replaced, `;` comments are stripped and the function index is dropped from .LBB<n>_ / .Lfunc_end<n> labels.
-usage: isa_equal.py old.s new.s [--rename OLD=NEW ...] [--allow DIRECTIVE ...] [--dump DIR]
-  --rename  literal substring of an old mangled name and what stands in its place in the new file (template lists that changed)
+usage: isa_equal.py old.s new.s [--rename OLD=NEW ...] [--rename-re PATTERN=REPL ...] [--allow DIRECTIVE ...] [--dump DIR]
+  --rename  literal substring of an old mangled name and what stands in its place in the new file (template lists that changed);
+            the first one that matches a name is applied
+  --rename-re  the same with a regular expression (re.sub); every one is applied, in the order given, after --rename
   --allow   an .amdhsa_* directive whose value may differ (reported next to SAME), e.g. .amdhsa_kernarg_size
   --dump    write the normalised bodies of differing kernels to DIR/<n>.old / .new (for diff)"""
 import os
@@ -35,11 +37,13 @@ def kernels(path):
 
 
 def main(argv):
-    renames, allow, dump, files = [], [], None, []
+    renames, renames_re, allow, dump, files = [], [], [], None, []
     it = iter(argv)
     for a in it:
         if a == "--rename":
             renames.append(next(it).split("=", 1))
+        elif a == "--rename-re":
+            renames_re.append(next(it).split("=", 1))
         elif a == "--allow":
             allow.append(next(it))
         elif a == "--dump":
@@ -54,6 +58,8 @@ def main(argv):
             if a in to:
                 to = to.replace(a, b)
                 break
+        for a, b in renames_re:
+            to = re.sub(a, b, to)
         if to not in new:
             counts["GONE"] += 1
             print(f"GONE  {name}")

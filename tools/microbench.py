@@ -178,6 +178,65 @@ elif what == "coordgrad":
             timeit(step, f"{prec} train step fwd+bwd, batch.pos.requires_grad={want}")
         batch.pos = pos0
         del model
+elif what == "gno_nonlinear":
+    # transform_type 'nonlinear' / 'nonlinear_kernelonly' at the configs[1] graph (500K points, 64x64x32 tokens, knn k=8: E = 4 M; encoder
+    # direction with NH = 3, decoder direction with NH = 2), both precision modes: forward and backward of the module on (1) the fused
+    # linear transform, (2) the fused kernels of the type, per-node products (t = W_0f f_y, dW_0f, dt W_0f) included, (3) the general
+    # per-edge path of the type (MB_GENERAL=0 leaves it out).  HIP events around the forward and around the backward, median of `reps`
+    # after one warm-up; the module's own kernels per call follow.  Output kept in profiles/gno_nonlinear_microbench.txt.
+    from gaot_3d_amd.data import make_synthetic_sample
+    from gaot_3d_amd.model.layers.integral_transform import IntegralTransform
+    batch, tokens = make_synthetic_sample(500000, (64, 64, 32), k=8, seed=0, device=dev)
+    n, m = 500000, tokens.shape[0]
+    tokens = tokens.to(dev)
+    general = os.environ.get("MB_GENERAL", "1") != "0"
+
+    def fwd_bwd_ms(it, yp, xp, f, g, go):
+        def once():
+            for p in it.parameters():
+                p.grad = None
+            f.grad = None
+            e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+            e0.record(); out = it(yp, xp, None, f_y=f, graph=g); e1.record(); out.backward(go); e2.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1), e1.elapsed_time(e2)
+        once()
+        ts = sorted(once() for _ in range(reps))
+        fw = sorted(t[0] for t in ts)[len(ts) // 2]
+        bw = sorted(t[1] for t in ts)[len(ts) // 2]
+        return fw, bw
+
+    for prec in ("fp32", "bf16"):
+        gaot_3d_amd.set_precision(prec)
+        for nh, ei, ns, nd, yp, xp in ((3, batch.encoder_edge_index_s0, n, m, batch.pos, tokens),
+                                       (2, batch.decoder_edge_index_s0, m, n, tokens, batch.pos)):
+            g = ops.build_graph(ei, ns, nd)
+            f = torch.randn(ns, 32, device=dev).requires_grad_(); go = torch.randn(nd, 32, device=dev)
+            torch.manual_seed(1)
+            lin = IntegralTransform(channel_mlp_layers=[6] + [64] * nh + [32], transform_type="linear").to(dev)
+            lf, lb = fwd_bwd_ms(lin, yp, xp, f, g, go)
+            print(f"{prec} nh={nh} E={ei.shape[1]} linear (fused): fwd {lf:.3f} ms  bwd {lb:.3f} ms  fwd+bwd {lf + lb:.3f} ms")
+            for tt in ("nonlinear", "nonlinear_kernelonly"):
+                it = IntegralTransform(channel_mlp_layers=[6 + 32] + [64] * nh + [32], transform_type=tt).to(dev)
+                ff, fb = fwd_bwd_ms(it, yp, xp, f, g, go)
+                line = (f"{prec} nh={nh} {tt} (fused + per-node products): fwd {ff:.3f} ms  bwd {fb:.3f} ms  fwd+bwd {ff + fb:.3f} ms"
+                        f"  = {(ff + fb) / (lf + lb):.2f} x linear (fwd {ff / lf:.2f} x, bwd {fb / lb:.2f} x)")
+                if general:
+                    plan = it._fused_plan
+                    it._fused_plan = lambda *a, **k: None
+                    gf_, gb_ = fwd_bwd_ms(it, yp, xp, f, g, go)
+                    it._fused_plan = plan
+                    line += f";  general path: fwd {gf_:.3f} ms  bwd {gb_:.3f} ms  fwd+bwd {gf_ + gb_:.3f} ms  = {(gf_ + gb_) / (lf + lb):.1f} x linear"
+                print(line)
+                ops.timing_reset(True)
+                for _ in range(reps):
+                    f.grad = None
+                    it(yp, xp, None, f_y=f, graph=g).backward(go)
+                torch.cuda.synchronize()
+                for name, (calls, tot) in ops.timing_summary().items():
+                    print(f"    {name}: {tot / calls:.4f} ms")
+                ops.timing_reset(False)
+                del it
 elif what == "attn_headdim":
     # head sizes 64 and 128 in bf16 mode at hidden 256, S = 16 384, b = 1, RoPE on, p = 0.1: forward + backward of (1) the unfused
     # general path (functional._attention_unfused: the path every head size other than 32 took before the flash kernels), (2) the
