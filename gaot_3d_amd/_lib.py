@@ -163,6 +163,9 @@ SIGNATURES = {
     "gaot_mul": (_i, [_p, _p, _i64, _i, _i, _p, _p]),
     "gaot_mul_rowsum": (_i, [_p, _p, _i64, _i, _p, _p]),
     "gaot_affine_cols": (_i, [_p, _p, _p, _i64, _i, _p, _p]),
+    "gaot_pointnet_fwd": (_i, [_p, _p, _i, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _i, _p, _p, _p]),
+    "gaot_pointnet_bwd_parts": (_i64, [_i64]),
+    "gaot_pointnet_bwd": (_i, [_p, _p, _i, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "gaot_scale_mix_fwd": (_i, [_p, _i, _p, _p, _p, _i64, _i, _p]),
     "gaot_scale_mix_bwd": (_i, [_p, _i, _p, _p, _p, _p, _i64, _i, _p]),
 }

@@ -1131,6 +1131,45 @@ class Mlp2Fn(Function):
         return dx.view(xshape), dw1.view(w1shape), db1, dw2.view(w2shape), db2
 
 
+class PointNetPoolFn(Function):
+    """PointNet GeometricEmbedding up to the pooling (reference geoembed.py:196-216), fused (csrc/pointnet.hip):
+    pooled [Q, 32] = max | mean over a query's edges of relu(w2 relu(w1 (source_pos[src] - query_pos[q]) + b1) + b2), exact
+    fp32 in both precision modes.  ``mode``: edgeops.MEAN / edgeops.MAX.  Only the inputs and the arg-max edges are kept: the
+    backward recomputes the hidden layers per edge.  The general path writes the [E, 3] offsets and two [E, 32] hidden tensors,
+    keeps them for the backward and builds two more [E, 32] gradients there."""
+
+    @staticmethod
+    def eligible(mlp, source_pos: Tensor, query_pos: Tensor) -> bool:
+        """``mlp`` is the reference's Linear(D, 32) / ReLU / Linear(32, 32) / ReLU with biases, D in 1..3 = the coordinates' width"""
+        nn = torch.nn
+        if len(mlp) != 4 or not (isinstance(mlp[0], nn.Linear) and isinstance(mlp[1], nn.ReLU) and isinstance(mlp[2], nn.Linear)
+                                 and isinstance(mlp[3], nn.ReLU)):
+            return False
+        l1, l2 = mlp[0], mlp[2]
+        d = l1.in_features
+        return (1 <= d <= 3 and l1.out_features == 32 and (l2.in_features, l2.out_features) == (32, 32) and l1.bias is not None
+                and l2.bias is not None and source_pos.dim() == 2 and query_pos.dim() == 2 and source_pos.shape[1] == d
+                and query_pos.shape[1] == d and source_pos.is_cuda and source_pos.dtype == torch.float32
+                and query_pos.dtype == torch.float32 and l1.weight.dtype == torch.float32)
+
+    @staticmethod
+    def forward(ctx, source_pos: Tensor, query_pos: Tensor, graph, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, mode: int):
+        pooled, arg = ops.pointnet_fwd(source_pos, query_pos, graph, w1, b1, w2, b2, mode)
+        ctx.graph, ctx.mode = graph, mode
+        ctx.save_for_backward(source_pos, query_pos, w1, b1, w2, b2, *(() if arg is None else (arg,)))
+        return pooled
+
+    @staticmethod
+    def backward(ctx, d: Tensor):
+        source_pos, query_pos, w1, b1, w2, b2 = ctx.saved_tensors[:6]
+        arg = ctx.saved_tensors[6] if ctx.mode == 2 else None
+        need = ctx.needs_input_grad
+        dw1, db1, dw2, db2, gs, gq = ops.pointnet_bwd(source_pos, query_pos, ctx.graph, w1, b1, w2, b2, ctx.mode, d, arg,
+                                                      want_source=need[0], want_query=need[1])
+        return (gs, gq, None, dw1 if need[3] else None, db1 if need[4] else None, dw2 if need[5] else None,
+                db2 if need[6] else None, None)
+
+
 class AddFn(Function):
     """a + b (b optionally broadcast over leading rows with `period` elements)."""
 

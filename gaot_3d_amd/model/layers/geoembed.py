@@ -1,8 +1,9 @@
 """GeometricEmbedding with the reference's signature (src/model/layers/geoembed.py:24, 57-64).
 method='statistical' runs csrc/geoembed.hip (one neighbour-list sweep + in-register 3x3 eigen-solve)
-followed by the 9 -> 64 -> C MLP on the HIP GEMM.  method='pointnet' (geoembed.py:184-222) runs the general per-edge
-path: edge offsets, the 3 -> 32 -> 32 ReLU MLP on the GEMM kernels, segment max / mean and the output linear
-(csrc/edgeops.hip)."""
+followed by the 9 -> 64 -> C MLP on the HIP GEMM.  method='pointnet' (geoembed.py:184-222) runs the fused kernels of
+csrc/pointnet.hip (functional.PointNetPoolFn: offsets, the D -> 32 -> 32 ReLU MLP and the segment max / mean in one pass, no
+per-edge tensor, D = 1..3) followed by the output linear; a ``pointnet_mlp`` of another shape keeps the general per-edge path
+(edge offsets, the MLP on the GEMM kernels, segment max / mean: csrc/edgeops.hip)."""
 from typing import Optional
 
 import torch
@@ -112,10 +113,7 @@ class GeometricEmbedding(nn.Module):
         if g.by_dst.num_edges == 0:            # this rank holds no edge: it still takes part in the exchanges
             local = torch.zeros(nq, 32, dtype=query_pos.dtype, device=query_pos.device)
         else:
-            c = EO.edge_coords(source_pos, query_pos, g, 1)
-            h = GF.linear(c, self.pointnet_mlp[0].weight, self.pointnet_mlp[0].bias, act="relu", precision=0)
-            h = GF.linear(h, self.pointnet_mlp[2].weight, self.pointnet_mlp[2].bias, act="relu", precision=0)
-            local = EO.SegmentReduceFn.apply(h, g, EO.MAX if self.pooling == "max" else EO.MEAN)
+            local = self._pool(source_pos, query_pos, g, False)
         if self.pooling == "max":
             pooled, gdeg = GlobalSegmentMaxFn.apply(local, deg, group)
         else:
@@ -127,15 +125,24 @@ class GeometricEmbedding(nn.Module):
         po = GF.linear(pooled, self.fc[0].weight, self.fc[0].bias, precision=0)
         return EO.RowScaleFn.apply(po, (gdeg > 0).to(torch.float32))
 
+    def _pool(self, source_pos, query_pos, g, coord_grad: bool):
+        """geoembed.py:196-216: MLP(nbr - query) per edge and the segment max | mean over the local edges -> [Q, 32].  The
+        reference's MLP shape runs fused (one kernel, nothing per edge in memory); any other ``pointnet_mlp`` the general path"""
+        mode = EO.MAX if self.pooling == "max" else EO.MEAN
+        mlp = self.pointnet_mlp
+        if GF.PointNetPoolFn.eligible(mlp, source_pos, query_pos):
+            return GF.PointNetPoolFn.apply(source_pos, query_pos, g, mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias, mode)
+        c = EO.EdgeOffsetFn.apply(source_pos, query_pos, g) if coord_grad else EO.edge_coords(source_pos, query_pos, g, 1)
+        h = GF.linear(c, mlp[0].weight, mlp[0].bias, act="relu", precision=0)
+        h = GF.linear(h, mlp[2].weight, mlp[2].bias, act="relu", precision=0)
+        return EO.SegmentReduceFn.apply(h, g, mode)
+
     def _forward_pointnet(self, source_pos, query_pos, g):
         """geoembed.py:184-222: MLP(nbr - query) per edge, segment max | mean, fc; rows without neighbours = 0"""
         nq = query_pos.shape[0]
         if g.by_dst.num_edges == 0:
             return torch.zeros(nq, self.output_dim, dtype=query_pos.dtype, device=query_pos.device)
-        c = EO.EdgeOffsetFn.apply(source_pos, query_pos, g)                                # :196-198
-        h = GF.linear(c, self.pointnet_mlp[0].weight, self.pointnet_mlp[0].bias, act="relu", precision=0)
-        h = GF.linear(h, self.pointnet_mlp[2].weight, self.pointnet_mlp[2].bias, act="relu", precision=0)
-        pooled = EO.SegmentReduceFn.apply(h, g, EO.MAX if self.pooling == "max" else EO.MEAN)   # :211-216
+        pooled = self._pool(source_pos, query_pos, g, True)                                # :196-216
         po = GF.linear(pooled, self.fc[0].weight, self.fc[0].bias, precision=0)
         rp = g.by_dst.rowptr
         has = (rp[1:] > rp[:-1]).to(torch.float32)                                          # :219 masked assignment

@@ -1498,6 +1498,68 @@ def mlp2_backward(x: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, dout: Tensor, d
     return dx, dw1, db1, dw2
 
 
+def _pointnet_args(source_pos: Tensor, query_pos: Tensor, g: BipartiteGraph, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, mode: int):
+    source_pos = _req(source_pos, torch.float32, "source_pos")
+    query_pos = _req(query_pos, torch.float32, "query_pos")
+    w1, b1, w2, b2 = (_req(t, torch.float32, n) for t, n in ((w1, "w1"), (b1, "b1"), (w2, "w2"), (b2, "b2")))
+    d = int(query_pos.shape[1]) if query_pos.dim() == 2 else 0
+    if source_pos.dim() != 2 or source_pos.shape[1] != d or query_pos.shape[0] != g.num_dst or source_pos.shape[0] != g.num_src:
+        raise GaotError(f"pointnet: source_pos [{g.num_src}, D] and query_pos [{g.num_dst}, D] expected, got "
+                        f"{tuple(source_pos.shape)} and {tuple(query_pos.shape)}")
+    if tuple(w1.shape) != (32, d) or tuple(b1.shape) != (32,) or tuple(w2.shape) != (32, 32) or tuple(b2.shape) != (32,):
+        raise GaotError(f"pointnet: the MLP must be Linear({d}, 32) / Linear(32, 32), got weights {tuple(w1.shape)}, {tuple(w2.shape)}")
+    if mode not in (1, 2):
+        raise GaotError(f"pointnet: mode must be 1 (mean) or 2 (max), got {mode}")
+    s = g.by_dst
+    head = (_ptr(source_pos), _ptr(query_pos), d, _ptr(s.rowptr), _ptr(s.other), _ptr(s.key), g.num_dst, s.num_edges,
+            _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), mode)
+    return head, d, (source_pos, query_pos, w1, b1, w2, b2)
+
+
+def pointnet_fwd(source_pos: Tensor, query_pos: Tensor, g: BipartiteGraph, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor,
+                 mode: int):
+    """PointNet GeometricEmbedding up to the pooling, fused (include/gaot3d_hip.h: gaot_pointnet_fwd): -> (pooled [Q, 32],
+    argmax int32 [Q, 32] for max pooling, else None).  ``mode``: edgeops.MEAN (1) or edgeops.MAX (2)"""
+    head, _, keep = _pointnet_args(source_pos, query_pos, g, w1, b1, w2, b2, mode)
+    dev = keep[1].device
+    pooled = torch.empty(g.num_dst, 32, dtype=torch.float32, device=dev)
+    arg = torch.empty(g.num_dst, 32, dtype=torch.int32, device=dev) if mode == 2 else None
+    with _timed("pointnet_fwd"):
+        check(_lib.load().gaot_pointnet_fwd(*head, _ptr(pooled), _ptr(arg), _stream()), "gaot_pointnet_fwd")
+    return pooled, arg
+
+
+def pointnet_bwd(source_pos: Tensor, query_pos: Tensor, g: BipartiteGraph, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor,
+                 mode: int, d_pooled: Tensor, argmax: Optional[Tensor], want_source: bool = False, want_query: bool = False):
+    """-> (dw1 [32, D], db1, dw2, db2 (views of one flat gradient), d_source or None, d_query or None): the hidden layers are
+    recomputed per edge (gaot_pointnet_bwd); the per-edge W1^T dz1 rows are written only for ``want_source`` and summed by
+    source here with the fixed-order segmented sum, as EdgeOffsetFn does"""
+    lib = _lib.load()
+    head, d, keep = _pointnet_args(source_pos, query_pos, g, w1, b1, w2, b2, mode)
+    dev = keep[1].device
+    d_pooled = _req(d_pooled, torch.float32, "d_pooled")
+    if tuple(d_pooled.shape) != (g.num_dst, 32) or (mode == 2 and (argmax is None or tuple(argmax.shape) != (g.num_dst, 32))):
+        raise GaotError("pointnet_bwd: d_pooled (and argmax for max pooling) must be [num_queries, 32]")
+    e = g.by_dst.num_edges
+    n = 32 * d + 1088
+    flat = torch.empty(n, dtype=torch.float32, device=dev)
+    dq = torch.empty(g.num_dst, d, dtype=torch.float32, device=dev) if want_query else None
+    de = torch.empty(e, d, dtype=torch.float32, device=dev) if want_source else None
+    ws = _ws(4 * n * int(lib.gaot_pointnet_bwd_parts(e)), dev)
+    with _timed("pointnet_bwd"):
+        check(lib.gaot_pointnet_bwd(*head, _ptr(d_pooled), _ptr(argmax if mode == 2 else None), _ptr(flat), _ptr(dq), _ptr(de),
+                                    _ptr(ws), ws.numel(), _stream()), "gaot_pointnet_bwd")
+    ds = None
+    if want_source:
+        from . import edgeops as EO
+        if e == 0:
+            ds = torch.zeros(g.num_src, d, dtype=torch.float32, device=dev)
+        else:
+            ds = EO.segment_reduce(de, g.by_src.rowptr, EO.src_to_dst_map(g), g.num_src, EO.SUM, channels=d)
+    o1, o2 = 32 * d, 32 * d + 32
+    return flat[:o1].view(32, d), flat[o1:o2], flat[o2:o2 + 1024].view(32, 32), flat[o2 + 1024:], ds, dq
+
+
 # single-pass thin fp32 linears (csrc/rowlinear.hip).  ROWLIN counts the calls that took them (tests assert the route)
 ROWLIN = {"enabled": True, "fwd": 0, "bwd": 0}
 

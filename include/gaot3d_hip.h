@@ -634,6 +634,36 @@ int gaot_mul_rowsum(const float* a, const float* b, int64_t rows, int channels, 
 int gaot_affine_cols(const float* x, const float* scale_minus_one, const float* bias, int64_t rows, int channels,
                      float* out, gaot_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Fused PointNet GeometricEmbedding (csrc/pointnet.hip; reference geoembed.py:184-222) and its autograd:
+ *   pooled[q] = max | mean over the edges e of q of  relu(W2 relu(W1 (source_pos[src_e] - query_pos[q]) + b1) + b2)
+ * coord_dim D = 1..3 (the width of source_pos [*, D] and query_pos [num_queries, D]), w1 [32, D], w2 [32, 32] row-major,
+ * mode 1 = mean, 2 = max (gaot_segment_reduce's codes).  The edges are the by-query neighbour list of gaot_csr_build:
+ * rowptr_dst [num_queries + 1], src_sorted / dst_sorted [num_edges] = the source / query of every edge in that order.
+ * Exact fp32, fixed summation orders, no atomics; no per-edge tensor is written or kept.
+ *   gaot_pointnet_fwd : pooled [num_queries, 32] (rows without edges: 0); max also writes argmax [num_queries, 32], the
+ *                       position in the dst-sorted order of the first maximal edge (-1: empty row) -- gaot_segment_reduce's rule
+ *   gaot_pointnet_bwd : recomputes the hidden layers per edge from d_pooled (and argmax, max mode).
+ *                       d_params [32 D + 1088] = [dW1 | db1 | dW2 | db2], summed from gaot_pointnet_bwd_parts(num_edges)
+ *                       per-workgroup rows in `workspace` (that many rows of 32 D + 1088 floats, 16-byte aligned) by one
+ *                       gaot_reduce_multi launch inside the call;
+ *                       d_query [num_queries, D] (if not NULL) = minus the sum over the row's edges, in edge order, of
+ *                       dd_e = W1^T dz1_e;  d_edge_offset [num_edges, D] (if not NULL) = dd_e in the dst-sorted order (its sum by
+ *                       source is the gradient of source_pos: gaot_segment_reduce over the by-source list).
+ * gaot_pointnet_bwd reads d_pooled and argmax 16 bytes at a time: both must be 16-byte aligned (the forward has no such need).
+ * num_edges == 0 or num_queries == 0 are valid: zeros / -1, no list is walked.
+ * ------------------------------------------------------------------------------------------- */
+int gaot_pointnet_fwd(const float* source_pos, const float* query_pos, int coord_dim, const int32_t* rowptr_dst,
+                      const int32_t* src_sorted, const int32_t* dst_sorted, int64_t num_queries, int64_t num_edges,
+                      const float* w1, const float* b1, const float* w2, const float* b2, int mode, float* pooled,
+                      int32_t* argmax, gaot_stream_t stream);
+int64_t gaot_pointnet_bwd_parts(int64_t num_edges);
+int gaot_pointnet_bwd(const float* source_pos, const float* query_pos, int coord_dim, const int32_t* rowptr_dst,
+                      const int32_t* src_sorted, const int32_t* dst_sorted, int64_t num_queries, int64_t num_edges,
+                      const float* w1, const float* b1, const float* w2, const float* b2, int mode, const float* d_pooled,
+                      const int32_t* argmax, float* d_params, float* d_query, float* d_edge_offset, void* workspace,
+                      size_t workspace_bytes, gaot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

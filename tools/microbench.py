@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Kernel microbenchmarks at the configs[1] shapes (for rocprofv3 / quick A-B): attention fwd+bwd, GEMM shapes, GNO."""
+"""Kernel microbenchmarks at the configs[1] shapes (for rocprofv3 / quick A-B): attention fwd+bwd, GEMM shapes, GNO, PointNet GeoEmbed."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -237,6 +237,58 @@ elif what == "gno_nonlinear":
                     print(f"    {name}: {tot / calls:.4f} ms")
                 ops.timing_reset(False)
                 del it
+elif what == "pointnet":
+    # GeometricEmbedding(3, 32, "pointnet") on the two configs[1] graphs (500K points, 64x64x32 tokens, knn k=8): encoder side
+    # (Q = 131 072 tokens) and decoder side (Q = 500 000 points, E = 4 M), max and mean pooling, no coordinate gradients: forward, and
+    # forward + backward, HIP events, median (min, max) of `reps` after one warm-up; peak memory = the growth of
+    # torch.cuda.max_memory_allocated over one forward + backward; then the library's own timed calls of a forward + backward.  Output kept in profiles/pointnet_microbench.txt.
+    from gaot_3d_amd.data import make_synthetic_sample
+    from gaot_3d_amd.model.layers.geoembed import GeometricEmbedding
+    batch, tokens = make_synthetic_sample(500000, (64, 64, 32), k=8, seed=0, device=dev)
+    n, m = 500000, tokens.shape[0]
+    tokens = tokens.to(dev)
+
+    def median_ms(fn):
+        fn(); torch.cuda.synchronize()
+        ts = []
+        for _ in range(reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); fn(); e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        ts.sort()
+        return f"{ts[len(ts) // 2]:.3f} ms (min {ts[0]:.3f}, max {ts[-1]:.3f})"
+
+    for side, ei, ns, nd, sp, qp in (("encoder", batch.encoder_edge_index_s0, n, m, batch.pos, tokens),
+                                     ("decoder", batch.decoder_edge_index_s0, m, n, tokens, batch.pos)):
+        g = ops.build_graph(ei, ns, nd)
+        go = torch.randn(nd, 32, device=dev)
+        for pooling in ("max", "mean"):
+            torch.manual_seed(1)
+            ge = GeometricEmbedding(3, 32, method="pointnet", pooling=pooling).to(dev)
+
+            def fwd():
+                with torch.no_grad():
+                    return ge(sp, qp, ei, graph=g)
+
+            def fwd_bwd():
+                for p in ge.parameters():
+                    p.grad = None
+                ge(sp, qp, ei, graph=g).backward(go)
+            tf, tb = median_ms(fwd), median_ms(fwd_bwd)
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            fwd_bwd()
+            torch.cuda.synchronize()
+            peak = (torch.cuda.max_memory_allocated() - base) / 1e6
+            print(f"pointnet {side} Q={nd} E={ei.shape[1]} {pooling}: fwd {tf}  fwd+bwd {tb}  peak memory of fwd+bwd {peak:.1f} MB")
+            ops.timing_reset(True)
+            for _ in range(reps):
+                fwd_bwd()
+            torch.cuda.synchronize()
+            print("    " + "  ".join(f"{name}: {tot / calls:.4f} ms" for name, (calls, tot) in sorted(ops.timing_summary().items())))
+            ops.timing_reset(False)
 elif what == "attn_headdim":
     # head sizes 64 and 128 in bf16 mode at hidden 256, S = 16 384, b = 1, RoPE on, p = 0.1: forward + backward of (1) the unfused
     # general path (functional._attention_unfused: the path every head size other than 32 took before the flash kernels), (2) the
