@@ -87,7 +87,8 @@ __device__ __forceinline__ float gaot_act_fwd(float v, int act) {
         default: return v;
     }
 }
-// d act(v) / dv  (torch autograd's formulas)
+// d act(v) / dv  (torch autograd's formulas, its side of every kink too: relu6' is 1 inside (0, 6) only, hardswish' is 0 AT -3 and
+// 1 AT 3 -- the outer one-sided values --, softplus' is 1 above the threshold only)
 __device__ __forceinline__ float gaot_act_grad(float v, int act) {
     switch (act) {
         case GAOT_ACT_GELU: return gelu_grad_f(v);
@@ -100,7 +101,7 @@ __device__ __forceinline__ float gaot_act_grad(float v, int act) {
         case GAOT_ACT_SOFTPLUS: return v > 20.f ? 1.f : 1.f / (1.f + expf(-v));
         case GAOT_ACT_SELU: return 1.0507009873554804934193349852946f * (v > 0.f ? 1.f : 1.6732632423543772848170429916717f * expf(v));
         case GAOT_ACT_RELU6: return (v > 0.f && v < 6.f) ? 1.f : 0.f;
-        case GAOT_ACT_HARDSWISH: return v < -3.f ? 0.f : (v > 3.f ? 1.f : (2.f * v + 3.f) * (1.f / 6.f));
+        case GAOT_ACT_HARDSWISH: return v <= -3.f ? 0.f : (v >= 3.f ? 1.f : (2.f * v + 3.f) * (1.f / 6.f));
         case GAOT_ACT_MISH: {
             const float sp = gaot_softplus(v), t = tanhf(sp), sg = 1.f / (1.f + expf(-v));
             return t + v * (1.f - t * t) * sg;

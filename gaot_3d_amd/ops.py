@@ -938,8 +938,9 @@ def swiglu_bwd(ag: Tensor, du: Tensor, f: int) -> Tensor:
 
 
 def cast_bf16(x: Tensor) -> Tensor:
-    """bf16 copy (round to nearest even) of a contiguous fp32 tensor"""
+    """bf16 copy (round to nearest even) of an fp32 tensor, in the order of its SHAPE (a strided view is copied first)"""
     lib = _lib.load()
+    x = _req(x, torch.float32, "x")
     out = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
     check(lib.gaot_cast_bf16(_ptr(x), _ptr(out), x.numel(), _stream()), "gaot_cast_bf16")
     return out
@@ -950,33 +951,38 @@ class _CastEntry(C.Structure):   # gaot_cast_tensor_t
 
 
 def cast_bf16_multi(xs: Sequence[Tensor]) -> List[Tensor]:
-    """bf16 copies of many contiguous fp32 tensors in ONE launch; the copies are slices of one buffer (16-byte aligned)"""
+    """bf16 copies of many fp32 tensors in ONE launch; the copies are slices of one buffer (16-byte aligned).  A strided input is
+    copied first, in the order of its shape"""
     lib = _lib.load()
     if not xs:
         return []
     flat = _slices_of_one_buffer(len(xs), [x.numel() for x in xs], torch.bfloat16, xs[0].device, align=8)
     outs = [o.view(x.shape) for o, x in zip(flat, xs)]
     entries = (_CastEntry * len(xs))()
-    for i, (x, o) in enumerate(zip(xs, outs)):
-        x = _req(x, torch.float32, "x")
+    # the contiguous copies _req makes stay referenced until the launch is enqueued: a copy released inside the loop gives its block
+    # back to the caching allocator, which hands it to the NEXT input's copy -- two entries of the table then name one address
+    srcs = [_req(x, torch.float32, "x") for x in xs]
+    for i, (x, o) in enumerate(zip(srcs, outs)):
         entries[i] = _CastEntry(x.data_ptr(), o.data_ptr(), x.numel())
     check(lib.gaot_cast_bf16_multi(entries, len(xs), _stream()), "gaot_cast_bf16_multi")
     return outs
 
 
 def cast_bf16_transpose_multi(xs: Sequence[Tensor]) -> List[Tensor]:
-    """bf16 TRANSPOSED copies ([cols, rows]) of many contiguous fp32 matrices in ONE launch"""
+    """bf16 TRANSPOSED copies ([cols, rows]) of many fp32 matrices in ONE launch.  A strided matrix (a transposed view, a column
+    slice) is copied first, like every other operand that goes through _req; anything but a matrix is refused"""
     lib = _lib.load()
     if not xs:
         return []
+    for x in xs:
+        if x.dim() != 2:
+            raise GaotError(f"cast_bf16_transpose_multi: 2-D tensors expected, got shape {tuple(x.shape)}")
     flat = _slices_of_one_buffer(len(xs), [x.numel() for x in xs], torch.bfloat16, xs[0].device, align=8)
     outs = [o.view(x.shape[1], x.shape[0]) for o, x in zip(flat, xs)]
     entries = (_CastEntry * len(xs))()
     rows, cols = (C.c_int * len(xs))(), (C.c_int * len(xs))()
-    for i, (x, o) in enumerate(zip(xs, outs)):
-        x = _req(x, torch.float32, "x")
-        if x.dim() != 2 or not x.is_contiguous():
-            raise GaotError("cast_bf16_transpose_multi: contiguous 2-D tensors expected")
+    srcs = [_req(x, torch.float32, "x") for x in xs]     # kept until the launch is enqueued (see cast_bf16_multi)
+    for i, (x, o) in enumerate(zip(srcs, outs)):
         entries[i] = _CastEntry(x.data_ptr(), o.data_ptr(), x.numel())
         rows[i], cols[i] = x.shape[0], x.shape[1]
     check(lib.gaot_cast_bf16_transpose_multi(entries, rows, cols, len(xs), _stream()), "gaot_cast_bf16_transpose_multi")
