@@ -41,7 +41,9 @@ struct FwdLds {
     static constexpr int weights_end = bL + 32;
 };
 
-// MODE (gno_common.h): in the nonlinear / kernel-only modes `nl_` is one NlFwd and layer 0 starts from b_0 + t[src]
+// MODE (gno_common.h): in the nonlinear / kernel-only modes `nl_` begins with one NlFwd and layer 0 starts from b_0 + t[src]
+// WEIGHTED (a WFwd ends the pack): the staged value is alpha_e k_e f[s_e], alpha applied in fp32 after the last layer's accumulator,
+// and the rows are summed, not averaged
 template <int NH, int H, int T, int MODE, class... Nl>
 __global__ __launch_bounds__(256, 2) void k_gno_fwd(MlpPtrs mlp, const float* __restrict__ y_pos,
                                                     const float* __restrict__ x_pos, const float* __restrict__ f_y,
@@ -51,6 +53,7 @@ __global__ __launch_bounds__(256, 2) void k_gno_fwd(MlpPtrs mlp, const float* __
     static_assert(MODE == MODE_LINEAR || H == NLH, "t rows are 64 wide");
     constexpr int C = 32;
     constexpr int KB = H / 32;
+    constexpr bool W = pack_has<WFwd, Nl...>;
     using L = FwdLds<NH, H>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* stage_all = lds + L::weights_end;             // [4 waves][T][32][C]
@@ -90,6 +93,7 @@ __global__ __launch_bounds__(256, 2) void k_gno_fwd(MlpPtrs mlp, const float* __
         // MLP input k = 2i+hf of this lane's edge: [y.x y.y y.z x.x x.y x.z][2i+hf], i = 0..2
         float bin[T][3];
         [[maybe_unused]] int sid[T];   // source of this lane's edge (edges past E: row 0, a valid row)
+        [[maybe_unused]] float aw[T];  // weight of this lane's edge (edges past E: 0)
 #pragma unroll
         for (int t = 0; t < T; ++t) {
             const int64_t e = base + 32 * t + l31;
@@ -102,6 +106,7 @@ __global__ __launch_bounds__(256, 2) void k_gno_fwd(MlpPtrs mlp, const float* __
             bin[t][1] = hf ? xq[0] : ys[2];
             bin[t][2] = xq[1 + hf];
             if constexpr (MODE != MODE_LINEAR) sid[t] = s;
+            if constexpr (W) aw[t] = valid ? last_arg(nl_...).alpha[e] : 0.f;
             if (hf == 0) {
                 ids[(t * 2 + 0) * 32 + l31] = s;
                 ids[(t * 2 + 1) * 32 + l31] = valid ? q : -1;
@@ -191,20 +196,26 @@ __global__ __launch_bounds__(256, 2) void k_gno_fwd(MlpPtrs mlp, const float* __
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int el = mfma32_row(r, hf);
+                float kv = acc[r];
+                if constexpr (W) {   // lane el holds edge el of the tile: el = mfma32_row(r, 0) + 4 hf, two scalar reads and a select
+                    const int wa = __builtin_bit_cast(int, aw[t]);
+                    const int a0 = __builtin_amdgcn_readlane(wa, mfma32_row(r, 0)), a1 = __builtin_amdgcn_readlane(wa, mfma32_row(r, 0) + 4);
+                    kv *= __builtin_bit_cast(float, hf ? a1 : a0);
+                }
                 if constexpr (MODE == MODE_KERNELONLY) {
-                    stage[(t * 32 + el) * C + l31] = acc[r];
+                    stage[(t * 32 + el) * C + l31] = kv;
                 } else {
                     const int s = ids[(t * 2 + 0) * 32 + el];
                     const float fv = f_y[(int64_t)s * C + l31];
-                    stage[(t * 32 + el) * C + l31] = acc[r] * fv;
+                    stage[(t * 32 + el) * C + l31] = kv * fv;
                 }
             }
         }
         wave_lds_fence();
-        // ---- segmented mean: half h walks tile h (T==2) / lower half walks the tile (T==1) --------
+        // ---- segmented mean (weighted: sum): half h walks tile h (T==2) / lower half walks the tile (T==1) --------
         if (hf < T) {
             segment_walk<C>(stage + hf * 32 * C, C, ids + (hf * 2 + 1) * 32, l31, base + 32 * hf, rowptr, out, part,
-                            true);
+                            !W);
         }
         wave_lds_fence();
     }
@@ -300,6 +311,8 @@ __device__ __forceinline__ void load_wgroup(float (&w)[16], const WRsrc& rs, int
 // MODE (gno_common.h): the nonlinear / kernel-only modes append one NlBwd to the pack: layer 0 is recomputed from b_0 + t[src], and
 // dt[s] = sum of dz_0 over the edges of source s is written beside grad_f (64 lanes = 64 features walk the wave's dz_0 tile).
 // Kernel-only mode: dk = gs (no f), and grad_f is not written (its only term, dt W_0f, is a per-node product of the caller's).
+// WEIGHTED (a WBwd begins the pack, gno_common.h): `gs` is grad_out itself; the kernel forms gv = alpha_e g per edge and, when asked,
+// dalpha_e = sum_c g_c k_c f_c over the 32 channel lanes (through columns 32.. of the wave's buf tile, a fixed order).
 template <int NH, int H, bool CG, int MODE, class... CoordOut>
 __global__ __launch_bounds__(256, 1) void k_gno_bwd(
     MlpPtrs mlp, MlpPtrs mlp_t /* w = transposed copies [in][out] */, const float* __restrict__ y_pos,
@@ -314,6 +327,8 @@ __global__ __launch_bounds__(256, 1) void k_gno_bwd(
     constexpr int C = 32;
     constexpr int KB = H / 32;
     static_assert(KB == 2, "weight-gradient wave split is written for hidden == 64");
+    constexpr bool W = pack_has<WBwd, CoordOut...>;
+    static_assert(!(W && CG), "no coordinate gradients in the weighted variant");
     constexpr int LDH = H + 1;
     constexpr int NR = 4 * (NH - 1);
     using PL = ParamLayout<NH, H>;
@@ -377,6 +392,7 @@ __global__ __launch_bounds__(256, 1) void k_gno_bwd(
             const int s = valid ? src_s[e] : 0;
             const int q = valid ? dst_s[e] : 0;
             if constexpr (MODE != MODE_LINEAR) sid = s;
+
             const float* ys = y_pos + (int64_t)s * 3;
             const float* xq = x_pos + (int64_t)q * 3;
             bin[0] = ys[hf];
@@ -455,6 +471,12 @@ __global__ __launch_bounds__(256, 1) void k_gno_bwd(
         });
         // ---- gather f[src] and g[dst] rows now: their latency hides under the last layer's MFMA chain ---------
         wave_lds_fence();
+        [[maybe_unused]] int wa = 0;   // weighted: the weight of this lane's edge (edges past E: 0), read at its dst-sorted position
+        if constexpr (W) {
+            const WBwd w = first_arg(gcoord_...);
+            const int64_t e = base + l31;
+            wa = e < E ? __builtin_bit_cast(int, w.alpha[w.s2d[e]]) : 0;
+        }
         float fv[16], gv[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -484,6 +506,29 @@ __global__ __launch_bounds__(256, 1) void k_gno_bwd(
                 kp = __builtin_amdgcn_mfma_f32_32x32x2f32(h[kb][r], (G % 2 == 0) ? wA[r] : wB[r], kp, 0, 0, 0);
         });
         // ---- per edge: g = grad_out[dst]/deg (pre-scaled) ; m' = g*k' (-> grad_f) ; dk' = g*f --------------
+        if constexpr (W) {
+            // weighted: gv holds the raw g.  dalpha_e = sum_c g k f goes through columns 32.. of buf (m' / dk' use 0..31): lane (edge
+            // l31, half hf) adds 16 channels in order, the two halves are added, each edge is stored once at its dst-sorted position
+            const WBwd w = first_arg(gcoord_...);
+            const bool want = w.dalpha != nullptr;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int el = mfma32_row(r, hf);
+                const float g0 = gv[r];
+                if (want) buf[el * LDH + 32 + l31] = g0 * kp[r] * fv[r];
+                // lane el holds edge el: el = mfma32_row(r, 0) + 4 hf, two scalar reads and a select
+                const int a0 = __builtin_amdgcn_readlane(wa, mfma32_row(r, 0)), a1 = __builtin_amdgcn_readlane(wa, mfma32_row(r, 0) + 4);
+                gv[r] = __builtin_bit_cast(float, hf ? a1 : a0) * g0;
+            }
+            if (want) {
+                wave_lds_fence();
+                float s = 0.f;
+#pragma unroll
+                for (int c = 0; c < 16; ++c) s += buf[l31 * LDH + 32 + 16 * hf + c];
+                s += __shfl_xor(s, 32, 64);
+                if (hf == 0 && base + l31 < E) w.dalpha[w.s2d[base + l31]] = s;
+            }
+        }
         f32x16 dkp;
         if constexpr (MODE == MODE_KERNELONLY) {
 #pragma unroll
@@ -719,14 +764,21 @@ size_t bwd_lds_bytes(int nh, int h, bool coords = false) {
     return sizeof(float) * (size_t)(4 * per_wave + nh * h + 32 + (coords ? IN0 * h : 0));
 }
 
-template <int NH, int H, int MODE>
+// W: the weighted variant (edge_w [E], dst-sorted); its instantiations are the ones whose pack ends with a WFwd
+template <int NH, int H, int MODE, bool W = false>
 int launch_fwd(const MlpPtrs& p, const float* y_pos, const float* x_pos, const float* f_y, const float* ttab, const int* src_s,
-               const int* dst_s, const int* rowptr, int64_t E, float* out, float* part, hipStream_t st) {
+               const int* dst_s, const int* rowptr, int64_t E, float* out, float* part, hipStream_t st,
+               const float* edge_w = nullptr) {
     constexpr int T = 2;
     const size_t lds = fwd_lds_bytes(NH, H, T);
     auto kern = [] {
-        if constexpr (MODE == MODE_LINEAR) return k_gno_fwd<NH, H, T, MODE>;
-        else return k_gno_fwd<NH, H, T, MODE, NlFwd>;
+        if constexpr (W) {
+            if constexpr (MODE == MODE_LINEAR) return k_gno_fwd<NH, H, T, MODE, WFwd>;
+            else return k_gno_fwd<NH, H, T, MODE, NlFwd, WFwd>;
+        } else {
+            if constexpr (MODE == MODE_LINEAR) return k_gno_fwd<NH, H, T, MODE>;
+            else return k_gno_fwd<NH, H, T, MODE, NlFwd>;
+        }
     }();
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) {
@@ -735,20 +787,31 @@ int launch_fwd(const MlpPtrs& p, const float* y_pos, const float* x_pos, const f
     }
     const int64_t n_macro = ceil_div(E, 32 * T);
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n_macro, 4), 256 * 2));
-    if constexpr (MODE == MODE_LINEAR)
+    if constexpr (W) {
+        if constexpr (MODE == MODE_LINEAR)
+            GAOT_KLAUNCH(kern, dim3(grid), dim3(256), lds, st, p, y_pos, x_pos, f_y, src_s, dst_s, rowptr, E, out, part, WFwd{edge_w});
+        else
+            GAOT_KLAUNCH(kern, dim3(grid), dim3(256), lds, st, p, y_pos, x_pos, f_y, src_s, dst_s, rowptr, E, out, part, NlFwd{ttab},
+                         WFwd{edge_w});
+    } else if constexpr (MODE == MODE_LINEAR)
         GAOT_KLAUNCH(kern, dim3(grid), dim3(256), lds, st, p, y_pos, x_pos, f_y, src_s, dst_s, rowptr, E, out, part);
     else
         GAOT_KLAUNCH(kern, dim3(grid), dim3(256), lds, st, p, y_pos, x_pos, f_y, src_s, dst_s, rowptr, E, out, part, NlFwd{ttab});
     return GAOT_OK;
 }
 
-template <int NH, int H, bool CG, int MODE>
+// W: the weighted variant (gs = grad_out itself, wb = alpha / map / dalpha); its instantiations are the ones whose pack begins with a WBwd
+template <int NH, int H, bool CG, int MODE, bool W = false>
 int launch_bwd(const MlpPtrs& p, const MlpPtrs& pt, const float* y_pos, const float* x_pos, const float* f_y,
                const float* gs, const int* src_s, const int* dst_s, const int* rowptr_src,
-               int64_t E, float* grad_f, float* part, float* wpart, float* gcoord, const NlBwd& nl, int grid, hipStream_t st) {
+               int64_t E, float* grad_f, float* part, float* wpart, float* gcoord, const NlBwd& nl, int grid, hipStream_t st,
+               const WBwd& wb = WBwd{nullptr, nullptr, nullptr}) {
     const size_t lds = bwd_lds_bytes(NH, H, CG);
     auto kern = [] {
-        if constexpr (MODE == MODE_LINEAR) {
+        if constexpr (W) {
+            if constexpr (MODE == MODE_LINEAR) return k_gno_bwd<NH, H, false, MODE, WBwd>;
+            else return k_gno_bwd<NH, H, false, MODE, WBwd, NlBwd>;
+        } else if constexpr (MODE == MODE_LINEAR) {
             if constexpr (CG) return k_gno_bwd<NH, H, true, MODE, float*>;
             else return k_gno_bwd<NH, H, false, MODE>;
         } else {
@@ -761,7 +824,14 @@ int launch_bwd(const MlpPtrs& p, const MlpPtrs& pt, const float* y_pos, const fl
         gaot_set_error("gno_bwd: cannot set dynamic LDS %zu: %s", lds, hipGetErrorString(e));
         return GAOT_ERR_LAUNCH;
     }
-    if constexpr (MODE == MODE_LINEAR) {
+    if constexpr (W) {
+        if constexpr (MODE == MODE_LINEAR)
+            GAOT_KLAUNCH(kern, dim3(grid), dim3(256), lds, st, p, pt, y_pos, x_pos, f_y, gs, src_s, dst_s,
+                               rowptr_src, E, grad_f, part, wpart, wb);
+        else
+            GAOT_KLAUNCH(kern, dim3(grid), dim3(256), lds, st, p, pt, y_pos, x_pos, f_y, gs, src_s, dst_s,
+                               rowptr_src, E, grad_f, part, wpart, wb, nl);
+    } else if constexpr (MODE == MODE_LINEAR) {
         if constexpr (CG)
             GAOT_KLAUNCH(kern, dim3(grid), dim3(256), lds, st, p, pt, y_pos, x_pos, f_y, gs, src_s, dst_s,
                                rowptr_src, E, grad_f, part, wpart, gcoord);
@@ -796,14 +866,14 @@ bool mlp_supported(const gaot_mlp_t* m, bool backward, int precision = 0) {
 int gaot_gno_fwd_bf16_dispatch(int n_hidden, int mode, const float* const* w, const float* const* b, const float* y_pos,
                                const float* x_pos, const float* f_y, const float* ttab, const int32_t* src_sorted,
                                const int32_t* dst_sorted, const int32_t* rowptr_dst, int64_t num_edges, float* out, float* part,
-                               hipStream_t st);
+                               const float* edge_w, hipStream_t st);
 
 size_t gaot_gno_bwd_bf16_image_bytes(int n_hidden);
 int gaot_gno_bwd_bf16_dispatch(int n_hidden, int mode, const float* const* w, const float* const* b, const float* w0t,
                                void* images, const float* y_pos, const float* x_pos, const float* f_y, const float* gs,
                                const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr_src,
                                int64_t num_edges, float* grad_f, float* part, float* wpart, float* gcoord, const float* ttab,
-                               float* dt, float* part_dt, int grid, hipStream_t st);
+                               float* dt, float* part_dt, const gno::WBwd* wb, int grid, hipStream_t st);
 
 extern "C" size_t gaot_gno_fwd_workspace_bytes(int64_t num_edges, int channels) {
     return sizeof(float) * (size_t)(ceil_div(num_edges, 32) * 2 * channels) + 64;
@@ -818,11 +888,11 @@ namespace {
             return GAOT_ERR_ARG;                          \
         }                                                 \
     } while (0)
-// gaot_gno_fwd (mode = linear, ttab = null) and gaot_gno_fwd_nl
+// gaot_gno_fwd (mode = linear, ttab = null), gaot_gno_fwd_nl and gaot_gno_fwd_w (weighted: edge_w [num_edges], rows are summed)
 int gno_fwd_impl(const char* fn, const gaot_mlp_t* mlp, const float* y_pos, const float* x_pos, const float* f_y,
                  const float* ttab, int mode, const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr_dst,
                  int64_t num_edges, int64_t num_queries, float* out, int precision, void* workspace, size_t workspace_bytes,
-                 gaot_stream_t stream) {
+                 gaot_stream_t stream, bool weighted = false, const float* edge_w = nullptr) {
     GNO_CHECK(mlp, "null mlp");
     if (!mlp_supported(mlp, false)) {
         gaot_set_error("%s: unsupported MLP shape (n_hidden=%d hidden=%d channels=%d)", fn, mlp->n_hidden,
@@ -845,10 +915,23 @@ int gno_fwd_impl(const char* fn, const gaot_mlp_t* mlp, const float* y_pos, cons
     if (num_edges > 0) {
         GNO_CHECK(y_pos && x_pos && (f_y || mode == MODE_KERNELONLY) && src_sorted && dst_sorted, "null pointer");
         GNO_CHECK(mode == MODE_LINEAR || ttab, "null t");
+        GNO_CHECK(!weighted || edge_w, "null edge_w");
         GNO_CHECK(precision == 0 || precision == 1, "precision must be 0 (fp32) or 1 (bf16 matrix cores)");
         if (precision == 1) {
             rc = gaot_gno_fwd_bf16_dispatch(mlp->n_hidden, mode, p.w, p.b, y_pos, x_pos, f_y, ttab, src_sorted, dst_sorted,
-                                            rowptr_dst, num_edges, out, part, st);
+                                            rowptr_dst, num_edges, out, part, weighted ? edge_w : nullptr, st);
+        } else if (weighted) {
+#define GNO_FWD_CASE(NH_, MODE_)                                                                                          \
+    case NH_ * 3 + MODE_:                                                                                                 \
+        rc = launch_fwd<NH_, 64, MODE_, true>(p, y_pos, x_pos, f_y, ttab, src_sorted, dst_sorted, rowptr_dst, num_edges, out, part, \
+                                              st, edge_w);                                                                \
+        break;
+#define GNO_FWD_CASES(NH_) GNO_FWD_CASE(NH_, MODE_LINEAR) GNO_FWD_CASE(NH_, MODE_NONLINEAR) GNO_FWD_CASE(NH_, MODE_KERNELONLY)
+            switch (mlp->n_hidden * 3 + mode) {
+                GNO_FWD_CASES(1) GNO_FWD_CASES(2) GNO_FWD_CASES(3) GNO_FWD_CASES(4)
+            }
+#undef GNO_FWD_CASES
+#undef GNO_FWD_CASE
         } else {
 #define GNO_FWD_CASE(NH_, MODE_)                                                                                          \
     case NH_ * 3 + MODE_:                                                                                                 \
@@ -865,7 +948,7 @@ int gno_fwd_impl(const char* fn, const gaot_mlp_t* mlp, const float* y_pos, cons
     }
     const int64_t n = num_queries * 8;   // four channels per thread
     GAOT_KLAUNCH((k_segment_fixup<32>), dim3(segment_fixup_grid(n)), dim3(256), 0, st, rowptr_dst,
-                       num_queries, part, out, 1);
+                       num_queries, part, out, weighted ? 0 : 1);
     GAOT_LAUNCH_CHECK();
     return GAOT_OK;
 }
@@ -908,13 +991,19 @@ extern "C" size_t gaot_gno_bwd_nl_workspace_bytes(const gaot_mlp_t* mlp, int64_t
     return gaot_gno_bwd_workspace_bytes(mlp, num_edges, num_queries) + sizeof(float) * (size_t)(ceil_div(num_edges, 16) * 2 * NLH) + 512;
 }
 
+// the weighted backward: the layout of the nonlinear modes' workspace in every mode (its grad_out / deg block stays unused)
+extern "C" size_t gaot_gno_bwd_w_workspace_bytes(const gaot_mlp_t* mlp, int64_t num_edges, int64_t num_queries) {
+    return gaot_gno_bwd_nl_workspace_bytes(mlp, num_edges, num_queries);
+}
+
 namespace {
-// gaot_gno_bwd (gcoord = null), gaot_gno_bwd_coords (gcoord = [num_edges][6]) and gaot_gno_bwd_nl (mode != linear: ttab, dt)
+// gaot_gno_bwd (gcoord = null), gaot_gno_bwd_coords (gcoord = [num_edges][6]), gaot_gno_bwd_nl (mode != linear: ttab, dt) and
+// gaot_gno_bwd_w (wb: the weighted variant -- no 1/deg pre-pass, the kernels read grad_out and the edge weights themselves)
 int gno_bwd_impl(const char* fn, const gaot_mlp_t* mlp, const float* y_pos, const float* x_pos, const float* f_y,
                  const float* grad_out, const int32_t* rowptr_dst, const int32_t* src_sorted, const int32_t* dst_sorted,
                  const int32_t* rowptr_src, int64_t num_edges, int64_t num_sources, int64_t num_queries, float* grad_f_y,
                  const gaot_mlp_grad_t* grads, float* gcoord, int mode, const float* ttab, float* dt, int precision,
-                 void* workspace, size_t workspace_bytes, gaot_stream_t stream) {
+                 void* workspace, size_t workspace_bytes, gaot_stream_t stream, const WBwd* wb = nullptr) {
     GNO_CHECK(mlp && grads, "null mlp");
     if (!mlp_supported(mlp, true, precision)) {
         gaot_set_error("%s: unsupported MLP shape (n_hidden=%d hidden=%d channels=%d; four hidden layers in bf16 mode only)", fn,
@@ -929,9 +1018,9 @@ int gno_bwd_impl(const char* fn, const gaot_mlp_t* mlp, const float* y_pos, cons
     GNO_CHECK(precision != 1 || num_edges < ((int64_t)1 << 27),
                    "bf16 GNO backward: 2^27 or more edges in one launch (run the mesh point-sharded or in fp32 mode)");
     const bool nlm = mode != MODE_LINEAR;
-    GNO_CHECK(workspace_bytes >= (nlm ? gaot_gno_bwd_nl_workspace_bytes(mlp, num_edges, num_queries)
-                                      : gaot_gno_bwd_workspace_bytes(mlp, num_edges, num_queries)), "workspace too small");
-    GNO_CHECK(rowptr_src && rowptr_dst, "null rowptr");
+    GNO_CHECK(workspace_bytes >= ((nlm || wb) ? gaot_gno_bwd_nl_workspace_bytes(mlp, num_edges, num_queries)
+                                              : gaot_gno_bwd_workspace_bytes(mlp, num_edges, num_queries)), "workspace too small");
+    GNO_CHECK(rowptr_src && (rowptr_dst || wb), "null rowptr");
     GNO_CHECK(!nlm || num_sources == 0 || dt, "null grad_src_table");
     hipStream_t st = (hipStream_t)stream;
     const int nh = mlp->n_hidden, h = mlp->hidden;
@@ -985,13 +1074,28 @@ int gno_bwd_impl(const char* fn, const gaot_mlp_t* mlp, const float* y_pos, cons
         GNO_CHECK(y_pos && x_pos && grad_out && src_sorted && dst_sorted && (!want_gf || (f_y && grad_f_y)), "null pointer");
         GNO_CHECK(!nlm || ttab, "null src_table");
         const bool cg = gcoord != nullptr;
-        GAOT_KLAUNCH(k_scale_by_inv_deg, dim3((unsigned)ceil_div(num_queries * 8, 256)), dim3(256), 0, st, grad_out,
-                           rowptr_dst, num_queries, gs);
+        GNO_CHECK(!wb || (wb->alpha && wb->s2d && !cg), "null edge_w / src2dst");
+        if (!wb)
+            GAOT_KLAUNCH(k_scale_by_inv_deg, dim3((unsigned)ceil_div(num_queries * 8, 256)), dim3(256), 0, st, grad_out,
+                               rowptr_dst, num_queries, gs);
         int rc = GAOT_OK;
         const NlBwd nl{ttab, dt, part_dt};
         if (precision == 1) {
-            rc = gaot_gno_bwd_bf16_dispatch(nh, mode, p.w, p.b, pt.w[0], images, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted,
-                                            rowptr_src, num_edges, grad_f_y, part, wpart, gcoord, ttab, dt, part_dt, grid, st);
+            rc = gaot_gno_bwd_bf16_dispatch(nh, mode, p.w, p.b, pt.w[0], images, y_pos, x_pos, f_y, wb ? grad_out : gs, src_sorted,
+                                            dst_sorted, rowptr_src, num_edges, grad_f_y, part, wpart, gcoord, ttab, dt, part_dt, wb,
+                                            grid, st);
+        } else if (wb) {
+#define GNO_BWD_CASE(NH_, MODE_)                                                                                            \
+    case NH_ * 3 + MODE_:                                                                                                   \
+        rc = launch_bwd<NH_, 64, false, MODE_, true>(p, pt, y_pos, x_pos, f_y, grad_out, src_sorted, dst_sorted, rowptr_src,  \
+                                                     num_edges, grad_f_y, part, wpart, nullptr, nl, grid, st, *wb);         \
+        break;
+#define GNO_BWD_CASES(NH_) GNO_BWD_CASE(NH_, MODE_LINEAR) GNO_BWD_CASE(NH_, MODE_NONLINEAR) GNO_BWD_CASE(NH_, MODE_KERNELONLY)
+            switch (nh * 3 + mode) {
+                GNO_BWD_CASES(1) GNO_BWD_CASES(2) GNO_BWD_CASES(3)
+            }
+#undef GNO_BWD_CASES
+#undef GNO_BWD_CASE
         } else {
 #define GNO_BWD_CASE(NH_, CG_, MODE_)                                                                                       \
     case (NH_ * 2 + CG_) * 3 + MODE_:                                                                                       \
@@ -1070,4 +1174,32 @@ extern "C" int gaot_gno_bwd_nl(const gaot_mlp_t* mlp, int mode, const float* y_p
     return gno_bwd_impl("gaot_gno_bwd_nl", mlp, y_pos, x_pos, f_y, grad_out, rowptr_dst, src_sorted, dst_sorted, rowptr_src,
                         num_edges, num_sources, num_queries, grad_f_y, grads, grad_edge_coords, mode, src_table, grad_src_table,
                         precision, workspace, workspace_bytes, stream);
+}
+
+extern "C" int gaot_gno_fwd_w(const gaot_mlp_t* mlp, int mode, const float* y_pos, const float* x_pos, const float* f_y,
+                              const float* src_table, const float* edge_w, const int32_t* src_sorted, const int32_t* dst_sorted,
+                              const int32_t* rowptr_dst, int64_t num_edges, int64_t num_queries, float* out, int precision,
+                              void* workspace, size_t workspace_bytes, gaot_stream_t stream) {
+    GAOT_ENTER();
+    GAOT_CHECK_ARG(mode == MODE_LINEAR || mode == MODE_NONLINEAR || mode == MODE_KERNELONLY,
+                   "mode must be 0 (linear), 1 (nonlinear) or 2 (nonlinear_kernelonly)");
+    GAOT_CHECK_ARG(num_edges <= 0 || edge_w, "null edge_w");
+    return gno_fwd_impl("gaot_gno_fwd_w", mlp, y_pos, x_pos, f_y, src_table, mode, src_sorted, dst_sorted, rowptr_dst, num_edges,
+                        num_queries, out, precision, workspace, workspace_bytes, stream, true, edge_w);
+}
+
+extern "C" int gaot_gno_bwd_w(const gaot_mlp_t* mlp, int mode, const float* y_pos, const float* x_pos, const float* f_y,
+                              const float* src_table, const float* grad_out, const float* edge_w, const int32_t* src2dst,
+                              const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr_src, int64_t num_edges,
+                              int64_t num_sources, int64_t num_queries, float* grad_f_y, float* grad_src_table,
+                              const gaot_mlp_grad_t* grads, float* grad_edge_w, int precision, void* workspace,
+                              size_t workspace_bytes, gaot_stream_t stream) {
+    GAOT_ENTER();
+    GAOT_CHECK_ARG(mode == MODE_LINEAR || mode == MODE_NONLINEAR || mode == MODE_KERNELONLY,
+                   "mode must be 0 (linear), 1 (nonlinear) or 2 (nonlinear_kernelonly)");
+    GAOT_CHECK_ARG(num_edges <= 0 || (edge_w && src2dst), "null edge_w / src2dst");
+    const WBwd wb{edge_w, src2dst, grad_edge_w};
+    return gno_bwd_impl("gaot_gno_bwd_w", mlp, y_pos, x_pos, f_y, grad_out, nullptr, src_sorted, dst_sorted, rowptr_src, num_edges,
+                        num_sources, num_queries, grad_f_y, grads, nullptr, mode, src_table, grad_src_table, precision, workspace,
+                        workspace_bytes, stream, &wb);
 }

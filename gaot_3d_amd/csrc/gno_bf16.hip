@@ -49,7 +49,9 @@ struct FwdLdsB {
 
 // The 12 waves of the one workgroup per CU (THREE waves per SIMD) share one copy of the weight images.
 constexpr int FWD_NW = 12;
-// MODE (gno_common.h): in the nonlinear / kernel-only modes `nl_` is one NlFwd and layer 0 starts from b_0 + t[src]
+// MODE (gno_common.h): in the nonlinear / kernel-only modes `nl_` begins with one NlFwd and layer 0 starts from b_0 + t[src]
+// WEIGHTED (a WFwd ends the pack): the staged value is alpha_e k_e f[s_e], alpha applied in fp32 after the last layer's accumulator,
+// and the rows are summed, not averaged
 template <int NH, int T, int MODE, class... Nl>
 __global__ __launch_bounds__(FWD_NW * 64, 1) void k_gno_fwd_bf16(MlpPtrs mlp, const float* __restrict__ y_pos,
                                                          const float* __restrict__ x_pos, const float* __restrict__ f_y,
@@ -57,6 +59,7 @@ __global__ __launch_bounds__(FWD_NW * 64, 1) void k_gno_fwd_bf16(MlpPtrs mlp, co
                                                          const int* __restrict__ rowptr, int64_t E, float* __restrict__ out,
                                                          float* __restrict__ part, Nl... nl_) {
     constexpr int C = 32, H = 64, KB = 2, NW = FWD_NW;
+    constexpr bool W = pack_has<WFwd, Nl...>;
     using L = FwdLdsB<NH>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* stage_all = lds + L::weights_end;             // [NW waves][T][32][C]
@@ -138,6 +141,7 @@ __global__ __launch_bounds__(FWD_NW * 64, 1) void k_gno_fwd_bf16(MlpPtrs mlp, co
         for (int t = 0; t < T; ++t) {
             bin[t][0] = pbin[t][0]; bin[t][1] = pbin[t][1]; bin[t][2] = pbin[t][2];
             if constexpr (MODE != MODE_LINEAR) sid[t] = cs[t];
+
             if (hf == 0) {
                 ids[(t * 2 + 0) * 32 + l31] = cs[t];
                 ids[(t * 2 + 1) * 32 + l31] = cq[t];
@@ -223,6 +227,14 @@ __global__ __launch_bounds__(FWD_NW * 64, 1) void k_gno_fwd_bf16(MlpPtrs mlp, co
         }
         // ---- last layer, transposed: K'[e][c] = sum_k Hlast[k][e] * WL[c][k] + bL[c] ------------------------
         wave_lds_fence();  // ids visible to the whole wave
+        [[maybe_unused]] float aw[T];  // weight of this lane's edge (edges past E: 0), requested here: the hidden layers' registers are free
+        if constexpr (W) {
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                const int64_t e = base + 32 * t + l31;
+                aw[t] = e < E ? last_arg(nl_...).alpha[e] : 0.f;
+            }
+        }
         const bf16x8* imL = reinterpret_cast<const bf16x8*>(lds + L::imgL);
 #pragma unroll
         for (int t = 0; t < T; ++t) {
@@ -238,18 +250,24 @@ __global__ __launch_bounds__(FWD_NW * 64, 1) void k_gno_fwd_bf16(MlpPtrs mlp, co
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int el = mfma32_row(r, hf);
+                float kv = acc[r];
+                if constexpr (W) {   // lane el holds edge el of the tile: el = mfma32_row(r, 0) + 4 hf, two scalar reads and a select
+                    const int wa = __builtin_bit_cast(int, aw[t]);
+                    const int a0 = __builtin_amdgcn_readlane(wa, mfma32_row(r, 0)), a1 = __builtin_amdgcn_readlane(wa, mfma32_row(r, 0) + 4);
+                    kv *= __builtin_bit_cast(float, hf ? a1 : a0);
+                }
                 if constexpr (MODE == MODE_KERNELONLY) {   // the kernel value itself
-                    stage[(t * 32 + el) * C + l31] = acc[r];
+                    stage[(t * 32 + el) * C + l31] = kv;
                 } else {
                     const int s = ids[(t * 2 + 0) * 32 + el];
                     const float fval = f_y[(int64_t)s * C + l31];
-                    stage[(t * 32 + el) * C + l31] = acc[r] * fval;
+                    stage[(t * 32 + el) * C + l31] = kv * fval;
                 }
             }
         }
         wave_lds_fence();
         if (hf < T) {
-            segment_walk<C>(stage + hf * 32 * C, C, ids + (hf * 2 + 1) * 32, l31, base + 32 * hf, rowptr, out, part, true);
+            segment_walk<C>(stage + hf * 32 * C, C, ids + (hf * 2 + 1) * 32, l31, base + 32 * hf, rowptr, out, part, !W);
         }
         wave_lds_fence();
     }
@@ -260,9 +278,10 @@ size_t fwd_lds_bytes_b(int nh, int t, int nw) {
     return sizeof(float) * (size_t)(weights + nw * t * 32 * 32) + sizeof(int) * (size_t)(nw * t * 2 * 32);
 }
 
-template <int NH, int MODE>
+template <int NH, int MODE, bool W = false>
 int launch_fwd_b(const MlpPtrs& p, const float* y_pos, const float* x_pos, const float* f_y, const float* ttab, const int* src_s,
-                 const int* dst_s, const int* rowptr, int64_t E, float* out, float* part, hipStream_t st) {
+                 const int* dst_s, const int* rowptr, int64_t E, float* out, float* part, hipStream_t st,
+                 const float* edge_w = nullptr) {
     // 12 waves per workgroup (one weight image per CU, THREE waves per SIMD; 127 KB of LDS at three hidden layers) with the
     // id / coordinate loads pipelined.  Measured at E = 4 M (profiles/archive/r5_w_gno_fwd_variants_lab.txt; nh = 3 / 2 / 4): round-4 form
     // (4 waves, two workgroups per CU, loads at the point of use) 0.402 / 0.317 / 0.466 ms, 4 waves + full pipeline (the f rows
@@ -271,8 +290,13 @@ int launch_fwd_b(const MlpPtrs& p, const float* y_pos, const float* x_pos, const
     constexpr int T = 2, NW = FWD_NW;
     const size_t lds = fwd_lds_bytes_b(NH, T, NW);
     auto kern = [] {
-        if constexpr (MODE == MODE_LINEAR) return k_gno_fwd_bf16<NH, T, MODE>;
-        else return k_gno_fwd_bf16<NH, T, MODE, NlFwd>;
+        if constexpr (W) {
+            if constexpr (MODE == MODE_LINEAR) return k_gno_fwd_bf16<NH, T, MODE, WFwd>;
+            else return k_gno_fwd_bf16<NH, T, MODE, NlFwd, WFwd>;
+        } else {
+            if constexpr (MODE == MODE_LINEAR) return k_gno_fwd_bf16<NH, T, MODE>;
+            else return k_gno_fwd_bf16<NH, T, MODE, NlFwd>;
+        }
     }();
     static bool attr_set = false;
     if (!attr_set) {
@@ -285,7 +309,13 @@ int launch_fwd_b(const MlpPtrs& p, const float* y_pos, const float* x_pos, const
     }
     const int64_t n_macro = ceil_div(E, 32 * T);
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n_macro, NW), 256));
-    if constexpr (MODE == MODE_LINEAR)
+    if constexpr (W) {
+        if constexpr (MODE == MODE_LINEAR)
+            GAOT_KLAUNCH(kern, dim3(grid), dim3(NW * 64), lds, st, p, y_pos, x_pos, f_y, src_s, dst_s, rowptr, E, out, part, WFwd{edge_w});
+        else
+            GAOT_KLAUNCH(kern, dim3(grid), dim3(NW * 64), lds, st, p, y_pos, x_pos, f_y, src_s, dst_s, rowptr, E, out, part, NlFwd{ttab},
+                         WFwd{edge_w});
+    } else if constexpr (MODE == MODE_LINEAR)
         GAOT_KLAUNCH(kern, dim3(grid), dim3(NW * 64), lds, st, p, y_pos, x_pos, f_y, src_s, dst_s, rowptr, E, out, part);
     else
         GAOT_KLAUNCH(kern, dim3(grid), dim3(NW * 64), lds, st, p, y_pos, x_pos, f_y, src_s, dst_s, rowptr, E, out, part, NlFwd{ttab});
@@ -294,13 +324,22 @@ int launch_fwd_b(const MlpPtrs& p, const float* y_pos, const float* x_pos, const
 
 }  // namespace
 
-// called from gaot_gno_fwd / gaot_gno_fwd_nl (gno.hip) when precision == 1; num_edges > 0, shapes already validated
+// called from gaot_gno_fwd / gaot_gno_fwd_nl / gaot_gno_fwd_w (gno.hip) when precision == 1; num_edges > 0, shapes already validated;
+// edge_w: null, or the [num_edges] weights of the weighted variant
 int gaot_gno_fwd_bf16_dispatch(int n_hidden, int mode, const float* const* w, const float* const* b, const float* y_pos,
                                const float* x_pos, const float* f_y, const float* ttab, const int32_t* src_sorted,
                                const int32_t* dst_sorted, const int32_t* rowptr_dst, int64_t num_edges, float* out, float* part,
-                               hipStream_t st) {
+                               const float* edge_w, hipStream_t st) {
     MlpPtrs p;
     for (int l = 0; l <= n_hidden; ++l) { p.w[l] = w[l]; p.b[l] = b[l]; }
+#define GNO_FWDB_CASE(NH_, MODE_) \
+    case NH_ * 3 + MODE_: return launch_fwd_b<NH_, MODE_, true>(p, y_pos, x_pos, f_y, ttab, src_sorted, dst_sorted, rowptr_dst, num_edges, out, part, st, edge_w);
+#define GNO_FWDB_CASES(NH_) GNO_FWDB_CASE(NH_, MODE_LINEAR) GNO_FWDB_CASE(NH_, MODE_NONLINEAR) GNO_FWDB_CASE(NH_, MODE_KERNELONLY)
+    if (edge_w && n_hidden >= 1 && n_hidden <= 4 && mode >= 0 && mode <= 2) switch (n_hidden * 3 + mode) {
+        GNO_FWDB_CASES(1) GNO_FWDB_CASES(2) GNO_FWDB_CASES(3) GNO_FWDB_CASES(4)
+    }
+#undef GNO_FWDB_CASES
+#undef GNO_FWDB_CASE
 #define GNO_FWDB_CASE(NH_, MODE_) \
     case NH_ * 3 + MODE_: return launch_fwd_b<NH_, MODE_>(p, y_pos, x_pos, f_y, ttab, src_sorted, dst_sorted, rowptr_dst, num_edges, out, part, st);
 #define GNO_FWDB_CASES(NH_) GNO_FWDB_CASE(NH_, MODE_LINEAR) GNO_FWDB_CASE(NH_, MODE_NONLINEAR) GNO_FWDB_CASE(NH_, MODE_KERNELONLY)
@@ -320,7 +359,7 @@ int gaot_gno_bwd3_bf16_launch(int n_hidden, int mode, void* images, const float*
                               const float* y_pos, const float* x_pos, const float* f_y, const float* gs,
                               const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr_src,
                               int64_t num_edges, float* grad_f, float* part, float* wpart, float* gcoord, const float* ttab,
-                              float* dt, float* part_dt, int grid, hipStream_t st);
+                              float* dt, float* part_dt, const gno::WBwd* wb, int grid, hipStream_t st);
 
 // recompute and transposed data-gradient fragment images of the hidden layers (8 KB each) and of the last layer (4 KB each)
 size_t gaot_gno_bwd_bf16_image_bytes(int n_hidden) { return (size_t)(n_hidden - 1) * 2 * 8192 + 2 * 4096 + 256; }
@@ -331,7 +370,7 @@ int gaot_gno_bwd_bf16_dispatch(int n_hidden, int mode, const float* const* w, co
                                void* images, const float* y_pos, const float* x_pos, const float* f_y, const float* gs,
                                const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr_src,
                                int64_t num_edges, float* grad_f, float* part, float* wpart, float* gcoord, const float* ttab,
-                               float* dt, float* part_dt, int grid, hipStream_t st) {
+                               float* dt, float* part_dt, const gno::WBwd* wb, int grid, hipStream_t st) {
     return gaot_gno_bwd3_bf16_launch(n_hidden, mode, images, w0t, w, b, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src,
-                                     num_edges, grad_f, part, wpart, gcoord, ttab, dt, part_dt, grid, st);
+                                     num_edges, grad_f, part, wpart, gcoord, ttab, dt, part_dt, wb, grid, st);
 }

@@ -172,6 +172,10 @@ __global__ void k_prep_bwd3_images(MlpPtrs mlp, int nh, bf16_t* base) {
 // dz_0 over the edges of source s is formed in registers by a segmented scan along the 16 edge lanes (seg_scan_step): direct
 // stores for rows that end inside the tile, the tile-ordered partial buffer for the rest.  Kernel-only mode: dk = bf16(gs), no f
 // gather, grad_f is not written.
+// WEIGHTED (a WBwd begins the pack, gno_common.h): `gs` is grad_out itself.  The edge's dst-sorted position is fetched with its ids and
+// its weight with its coordinates, one tile ahead; after the last layer gv becomes alpha_e g, and dalpha_e = sum_c g_c k_c f_c -- the
+// lane's two channels, then the 16 lanes of the group's DPP row (row_ror 8, 4, 2, 1) -- is stored once per edge by the lane of
+// group e >> 2 whose edge it is.
 template <int NH, bool CG, int MODE, class... CoordOut>
 __global__ __launch_bounds__(512, 1) void k_gno_bwd3_bf16(
     const uint4* __restrict__ images, const float* __restrict__ w0t_g, MlpPtrs mlp, const float* __restrict__ y_pos,
@@ -179,6 +183,8 @@ __global__ __launch_bounds__(512, 1) void k_gno_bwd3_bf16(
     const int* __restrict__ src_s, const int* __restrict__ dst_s, const int* __restrict__ rowptr_src, int64_t E,
     float* __restrict__ grad_f, float* __restrict__ part, float* __restrict__ wpart, CoordOut... gcoord_) {
     constexpr int C = 32, H = 64;
+    constexpr bool W = pack_has<WBwd, CoordOut...>;
+    static_assert(!(W && CG), "no coordinate gradients in the weighted variant");
     using L = Lds3<NH>;
     using PL = ParamLayout3<NH>;
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -244,17 +250,21 @@ __global__ __launch_bounds__(512, 1) void k_gno_bwd3_bf16(
     bool v_nx = false;
     float bin_nx[2] = {0.f, 0.f};
     [[maybe_unused]] f32x4 t_nx[4];   // t[src] of the next tile: features 16 mb + 4 g .. + 3
+    [[maybe_unused]] int p_nx = 0;    // weighted: dst-sorted position of the next tile's edge, and its weight
+    [[maybe_unused]] float a_nx = 0.f;
     auto fetch_ids = [&](int64_t tb_) {
         const int64_t e = (tb_ + wave) * 16 + n;
         v_nx = tb_ < n_tiles && e < E;
         s_nx = v_nx ? src_s[e] : 0;
         q_nx = v_nx ? dst_s[e] : 0;
+        if constexpr (W) p_nx = v_nx ? first_arg(gcoord_...).s2d[e] : 0;
     };
     auto fetch_pos = [&]() {   // lane (edge n, group g): input rows g and 4 + g of [y(3), x(3), 1, 0]
         const float* ys = y_pos + (int64_t)s_nx * 3;
         const float* xq = x_pos + (int64_t)q_nx * 3;
         bin_nx[0] = g < 3 ? ys[g] : xq[0];
         bin_nx[1] = g < 2 ? xq[1 + g] : 0.f;
+        if constexpr (W) a_nx = v_nx ? first_arg(gcoord_...).alpha[p_nx] : 0.f;
         if constexpr (MODE != MODE_LINEAR) {
             const float* tr = last_arg(gcoord_...).t + (int64_t)s_nx * NLH + 4 * g;
 #pragma unroll
@@ -276,6 +286,8 @@ __global__ __launch_bounds__(512, 1) void k_gno_bwd3_bf16(
         }
         int idv, rbv = 0, rev = 0;   // per edge (lane n, all groups alike): source row or -1, and its [rb, re) edge range
         int s_raw, q_raw;            // endpoints as fetched (0 for edges past E)
+        [[maybe_unused]] const int wpos = p_nx;     // weighted: this lane's edge in the dst-sorted order, and its weight (past E: 0)
+        [[maybe_unused]] const float aw = a_nx;
         {
             const bool valid = v_nx;
             const int s = s_nx, q = q_nx;
@@ -398,6 +410,33 @@ __global__ __launch_bounds__(512, 1) void k_gno_bwd3_bf16(
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 if (4 * g + r >= nvalid) { gv[0][r] = 0.f; gv[1][r] = 0.f; }
+        }
+        if constexpr (W) {
+            const WBwd w = first_arg(gcoord_...);
+            const bool want = w.dalpha != nullptr;
+            float da[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float ar = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(4 * (4 * g + r), __builtin_bit_cast(int, aw)));
+                const float ga = gv[0][r], gb = gv[1][r];
+                da[r] = ga * kp[0][r] * fv[0][r] + gb * kp[1][r] * fv[1][r];
+                gv[0][r] = ar * ga;
+                gv[1][r] = ar * gb;
+            }
+            if (want) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float x = da[r];
+                    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x128, 0xf, 0xf, false));
+                    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x124, 0xf, 0xf, false));
+                    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x122, 0xf, 0xf, false));
+                    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x121, 0xf, 0xf, false));
+                    da[r] = x;
+                }
+                const int rr = n & 3;
+                const float v = rr == 0 ? da[0] : (rr == 1 ? da[1] : (rr == 2 ? da[2] : da[3]));
+                if ((n >> 2) == g && idv >= 0) w.dalpha[wpos] = v;
+            }
         }
         if constexpr (MODE != MODE_KERNELONLY) {
             // the rows of the tile are runs of equal source ids; a run ends where the edge is the last of its row or of the
@@ -635,14 +674,18 @@ __global__ __launch_bounds__(512, 1) void k_gno_bwd3_bf16(
     }
 }
 
-template <int NH, bool CG, int MODE>
+template <int NH, bool CG, int MODE, bool W = false>
 int launch_bwd3(const void* images, const float* w0t, const MlpPtrs& p, const float* y_pos, const float* x_pos,
                 const float* f_y, const float* gs, const int* src_s, const int* dst_s, const int* rowptr_src, int64_t E,
-                float* grad_f, float* part, float* wpart, float* gcoord, const NlBwd& nl, int grid, hipStream_t st) {
+                float* grad_f, float* part, float* wpart, float* gcoord, const NlBwd& nl, int grid, hipStream_t st,
+                const WBwd& wb = WBwd{nullptr, nullptr, nullptr}) {
     constexpr int lds = Lds3<NH>::total;
     static_assert(lds <= 160 * 1024, "LDS budget");
     auto kern = [] {
-        if constexpr (MODE == MODE_LINEAR) {
+        if constexpr (W) {
+            if constexpr (MODE == MODE_LINEAR) return k_gno_bwd3_bf16<NH, false, MODE, WBwd>;
+            else return k_gno_bwd3_bf16<NH, false, MODE, WBwd, NlBwd>;
+        } else if constexpr (MODE == MODE_LINEAR) {
             if constexpr (CG) return k_gno_bwd3_bf16<NH, true, MODE, float*>;
             else return k_gno_bwd3_bf16<NH, false, MODE>;
         } else {
@@ -659,7 +702,14 @@ int launch_bwd3(const void* images, const float* w0t, const MlpPtrs& p, const fl
         }
         attr_set = true;
     }
-    if constexpr (MODE == MODE_LINEAR) {
+    if constexpr (W) {
+        if constexpr (MODE == MODE_LINEAR)
+            GAOT_KLAUNCH(kern, dim3(grid), dim3(512), lds, st, (const uint4*)images, w0t, p, y_pos, x_pos, f_y, gs, src_s, dst_s,
+                         rowptr_src, E, grad_f, part, wpart, wb);
+        else
+            GAOT_KLAUNCH(kern, dim3(grid), dim3(512), lds, st, (const uint4*)images, w0t, p, y_pos, x_pos, f_y, gs, src_s, dst_s,
+                         rowptr_src, E, grad_f, part, wpart, wb, nl);
+    } else if constexpr (MODE == MODE_LINEAR) {
         if constexpr (CG)
             GAOT_KLAUNCH(kern, dim3(grid), dim3(512), lds, st, (const uint4*)images, w0t, p, y_pos, x_pos, f_y, gs, src_s, dst_s,
                          rowptr_src, E, grad_f, part, wpart, gcoord);
@@ -682,12 +732,13 @@ int launch_bwd3(const void* images, const float* w0t, const MlpPtrs& p, const fl
 // images: scratch of gaot_gno_bwd_bf16_image_bytes() (gno_bf16.hip); w0t = fp32 [6][64] transposed first-layer weight; part: two
 // 32-channel slots per 16-EDGE tile (k_segment_fixup<32, 4>); wpart: one flat parameter-gradient partial per workgroup;
 // gcoord: null, or [num_edges][6] coordinate gradients per edge (source-sorted order); mode != linear: ttab / dt [N_y][64] and
-// part_dt, two 64-float slots per 16-edge tile (k_segment_fixup<64, 4>)
+// part_dt, two 64-float slots per 16-edge tile (k_segment_fixup<64, 4>); wb: null, or the operands of the weighted variant (gs is
+// then grad_out itself, gcoord null)
 int gaot_gno_bwd3_bf16_launch(int n_hidden, int mode, void* images, const float* w0t, const float* const* w, const float* const* b,
                               const float* y_pos, const float* x_pos, const float* f_y, const float* gs,
                               const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr_src,
                               int64_t num_edges, float* grad_f, float* part, float* wpart, float* gcoord, const float* ttab,
-                              float* dt, float* part_dt, int grid, hipStream_t st) {
+                              float* dt, float* part_dt, const gno::WBwd* wb, int grid, hipStream_t st) {
     if (n_hidden < 1 || n_hidden > 4 || mode < 0 || mode > 2) {      // before anything indexes w / b / MlpPtrs with it
         gaot_set_error("gaot_gno_bwd (bf16): unsupported n_hidden %d / mode %d", n_hidden, mode);
         return GAOT_ERR_UNSUPPORTED;
@@ -696,6 +747,19 @@ int gaot_gno_bwd3_bf16_launch(int n_hidden, int mode, void* images, const float*
     for (int l = 0; l <= n_hidden; ++l) { p.w[l] = w[l]; p.b[l] = b[l]; }
     GAOT_KLAUNCH(k_prep_bwd3_images, dim3(32), dim3(256), 0, st, p, n_hidden, (bf16_t*)images);
     const NlBwd nl{ttab, dt, part_dt};
+    if (wb) {
+#define GNO_BWD3W_CASE(NH_, MODE_)                                                                                          \
+    case NH_ * 3 + MODE_:                                                                                                   \
+        return launch_bwd3<NH_, false, MODE_, true>(images, w0t, p, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src, \
+                                                    num_edges, grad_f, part, wpart, nullptr, nl, grid, st, *wb);
+#define GNO_BWD3W_CASES(NH_) GNO_BWD3W_CASE(NH_, MODE_LINEAR) GNO_BWD3W_CASE(NH_, MODE_NONLINEAR) GNO_BWD3W_CASE(NH_, MODE_KERNELONLY)
+        switch (n_hidden * 3 + mode) {
+            GNO_BWD3W_CASES(1) GNO_BWD3W_CASES(2) GNO_BWD3W_CASES(3) GNO_BWD3W_CASES(4)
+        }
+#undef GNO_BWD3W_CASES
+#undef GNO_BWD3W_CASE
+        return GAOT_ERR_UNSUPPORTED;
+    }
 #define GNO_BWD3_CASE(NH_, CG_, MODE_)                                                                                      \
     case (NH_ * 2 + CG_) * 3 + MODE_:                                                                                       \
         return launch_bwd3<NH_, CG_ != 0, MODE_>(images, w0t, p, y_pos, x_pos, f_y, gs, src_sorted, dst_sorted, rowptr_src,   \

@@ -1,6 +1,8 @@
 // Pieces shared by the fp32 (gno.hip) and bf16 (gno_bf16.hip) GNO kernels: the per-lane segmented walk over a
 // 32-edge LDS tile, the tile-ordered fix-up of rows that straddle tiles, small structs.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace gno {
@@ -37,6 +39,24 @@ struct NlBwd {
     float* dt;              // [N_y][64]
     float* part_dt;         // two 64-float slots per tile: rows of dt that straddle tiles (k_segment_fixup<64, ..>)
 };
+
+// WEIGHTED variant (the attention-weighted transform, use_attn): out_q = sum_{e -> q} alpha_e k_e * f_y[s_e] with an fp32 weight per
+// edge instead of the mean's 1/deg.  Every per-edge scalar at the ABI is in the DST-sorted edge order: the forward, which walks that
+// list, reads alpha at its own edge index; the backward, which walks the source-sorted list, reads alpha and writes
+//   dalpha_e = sum_c grad_out[q_e][c] k_e[c] f_y[s_e][c]        (kernel-only mode: without f; the UNWEIGHTED grad_out)
+// through the src -> dst position map, each edge exactly once.  The operands ride in the same parameter packs: WFwd LAST in the
+// forward's pack, WBwd FIRST in the backward's (before the NlBwd of the nonlinear modes; never together with a coordinate output),
+// so first_arg / last_arg keep finding what they found and the unweighted instantiations keep their arguments and instructions.
+struct WFwd {
+    const float* alpha;     // [E], dst-sorted
+};
+struct WBwd {
+    const float* alpha;     // [E], dst-sorted
+    const int* s2d;         // [E]: position in the source-sorted order -> position in the dst-sorted order
+    float* dalpha;          // [E], dst-sorted; null: not wanted
+};
+template <class T, class... P>
+constexpr bool pack_has = (std::is_same_v<T, P> || ...);
 
 __device__ __forceinline__ void wave_lds_fence() {
     // LDS ops of one wave execute in order; this only stops the compiler from reordering.

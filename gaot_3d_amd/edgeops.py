@@ -2,7 +2,8 @@
 kernels do not cover -- IntegralTransform ``transform_type`` "nonlinear" / "nonlinear_kernelonly", segment-softmax
 attention weights (reference src/model/layers/integral_transform.py:68-78, 126-171; the dot-product scores are ``EdgeBilinearFn``
 over csrc/gno_attn.hip: no per-edge projection rows), kernel MLPs of other shapes, PointNet GeometricEmbedding
-(src/model/layers/geoembed.py:184-222).
+(src/model/layers/geoembed.py:184-222).  The per-edge SCALARS of the attention-weighted transform -- the scores, ``SegmentSoftmaxFn``
+and the maps between the two edge orders -- also serve the fused weighted kernels (functional.GnoWFn).
 
 All per-edge tensors are in the dst-sorted edge order of ``ops.build_graph`` (``g.by_dst``): ``src = g.by_dst.other``,
 ``dst = g.by_dst.key``; a query's edges are the contiguous rows ``rowptr[q] : rowptr[q+1]``.  The per-edge MLP runs

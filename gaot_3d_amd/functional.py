@@ -383,6 +383,47 @@ class GnoNlFn(Function):
                 gx if need[4] else None, None, *grads)
 
 
+class GnoWFn(Function):
+    """Fused WEIGHTED IntegralTransform (use_attn: out_q = sum_e edge_w[e] k_e f_y[s_e], rows summed), one 32-channel pass, for
+    ``mode`` 'linear' (``t`` None), 'nonlinear' or 'nonlinear_kernelonly' (``f_y`` None); ``t`` and ``params`` as in ``GnoNlFn``.
+    ``edge_w`` [E] is in the dst-sorted edge order.  Returns the gradients of f_y, t, edge_w (asked of the kernel only when autograd
+    wants it) and the parameters; none with respect to the coordinates."""
+
+    @staticmethod
+    def forward(ctx, mode: str, f_y: Optional[Tensor], t: Optional[Tensor], edge_w: Tensor, y_pos: Tensor, x_pos: Tensor, graph,
+                *params):
+        nl = len(params) // 2
+        ws = [_w2d(p) for p in params[0::2]]
+        bs = list(params[1::2])
+        f = f_y if (f_y is None or f_y.is_contiguous()) else f_y.contiguous()
+        tc = t if (t is None or t.is_contiguous()) else t.contiguous()
+        ew = edge_w if edge_w.is_contiguous() else edge_w.contiguous()
+        out = ops.gno_w_forward(mode, ws, bs, y_pos, x_pos, f, tc, ew, graph)
+        ctx.graph, ctx.nl, ctx.mode, ctx.has_f, ctx.has_t = graph, nl, mode, f is not None, tc is not None
+        ctx.wshapes = [p.shape for p in params[0::2]]
+        ctx.save_for_backward(*([f] if f is not None else []), *([tc] if tc is not None else []), ew, y_pos, x_pos, *ws, *bs)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout: Tensor):
+        saved = list(ctx.saved_tensors)
+        f = saved.pop(0) if ctx.has_f else None
+        tc = saved.pop(0) if ctx.has_t else None
+        ew, y_pos, x_pos = saved[:3]
+        ws = list(saved[3:3 + ctx.nl])
+        bs = list(saved[3 + ctx.nl:])
+        d = dout if dout.is_contiguous() else dout.contiguous()
+        need = ctx.needs_input_grad
+        if need[4] or need[5]:
+            raise NotImplementedError("GnoWFn: no gradients with respect to the coordinates in the weighted transform")
+        gf, gt, gw, gb, gew = ops.gno_w_backward(ctx.mode, ws, bs, y_pos, x_pos, f, tc, ew, d, ctx.graph, want_grad_w=need[3])
+        grads: List[Optional[Tensor]] = []
+        for l in range(ctx.nl):
+            grads += [gw[l].view(ctx.wshapes[l]) if need[7 + 2 * l] else None, gb[l] if need[8 + 2 * l] else None]
+        return (None, gf if (ctx.has_f and need[1]) else None, gt if (ctx.has_t and need[2]) else None, gew if need[3] else None,
+                None, None, None, *grads)
+
+
 def _want_bf16_copy(x: Tensor) -> bool:
     return ops.get_precision() == "bf16" and x.is_cuda and x.shape[-1] % 8 == 0
 

@@ -7,11 +7,16 @@ transform_type='nonlinear' and 'nonlinear_kernelonly' (kernel MLP 6 + C_in -> 64
 first layer act on the SOURCE node only, so t = W_0f f_y is one per-node product ([N_y, 64], fp32) and the kernels start every
 edge's first-layer accumulator from b_0 + t[src]; the backward returns dt[s] = sum of dz_0 over the edges of s, from which
 dW_0f = dt^T f_y and grad f_y += dt W_0f follow as per-node products (the autograd of the linear that formed t).
-Every other variant the reference offers (use_attn cosine / dot_product, other MLP shapes, f_y=None)
+use_attn=True (cosine / dot_product edge scores, softmax per query, weighted SUM) runs the same kernels in their WEIGHTED
+instantiation (``_fused_attn_plan``, ``functional.GnoWFn``): out_q = sum_e alpha_e k_e f_y[s_e] with alpha [E] one fp32 scalar per
+edge in the dst-sorted order (``_attn_weights``); the backward returns d alpha_e = sum_c g_c k_e,c f_y[s_e]_c beside the gradients
+of f_y, t and the parameters, and autograd carries it through the softmax into the scores.  The dot-product scores are a bilinear
+form of the endpoints' homogeneous coordinates (``attn_bilinear_form``, csrc/gno_attn.hip): a scalar per edge, no gathered [E, 64]
+projection rows.  Coordinates that require grad are refused with use_attn.
+Every other variant the reference offers (other MLP shapes, MLP dropout in training, f_y=None)
 runs the general path: per-edge tensors in dst-sorted order, the MLP on the GEMM kernels, gather / segment /
-element-wise glue and its autograd in csrc/edgeops.hip (gaot_3d_amd/edgeops.py).  The dot-product attention scores are a
-bilinear form of the endpoints' homogeneous coordinates (``attn_bilinear_form``, csrc/gno_attn.hip): a scalar per edge, no
-gathered [E, 64] projection rows.  HIP only, no CPU fallback."""
+element-wise glue and its autograd in csrc/edgeops.hip (gaot_3d_amd/edgeops.py), with the same ``_attn_weights`` under use_attn.
+HIP only, no CPU fallback."""
 from typing import Optional
 
 import torch
@@ -129,7 +134,18 @@ class IntegralTransform(nn.Module):
         plan = self._fused_plan(fcs, f_y, y_pos, x_pos)
         if plan is not None:
             return self._forward_fused(fcs, y_pos, x_pos, f_y, graph, *plan)
+        if self.use_attn:
+            plan = self._fused_attn_plan(fcs, f_y, y_pos, x_pos)
+            if plan is not None:
+                y3, x3 = self._pad3(y_pos), self._pad3(x_pos)
+                return self._forward_fused(fcs, y_pos, x_pos, f_y, graph, *plan,
+                                           edge_w=self._attn_weights(y_pos, x_pos, y3, x3, graph))
         return self._forward_general(fcs, y_pos, x_pos, f_y, graph)
+
+    @staticmethod
+    def _pad3(pos):
+        """coordinates of dimension 1 / 2 padded with zeros to the kernels' 3-D rows"""
+        return pos if pos.shape[1] >= 3 else torch.nn.functional.pad(pos, (0, 3 - pos.shape[1]))
 
     def _fused_plan(self, fcs, f_y, y_pos, x_pos=None):
         """(coord_dim, channels) when the fused kernels (csrc/gno*.hip: coordinates of dimension 3, hidden width 64, 32
@@ -142,13 +158,36 @@ class IntegralTransform(nn.Module):
           * C != 32 (the reference's default is 16, magno.py:25): the last layer / f_y / the output are cut into blocks of 32
             channels (the last one zero-padded); every block is one pass of the 32-channel kernels, so C = 16 costs what
             C = 32 costs and C = 64 two passes (the hidden layers are recomputed), still without a per-edge tensor in HBM."""
-        if self.use_attn or self.transform_type not in ("linear", "nonlinear", "nonlinear_kernelonly") or f_y is None:
+        if self.use_attn:
+            return None
+        return self._fused_shape_plan(fcs, f_y, y_pos, x_pos)
+
+    def _fused_attn_plan(self, fcs, f_y, y_pos, x_pos=None):
+        """``_fused_plan`` for use_attn=True: the same shape rules (``_fused_shape_plan``) decide whether the WEIGHTED instantiations of
+        the fused kernels (``functional.GnoWFn``: a softmax weight per edge, rows summed) evaluate this transform; None -> general
+        path.  The scores' own parameters (query_proj / key_proj) count among the tensors that may need a gradient."""
+        if not self.use_attn or self.attention_type not in ("cosine", "dot_product"):
+            return None
+        cdp = y_pos.shape[1]
+        cd = int(self.coord_dim) if self.coord_dim is not None else cdp
+        if not (1 <= cd <= min(3, cdp)) or (x_pos is not None and x_pos.shape[1] != cdp):
+            return None                                   # the general path raises for these
+        also = []
+        if self.attention_type == "dot_product":
+            also = list(self.query_proj.parameters()) + list(self.key_proj.parameters())
+        return self._fused_shape_plan(fcs, f_y, y_pos, x_pos, also)
+
+    def _fused_shape_plan(self, fcs, f_y, y_pos, x_pos=None, also=()):
+        """the shape rules shared by ``_fused_plan`` and ``_fused_attn_plan`` (see ``_fused_plan``); ``also``: further tensors whose
+        ``requires_grad`` makes the transform need its backward"""
+        if self.transform_type not in ("linear", "nonlinear", "nonlinear_kernelonly") or f_y is None:
             return None
         cin = 0 if self.transform_type == "linear" else f_y.shape[1]      # feature columns of the first layer
         # the exact-fp32 backward keeps the hidden activations of 128 edges in LDS: three hidden layers at most when gradients
         # are needed in fp32 mode; the bf16 backward takes four (its operand fragments then come from L2, gno_bwd3_bf16.hip)
         need_grad = torch.is_grad_enabled() and (f_y.requires_grad or any(fc.weight.requires_grad for fc in fcs)
-                                                 or y_pos.requires_grad or (x_pos is not None and x_pos.requires_grad))
+                                                 or y_pos.requires_grad or (x_pos is not None and x_pos.requires_grad)
+                                                 or any(p.requires_grad for p in also))
         from ... import ops as _ops
         max_fcs = 4 if (need_grad and _ops.get_precision() != "bf16") else 5
         if activation_name(getattr(self.channel_mlp, "non_linearity", "gelu")) != "gelu" or not (2 <= len(fcs) <= max_fcs):
@@ -173,11 +212,13 @@ class IntegralTransform(nn.Module):
         return (not self.use_attn and self.transform_type == "linear" and f_y is not None and dims[0] == (64, 6)
                 and dims[-1] == (32, 64) and f_y.shape[1] == 32)
 
-    def _forward_fused(self, fcs, y_pos, x_pos, f_y, graph, cd: int, c: int):
+    def _forward_fused(self, fcs, y_pos, x_pos, f_y, graph, cd: int, c: int, edge_w=None):
+        """``edge_w`` [E] (dst-sorted order): the weighted transform of use_attn -- every pass runs ``GnoWFn`` with the same weights and
+        autograd adds the passes' gradients with respect to them (padded channels carry zero grad_out and zero f: exact zeros)"""
         w2 = lambda fc: fc.weight[:, :, 0] if fc.weight.dim() == 3 else fc.weight    # Conv1d(k=1) storage of mlp_type='channel'
         pad_hidden = any(fc.weight.shape[0] != 64 for fc in fcs[:-1])
         tt = self.transform_type
-        if tt == "linear" and cd == 3 and c == 32 and not pad_hidden:                 # the shipped shape: straight through
+        if tt == "linear" and cd == 3 and c == 32 and not pad_hidden and edge_w is None:   # the shipped shape: straight through
             params = []
             for fc in fcs:
                 params += [fc.weight, fc.bias]
@@ -218,7 +259,10 @@ class IntegralTransform(nn.Module):
                 wb = torch.nn.functional.pad(wb, (0, 0, 0, 32 - n))
                 bb = torch.nn.functional.pad(bb, (0, 32 - n))
                 fb = None if fb is None else torch.nn.functional.pad(fb, (0, 32 - n))
-            if tt == "linear":
+            if edge_w is not None:
+                o = GF.GnoWFn.apply(tt, None if fb is None else fb.contiguous(), t, edge_w, y3, x3, graph, w0.contiguous(), b0, *mid,
+                                    wb.contiguous(), bb.contiguous())
+            elif tt == "linear":
                 o = GF.GnoFn.apply(fb.contiguous(), y3, x3, graph, w0, b0, *mid, wb.contiguous(), bb.contiguous())
             else:
                 o = GF.GnoNlFn.apply(tt, None if fb is None else fb.contiguous(), t, y3, x3, graph, w0.contiguous(), b0, *mid,
@@ -253,22 +297,29 @@ class IntegralTransform(nn.Module):
             k = EO.MulFn.apply(k, EO.GatherFn.apply(f_y, g, 0))
         mode = EO.MEAN
         if self.use_attn:                                                                                   # :126-142
-            # the scores see the first coord_dim coordinates only (integral_transform.py:128-129: `[:, :self.coord_dim]`)
-            cd = int(self.coord_dim) if self.coord_dim is not None else cdp
-            if not 1 <= cd <= min(3, cdp):
-                raise ValueError(f"coord_dim {cd} with {cdp}-dimensional coordinates")
-            xa, ya = x3, y3
-            if cd < cdp:             # drop the coordinates the scores do not see, keep the kernels' 3-D rows
-                xa = torch.nn.functional.pad(x_pos[:, :cd], (0, 3 - cd))
-                ya = torch.nn.functional.pad(y_pos[:, :cd], (0, 3 - cd))
-            if self.attention_type == "dot_product":
-                # (W_q x + b_q) . (W_k y + b_k) / 8 as scale * [x, 1]^T M [y, 1] with the 4 x 4 M = [W_q | b_q]^T [W_k | b_k]: one scalar
-                # per edge from the two 12-byte coordinate rows instead of two gathered [E, 64] rows kept for the backward; the
-                # gradient comes back as dM (16 numbers, fixed summation order) and autograd carries it into the projections
-                m = attn_bilinear_form(self.query_proj.weight, self.query_proj.bias, self.key_proj.weight, self.key_proj.bias)
-                sc = EO.EdgeBilinearFn.apply(xa.contiguous(), ya.contiguous(), g, m, self.scaling_factor)
-            else:
-                sc = EO.edge_coords(ya.contiguous(), xa.contiguous(), g, 2)   # cosine of the raw coordinates: no parameters
-            k = EO.RowScaleFn.apply(k, EO.SegmentSoftmaxFn.apply(sc, g))                                    # :159-160
+            k = EO.RowScaleFn.apply(k, self._attn_weights(y_pos, x_pos, y3, x3, g))                         # :159-160
             mode = EO.SUM                                                                                   # :163
         return EO.SegmentReduceFn.apply(k, g, mode)
+
+    def _attn_weights(self, y_pos, x_pos, y3, x3, g):
+        """alpha [E] in the dst-sorted edge order: the edge scores (cosine or dot product of the endpoints' first coord_dim
+        coordinates, integral_transform.py:126-137) under the softmax over every query's edges (:139-142).  ``y3`` / ``x3``: the
+        coordinates as the kernels' 3-D rows.  Shared by the fused weighted path and the general path."""
+        cdp = y_pos.shape[1]
+        # the scores see the first coord_dim coordinates only (integral_transform.py:128-129: `[:, :self.coord_dim]`)
+        cd = int(self.coord_dim) if self.coord_dim is not None else cdp
+        if not 1 <= cd <= min(3, cdp):
+            raise ValueError(f"coord_dim {cd} with {cdp}-dimensional coordinates")
+        xa, ya = x3, y3
+        if cd < cdp:             # drop the coordinates the scores do not see, keep the kernels' 3-D rows
+            xa = torch.nn.functional.pad(x_pos[:, :cd], (0, 3 - cd))
+            ya = torch.nn.functional.pad(y_pos[:, :cd], (0, 3 - cd))
+        if self.attention_type == "dot_product":
+            # (W_q x + b_q) . (W_k y + b_k) / 8 as scale * [x, 1]^T M [y, 1] with the 4 x 4 M = [W_q | b_q]^T [W_k | b_k]: one scalar
+            # per edge from the two 12-byte coordinate rows instead of two gathered [E, 64] rows kept for the backward; the
+            # gradient comes back as dM (16 numbers, fixed summation order) and autograd carries it into the projections
+            m = attn_bilinear_form(self.query_proj.weight, self.query_proj.bias, self.key_proj.weight, self.key_proj.bias)
+            sc = EO.EdgeBilinearFn.apply(xa.contiguous(), ya.contiguous(), g, m, self.scaling_factor)
+        else:
+            sc = EO.edge_coords(ya.contiguous(), xa.contiguous(), g, 2)   # cosine of the raw coordinates: no parameters
+        return EO.SegmentSoftmaxFn.apply(sc, g)

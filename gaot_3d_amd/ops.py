@@ -317,6 +317,84 @@ def gno_nl_backward(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Op
     return grad_f, grad_t, gw, gb
 
 
+GNO_W_MODES = {"linear": 0, "nonlinear": 1, "nonlinear_kernelonly": 2}      # csrc/gno_common.h MODE_*
+
+
+def _gno_w_args(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], src_table: Optional[Tensor],
+                edge_w: Tensor, g: BipartiteGraph):
+    """shape checks of the weighted transform: those of ``_gno_nl_args`` (mode 0: no src_table), and edge_w [E] fp32"""
+    md = GNO_W_MODES.get(mode, mode)
+    if md not in (0, 1, 2):
+        raise GaotError(f"gno (weighted): mode must be one of {tuple(GNO_W_MODES)}, got {mode!r}")
+    if md == 0:
+        m, keep = _mlp_struct(weights, biases)
+        y_pos = _req(y_pos, torch.float32, "y_pos")
+        x_pos = _req(x_pos, torch.float32, "x_pos")
+        if y_pos.shape[0] != g.num_src or x_pos.shape[0] != g.num_dst:
+            raise GaotError(f"y_pos / x_pos have {y_pos.shape[0]} / {x_pos.shape[0]} rows, the graph {g.num_src} / {g.num_dst}")
+        f_y = _req(f_y, torch.float32, "f_y")
+        if tuple(f_y.shape) != (g.num_src, m.channels):
+            raise GaotError(f"f_y must be [{g.num_src}, {m.channels}], got {tuple(f_y.shape)}")
+        src_table = None
+    else:
+        md, m, keep, y_pos, x_pos, f_y, src_table = _gno_nl_args(md, weights, biases, y_pos, x_pos, f_y, src_table, g)
+    edge_w = _req(edge_w, torch.float32, "edge_w")
+    if tuple(edge_w.shape) != (g.by_dst.num_edges,):
+        raise GaotError(f"edge_w must be [{g.by_dst.num_edges}] (one weight per edge, dst-sorted order), got {tuple(edge_w.shape)}")
+    return md, m, keep, y_pos, x_pos, f_y, src_table, edge_w
+
+
+def gno_w_forward(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], src_table: Optional[Tensor],
+                  edge_w: Tensor, g: BipartiteGraph, precision: Optional[int] = None) -> Tensor:
+    """the fused WEIGHTED transform out_q = sum_{e -> q} edge_w[e] k_e f_y[s_e] (use_attn: a weight per edge in the dst-sorted
+    order, rows summed) for ``mode`` 'linear' (src_table None), 'nonlinear' or 'nonlinear_kernelonly' (f_y None); the other
+    operands as in ``gno_forward`` / ``gno_nl_forward``"""
+    lib = _lib.load()
+    prec = _PRECISION["mode"] if precision is None else precision
+    md, m, keep, y_pos, x_pos, f_y, src_table, edge_w = _gno_w_args(mode, weights, biases, y_pos, x_pos, f_y, src_table, edge_w, g)
+    q, e = g.num_dst, g.by_dst.num_edges
+    out = torch.empty(q, m.channels, dtype=torch.float32, device=x_pos.device)
+    ws = _ws(lib.gaot_gno_fwd_workspace_bytes(e, m.channels), x_pos.device)
+    with _timed(f"gno_fwd_w{md}_nh{m.n_hidden}"):
+        check(lib.gaot_gno_fwd_w(C.byref(m), md, _ptr(y_pos), _ptr(x_pos), _ptr(f_y), _ptr(src_table), _ptr(edge_w),
+                                 _ptr(g.by_dst.other), _ptr(g.by_dst.key), _ptr(g.by_dst.rowptr), e, q, _ptr(out), prec, _ptr(ws),
+                                 ws.numel(), _stream()), "gaot_gno_fwd_w")
+    return out
+
+
+def gno_w_backward(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], src_table: Optional[Tensor],
+                   edge_w: Tensor, grad_out: Tensor, g: BipartiteGraph, precision: Optional[int] = None, want_grad_w: bool = True):
+    """-> (grad_f_y, grad_src_table, [grad_w...], [grad_b...], grad_edge_w): as ``gno_nl_backward`` (grad_src_table None for
+    'linear', grad_f_y None for 'nonlinear_kernelonly'), and grad_edge_w[e] = sum_c grad_out[q_e, c] k_e[c] f_y[s_e, c] in the
+    dst-sorted order (None unless ``want_grad_w``: the kernel then skips its reduction over the channels)"""
+    lib = _lib.load()
+    prec = _PRECISION["mode"] if precision is None else precision
+    md, m, keep, y_pos, x_pos, f_y, src_table, edge_w = _gno_w_args(mode, weights, biases, y_pos, x_pos, f_y, src_table, edge_w, g)
+    grad_out = _req(grad_out, torch.float32, "grad_out")
+    if tuple(grad_out.shape) != (g.num_dst, m.channels):
+        raise GaotError(f"grad_out must be [{g.num_dst}, {m.channels}], got {tuple(grad_out.shape)}")
+    from . import edgeops as EO
+    e = g.by_src.num_edges
+    dev = x_pos.device
+    grad_f = torch.empty(g.num_src, m.channels, dtype=torch.float32, device=dev) if md != 2 else None
+    grad_t = torch.empty(g.num_src, 64, dtype=torch.float32, device=dev) if md != 0 else None
+    grad_ew = torch.empty(e, dtype=torch.float32, device=dev) if want_grad_w else None
+    gw = [torch.empty(tuple(w.shape[:2]), dtype=torch.float32, device=dev) for w in weights]
+    gb = [torch.empty(tuple(b.shape), dtype=torch.float32, device=dev) for b in biases]
+    gs = MlpGradT()
+    for l in range(len(weights)):
+        gs.weight[l] = gw[l].data_ptr()
+        gs.bias[l] = gb[l].data_ptr()
+    s2d = EO.src_to_dst_map(g)
+    ws = _ws(lib.gaot_gno_bwd_w_workspace_bytes(C.byref(m), e, g.num_dst), dev)
+    with _timed(f"gno_bwd_w{md}_nh{m.n_hidden}"):
+        check(lib.gaot_gno_bwd_w(C.byref(m), md, _ptr(y_pos), _ptr(x_pos), _ptr(f_y), _ptr(src_table), _ptr(grad_out), _ptr(edge_w),
+                                 _ptr(s2d), _ptr(g.by_src.key), _ptr(g.by_src.other), _ptr(g.by_src.rowptr), e, g.num_src,
+                                 g.num_dst, _ptr(grad_f), _ptr(grad_t), C.byref(gs), _ptr(grad_ew), prec, _ptr(ws), ws.numel(),
+                                 _stream()), "gaot_gno_bwd_w")
+    return grad_f, grad_t, gw, gb, grad_ew
+
+
 EDGE_BILINEAR_WS_BYTES = 65536      # include/gaot3d_hip.h GAOT_EDGE_BILINEAR_WS_BYTES
 
 

@@ -120,6 +120,29 @@ int gaot_gno_bwd_nl(const gaot_mlp_t* mlp /* host */, int mode, const float* y_p
                     float* grad_edge_coords /* [num_edges, 6] or null */, int precision, void* workspace, size_t workspace_bytes,
                     gaot_stream_t stream);
 
+/* The WEIGHTED transform (reference integral_transform.py:126-142, 159-163: use_attn -- a softmax weight per edge, summed rows):
+ *   out_q = sum_{e -> q} edge_w[e] * k_e * f_y[src_e]          (mode 2: without f_y)
+ * for mode 0 (linear: src_table null), 1 (nonlinear) and 2 (nonlinear_kernelonly) of the entries above, on the same kernels in
+ * their weighted instantiations.  edge_w is [num_edges] fp32 in the DST-sorted edge order (the order of the forward's lists), any
+ * sign; it is applied in fp32 after the kernel MLP's last layer in both precisions.  Workspace of the forward:
+ * gaot_gno_fwd_workspace_bytes.
+ * Backward: the lists are SOURCE-sorted as in gaot_gno_bwd; src2dst[e] is the position of source-sorted edge e in the dst-sorted
+ * order, through which the kernel reads edge_w and writes grad_edge_w, so that both stay dst-sorted:
+ *   grad_edge_w[e] = sum_c grad_out[dst_e][c] * k_e[c] * f_y[src_e][c]     (mode 2: without f_y; every edge written exactly once)
+ * grad_edge_w may be null (not wanted).  grad_f_y / grad_src_table / grads as in gaot_gno_bwd_nl (mode 0: grad_src_table unused,
+ * may be null).  No coordinate gradients.  fp32 mode: 1-3 hidden layers, bf16 mode: 1-4.  Fixed summation orders, no atomics. */
+int gaot_gno_fwd_w(const gaot_mlp_t* mlp /* host */, int mode, const float* y_pos, const float* x_pos, const float* f_y,
+                   const float* src_table, const float* edge_w, const int32_t* src_sorted, const int32_t* dst_sorted,
+                   const int32_t* rowptr_dst, int64_t num_edges, int64_t num_queries, float* out, int precision, void* workspace,
+                   size_t workspace_bytes, gaot_stream_t stream);
+size_t gaot_gno_bwd_w_workspace_bytes(const gaot_mlp_t* mlp /* host */, int64_t num_edges, int64_t num_queries);
+int gaot_gno_bwd_w(const gaot_mlp_t* mlp /* host */, int mode, const float* y_pos, const float* x_pos, const float* f_y,
+                   const float* src_table, const float* grad_out, const float* edge_w, const int32_t* src2dst,
+                   const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr_src, int64_t num_edges,
+                   int64_t num_sources, int64_t num_queries, float* grad_f_y, float* grad_src_table,
+                   const gaot_mlp_grad_t* grads /* host */, float* grad_edge_w /* [num_edges] or null */, int precision,
+                   void* workspace, size_t workspace_bytes, gaot_stream_t stream);
+
 /* Dot-product attention scores of the attention-weighted transform (reference integral_transform.py:128-137, use_attn with
  * attention_type "dot_product") as a bilinear form of the homogeneous endpoint coordinates (csrc/gno_attn.hip):
  *   scores[e] = scale * [x_pos[dst[e]], 1]^T M [y_pos[src[e]], 1]        x_pos / y_pos: [*, 3] rows, m: DEVICE [4][4] fp32

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
-"""Kernel microbenchmarks at the configs[1] shapes (for rocprofv3 / quick A-B): attention fwd+bwd, GEMM shapes, GNO, PointNet GeoEmbed."""
+"""Kernel microbenchmarks at the configs[1] shapes (for rocprofv3 / quick A-B): attention fwd+bwd, GEMM shapes, GNO, PointNet GeoEmbed,
+the attention-weighted GNO."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+if os.environ.get("MB_TREE"):      # measure another checkout's package (gno_weighted: the parent commit's) with this script
+    sys.path.insert(0, os.environ["MB_TREE"])
 import torch
 import gaot_3d_amd
 from gaot_3d_amd import ops, functional as GF
@@ -351,3 +354,86 @@ elif what == "attn_headdim":
             if name.startswith("attn_hd"):
                 print(f"  D={d} {name}: {tot / calls:.4f} ms")
     ops.timing_reset(False)
+elif what == "gno_weighted":
+    # IntegralTransform with use_attn=True on the two configs[1] graphs (500K points, 64x64x32 tokens, knn k=8: E = 4 M; encoder
+    # direction NH = 3, decoder direction NH = 2): forward + backward of the module, {cosine, dot_product} x three transform types x
+    # {fp32, bf16}, graph and maps built before timing, HIP events, one warm-up, median of `reps`.  Legs: (a) this tree (the weighted
+    # fused kernels), (b) the checkout named by MB_PARENT -- its use_attn module (the general per-edge path) and its UNWEIGHTED fused
+    # transform of the same type.  MB_ROUNDS (default 5) rounds alternate one fresh child process per leg; a row is the median over
+    # the rounds, the spread (max - min) / median over the rounds.  Output kept in profiles/gno_weighted_microbench.txt.
+    import json
+    import subprocess
+    if os.environ.get("MB_CHILD") != "1":
+        rounds = int(os.environ.get("MB_ROUNDS", 5))
+        trees = [("new", os.path.dirname(os.path.dirname(os.path.abspath(__file__))))]
+        if os.environ.get("MB_PARENT"):
+            trees.insert(0, ("parent", os.path.abspath(os.environ["MB_PARENT"])))
+        runs = {name: [] for name, _ in trees}
+        for r in range(rounds):
+            for name, tree in trees:
+                env = dict(os.environ, MB_CHILD="1", MB_TREE=tree)
+                env.pop("GAOT_LIB", None)
+                out = subprocess.run([sys.executable, os.path.abspath(__file__), "gno_weighted", str(reps)], env=env, check=True,
+                                     capture_output=True, text=True, timeout=600).stdout
+                runs[name].append(json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1]))
+                print(f"# round {r} {name}: done", flush=True)
+        med = lambda v: sorted(v)[len(v) // 2]
+        def row(name, key):
+            tot = [d[key][0] + d[key][1] for d in runs[name] if key in d]
+            if not tot:
+                return None
+            return med(tot), (max(tot) - min(tot)) / med(tot), med([d[key][0] for d in runs[name]]), med([d[key][1] for d in runs[name]]), \
+                max(d[key][2] for d in runs[name])
+        print(f"# fwd+bwd of IntegralTransform, ms: median over {rounds} alternated rounds of per-process medians of {reps}; spread = (max - min) / median over rounds")
+        for key in sorted(runs["new"][0]):
+            if not key.endswith("/attn"):
+                continue
+            n_ = row("new", key)
+            line = f"{key[:-5]:58s} fused weighted {n_[0]:8.3f} (fwd {n_[2]:.3f} bwd {n_[3]:.3f}, spread {100 * n_[1]:.1f} %, peak {n_[4] / 2**20:.0f} MiB)"
+            if "parent" in runs:
+                g_, u_ = row("parent", key), row("parent", "/".join(key.split("/")[:-2]) + "/plain")
+                line += (f" | parent general {g_[0]:8.3f} (spread {100 * g_[1]:.1f} %, peak {g_[4] / 2**20:.0f} MiB) = {g_[0] / n_[0]:.1f} x"
+                         f" | parent unweighted fused {u_[0]:8.3f} (spread {100 * u_[1]:.1f} %): weighted = {n_[0] / u_[0]:.2f} x")
+            print(line)
+        sys.exit(0)
+    from gaot_3d_amd.data import make_synthetic_sample
+    from gaot_3d_amd.model.layers.integral_transform import IntegralTransform
+    from gaot_3d_amd import edgeops as EO
+    batch, tokens = make_synthetic_sample(500000, (64, 64, 32), k=8, seed=0, device=dev)
+    n, m = 500000, tokens.shape[0]
+    tokens = tokens.to(dev)
+    res = {}
+
+    def measure(it, yp, xp, f, g, go):
+        def once():
+            for p in it.parameters():
+                p.grad = None
+            f.grad = None
+            e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+            e0.record(); out = it(yp, xp, None, f_y=f, graph=g); e1.record(); out.backward(go); e2.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1), e1.elapsed_time(e2)
+        once()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        ts = [once() for _ in range(reps)]
+        peak = torch.cuda.max_memory_allocated() - base
+        return sorted(t[0] for t in ts)[len(ts) // 2], sorted(t[1] for t in ts)[len(ts) // 2], peak
+
+    for side, nh, ei, ns, nd, yp, xp in (("enc", 3, batch.encoder_edge_index_s0, n, m, batch.pos, tokens),
+                                         ("dec", 2, batch.decoder_edge_index_s0, m, n, tokens, batch.pos)):
+        g = ops.build_graph(ei, ns, nd)
+        EO.src_to_dst_map(g); EO.dst_to_src_map(g)
+        f = torch.randn(ns, 32, device=dev).requires_grad_(); go = torch.randn(nd, 32, device=dev)
+        for prec in ("fp32", "bf16"):
+            gaot_3d_amd.set_precision(prec)
+            for tt in ("linear", "nonlinear", "nonlinear_kernelonly"):
+                layers = [6 + (0 if tt == "linear" else 32)] + [64] * nh + [32]
+                torch.manual_seed(1)
+                res[f"{side}_nh{nh}_E{ei.shape[1]}/{prec}/{tt}/plain"] = measure(
+                    IntegralTransform(channel_mlp_layers=layers, transform_type=tt).to(dev), yp, xp, f, g, go)
+                for at in ("cosine", "dot_product"):
+                    it = IntegralTransform(channel_mlp_layers=layers, transform_type=tt, use_attn=True, coord_dim=3, attention_type=at).to(dev)
+                    res[f"{side}_nh{nh}_E{ei.shape[1]}/{prec}/{tt}/{at}/attn"] = measure(it, yp, xp, f, g, go)
+                    del it
+    print(json.dumps(res))
