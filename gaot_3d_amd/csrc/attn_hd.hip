@@ -1,4 +1,4 @@
-// Flash attention for head sizes 64 and 128 in bf16 mode (reference GroupQueryFlashAttention.forward,
+// Flash attention for every head size dh with dh % 4 == 0, 4 <= dh <= 128 in bf16 mode (reference GroupQueryFlashAttention.forward,
 // src/model/layers/attn.py:110-127: head split, GQA repeat, F.scaled_dot_product_attention with no mask, scale
 // 1/sqrt(head_dim), dropout on the attention weights) and its autograd.  Never an S x S tensor: every buffer is O(S * D).
 //
@@ -20,6 +20,14 @@
 // row 16 s + 8 (j >> 2) + 4 h + (j & 3).
 // dQ has its own pass and dK / dV are summed inside one workgroup over heads and query tiles in a fixed order: no float
 // atomics, two runs on the same inputs are bit-identical.  FLOPs: forward 4, dK/dV 8, dQ 6 S^2 D per head -- 18 S^2 D.
+//
+// Head width and tile width: the true head width dh is a runtime value (addressing is head * dh, the scale 1 / sqrt(dh) comes from
+// the host); the tile width D in {32, 64, 96, 128} is a template parameter, the smallest instance >= dh.  dh == D runs the plain
+// instances (PAD = false).  dh < D runs the padded ones (PAD = true): heads are adjacent in memory, so every float4 of columns >=
+// dh is PREDICATED, never loaded and then zeroed -- an unpredicated load would read the neighbouring head's columns and, for the
+// last head of v in the last row, run past the allocation.  The staged LDS images and the register fragments then hold exact
+// zeros in the padding, so scores and delta are what the dh columns alone give, the accumulator rows >= dh stay zero, and the
+// stores skip them (the next head's columns are not touched).  dh % 4 == 0 keeps every access 16-byte aligned.
 #include "common.h"
 #include "attn_dropout.h"
 
@@ -36,6 +44,7 @@ struct HdArgs {
     int B, S, H, HKV;
     float scale;
     gdrop::Drop drop;
+    int dh;                                     // true head width (<= the tile width D of the instance)
 };
 
 struct HdBwdArgs {
@@ -46,6 +55,7 @@ struct HdBwdArgs {
     int B, S, H, HKV;
     float scale;
     gdrop::Drop drop;
+    int dh;
 };
 
 __device__ __forceinline__ short f2bf(float f) {  // round-to-nearest-even
@@ -69,13 +79,18 @@ template <int D>
 struct Tile {
     float4 v[D / 32];
 };
-template <int D>
-__device__ __forceinline__ void tile_ld(Tile<D>& t, const float* __restrict__ base, int64_t ld, int64_t row0, int64_t nrows) {
+// (PAD: the float4s of columns >= dh are not read and stay zero)
+template <int D, bool PAD>
+__device__ __forceinline__ void tile_ld(Tile<D>& t, const float* __restrict__ base, int64_t ld, int64_t row0, int64_t nrows, int dh) {
 #pragma unroll
     for (int e = 0; e < D / 32; ++e) {
         const int idx = threadIdx.x + 256 * e, r = idx / (D / 4), c4 = idx % (D / 4);
         t.v[e] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (row0 + r < nrows) t.v[e] = *reinterpret_cast<const float4*>(base + (row0 + r) * ld + 4 * c4);
+        if constexpr (PAD) {
+            if (row0 + r < nrows && 4 * c4 < dh) t.v[e] = *reinterpret_cast<const float4*>(base + (row0 + r) * ld + 4 * c4);
+        } else {
+            if (row0 + r < nrows) t.v[e] = *reinterpret_cast<const float4*>(base + (row0 + r) * ld + 4 * c4);
+        }
     }
 }
 // rounds the tile to bf16 and writes its row image [32][D + 8] and / or its transposed image [D][TP]
@@ -108,12 +123,17 @@ __device__ __forceinline__ bf16x8 frag_trans(const short* trans, int d, int s2, 
     return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }
 // the wave's own rows as B fragments, straight from global memory: lane (l31, hf) holds d = 16 ks + 8 hf .. + 7 of row l31
-template <int D>
-__device__ __forceinline__ void frags_ld(bf16x8 (&f)[D / 16], const float* __restrict__ rowp, bool valid, int hf) {
+// (PAD: each of the two float4s of a lane's 8-column run is read only if it lies below dh)
+template <int D, bool PAD>
+__device__ __forceinline__ void frags_ld(bf16x8 (&f)[D / 16], const float* __restrict__ rowp, bool valid, int hf, int dh) {
 #pragma unroll
     for (int ks = 0; ks < D / 16; ++ks) {
         float4 x = make_float4(0.f, 0.f, 0.f, 0.f), y = x;
-        if (valid) {
+        if constexpr (PAD) {
+            const int c = 16 * ks + 8 * hf;
+            if (valid && c < dh) x = *reinterpret_cast<const float4*>(rowp + c);
+            if (valid && c + 4 < dh) y = *reinterpret_cast<const float4*>(rowp + c + 4);
+        } else if (valid) {
             x = *reinterpret_cast<const float4*>(rowp + 16 * ks + 8 * hf);
             y = *reinterpret_cast<const float4*>(rowp + 16 * ks + 8 * hf + 4);
         }
@@ -134,18 +154,25 @@ __device__ __forceinline__ f32x16 zero16() {
     return z;
 }
 // acc^T[d][lane] of one 32-wide d block -> row `p` (the lane's query or key), columns 32 t ..: four float4 per lane half
-__device__ __forceinline__ void store_t(float* __restrict__ p, const f32x16& acc, float sc, int hf) {
+// (PAD: `ncols` = dh - 32 t columns of the block exist; the float4s at or past them belong to the next head and are not written)
+template <bool PAD>
+__device__ __forceinline__ void store_t(float* __restrict__ p, const f32x16& acc, float sc, int hf, int ncols) {
 #pragma unroll
-    for (int g = 0; g < 4; ++g)
+    for (int g = 0; g < 4; ++g) {
+        if constexpr (PAD) {
+            if (8 * g + 4 * hf >= ncols) continue;
+        }
         *reinterpret_cast<float4*>(p + 8 * g + 4 * hf) = make_float4(acc[4 * g] * sc, acc[4 * g + 1] * sc, acc[4 * g + 2] * sc, acc[4 * g + 3] * sc);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
 // forward: block = 4 waves x 32 queries; grid (ceil(S/128), H, B)
 // ------------------------------------------------------------------------------------------------
-template <int D, bool DROP>
+template <int D, bool PAD, bool DROP>
 __global__ __launch_bounds__(256, 2) void k_attn_hd_fwd(HdArgs a) {
     constexpr int NS = D / 16, NT = D / 32;
+    const int dh = PAD ? a.dh : D;
     __shared__ __attribute__((aligned(16))) short Ks[32 * (D + 8)];
     __shared__ __attribute__((aligned(16))) short Vt[D * TP];
     __shared__ uint32_t bw_s[16];
@@ -154,13 +181,13 @@ __global__ __launch_bounds__(256, 2) void k_attn_hd_fwd(HdArgs a) {
     const int hkv = head / (a.H / a.HKV);
     const int64_t q0 = (int64_t)blockIdx.x * 128 + wave * 32;
     const int64_t rowbase = (int64_t)b * a.S;
-    const float* kp = a.k + rowbase * a.ldk + hkv * D;
-    const float* vp = a.v + rowbase * a.ldv + hkv * D;
+    const float* kp = a.k + rowbase * a.ldk + hkv * dh;
+    const float* vp = a.v + rowbase * a.ldv + hkv * dh;
     const float sc = a.scale * LOG2E;
     const int64_t qi = q0 + l31;
 
     bf16x8 qf[NS];
-    frags_ld<D>(qf, a.q + (rowbase + (qi < a.S ? qi : 0)) * a.ldq + head * D, qi < a.S, hf);
+    frags_ld<D, PAD>(qf, a.q + (rowbase + (qi < a.S ? qi : 0)) * a.ldq + head * dh, qi < a.S, hf, dh);
     f32x16 acc[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) acc[t] = zero16();
@@ -174,8 +201,8 @@ __global__ __launch_bounds__(256, 2) void k_attn_hd_fwd(HdArgs a) {
     }
 
     Tile<D> kt, vt;
-    tile_ld<D>(kt, kp, a.ldk, 0, a.S);
-    tile_ld<D>(vt, vp, a.ldv, 0, a.S);
+    tile_ld<D, PAD>(kt, kp, a.ldk, 0, a.S, dh);
+    tile_ld<D, PAD>(vt, vp, a.ldv, 0, a.S, dh);
     for (int64_t k0 = 0; k0 < a.S; k0 += 32) {
         __syncthreads();
         tile_st<D, true, false>(kt, Ks, nullptr);
@@ -183,8 +210,8 @@ __global__ __launch_bounds__(256, 2) void k_attn_hd_fwd(HdArgs a) {
         if constexpr (DROP) stage_col_words(bw_s, ck, k0);
         __syncthreads();
         if (k0 + 32 < a.S) {
-            tile_ld<D>(kt, kp, a.ldk, k0 + 32, a.S);
-            tile_ld<D>(vt, vp, a.ldv, k0 + 32, a.S);
+            tile_ld<D, PAD>(kt, kp, a.ldk, k0 + 32, a.S, dh);
+            tile_ld<D, PAD>(vt, vp, a.ldv, k0 + 32, a.S, dh);
         }
         // S^T[key][q]
         f32x16 s = zero16();
@@ -232,9 +259,9 @@ __global__ __launch_bounds__(256, 2) void k_attn_hd_fwd(HdArgs a) {
     }
     if (qi < a.S) {
         const float inv = DROP ? a.drop.inv_keep / l : 1.f / l;
-        float* op = a.o + (rowbase + qi) * a.ldo + head * D;
+        float* op = a.o + (rowbase + qi) * a.ldo + head * dh;
 #pragma unroll
-        for (int t = 0; t < NT; ++t) store_t(op + 32 * t, acc[t], inv, hf);
+        for (int t = 0; t < NT; ++t) store_t<PAD>(op + 32 * t, acc[t], inv, hf, dh - 32 * t);
         if (hf == 0) a.lse[((int64_t)b * a.H + head) * a.S + qi] = m * LN2 + logf(l);
     }
 }
@@ -244,18 +271,22 @@ __global__ __launch_bounds__(256, 2) void k_attn_hd_fwd(HdArgs a) {
 // for the SAME dO', so a row of dS sums to zero as in exact arithmetic and a component common to all keys (values) cancels in dQ
 // (dK) instead of being multiplied by the rounding error of dO
 // ------------------------------------------------------------------------------------------------
-template <int D>
+template <int D, bool PAD>
 __global__ __launch_bounds__(256) void k_attn_hd_delta(HdBwdArgs a) {
+    const int dh = PAD ? a.dh : D;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t n = (int64_t)a.B * a.S * a.H;
     if (i >= n) return;
     const int head = (int)(i % a.H);
     const int64_t row = i / a.H;  // b*S + s
-    const float* op = a.o + row * a.ldo + head * D;
-    const float* dp = a.d_o + row * a.lddo + head * D;
+    const float* op = a.o + row * a.ldo + head * dh;
+    const float* dp = a.d_o + row * a.lddo + head * dh;
     float s = 0.f;
 #pragma unroll 8
     for (int c = 0; c < D / 4; ++c) {
+        if constexpr (PAD) {
+            if (4 * c >= dh) break;          // the columns from dh on are the next head's
+        }
         const float4 x = *reinterpret_cast<const float4*>(op + 4 * c);
         const float4 y = *reinterpret_cast<const float4*>(dp + 4 * c);
         s += x.x * bfr(y.x) + x.y * bfr(y.y) + x.z * bfr(y.z) + x.w * bfr(y.w);
@@ -268,9 +299,10 @@ __global__ __launch_bounds__(256) void k_attn_hd_delta(HdBwdArgs a) {
 // dK / dV: block = 4 waves x 32 keys; grid (ceil(S/128), HKV, B); loops over the group's q heads in head order.
 // dK^T and dV^T of the wave's 32 keys stay in 2 * D / 2 accumulator registers (128 at D = 128: one wave per SIMD)
 // ------------------------------------------------------------------------------------------------
-template <int D, bool DROP>
-__global__ __launch_bounds__(256, D == 64 ? 2 : 1) void k_attn_hd_dkv(HdBwdArgs a) {
+template <int D, bool PAD, bool DROP>
+__global__ __launch_bounds__(256, D <= 64 ? 2 : 1) void k_attn_hd_dkv(HdBwdArgs a) {
     constexpr int NS = D / 16, NT = D / 32;
+    const int dh = PAD ? a.dh : D;
     __shared__ __attribute__((aligned(16))) short Qs[32 * (D + 8)];
     __shared__ __attribute__((aligned(16))) short dOs[32 * (D + 8)];
     __shared__ __attribute__((aligned(16))) short Qt[D * TP];
@@ -291,21 +323,21 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void k_attn_hd_dkv(HdBwdArgs 
     const float sc = a.scale * LOG2E;
     const int64_t ki = key0 + l31;
     bf16x8 kf[NS], vf[NS];
-    frags_ld<D>(kf, a.k + (rowbase + (ki < a.S ? ki : 0)) * a.ldk + hkv * D, ki < a.S, hf);
-    frags_ld<D>(vf, a.v + (rowbase + (ki < a.S ? ki : 0)) * a.ldv + hkv * D, ki < a.S, hf);
+    frags_ld<D, PAD>(kf, a.k + (rowbase + (ki < a.S ? ki : 0)) * a.ldk + hkv * dh, ki < a.S, hf, dh);
+    frags_ld<D, PAD>(vf, a.v + (rowbase + (ki < a.S ? ki : 0)) * a.ldv + hkv * dh, ki < a.S, hf, dh);
     f32x16 dkt[NT], dvt[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) { dkt[t] = zero16(); dvt[t] = zero16(); }
 
     for (int hr = 0; hr < rep; ++hr) {
         const int head = hkv * rep + hr;
-        const float* qp = a.q + rowbase * a.ldq + head * D;
-        const float* dop = a.d_o + rowbase * a.lddo + head * D;
+        const float* qp = a.q + rowbase * a.ldq + head * dh;
+        const float* dop = a.d_o + rowbase * a.lddo + head * dh;
         const float* lsep = a.lse + ((int64_t)b * a.H + head) * a.S;
         const float* delp = a.delta + ((int64_t)b * a.H + head) * a.S;
         Tile<D> qt, dt;
-        tile_ld<D>(qt, qp, a.ldq, 0, a.S);
-        tile_ld<D>(dt, dop, a.lddo, 0, a.S);
+        tile_ld<D, PAD>(qt, qp, a.ldq, 0, a.S, dh);
+        tile_ld<D, PAD>(dt, dop, a.lddo, 0, a.S, dh);
         float lt = 0.f, et = 0.f;
         if (threadIdx.x < 32) {
             lt = (threadIdx.x < a.S) ? lsep[threadIdx.x] * LOG2E : INFINITY;
@@ -332,8 +364,8 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void k_attn_hd_dkv(HdBwdArgs 
             }
             __syncthreads();
             if (q0 + 32 < a.S) {
-                tile_ld<D>(qt, qp, a.ldq, q0 + 32, a.S);
-                tile_ld<D>(dt, dop, a.lddo, q0 + 32, a.S);
+                tile_ld<D, PAD>(qt, qp, a.ldq, q0 + 32, a.S, dh);
+                tile_ld<D, PAD>(dt, dop, a.lddo, q0 + 32, a.S, dh);
                 if (threadIdx.x < 32) {
                     const int64_t qq = q0 + 32 + threadIdx.x;
                     lt = (qq < a.S) ? lsep[qq] * LOG2E : INFINITY;
@@ -371,13 +403,13 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void k_attn_hd_dkv(HdBwdArgs 
         __syncthreads();
     }
     if (ki < a.S) {
-        float* dkp = a.dk + (rowbase + ki) * a.lddk + hkv * D;
-        float* dvp = a.dv + (rowbase + ki) * a.lddv + hkv * D;
+        float* dkp = a.dk + (rowbase + ki) * a.lddk + hkv * dh;
+        float* dvp = a.dv + (rowbase + ki) * a.lddv + hkv * dh;
         const float vsc = DROP ? a.drop.inv_keep : 1.f, ksc = a.scale * vsc;
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
-            store_t(dkp + 32 * t, dkt[t], ksc, hf);
-            store_t(dvp + 32 * t, dvt[t], vsc, hf);
+            store_t<PAD>(dkp + 32 * t, dkt[t], ksc, hf, dh - 32 * t);
+            store_t<PAD>(dvp + 32 * t, dvt[t], vsc, hf, dh - 32 * t);
         }
     }
 }
@@ -386,9 +418,10 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void k_attn_hd_dkv(HdBwdArgs 
 // dQ: block = 4 waves x 32 queries; grid (ceil(S/128), H, B).  At D = 128 the q and dO fragments (64 registers), dQ^T (64) and
 // the staged K / V tiles (32) leave no room for two waves per SIMD
 // ------------------------------------------------------------------------------------------------
-template <int D, bool DROP>
-__global__ __launch_bounds__(256, D == 64 ? 2 : 1) void k_attn_hd_dq(HdBwdArgs a) {
+template <int D, bool PAD, bool DROP>
+__global__ __launch_bounds__(256, D <= 64 ? 2 : 1) void k_attn_hd_dq(HdBwdArgs a) {
     constexpr int NS = D / 16, NT = D / 32;
+    const int dh = PAD ? a.dh : D;
     __shared__ __attribute__((aligned(16))) short Ks[32 * (D + 8)];
     __shared__ __attribute__((aligned(16))) short Vs[32 * (D + 8)];
     __shared__ __attribute__((aligned(16))) short Kt[D * TP];
@@ -398,13 +431,13 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void k_attn_hd_dq(HdBwdArgs a
     const int hkv = head / (a.H / a.HKV);
     const int64_t q0 = (int64_t)blockIdx.x * 128 + wave * 32;
     const int64_t rowbase = (int64_t)b * a.S;
-    const float* kp = a.k + rowbase * a.ldk + hkv * D;
-    const float* vp = a.v + rowbase * a.ldv + hkv * D;
+    const float* kp = a.k + rowbase * a.ldk + hkv * dh;
+    const float* vp = a.v + rowbase * a.ldv + hkv * dh;
     const float sc = a.scale * LOG2E;
     const int64_t qi = q0 + l31;
     bf16x8 qf[NS], dof[NS];
-    frags_ld<D>(qf, a.q + (rowbase + (qi < a.S ? qi : 0)) * a.ldq + head * D, qi < a.S, hf);
-    frags_ld<D>(dof, a.d_o + (rowbase + (qi < a.S ? qi : 0)) * a.lddo + head * D, qi < a.S, hf);
+    frags_ld<D, PAD>(qf, a.q + (rowbase + (qi < a.S ? qi : 0)) * a.ldq + head * dh, qi < a.S, hf, dh);
+    frags_ld<D, PAD>(dof, a.d_o + (rowbase + (qi < a.S ? qi : 0)) * a.lddo + head * dh, qi < a.S, hf, dh);
     const float lse2 = (qi < a.S) ? a.lse[((int64_t)b * a.H + head) * a.S + qi] * LOG2E : INFINITY;
     const float del = (qi < a.S) ? a.delta[((int64_t)b * a.H + head) * a.S + qi] * (DROP ? a.drop.keep : 1.f) : 0.f;
     f32x16 dqt[NT];
@@ -419,8 +452,8 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void k_attn_hd_dq(HdBwdArgs a
     }
 
     Tile<D> kt, vt;
-    tile_ld<D>(kt, kp, a.ldk, 0, a.S);
-    tile_ld<D>(vt, vp, a.ldv, 0, a.S);
+    tile_ld<D, PAD>(kt, kp, a.ldk, 0, a.S, dh);
+    tile_ld<D, PAD>(vt, vp, a.ldv, 0, a.S, dh);
     for (int64_t k0 = 0; k0 < a.S; k0 += 32) {
         __syncthreads();
         tile_st<D, true, true>(kt, Ks, Kt);
@@ -428,8 +461,8 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void k_attn_hd_dq(HdBwdArgs a
         if constexpr (DROP) stage_col_words(bw_s, ck, k0);
         __syncthreads();
         if (k0 + 32 < a.S) {
-            tile_ld<D>(kt, kp, a.ldk, k0 + 32, a.S);
-            tile_ld<D>(vt, vp, a.ldv, k0 + 32, a.S);
+            tile_ld<D, PAD>(kt, kp, a.ldk, k0 + 32, a.S, dh);
+            tile_ld<D, PAD>(vt, vp, a.ldv, k0 + 32, a.S, dh);
         }
         // S^T[key][q] ; dP^T[key][q]
         f32x16 s = zero16(), dp = zero16();
@@ -456,38 +489,53 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void k_attn_hd_dq(HdBwdArgs a
                 dqt[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_trans(Kt, 32 * t + l31, s2, hf), dsb[s2], dqt[t], 0, 0, 0);
     }
     if (qi < a.S) {
-        float* dqp = a.dq + (rowbase + qi) * a.lddq + head * D;
+        float* dqp = a.dq + (rowbase + qi) * a.lddq + head * dh;
         const float qsc = DROP ? a.scale * a.drop.inv_keep : a.scale;
 #pragma unroll
-        for (int t = 0; t < NT; ++t) store_t(dqp + 32 * t, dqt[t], qsc, hf);
+        for (int t = 0; t < NT; ++t) store_t<PAD>(dqp + 32 * t, dqt[t], qsc, hf, dh - 32 * t);
     }
 }
 
 bool aligned16(const void* p, int64_t ld) { return (((uintptr_t)p & 15) == 0) && (ld % 4 == 0); }
 
-template <int D>
+template <int D, bool PAD>
 void launch_fwd(const HdArgs& a, hipStream_t st) {
     const dim3 grid((unsigned)ceil_div(a.S, 128), (unsigned)a.H, (unsigned)a.B);
-    if (a.drop.thr) GAOT_KLAUNCH((k_attn_hd_fwd<D, true>), grid, dim3(256), 0, st, a);
-    else GAOT_KLAUNCH((k_attn_hd_fwd<D, false>), grid, dim3(256), 0, st, a);
+    if (a.drop.thr) GAOT_KLAUNCH((k_attn_hd_fwd<D, PAD, true>), grid, dim3(256), 0, st, a);
+    else GAOT_KLAUNCH((k_attn_hd_fwd<D, PAD, false>), grid, dim3(256), 0, st, a);
 }
 
-template <int D>
+template <int D, bool PAD>
 void launch_bwd(const HdBwdArgs& a, int phase_mask, hipStream_t st) {
     const bool drop = a.drop.thr != 0;
     const int64_t n = (int64_t)a.B * a.S * a.H;
-    if (phase_mask & 1) GAOT_KLAUNCH((k_attn_hd_delta<D>), dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, a);
+    if (phase_mask & 1) GAOT_KLAUNCH((k_attn_hd_delta<D, PAD>), dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, a);
     if (phase_mask & 2) {
         const dim3 g((unsigned)ceil_div(a.S, 128), (unsigned)a.HKV, (unsigned)a.B);
-        if (drop) GAOT_KLAUNCH((k_attn_hd_dkv<D, true>), g, dim3(256), 0, st, a);
-        else GAOT_KLAUNCH((k_attn_hd_dkv<D, false>), g, dim3(256), 0, st, a);
+        if (drop) GAOT_KLAUNCH((k_attn_hd_dkv<D, PAD, true>), g, dim3(256), 0, st, a);
+        else GAOT_KLAUNCH((k_attn_hd_dkv<D, PAD, false>), g, dim3(256), 0, st, a);
     }
     if (phase_mask & 4) {
         const dim3 g((unsigned)ceil_div(a.S, 128), (unsigned)a.H, (unsigned)a.B);
-        if (drop) GAOT_KLAUNCH((k_attn_hd_dq<D, true>), g, dim3(256), 0, st, a);
-        else GAOT_KLAUNCH((k_attn_hd_dq<D, false>), g, dim3(256), 0, st, a);
+        if (drop) GAOT_KLAUNCH((k_attn_hd_dq<D, PAD, true>), g, dim3(256), 0, st, a);
+        else GAOT_KLAUNCH((k_attn_hd_dq<D, PAD, false>), g, dim3(256), 0, st, a);
     }
 }
+
+// the tile width of a head width: the smallest instance that holds it; the plain instance when they are equal
+template <int D>
+void launch_fwd_d(const HdArgs& a, hipStream_t st) {
+    if (a.dh == D) launch_fwd<D, false>(a, st);
+    else launch_fwd<D, true>(a, st);
+}
+template <int D>
+void launch_bwd_d(const HdBwdArgs& a, int phase_mask, hipStream_t st) {
+    if (a.dh == D) launch_bwd<D, false>(a, phase_mask, st);
+    else launch_bwd<D, true>(a, phase_mask, st);
+}
+
+constexpr const char* HEAD_DIM_RULE = "head_dim must be a multiple of 4 with 4 <= head_dim <= 128";
+bool head_dim_ok(int head_dim) { return head_dim >= 4 && head_dim <= 128 && head_dim % 4 == 0; }
 
 }  // namespace
 
@@ -496,10 +544,7 @@ extern "C" int gaot_attn_hd_fwd(const float* q, const float* k, const float* v, 
                                 float scale, float dropout_p, const unsigned long long* dropout_seed, int head0, int heads_total,
                                 gaot_stream_t stream) {
     GAOT_ENTER();
-    if (head_dim != 64 && head_dim != 128) {
-        gaot_set_error("gaot_attn_hd_fwd: head_dim %d unsupported (only 64 and 128)", head_dim);
-        return GAOT_ERR_UNSUPPORTED;
-    }
+    GAOT_CHECK_ARG(head_dim_ok(head_dim), HEAD_DIM_RULE);
     GAOT_CHECK_ARG(B > 0 && S > 0 && H > 0 && HKV > 0 && H % HKV == 0, "bad shape");
     GAOT_CHECK_ARG(B <= 65535 && H <= 65535, "B and H must fit a grid dimension");
     GAOT_CHECK_ARG(q && k && v && o && lse, "null pointer");
@@ -507,9 +552,12 @@ extern "C" int gaot_attn_hd_fwd(const float* q, const float* k, const float* v, 
                    "q/k/v/o must be 16-byte aligned with row strides that are multiples of 4 floats");
     GAOT_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f && (dropout_p == 0.f || dropout_seed), "dropout_p in [0,1) and a seed");
     GAOT_CHECK_ARG(heads_total == 0 || (head0 >= 0 && head0 + H <= heads_total), "head0 + H <= heads_total");
-    HdArgs a{q, k, v, o, lse, ldq, ldk, ldv, ldo, B, S, H, HKV, scale, gdrop::make_drop(dropout_seed, dropout_p, H, head0, heads_total)};
-    if (head_dim == 64) launch_fwd<64>(a, (hipStream_t)stream);
-    else launch_fwd<128>(a, (hipStream_t)stream);
+    HdArgs a{q, k, v, o, lse, ldq, ldk, ldv, ldo, B, S, H, HKV, scale, gdrop::make_drop(dropout_seed, dropout_p, H, head0, heads_total),
+             head_dim};
+    if (head_dim <= 32) launch_fwd_d<32>(a, (hipStream_t)stream);
+    else if (head_dim <= 64) launch_fwd_d<64>(a, (hipStream_t)stream);
+    else if (head_dim <= 96) launch_fwd_d<96>(a, (hipStream_t)stream);
+    else launch_fwd_d<128>(a, (hipStream_t)stream);
     GAOT_LAUNCH_CHECK();
     return GAOT_OK;
 }
@@ -521,10 +569,7 @@ extern "C" int gaot_attn_hd_bwd(const float* q, const float* k, const float* v, 
                                 const unsigned long long* dropout_seed, int head0, int heads_total, int phase_mask,
                                 gaot_stream_t stream) {
     GAOT_ENTER();
-    if (head_dim != 64 && head_dim != 128) {
-        gaot_set_error("gaot_attn_hd_bwd: head_dim %d unsupported (only 64 and 128)", head_dim);
-        return GAOT_ERR_UNSUPPORTED;
-    }
+    GAOT_CHECK_ARG(head_dim_ok(head_dim), HEAD_DIM_RULE);
     GAOT_CHECK_ARG(B > 0 && S > 0 && H > 0 && HKV > 0 && H % HKV == 0, "bad shape");
     GAOT_CHECK_ARG(B <= 65535 && H <= 65535, "B and H must fit a grid dimension");
     GAOT_CHECK_ARG(q && k && v && o && d_o && lse && delta && dq && dk && dv, "null pointer");
@@ -534,9 +579,11 @@ extern "C" int gaot_attn_hd_bwd(const float* q, const float* k, const float* v, 
     GAOT_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f && (dropout_p == 0.f || dropout_seed), "dropout_p in [0,1) and a seed");
     GAOT_CHECK_ARG(heads_total == 0 || (head0 >= 0 && head0 + H <= heads_total), "head0 + H <= heads_total");
     HdBwdArgs a{q, k, v, o, d_o, lse, delta, dq, dk, dv, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, B, S, H, HKV, scale,
-                gdrop::make_drop(dropout_seed, dropout_p, H, head0, heads_total)};
-    if (head_dim == 64) launch_bwd<64>(a, phase_mask, (hipStream_t)stream);
-    else launch_bwd<128>(a, phase_mask, (hipStream_t)stream);
+                gdrop::make_drop(dropout_seed, dropout_p, H, head0, heads_total), head_dim};
+    if (head_dim <= 32) launch_bwd_d<32>(a, phase_mask, (hipStream_t)stream);
+    else if (head_dim <= 64) launch_bwd_d<64>(a, phase_mask, (hipStream_t)stream);
+    else if (head_dim <= 96) launch_bwd_d<96>(a, phase_mask, (hipStream_t)stream);
+    else launch_bwd_d<128>(a, phase_mask, (hipStream_t)stream);
     GAOT_LAUNCH_CHECK();
     return GAOT_OK;
 }

@@ -727,7 +727,8 @@ class RopeFn(Function):
 
 
 class AttentionHdFn(Function):
-    """softmax(QK^T/sqrt(d))V for head sizes 64 and 128 in bf16 mode on the flash kernels of csrc/attn_hd.hip (reference
+    """softmax(QK^T/sqrt(d))V for every head size hd_flash_eligible accepts (a multiple of 4, 4 .. 128) in bf16 mode on the flash
+    kernels of csrc/attn_hd.hip (tile width 32 / 64 / 96 / 128, the smallest that holds the head; padded instances in between; reference
     attn.py:110-127): q | k | v is the fused fp32 projection, already rotated (RopeFn outside); saves it with o, lse and the seed
     word -- every saved tensor is O(S * d)."""
 
@@ -756,16 +757,23 @@ class AttentionHdFn(Function):
         return dqkv, None, None, None, None, None, None, None, None
 
 
-HD_FLASH_HEAD_DIMS = (64, 128)
+def hd_flash_eligible(head_dim: int) -> bool:
+    """head sizes the flash kernels of csrc/attn_hd.hip take in bf16 mode: every multiple of 4 from 4 to 128 (ops.attn_hd_fwd and
+    the library apply the same rule).  Inside the model head size 32 keeps AttentionFn."""
+    return ops.attn_hd_head_dim_ok(int(head_dim))
+
+
+HD_FLASH_HEAD_DIMS = tuple(d for d in range(1, 129) if hd_flash_eligible(d))     # every eligible size: 4, 8, ..., 128
 
 
 def attention_general(qkv: Tensor, freqs: Optional[Tensor], b: int, s: int, h: int, hkv: int, head_dim: int,
                       dropout_p: float = 0.0, head0: int = 0, heads_total: int = 0) -> Tensor:
     """softmax(Q K^T / sqrt(d)) V for ANY head_dim other than 32 (reference attn.py:110-127 accepts every hidden_size % num_heads
-    == 0), the single dispatch point: head sizes 64 and 128 in bf16 mode on the GPU run the flash kernels of csrc/attn_hd.hip
-    (AttentionHdFn; RoPE outside through RopeFn); everything else -- fp32 mode, the other head sizes -- the unfused general path
-    (_attention_unfused).  head_dim 32 (every shipped configuration) runs AttentionFn."""
-    if ops.get_precision() == "bf16" and qkv.is_cuda and head_dim in HD_FLASH_HEAD_DIMS:
+    == 0), the single dispatch point: in bf16 mode on the GPU every head size that is a multiple of 4 up to 128
+    (hd_flash_eligible) runs the flash kernels of csrc/attn_hd.hip (AttentionHdFn; RoPE outside through RopeFn); everything else
+    -- fp32 mode, head sizes above 128 or not a multiple of 4 -- the unfused general path (_attention_unfused).  Inside the model
+    head_dim 32 (every shipped configuration) runs AttentionFn and does not come here."""
+    if ops.get_precision() == "bf16" and qkv.is_cuda and hd_flash_eligible(head_dim):
         if freqs is not None:
             qkv = RopeFn.apply(qkv, freqs, b * s, s, h + hkv, head_dim)
         return AttentionHdFn.apply(qkv, b, s, h, hkv, head_dim, float(dropout_p), int(head0), int(heads_total))

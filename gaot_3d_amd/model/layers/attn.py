@@ -76,7 +76,7 @@ class GroupQueryFlashAttention(nn.Module):
         self.num_heads = num_heads
         self.num_kv_heads = num_kv_heads
         self.num_repeat = num_heads // num_kv_heads
-        self.head_dim = hidden_size // num_heads   # 32: flash kernels; 64 / 128 in bf16 mode: those of csrc/attn_hd.hip; anything else: the unfused general path
+        self.head_dim = hidden_size // num_heads   # 32: flash kernels; a multiple of 4 up to 128 in bf16 mode: those of csrc/attn_hd.hip; anything else: the unfused general path
         self.atten_dropout = atten_dropout
         kv_hidden = self.head_dim * num_kv_heads
         self.q_proj = nn.Linear(input_size, hidden_size, bias=False)
@@ -130,7 +130,7 @@ class GroupQueryFlashAttention(nn.Module):
                 return y.view(b, s, -1)
         qkv = GF.multi_linear(x, [self.q_proj.weight, self.k_proj.weight, self.v_proj.weight], image_spec=spec)  # [B*S, (h+2hkv)*32]
         if self.head_dim != 32:
-            # any other head size: functional.attention_general (flash kernels for 64 / 128 in bf16 mode, else the unfused general path);
+            # any other head size: functional.attention_general (flash kernels for multiples of 4 up to 128 in bf16 mode, else the unfused general path);
             # sharded, the same exchanges around it
             head_group, hd = getattr(self, "_head_group", None), self.head_dim
             if seq_group is not None:
@@ -385,9 +385,10 @@ class Transformer(nn.Module):
             GF.prepack_skip([blk.skip_proj.weight for blk in blocks if blk.skip_connection] if torch.is_grad_enabled() else [])
             if self.training and getattr(self, "_seq_group", None) is None and SEED_BLOCK["on"]:
                 # the attention seeds of all blocks with ONE launch (each block draws its own otherwise)
-                # (blocks on the flash kernels draw one word each: head size 32, and 64 / 128 in bf16 mode)
-                hds = (32,) + (GF.HD_FLASH_HEAD_DIMS if GF.ops.get_precision() == "bf16" else ())
-                n_drop = sum(1 for blk in blocks if float(blk.attn.atten_dropout) > 0.0 and blk.attn.head_dim in hds)
+                # (blocks on the flash kernels draw one word each: head size 32, and in bf16 mode every size hd_flash_eligible accepts)
+                bf16 = GF.ops.get_precision() == "bf16"
+                n_drop = sum(1 for blk in blocks if float(blk.attn.atten_dropout) > 0.0
+                             and (blk.attn.head_dim == 32 or (bf16 and GF.hd_flash_eligible(blk.attn.head_dim))))
                 GF.reserve_dropout_seeds(x.device, n_drop)
         try:
             return self._forward(x, condition, relative_positions)

@@ -861,15 +861,23 @@ def attn_bwd(qkv: Tensor, o: Tensor, d_o: Tensor, lse: Tensor, b: int, s: int, h
     return dqkv
 
 
+HD_HEAD_DIM_RULE = "head_dim must be a multiple of 4 with 4 <= head_dim <= 128"
+
+
+def attn_hd_head_dim_ok(head_dim: int) -> bool:
+    """the head sizes csrc/attn_hd.hip takes (gaot_attn_hd_fwd / gaot_attn_hd_bwd apply the same rule)"""
+    return 4 <= head_dim <= 128 and head_dim % 4 == 0
+
+
 def attn_hd_fwd(qkv: Tensor, b: int, s: int, h: int, hkv: int, head_dim: int, scale: float, dropout_p: float = 0.0,
                 seed: Optional[Tensor] = None, head0: int = 0, heads_total: int = 0):
-    """flash attention for head sizes 64 and 128 in bf16 mode (csrc/attn_hd.hip).  qkv: [B*S, (h + 2*hkv)*head_dim] fused fp32
+    """flash attention for every head size that is a multiple of 4 up to 128 in bf16 mode (csrc/attn_hd.hip).  qkv: [B*S, (h + 2*hkv)*head_dim] fused fp32
     projection output (q | k | v column blocks), already rotated; -> (o [B*S, h*head_dim], lse [b, h, s]).  ``head0`` /
     ``heads_total`` as in attn_fwd"""
     lib = _lib.load()
     qkv = _req(qkv, torch.float32, "qkv")
-    if head_dim not in (64, 128):
-        raise GaotError(f"attn_hd_fwd: head_dim {head_dim} unsupported (only 64 and 128)")
+    if not attn_hd_head_dim_ok(head_dim):
+        raise GaotError(f"attn_hd_fwd: {HD_HEAD_DIM_RULE}, got {head_dim}")
     if qkv.dim() != 2 or tuple(qkv.shape) != (b * s, (h + 2 * hkv) * head_dim):
         raise GaotError(f"attn_hd_fwd: qkv must be [{b * s}, {(h + 2 * hkv) * head_dim}], got {tuple(qkv.shape)}")
     dev = qkv.device
@@ -893,8 +901,8 @@ def attn_hd_bwd(qkv: Tensor, o: Tensor, d_o: Tensor, lse: Tensor, b: int, s: int
     o = _req(o, torch.float32, "o")
     d_o = _req(d_o, torch.float32, "d_o")
     lse = _req(lse, torch.float32, "lse")
-    if head_dim not in (64, 128):
-        raise GaotError(f"attn_hd_bwd: head_dim {head_dim} unsupported (only 64 and 128)")
+    if not attn_hd_head_dim_ok(head_dim):
+        raise GaotError(f"attn_hd_bwd: {HD_HEAD_DIM_RULE}, got {head_dim}")
     if tuple(qkv.shape) != (b * s, (h + 2 * hkv) * head_dim) or tuple(o.shape) != (b * s, h * head_dim) or o.shape != d_o.shape \
             or lse.numel() != b * h * s:
         raise GaotError("attn_hd_bwd: qkv / o / d_o / lse do not match (b, s, h, hkv, head_dim)")

@@ -249,12 +249,15 @@ int gaot_attn_bwd_fused_f32(const float* q, const float* k, const float* v, cons
                             int64_t lddo, int64_t lddq, int64_t lddk, int64_t lddv, int B, int S, int H, int HKV, int head_dim,
                             float scale, float dropout_p, const unsigned long long* dropout_seed, int head0, int heads_total,
                             int run_delta, void* scratch, size_t scratch_bytes, gaot_stream_t stream);
-/* Head sizes 64 and 128 of the same operator (reference attn.py:110-127 accepts every hidden_size % num_heads == 0; attn.py:122-127
+/* Every head size that is a multiple of 4 up to 128 of the same operator (reference attn.py:110-127 accepts every hidden_size % num_heads == 0; attn.py:122-127
  * for the dropout), bf16 mode: bf16 operands on the matrix cores (the fp32 inputs are rounded as they are loaded), fp32 accumulation and
  * softmax, flash-style -- every buffer is O(S * head_dim), never an S x S tensor.  Arguments, layouts (q/k/v/o/d_o/dq/dk/dv are
  * [B*S, heads*head_dim] fp32 views with row strides ld*, q and k already rotated; lse/delta [B, H, S]), dropout semantics, head0 /
- * heads_total and phase_mask exactly as gaot_attn_fwd / gaot_attn_bwd; head_dim must be 64 or 128.  dK / dV are summed inside one
- * workgroup in a fixed order and dQ has its own pass: no float atomics, bit-reproducible.  No workspace beyond delta. */
+ * heads_total and phase_mask exactly as gaot_attn_fwd / gaot_attn_bwd; head_dim must be a multiple of 4 with 4 <= head_dim <= 128
+ * (GAOT_ERR_ARG otherwise).  The kernels are instantiated for tile widths 32, 64, 96 and 128; a head size in between runs the next
+ * width with the columns from head_dim on predicated off: never read (they belong to the neighbouring head) and never written.
+ * dK / dV are summed inside one workgroup in a fixed order and dQ has its own pass: no float atomics, bit-reproducible.  No
+ * workspace beyond delta. */
 int gaot_attn_hd_fwd(const float* q, const float* k, const float* v, float* o, float* lse, int64_t ldq, int64_t ldk,
                      int64_t ldv, int64_t ldo, int B, int S, int H, int HKV, int head_dim, float scale, float dropout_p,
                      const unsigned long long* dropout_seed, int head0, int heads_total, gaot_stream_t stream);

@@ -296,10 +296,16 @@ elif what == "attn_headdim":
     # head sizes 64 and 128 in bf16 mode at hidden 256, S = 16 384, b = 1, RoPE on, p = 0.1: forward + backward of (1) the unfused
     # general path (functional._attention_unfused: the path every head size other than 32 took before the flash kernels), (2) the
     # flash kernels of csrc/attn_hd.hip (functional.attention_general), and, FOR ORIENTATION ONLY -- hand-scheduled kernels, not a
-    # target -- (3) the head-size-32 kernels at the same hidden size (8 heads, equal FLOPs).  HIP events around each call, median
+    # target -- (3) the head-size-32 kernels at the same hidden size (hidden / 32 heads, equal FLOPs).  HIP events around each call, median
     # of `reps` after one warm-up, the three alternating in one process.
+    # MB_DIMS (comma-separated head sizes, default 64,128) and MB_HIDDEN (default 256; a multiple of every head size and of 32):
+    # any head size hd_flash_eligible accepts, e.g. MB_DIMS=16 MB_HIDDEN=256, MB_DIMS=48,96 MB_HIDDEN=384.
     gaot_3d_amd.set_precision("bf16")
-    s, hidden, pd = int(os.environ.get("MB_S", 16384)), 256, 0.1
+    s, hidden, pd = int(os.environ.get("MB_S", 16384)), int(os.environ.get("MB_HIDDEN", 256)), 0.1
+    dims = tuple(int(t) for t in os.environ.get("MB_DIMS", "64,128").split(","))
+    eligible = getattr(GF, "hd_flash_eligible", lambda d: d in GF.HD_FLASH_HEAD_DIMS)     # (MB_TREE: a checkout from before the predicate)
+    assert hidden % 32 == 0 and all(hidden % d == 0 and eligible(d) for d in dims), (hidden, dims)
+    h32 = hidden // 32
     GF.set_dropout_seed(2026, dev)
 
     def fwd_bwd(path, qkv, freqs, h, d, w):
@@ -326,7 +332,7 @@ elif what == "attn_headdim":
     w = torch.randn(s, hidden, device=dev)
     x32 = torch.randn(s, 3 * hidden, device=dev).requires_grad_(True)
     f32_ = (1.0 / (10000 ** (torch.arange(0, 32, 2).float() / 32))).to(dev)
-    for d in (64, 128):
+    for d in dims:
         h = hidden // d
         qkv = torch.randn(s, 3 * hidden, device=dev).requires_grad_(True)
         freqs = (1.0 / (10000 ** (torch.arange(0, d, 2).float() / d))).to(dev)
@@ -334,15 +340,15 @@ elif what == "attn_headdim":
         res = {}
         for name, fn in (("unfused", lambda: fwd_bwd("unfused", qkv, freqs, h, d, w)),
                          ("flash", lambda: fwd_bwd("flash", qkv, freqs, h, d, w)),
-                         ("hd32", lambda: fwd_bwd("hd32", x32, f32_, 8, 32, w))):
+                         ("hd32", lambda: fwd_bwd("hd32", x32, f32_, h32, 32, w))):
             res[name] = median_ms(fn)
         print(f"D={d} h={h} S={s} p={pd} rope: (1) _attention_unfused fwd+bwd: {res['unfused'][0]:.3f} ms (min {res['unfused'][1]:.3f}, max {res['unfused'][2]:.3f})")
         print(f"D={d} h={h} S={s} p={pd} rope: (2) flash kernels (attn_hd) fwd+bwd: {res['flash'][0]:.3f} ms (min {res['flash'][1]:.3f}, max {res['flash'][2]:.3f})"
               f"  = {res['flash'][0] / res['unfused'][0]:.3f} x (1);  {flops / res['flash'][0] / 1e9:.1f} TF/s of 18 S^2 D h, "
               f"{100 * flops / res['flash'][0] / 1e9 / 2500:.1f} % of the 2.5 PF/s bf16 roof (whole call incl. RoPE and the loss product)")
-        print(f"D={d}: (3) orientation only, head size 32 x 8 heads (hand-scheduled kernels): {res['hd32'][0]:.3f} ms (min {res['hd32'][1]:.3f}, max {res['hd32'][2]:.3f})")
+        print(f"D={d}: (3) orientation only, head size 32 x {h32} heads (hand-scheduled kernels): {res['hd32'][0]:.3f} ms (min {res['hd32'][1]:.3f}, max {res['hd32'][2]:.3f})")
     ops.timing_reset(True)
-    for d in (64, 128):
+    for d in dims:
         h = hidden // d
         qkv = torch.randn(s, 3 * hidden, device=dev).requires_grad_(True)
         freqs = (1.0 / (10000 ** (torch.arange(0, d, 2).float() / d))).to(dev)
