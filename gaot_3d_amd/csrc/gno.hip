@@ -44,6 +44,8 @@ struct FwdLds {
 // MODE (gno_common.h): in the nonlinear / kernel-only modes `nl_` begins with one NlFwd and layer 0 starts from b_0 + t[src]
 // WEIGHTED (a WFwd ends the pack): the staged value is alpha_e k_e f[s_e], alpha applied in fp32 after the last layer's accumulator,
 // and the rows are summed, not averaged
+// REGULAR LIST (a KnnFwd ends the pack, gno_common.h): sources from nbr, query = e >> lk, rows finished in the tile; src_s, dst_s, rowptr
+// and part are not read
 template <int NH, int H, int T, int MODE, class... Nl>
 __global__ __launch_bounds__(256, 2) void k_gno_fwd(MlpPtrs mlp, const float* __restrict__ y_pos,
                                                     const float* __restrict__ x_pos, const float* __restrict__ f_y,
@@ -54,6 +56,8 @@ __global__ __launch_bounds__(256, 2) void k_gno_fwd(MlpPtrs mlp, const float* __
     constexpr int C = 32;
     constexpr int KB = H / 32;
     constexpr bool W = pack_has<WFwd, Nl...>;
+    constexpr bool K = pack_has<KnnFwd, Nl...>;
+    static_assert(!(W && K), "no weighted variant on regular lists");
     using L = FwdLds<NH, H>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* stage_all = lds + L::weights_end;             // [4 waves][T][32][C]
@@ -98,8 +102,14 @@ __global__ __launch_bounds__(256, 2) void k_gno_fwd(MlpPtrs mlp, const float* __
         for (int t = 0; t < T; ++t) {
             const int64_t e = base + 32 * t + l31;
             const bool valid = e < E;
-            const int s = valid ? src_s[e] : 0;
-            const int q = valid ? dst_s[e] : 0;
+            int s, q;
+            if constexpr (K) {
+                s = valid ? last_arg(nl_...).nbr[e] : 0;
+                q = valid ? (int)(e >> last_arg(nl_...).lk) : 0;
+            } else {
+                s = valid ? src_s[e] : 0;
+                q = valid ? dst_s[e] : 0;
+            }
             const float* ys = y_pos + (int64_t)s * 3;
             const float* xq = x_pos + (int64_t)q * 3;
             bin[t][0] = ys[hf];
@@ -109,7 +119,7 @@ __global__ __launch_bounds__(256, 2) void k_gno_fwd(MlpPtrs mlp, const float* __
             if constexpr (W) aw[t] = valid ? last_arg(nl_...).alpha[e] : 0.f;
             if (hf == 0) {
                 ids[(t * 2 + 0) * 32 + l31] = s;
-                ids[(t * 2 + 1) * 32 + l31] = valid ? q : -1;
+                if constexpr (!K) ids[(t * 2 + 1) * 32 + l31] = valid ? q : -1;
             }
         }
         // ---- layer 0: 6 -> H ---------------------------------------------------------------------
@@ -214,8 +224,11 @@ __global__ __launch_bounds__(256, 2) void k_gno_fwd(MlpPtrs mlp, const float* __
         wave_lds_fence();
         // ---- segmented mean (weighted: sum): half h walks tile h (T==2) / lower half walks the tile (T==1) --------
         if (hf < T) {
-            segment_walk<C>(stage + hf * 32 * C, C, ids + (hf * 2 + 1) * 32, l31, base + 32 * hf, rowptr, out, part,
-                            !W);
+            if constexpr (K)
+                fixed_k_rows<C>(stage + hf * 32 * C, C, l31, base + 32 * hf, last_arg(nl_...).lk, E, out);
+            else
+                segment_walk<C>(stage + hf * 32 * C, C, ids + (hf * 2 + 1) * 32, l31, base + 32 * hf, rowptr, out, part,
+                                !W);
         }
         wave_lds_fence();
     }
@@ -849,6 +862,33 @@ int launch_bwd(const MlpPtrs& p, const MlpPtrs& pt, const float* y_pos, const fl
     return GAOT_OK;
 }
 
+// the regular-list instantiations (a KnnFwd ends the pack): E = num_queries * k, no lists, no partial buffer
+template <int NH, int H, int MODE>
+int launch_fwd_knn(const MlpPtrs& p, const float* y_pos, const float* x_pos, const float* f_y, const float* ttab, const int* nbr,
+                   int lk, int64_t E, float* out, hipStream_t st) {
+    constexpr int T = 2;
+    const size_t lds = fwd_lds_bytes(NH, H, T);
+    auto kern = [] {
+        if constexpr (MODE == MODE_LINEAR) return k_gno_fwd<NH, H, T, MODE, KnnFwd>;
+        else return k_gno_fwd<NH, H, T, MODE, NlFwd, KnnFwd>;
+    }();
+    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) {
+        gaot_set_error("gno_fwd_knn: cannot set dynamic LDS %zu: %s", lds, hipGetErrorString(e));
+        return GAOT_ERR_LAUNCH;
+    }
+    const int64_t n_macro = ceil_div(E, 32 * T);
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n_macro, 4), 256 * 2));
+    const int* none = nullptr;
+    float* no_part = nullptr;
+    if constexpr (MODE == MODE_LINEAR)
+        GAOT_KLAUNCH(kern, dim3(grid), dim3(256), lds, st, p, y_pos, x_pos, f_y, none, none, none, E, out, no_part, KnnFwd{nbr, lk});
+    else
+        GAOT_KLAUNCH(kern, dim3(grid), dim3(256), lds, st, p, y_pos, x_pos, f_y, none, none, none, E, out, no_part, NlFwd{ttab},
+                     KnnFwd{nbr, lk});
+    return GAOT_OK;
+}
+
 int bwd_grid(int64_t E) {
     const int64_t n_tiles = ceil_div(E, 32);
     return (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n_tiles, 4), 256));
@@ -867,6 +907,10 @@ int gaot_gno_fwd_bf16_dispatch(int n_hidden, int mode, const float* const* w, co
                                const float* x_pos, const float* f_y, const float* ttab, const int32_t* src_sorted,
                                const int32_t* dst_sorted, const int32_t* rowptr_dst, int64_t num_edges, float* out, float* part,
                                const float* edge_w, hipStream_t st);
+
+int gaot_gno_fwd_knn_bf16_dispatch(int n_hidden, int mode, const float* const* w, const float* const* b, const float* y_pos,
+                                   const float* x_pos, const float* f_y, const float* ttab, const int32_t* nbr, int lk,
+                                   int64_t num_edges, float* out, hipStream_t st);
 
 size_t gaot_gno_bwd_bf16_image_bytes(int n_hidden);
 int gaot_gno_bwd_bf16_dispatch(int n_hidden, int mode, const float* const* w, const float* const* b, const float* w0t,
@@ -971,6 +1015,55 @@ extern "C" int gaot_gno_fwd_nl(const gaot_mlp_t* mlp, int mode, const float* y_p
     GAOT_CHECK_ARG(mode == MODE_NONLINEAR || mode == MODE_KERNELONLY, "mode must be 1 (nonlinear) or 2 (nonlinear_kernelonly)");
     return gno_fwd_impl("gaot_gno_fwd_nl", mlp, y_pos, x_pos, f_y, src_table, mode, src_sorted, dst_sorted, rowptr_dst,
                         num_edges, num_queries, out, precision, workspace, workspace_bytes, stream);
+}
+
+// The forward on a regular k-neighbour list (KnnFwd, gno_common.h): one launch, no workspace
+extern "C" int gaot_gno_fwd_knn(const gaot_mlp_t* mlp, int mode, const float* y_pos, const float* x_pos, const float* f_y,
+                                const float* src_table, const int32_t* nbr, int k, int64_t num_queries, float* out, int precision,
+                                gaot_stream_t stream) {
+    GAOT_ENTER();
+    GAOT_CHECK_ARG(mlp, "null mlp");
+    if (!mlp_supported(mlp, false)) {
+        gaot_set_error("gaot_gno_fwd_knn: unsupported MLP shape (n_hidden=%d hidden=%d channels=%d)", mlp->n_hidden, mlp->hidden,
+                       mlp->channels);
+        return GAOT_ERR_UNSUPPORTED;
+    }
+    GAOT_CHECK_ARG(mode == MODE_LINEAR || mode == MODE_NONLINEAR || mode == MODE_KERNELONLY,
+                   "mode must be 0 (linear), 1 (nonlinear) or 2 (nonlinear_kernelonly)");
+    GAOT_CHECK_ARG(k == 1 || k == 2 || k == 4 || k == 8 || k == 16 || k == 32, "k must be 1, 2, 4, 8, 16 or 32 (a divisor of the 32-edge tile)");
+    GAOT_CHECK_ARG(precision == 0 || precision == 1, "precision must be 0 (fp32) or 1 (bf16 matrix cores)");
+    GAOT_CHECK_ARG(num_queries >= 0, "negative size");
+    GAOT_CHECK_ARG(num_queries <= (int64_t)INT32_MAX / k, "num_queries * k beyond int32 (sample the queries in chunks)");
+    GAOT_CHECK_ARG(y_pos && x_pos && nbr && out && (f_y || mode == MODE_KERNELONLY), "null pointer");
+    GAOT_CHECK_ARG(mode == MODE_LINEAR || src_table, "null src_table");
+    MlpPtrs p;
+    for (int l = 0; l <= mlp->n_hidden; ++l) {
+        p.w[l] = mlp->weight[l];
+        p.b[l] = mlp->bias[l];
+        GAOT_CHECK_ARG(p.w[l] && p.b[l], "null MLP parameter");
+    }
+    if (num_queries == 0) return GAOT_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int lk = __builtin_ctz((unsigned)k);
+    const int64_t num_edges = num_queries * k;
+    int rc = GAOT_OK;
+    if (precision == 1) {
+        rc = gaot_gno_fwd_knn_bf16_dispatch(mlp->n_hidden, mode, p.w, p.b, y_pos, x_pos, f_y, src_table, nbr, lk, num_edges, out, st);
+    } else {
+#define GNO_FWD_CASE(NH_, MODE_)                                                                                      \
+    case NH_ * 3 + MODE_:                                                                                             \
+        rc = launch_fwd_knn<NH_, 64, MODE_>(p, y_pos, x_pos, f_y, src_table, nbr, lk, num_edges, out, st);            \
+        break;
+#define GNO_FWD_CASES(NH_) GNO_FWD_CASE(NH_, MODE_LINEAR) GNO_FWD_CASE(NH_, MODE_NONLINEAR) GNO_FWD_CASE(NH_, MODE_KERNELONLY)
+        switch (mlp->n_hidden * 3 + mode) {
+            GNO_FWD_CASES(1) GNO_FWD_CASES(2) GNO_FWD_CASES(3) GNO_FWD_CASES(4)
+        }
+#undef GNO_FWD_CASES
+#undef GNO_FWD_CASE
+    }
+    if (rc != GAOT_OK) return rc;
+    GAOT_LAUNCH_CHECK();
+    return GAOT_OK;
 }
 
 extern "C" size_t gaot_gno_bwd_workspace_bytes(const gaot_mlp_t* mlp, int64_t num_edges, int64_t num_queries) {

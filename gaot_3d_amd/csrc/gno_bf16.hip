@@ -52,6 +52,8 @@ constexpr int FWD_NW = 12;
 // MODE (gno_common.h): in the nonlinear / kernel-only modes `nl_` begins with one NlFwd and layer 0 starts from b_0 + t[src]
 // WEIGHTED (a WFwd ends the pack): the staged value is alpha_e k_e f[s_e], alpha applied in fp32 after the last layer's accumulator,
 // and the rows are summed, not averaged
+// REGULAR LIST (a KnnFwd ends the pack, gno_common.h): sources from nbr, query = e >> lk, rows finished in the tile; src_s, dst_s, rowptr
+// and part are not read
 template <int NH, int T, int MODE, class... Nl>
 __global__ __launch_bounds__(FWD_NW * 64, 1) void k_gno_fwd_bf16(MlpPtrs mlp, const float* __restrict__ y_pos,
                                                          const float* __restrict__ x_pos, const float* __restrict__ f_y,
@@ -60,6 +62,8 @@ __global__ __launch_bounds__(FWD_NW * 64, 1) void k_gno_fwd_bf16(MlpPtrs mlp, co
                                                          float* __restrict__ part, Nl... nl_) {
     constexpr int C = 32, H = 64, KB = 2, NW = FWD_NW;
     constexpr bool W = pack_has<WFwd, Nl...>;
+    constexpr bool K = pack_has<KnnFwd, Nl...>;
+    static_assert(!(W && K), "no weighted variant on regular lists");
     using L = FwdLdsB<NH>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* stage_all = lds + L::weights_end;             // [NW waves][T][32][C]
@@ -116,8 +120,13 @@ __global__ __launch_bounds__(FWD_NW * 64, 1) void k_gno_fwd_bf16(MlpPtrs mlp, co
         for (int t = 0; t < T; ++t) {
             const int64_t e = mt * 32 * T + 32 * t + l31;
             const bool valid = mt < n_macro && e < E;
-            s_[t] = valid ? src_s[e] : 0;
-            q_[t] = valid ? dst_s[e] : -1;
+            if constexpr (K) {
+                s_[t] = valid ? last_arg(nl_...).nbr[e] : 0;
+                q_[t] = valid ? (int)(e >> last_arg(nl_...).lk) : -1;
+            } else {
+                s_[t] = valid ? src_s[e] : 0;
+                q_[t] = valid ? dst_s[e] : -1;
+            }
         }
     };
     auto gather_pos = [&](const int (&s_)[T], const int (&q_)[T], float (&b_)[T][3]) {
@@ -144,7 +153,7 @@ __global__ __launch_bounds__(FWD_NW * 64, 1) void k_gno_fwd_bf16(MlpPtrs mlp, co
 
             if (hf == 0) {
                 ids[(t * 2 + 0) * 32 + l31] = cs[t];
-                ids[(t * 2 + 1) * 32 + l31] = cq[t];
+                if constexpr (!K) ids[(t * 2 + 1) * 32 + l31] = cq[t];
             }
             cs[t] = ps[t]; cq[t] = pq[t];
         }
@@ -267,7 +276,10 @@ __global__ __launch_bounds__(FWD_NW * 64, 1) void k_gno_fwd_bf16(MlpPtrs mlp, co
         }
         wave_lds_fence();
         if (hf < T) {
-            segment_walk<C>(stage + hf * 32 * C, C, ids + (hf * 2 + 1) * 32, l31, base + 32 * hf, rowptr, out, part, !W);
+            if constexpr (K)
+                fixed_k_rows<C>(stage + hf * 32 * C, C, l31, base + 32 * hf, last_arg(nl_...).lk, E, out);
+            else
+                segment_walk<C>(stage + hf * 32 * C, C, ids + (hf * 2 + 1) * 32, l31, base + 32 * hf, rowptr, out, part, !W);
         }
         wave_lds_fence();
     }
@@ -322,7 +334,56 @@ int launch_fwd_b(const MlpPtrs& p, const float* y_pos, const float* x_pos, const
     return GAOT_OK;
 }
 
+// the regular-list instantiations (a KnnFwd ends the pack): E = num_queries * k, no lists, no partial buffer; launched as launch_fwd_b
+template <int NH, int MODE>
+int launch_fwd_knn_b(const MlpPtrs& p, const float* y_pos, const float* x_pos, const float* f_y, const float* ttab, const int* nbr,
+                     int lk, int64_t E, float* out, hipStream_t st) {
+    constexpr int T = 2, NW = FWD_NW;
+    const size_t lds = fwd_lds_bytes_b(NH, T, NW);
+    auto kern = [] {
+        if constexpr (MODE == MODE_LINEAR) return k_gno_fwd_bf16<NH, T, MODE, KnnFwd>;
+        else return k_gno_fwd_bf16<NH, T, MODE, NlFwd, KnnFwd>;
+    }();
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) {
+            gaot_set_error("gno_fwd_knn (bf16): cannot set dynamic LDS %zu: %s", lds, hipGetErrorString(e));
+            return GAOT_ERR_LAUNCH;
+        }
+        attr_set = true;
+    }
+    const int64_t n_macro = ceil_div(E, 32 * T);
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n_macro, NW), 256));
+    const int* none = nullptr;
+    float* no_part = nullptr;
+    if constexpr (MODE == MODE_LINEAR)
+        GAOT_KLAUNCH(kern, dim3(grid), dim3(NW * 64), lds, st, p, y_pos, x_pos, f_y, none, none, none, E, out, no_part, KnnFwd{nbr, lk});
+    else
+        GAOT_KLAUNCH(kern, dim3(grid), dim3(NW * 64), lds, st, p, y_pos, x_pos, f_y, none, none, none, E, out, no_part, NlFwd{ttab},
+                     KnnFwd{nbr, lk});
+    return GAOT_OK;
+}
+
 }  // namespace
+
+// called from gaot_gno_fwd_knn (gno.hip) when precision == 1; num_edges = num_queries * 2^lk > 0, shapes already validated
+int gaot_gno_fwd_knn_bf16_dispatch(int n_hidden, int mode, const float* const* w, const float* const* b, const float* y_pos,
+                                   const float* x_pos, const float* f_y, const float* ttab, const int32_t* nbr, int lk,
+                                   int64_t num_edges, float* out, hipStream_t st) {
+    MlpPtrs p;
+    for (int l = 0; l <= n_hidden; ++l) { p.w[l] = w[l]; p.b[l] = b[l]; }
+#define GNO_FWDB_CASE(NH_, MODE_) \
+    case NH_ * 3 + MODE_: return launch_fwd_knn_b<NH_, MODE_>(p, y_pos, x_pos, f_y, ttab, nbr, lk, num_edges, out, st);
+#define GNO_FWDB_CASES(NH_) GNO_FWDB_CASE(NH_, MODE_LINEAR) GNO_FWDB_CASE(NH_, MODE_NONLINEAR) GNO_FWDB_CASE(NH_, MODE_KERNELONLY)
+    if (n_hidden >= 1 && n_hidden <= 4 && mode >= 0 && mode <= 2) switch (n_hidden * 3 + mode) {
+        GNO_FWDB_CASES(1) GNO_FWDB_CASES(2) GNO_FWDB_CASES(3) GNO_FWDB_CASES(4)
+    }
+#undef GNO_FWDB_CASES
+#undef GNO_FWDB_CASE
+    gaot_set_error("gaot_gno_fwd_knn (bf16): unsupported n_hidden %d / mode %d", n_hidden, mode);
+    return GAOT_ERR_UNSUPPORTED;
+}
 
 // called from gaot_gno_fwd / gaot_gno_fwd_nl / gaot_gno_fwd_w (gno.hip) when precision == 1; num_edges > 0, shapes already validated;
 // edge_w: null, or the [num_edges] weights of the weighted variant

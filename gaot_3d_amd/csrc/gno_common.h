@@ -55,6 +55,16 @@ struct WBwd {
     const int* s2d;         // [E]: position in the source-sorted order -> position in the dst-sorted order
     float* dalpha;          // [E], dst-sorted; null: not wanted
 };
+// REGULAR-LIST variant of the forward (gaot_gno_fwd_knn): every query has exactly k = 2^lk neighbours, k | 32, listed as
+// nbr[q*k + j] -- the out_idx of gaot_knn_grid, which IS the by-query list of a k-nearest graph (rowptr[q] = q k, dst[e] = e / k, rows
+// in the order a stable sort keeps).  The kernel reads its source ids from nbr, takes the query of edge e as e >> lk and loads no
+// dst_sorted / rowptr; no row is empty or straddles a 32-edge tile, so the rows are finished in the tile (fixed_k_rows below: no
+// partial buffer, no fix-up launch).  A KnnFwd ENDS the forward's pack (after the NlFwd of the nonlinear modes; never with a WFwd);
+// those instantiations are passed null src_s / dst_s / rowptr / part and E = num_queries * k.
+struct KnnFwd {
+    const int* nbr;         // [num_queries * k]
+    int lk;                 // log2(k), 0..5
+};
 template <class T, class... P>
 constexpr bool pack_has = (std::is_same_v<T, P> || ...);
 
@@ -106,6 +116,26 @@ __device__ __forceinline__ void segment_walk(const float* stage, int ld, const i
         if (d >= 0) sum += stage[e * ld + c];
     }
     flush(cur, sum);
+}
+
+// The regular-list epilogue (KnnFwd): the 32 edges of a tile staged as stage[e*ld + c] are 32/k complete rows of k = 2^lk edges, the
+// row that ends at edge e being query (tbase + e) >> lk.  Lane = channel c adds a row's k values in edge order starting from 0.f and
+// divides by (float)k: the operations, in the order, that segment_walk performs on a complete row of degree k, so the two agree bit
+// for bit.  E is a multiple of k: a row lies wholly below E or wholly at / above it (not stored).
+template <int C>
+__device__ __forceinline__ void fixed_k_rows(const float* stage, int ld, int c, int64_t tbase, int lk, int64_t E,
+                                             float* __restrict__ out) {
+    const int km1 = (1 << lk) - 1;
+    const float fk = (float)(1 << lk);
+    float sum = 0.f;
+#pragma unroll 4
+    for (int e = 0; e < 32; ++e) {
+        sum += stage[e * ld + c];
+        if ((e & km1) == km1) {
+            if (tbase + e < E) out[((tbase + e) >> lk) * C + c] = sum / fk;
+            sum = 0.f;
+        }
+    }
 }
 
 // rows with no edges -> 0; rows spanning several tiles -> ordered sum of the tile partials (tiles of 2^SHIFT edges: 32

@@ -105,11 +105,8 @@ class GAOT3D(nn.Module):
         x = GF.PatchifyFn.apply(x, b, d, h, w, p, c, False)
         return x.view(b, d * h * w, c)
 
-    def forward(self, batch, tokens_pos: Optional[torch.Tensor] = None, tokens_batch_idx: Optional[torch.Tensor] = None,
-                query_coord_pos: Optional[torch.Tensor] = None, query_coord_batch_idx: Optional[torch.Tensor] = None,
-                condition: Optional[float] = None) -> torch.Tensor:
-        num_graphs = batch.num_graphs
-        device = batch.pos.device
+    def _tokens(self, num_graphs: int, device, tokens_pos: Optional[torch.Tensor], tokens_batch_idx: Optional[torch.Tensor]):
+        """the token coordinates of every graph of the batch back to back, and their batch vector"""
         if tokens_pos is None:
             assert tokens_batch_idx is None, "tokens_batch_idx should be None if tokens_pos is None"
             tokens_pos = self.latent_tokens
@@ -125,16 +122,45 @@ class GAOT3D(nn.Module):
         else:
             assert tokens_pos.shape[0] == tokens_batch_idx.shape[0], "tokens_pos and tokens_batch_idx must have same length"
             lat, lat_bidx = tokens_pos.to(device), tokens_batch_idx.to(device)
+        return lat.contiguous(), lat_bidx
+
+    def _latent(self, batch, lat, lat_bidx, condition):
+        rndata = self.encoder(batch=batch, latent_tokens_pos=lat, latent_tokens_batch_idx=lat_bidx)
+        rndata = self.process(rndata=rndata, condition=condition)
+        return rndata.view(-1, self.node_latent_size)
+
+    def latent(self, batch, tokens_pos: Optional[torch.Tensor] = None, tokens_batch_idx: Optional[torch.Tensor] = None,
+               condition: Optional[float] = None) -> torch.Tensor:
+        """The first half of ``forward``: encoder and Transformer, the processed token features of every graph as rows
+        [B * D*H*W, lifting_channels].  Ordinary autograd semantics.  With ``sample`` it makes the neural-field use of a trained model
+        (reference trainer test loop, src/trainer/stat.py:604-620): encode a sample once, read the field wherever it is wanted."""
+        lat, lat_bidx = self._tokens(batch.num_graphs, batch.pos.device, tokens_pos, tokens_batch_idx)
+        return self._latent(batch, lat, lat_bidx, condition)
+
+    def sample(self, latent: torch.Tensor, query_pos: torch.Tensor, tokens_pos: Optional[torch.Tensor] = None,
+               chunk_points: Optional[int] = None) -> torch.Tensor:
+        """Predictions [Nq, output_size] of ONE encoded sample (``latent`` [D*H*W, lifting_channels] from ``latent``) at any query
+        coordinates, forward only (no autograd graph): ``MAGNODecoder.sample``.  ``tokens_pos``: the tokens ``latent`` was computed
+        with (default: the model's grid); ``chunk_points``: queries per pass (None: one pass of at most 2^20 points)."""
+        if latent.dim() != 2 or latent.shape[0] != self.num_latent_tokens:
+            raise ValueError(f"sample: latent {tuple(latent.shape)} is not ONE sample's [{self.num_latent_tokens}, "
+                             f"{self.node_latent_size}] token rows (sample the graphs of a batch one by one)")
+        lat, _ = self._tokens(1, latent.device, tokens_pos, None)
+        return self.decoder.sample(latent, query_pos.to(latent.device), lat, chunk_points=chunk_points)
+
+    def forward(self, batch, tokens_pos: Optional[torch.Tensor] = None, tokens_batch_idx: Optional[torch.Tensor] = None,
+                query_coord_pos: Optional[torch.Tensor] = None, query_coord_batch_idx: Optional[torch.Tensor] = None,
+                condition: Optional[float] = None) -> torch.Tensor:
+        num_graphs = batch.num_graphs
+        device = batch.pos.device
+        lat, lat_bidx = self._tokens(num_graphs, device, tokens_pos, tokens_batch_idx)
         if query_coord_pos is None:
             q_pos, q_bidx = batch.pos, batch.batch
         else:
             assert query_coord_batch_idx is not None, "query_coord_batch_idx is required if query_coord_pos is provided"
             assert query_coord_pos.shape[0] == query_coord_batch_idx.shape[0]
             q_pos, q_bidx = query_coord_pos.to(device), query_coord_batch_idx.to(device)
-        lat = lat.contiguous()
-        rndata = self.encoder(batch=batch, latent_tokens_pos=lat, latent_tokens_batch_idx=lat_bidx)
-        rndata = self.process(rndata=rndata, condition=condition)
-        flat = rndata.view(-1, self.node_latent_size)
+        flat = self._latent(batch, lat, lat_bidx, condition)
         shard_group = getattr(self, "_shard_group", None)
         if shard_group is not None and getattr(self, "_seq_group", None) is None:
             # decoder runs on this rank's points only: its latent gradient is a partial sum (sequence-parallel: the

@@ -16,6 +16,9 @@ projection rows.  Coordinates that require grad are refused with use_attn.
 Every other variant the reference offers (other MLP shapes, MLP dropout in training, f_y=None)
 runs the general path: per-edge tensors in dst-sorted order, the MLP on the GEMM kernels, gather / segment /
 element-wise glue and its autograd in csrc/edgeops.hip (gaot_3d_amd/edgeops.py), with the same ``_attn_weights`` under use_attn.
+``forward_knn`` is the forward alone on a regular k-neighbour list (the [n, k] ids of ``graph.knn_to_grid`` as they stand, k | 32):
+the same operands, one ``gaot_gno_fwd_knn`` launch per 32-channel pass, no edge list or sorted lists, bit-identical to ``forward`` on
+the graph of those lists -- what ``MAGNODecoder.sample`` streams query chunks through.
 HIP only, no CPU fallback."""
 from typing import Optional
 
@@ -142,6 +145,23 @@ class IntegralTransform(nn.Module):
                                            edge_w=self._attn_weights(y_pos, x_pos, y3, x3, graph))
         return self._forward_general(fcs, y_pos, x_pos, f_y, graph)
 
+    def forward_knn(self, y_pos, x_pos, nbr, k: int, f_y: Optional[torch.Tensor] = None):
+        """The transform's forward on a REGULAR neighbour list, without an edge list: ``nbr`` int32 [N_x * k] with nbr[q*k + j] = the
+        j-th source of query q (``graph.knn_to_grid`` / ``ops.knn_grid`` output as it stands), k in ``ops.GNO_KNN_K``.  The operands
+        are prepared exactly as in ``_forward_fused`` (zero padding of coordinates / hidden widths / channel blocks, t = W_0f f_y of
+        the nonlinear types) and every 32-channel pass is one ``ops.gno_forward_knn`` launch: bit-identical to ``forward`` on the graph
+        of the same lists.  Forward only (nothing is recorded for autograd); runs exactly when ``_fused_plan`` is not None and raises
+        otherwise -- there is no general path on these lists."""
+        if self.transform_type not in ("linear", "nonlinear", "nonlinear_kernelonly"):
+            raise ValueError(f"Invalid transform_type: {self.transform_type}")
+        fcs = list(self.channel_mlp.fcs)
+        with torch.no_grad():
+            plan = self._fused_plan(fcs, f_y, y_pos, x_pos)
+            if plan is None or int(k) not in ops.GNO_KNN_K:
+                raise NotImplementedError("IntegralTransform.forward_knn: only the transforms the fused kernels evaluate (_fused_plan) "
+                                          f"on lists of k in {ops.GNO_KNN_K} neighbours per query; use forward() with an edge_index")
+            return self._forward_fused(fcs, y_pos, x_pos, f_y, None, *plan, knn=(nbr, int(k)))
+
     @staticmethod
     def _pad3(pos):
         """coordinates of dimension 1 / 2 padded with zeros to the kernels' 3-D rows"""
@@ -212,13 +232,17 @@ class IntegralTransform(nn.Module):
         return (not self.use_attn and self.transform_type == "linear" and f_y is not None and dims[0] == (64, 6)
                 and dims[-1] == (32, 64) and f_y.shape[1] == 32)
 
-    def _forward_fused(self, fcs, y_pos, x_pos, f_y, graph, cd: int, c: int, edge_w=None):
+    def _forward_fused(self, fcs, y_pos, x_pos, f_y, graph, cd: int, c: int, edge_w=None, knn=None):
         """``edge_w`` [E] (dst-sorted order): the weighted transform of use_attn -- every pass runs ``GnoWFn`` with the same weights and
-        autograd adds the passes' gradients with respect to them (padded channels carry zero grad_out and zero f: exact zeros)"""
+        autograd adds the passes' gradients with respect to them (padded channels carry zero grad_out and zero f: exact zeros).
+        ``knn`` = (nbr, k) (``forward_knn``; ``graph`` is None, no autograd): the passes run ``ops.gno_forward_knn`` on the regular
+        list instead of the autograd Functions."""
         w2 = lambda fc: fc.weight[:, :, 0] if fc.weight.dim() == 3 else fc.weight    # Conv1d(k=1) storage of mlp_type='channel'
         pad_hidden = any(fc.weight.shape[0] != 64 for fc in fcs[:-1])
         tt = self.transform_type
         if tt == "linear" and cd == 3 and c == 32 and not pad_hidden and edge_w is None:   # the shipped shape: straight through
+            if knn is not None:
+                return ops.gno_forward_knn(0, [w2(fc) for fc in fcs], [fc.bias for fc in fcs], y_pos, x_pos, f_y, None, *knn)
             params = []
             for fc in fcs:
                 params += [fc.weight, fc.bias]
@@ -259,7 +283,10 @@ class IntegralTransform(nn.Module):
                 wb = torch.nn.functional.pad(wb, (0, 0, 0, 32 - n))
                 bb = torch.nn.functional.pad(bb, (0, 32 - n))
                 fb = None if fb is None else torch.nn.functional.pad(fb, (0, 32 - n))
-            if edge_w is not None:
+            if knn is not None:
+                o = ops.gno_forward_knn(tt, [w0.contiguous(), *mid[0::2], wb.contiguous()], [b0, *mid[1::2], bb.contiguous()], y3, x3,
+                                        None if fb is None else fb.contiguous(), t, *knn)
+            elif edge_w is not None:
                 o = GF.GnoWFn.apply(tt, None if fb is None else fb.contiguous(), t, edge_w, y3, x3, graph, w0.contiguous(), b0, *mid,
                                     wb.contiguous(), bb.contiguous())
             elif tt == "linear":

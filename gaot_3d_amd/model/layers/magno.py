@@ -329,10 +329,16 @@ class MAGNODecoder(nn.Module):
 
     def forward(self, rndata_flat, phys_pos_query, batch_idx_phys_query, latent_tokens_pos, latent_tokens_batch_idx,
                 batch=None) -> torch.Tensor:
+        return self._decode(rndata_flat, phys_pos_query, batch_idx_phys_query, latent_tokens_pos, latent_tokens_batch_idx, batch,
+                            self.precompute_edges)
+
+    def _decode(self, rndata_flat, phys_pos_query, batch_idx_phys_query, latent_tokens_pos, latent_tokens_batch_idx, batch,
+                precomputed: bool) -> torch.Tensor:
+        """``forward``; ``precomputed``: the edge lists are the batch's ``decoder_edge_index_s*`` (else built here for the queries)"""
         device = rndata_flat.device
         outs = []
         for si, scale in enumerate(self.scales):
-            if self.precompute_edges:
+            if precomputed:
                 attr = f"decoder_edge_index_s{si}"
                 if not hasattr(batch, attr):
                     raise AttributeError(f"Batch object missing pre-computed '{attr}'")
@@ -357,3 +363,93 @@ class MAGNODecoder(nn.Module):
                 dec = GF.cat_linear([dec, geo], self.recovery.fcs[0].weight, self.recovery.fcs[0].bias, precision=0)
             outs.append(dec)
         return self.projection.forward_rows(_mix_scales(self, outs, phys_pos_query))
+
+    SAMPLE_CHUNK = 1 << 20      # queries per pass of ``sample`` when the caller names no chunk size
+
+    def _sample_grid(self, latent_tokens_pos):
+        """The regular-grid descriptor of the tokens for the streaming path of ``sample`` (None: not the regular grid).  Found once
+        per token tensor (object identity + in-place version, as ``graph_for`` keys its cache): ``as_latent_grid`` reads the grid's
+        corners on the host, which is a synchronisation and illegal while a stream is being captured -- a capture must follow one
+        eager call with the same token tensor."""
+        from ... import graph as device_graph
+        from ..._lib import GaotError
+        dims = getattr(self, "latent_dims", None)
+        if dims is None or not latent_tokens_pos.is_cuda or latent_tokens_pos.dim() != 2 or latent_tokens_pos.shape[1] != 3:
+            return None
+        ent = self.__dict__.get("_gaot_sample_grid")
+        if ent is not None and ent[0] is latent_tokens_pos and ent[1] == latent_tokens_pos._version:
+            return ent[2]
+        if torch.cuda.is_current_stream_capturing():
+            raise GaotError("MAGNODecoder.sample: the token grid has not been described yet; call sample once eagerly with this "
+                            "token tensor before capturing it in a graph")
+        try:
+            grid = device_graph.as_latent_grid(latent_tokens_pos, dims)
+        except GaotError:
+            grid = None
+        self.__dict__["_gaot_sample_grid"] = (latent_tokens_pos, latent_tokens_pos._version, grid)
+        return grid
+
+    def _project_into(self, x, out) -> None:
+        """out[:] = projection(x), rows in blocks.  Unless the projection MLP runs as one fused launch (``Mlp2Fn``, bf16 mode) its
+        hidden layer [rows, projection_channels] goes through memory, 8 x the size of x at the shipped 32 -> 256: the blocks keep
+        that tensor no larger than x itself, so that a chunk's footprint stays its ids, its GNO rows and its predictions."""
+        fcs = self.projection.fcs
+        n, hid = x.shape[0], max([fc.weight.shape[0] for fc in fcs[:-1]], default=0)
+        step = n
+        if hid > x.shape[1] and not GF.Mlp2Fn.eligible(x, fcs, self.projection.non_linearity):
+            step = max(1024, n * x.shape[1] // hid)
+        for j in range(0, n, step):
+            out[j:j + step] = self.projection.forward_rows(x[j:j + step])
+
+    @torch.no_grad()
+    def sample(self, rndata_flat, query_pos, latent_tokens_pos, chunk_points: Optional[int] = None) -> torch.Tensor:
+        """Predictions [Nq, out_channels] of ONE sample's processed token features ``rndata_flat`` [M, C] at any query coordinates
+        ``query_pos`` [Nq, coord_dim]: what ``forward`` computes with edges built for the queries, forward only (no autograd graph is
+        recorded, the result never requires grad), ``chunk_points`` queries at a time (None: ``SAMPLE_CHUNK``) into one preallocated
+        result.
+
+        STREAMING path -- decoder strategy 'knn' with k_neighbors in ``ops.GNO_KNN_K``, tokens on the model's regular grid, no
+        neighbour sampling, no decoder GeoEmbed, a transform the fused kernels evaluate (``IntegralTransform._fused_plan``): per
+        chunk one ``knn_to_grid`` launch, whose [n, k] id array IS the by-query neighbour list, one ``forward_knn`` launch per
+        32-channel pass, the scale mix and the projection MLP.  No edge_index, no sorted lists, nothing sized by Nq but the result.
+        (The knn lists do not depend on the scale, so a multi-scale decoder evaluates the transform once and mixes that one result
+        with itself, as ``forward`` does with equal operands.)
+        Every other configuration FALLS BACK to ``forward``'s route -- ``get_neighbor_strategy`` + ``build_graph`` + the general
+        decoder -- chunked in the same way.  The exception is a 'statistical' decoder GeoEmbed: its z-score runs over ALL query rows
+        (geoembed.py:177-180), so it takes the queries in one piece whatever ``chunk_points`` says.
+        'reverse' raises ValueError: it is the flip of a graph of the ENCODER's points and is undefined for other queries."""
+        from ... import graph as device_graph
+        from ... import ops
+        if self.decoder_strategy == "reverse":
+            raise ValueError("MAGNODecoder.sample: decoder strategy 'reverse' is the flip of the encoder's graph of the sample's own "
+                             "points and is undefined for other query points")
+        if chunk_points is not None and int(chunk_points) < 1:
+            raise ValueError(f"chunk_points must be positive, got {chunk_points}")
+        nq = int(query_pos.shape[0])
+        chunk = int(chunk_points) if chunk_points is not None else self.SAMPLE_CHUNK
+        lat = latent_tokens_pos
+        k = int(self.k_neighbors)
+        grid = None
+        if (self.decoder_strategy == "knn" and k in ops.GNO_KNN_K and self.sampling_strategy is None and not self.use_geoembed
+                and rndata_flat.is_cuda and query_pos.dim() == 2 and query_pos.shape[1] == 3 and query_pos.dtype == torch.float32
+                and lat.dtype == torch.float32 and lat.is_contiguous() and rndata_flat.shape[0] == lat.shape[0]
+                and self.gno._fused_plan(list(self.gno.channel_mlp.fcs), rndata_flat, lat, query_pos) is not None):
+            grid = self._sample_grid(lat)
+            if grid is not None and grid.num_tokens != lat.shape[0]:
+                grid = None                                   # a batch of several graphs: no streaming
+        out = torch.empty(nq, self.out_channels, dtype=rndata_flat.dtype, device=rndata_flat.device)
+        if grid is not None:
+            for i in range(0, nq, chunk):
+                q = query_pos[i:i + chunk]
+                nbr = device_graph.knn_to_grid(q, grid, k)
+                dec = self.gno.forward_knn(lat, q, nbr, k, rndata_flat)
+                self._project_into(_mix_scales(self, [dec] * len(self.scales), q), out[i:i + chunk])
+            return out
+        if self.use_geoembed and self.geoembed.method == "statistical":
+            chunk = max(nq, 1)
+        lat_bidx = torch.zeros(lat.shape[0], dtype=torch.long, device=lat.device)
+        for i in range(0, nq, chunk):
+            q = query_pos[i:i + chunk]
+            q_bidx = torch.zeros(q.shape[0], dtype=torch.long, device=q.device)
+            out[i:i + chunk] = self._decode(rndata_flat, q, q_bidx, lat, lat_bidx, None, False)
+        return out

@@ -280,6 +280,51 @@ def gno_nl_forward(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Opt
     return out
 
 
+GNO_KNN_K = (1, 2, 4, 8, 16, 32)      # the divisors of the kernels' 32-edge tile (gaot_gno_fwd_knn)
+
+
+def gno_forward_knn(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], src_table: Optional[Tensor],
+                    nbr: Tensor, k: int, precision: Optional[int] = None) -> Tensor:
+    """the fused transform's FORWARD on a regular neighbour list (gaot_gno_fwd_knn): ``nbr`` int32 [n_query * k] with
+    nbr[q*k + j] = the j-th source of query q (``knn_grid``'s output as it stands), k in ``GNO_KNN_K``.  ``mode``: 0 / 'linear'
+    (``src_table`` None), 'nonlinear', 'nonlinear_kernelonly' (``f_y`` None), operands as in ``gno_forward`` / ``gno_nl_forward``.
+    One launch, no edge list, no sorted lists, no workspace; bit-identical to those two on ``build_graph`` of the same lists.  No
+    backward."""
+    lib = _lib.load()
+    prec = _PRECISION["mode"] if precision is None else precision
+    md = {"linear": 0, **GNO_MODES}.get(mode, mode)
+    if md not in (0, 1, 2):
+        raise GaotError(f"gno_forward_knn: mode must be 'linear' or one of {tuple(GNO_MODES)}, got {mode!r}")
+    m, keep = _mlp_struct(weights, biases)
+    y_pos = _req(y_pos, torch.float32, "y_pos")
+    x_pos = _req(x_pos, torch.float32, "x_pos")
+    nbr = _req(nbr, torch.int32, "nbr")
+    k = int(k)
+    q = int(x_pos.shape[0])
+    if y_pos.dim() != 2 or x_pos.dim() != 2 or y_pos.shape[1] != 3 or x_pos.shape[1] != 3:
+        raise GaotError(f"y_pos / x_pos must be [*, 3], got {tuple(y_pos.shape)} / {tuple(x_pos.shape)}")
+    if nbr.numel() != q * k:
+        raise GaotError(f"nbr must hold {q} x {k} ids, got {nbr.numel()}")
+    n_src = int(y_pos.shape[0])
+    if md != 2:
+        f_y = _req(f_y, torch.float32, "f_y")
+        if tuple(f_y.shape) != (n_src, m.channels):
+            raise GaotError(f"f_y must be [{n_src}, {m.channels}], got {tuple(f_y.shape)}")
+    else:
+        f_y = None
+    if md != 0:
+        src_table = _req(src_table, torch.float32, "src_table")
+        if tuple(src_table.shape) != (n_src, 64):
+            raise GaotError(f"src_table must be [{n_src}, 64], got {tuple(src_table.shape)}")
+    else:
+        src_table = None
+    out = torch.empty(q, m.channels, dtype=torch.float32, device=x_pos.device)
+    with _timed(f"gno_fwd_knn{f'_nl{md}' if md else ''}_nh{m.n_hidden}"):
+        check(lib.gaot_gno_fwd_knn(C.byref(m), md, _ptr(y_pos), _ptr(x_pos), _ptr(f_y), _ptr(src_table), _ptr(nbr), k, q, _ptr(out),
+                                   prec, _stream()), "gaot_gno_fwd_knn")
+    return out
+
+
 def gno_nl_backward(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], src_table: Tensor, grad_out: Tensor,
                     g: BipartiteGraph, precision: Optional[int] = None, coords: bool = False):
     """-> (grad_f_y, grad_src_table, [grad_w...], [grad_b...]); with ``coords`` also (grad_y_pos, grad_x_pos) appended.

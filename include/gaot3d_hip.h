@@ -5,6 +5,9 @@
  * enqueues on the given hipStream_t and returns without synchronising.  Return value: 0 = ok,
  * otherwise an error code; gaot_last_error() gives the message (thread local).
  *
+ * Forward-only use of a trained model (sampling the decoded field at arbitrary points) needs no edge list:
+ * gaot_knn_grid writes the regular k-neighbour list that gaot_gno_fwd_knn consumes as it stands.
+ *
  * Each entry point names the reference interface it stands in for (paths relative to the
  * reference repo Shizheng-Wen/GAOT-3D); the Python host side (gaot_3d_amd/model) mirrors the
  * reference's src/model operator API on top of these.
@@ -142,6 +145,19 @@ int gaot_gno_bwd_w(const gaot_mlp_t* mlp /* host */, int mode, const float* y_po
                    int64_t num_sources, int64_t num_queries, float* grad_f_y, float* grad_src_table,
                    const gaot_mlp_grad_t* grads /* host */, float* grad_edge_w /* [num_edges] or null */, int precision,
                    void* workspace, size_t workspace_bytes, gaot_stream_t stream);
+
+/* The forward of the (unweighted) transform on a REGULAR k-neighbour list, for sampling a decoded field without an edge list:
+ * every query has exactly k neighbours, nbr[q*k + j] = the j-th source of query q -- the out_idx of gaot_knn_grid as it stands, which
+ * is the by-query list of a k-nearest graph (rowptr[q] = q k, dst[e] = e / k, rows in the order a stable sort keeps).
+ *   out[q,:] = (1/k) sum_{j < k} k_e * f_y[nbr[q*k + j],:]        mode 0 (linear: src_table null), 1, 2 as in gaot_gno_fwd_nl
+ * k in {1, 2, 4, 8, 16, 32}: a divisor of the kernels' 32-edge tile, so no row straddles a tile and every row is finished inside
+ * the one launch -- no dst_sorted / rowptr loads, no partial buffer, no fix-up launch, no workspace.  The per-edge arithmetic and
+ * the order of the sum inside a row are those of gaot_gno_fwd / gaot_gno_fwd_nl: on a graph built from the same lists the results
+ * agree bit for bit, in both precisions.  1 <= n_hidden <= 4, hidden 64, channels 32; num_queries * k must fit int32 (sample in
+ * chunks beyond that).  Forward only: there is no backward on these lists. */
+int gaot_gno_fwd_knn(const gaot_mlp_t* mlp /* host */, int mode, const float* y_pos, const float* x_pos, const float* f_y,
+                     const float* src_table, const int32_t* nbr /* [num_queries * k] */, int k, int64_t num_queries,
+                     float* out /* [num_queries, channels] */, int precision, gaot_stream_t stream);
 
 /* Dot-product attention scores of the attention-weighted transform (reference integral_transform.py:128-137, use_attn with
  * attention_type "dot_product") as a bilinear form of the homogeneous endpoint coordinates (csrc/gno_attn.hip):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Kernel microbenchmarks at the configs[1] shapes (for rocprofv3 / quick A-B): attention fwd+bwd, GEMM shapes, GNO, PointNet GeoEmbed,
-the attention-weighted GNO."""
+the attention-weighted GNO, the forward-only decoder (decoder_sample)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 if os.environ.get("MB_TREE"):      # measure another checkout's package (gno_weighted: the parent commit's) with this script
@@ -443,3 +443,58 @@ elif what == "gno_weighted":
                     res[f"{side}_nh{nh}_E{ei.shape[1]}/{prec}/{tt}/{at}/attn"] = measure(it, yp, xp, f, g, go)
                     del it
     print(json.dumps(res))
+elif what == "decoder_sample":
+    # From query coordinates to predictions under no_grad on the configs[1] decoder (latent 64x64x32 tokens, C = 32, knn k = 8, kernel
+    # MLP hidden [64, 64], projection 32 -> 256 -> 1) at 500 K and 8 M random query points, both precisions:
+    #   (a) the existing route: neighbour strategy (knn_to_grid + edge_index) -> build_graph (two radix sorts) -> decoder;
+    #   (b) MAGNODecoder.sample: per chunk knn_to_grid -> gaot_gno_fwd_knn -> projection, no edge list (MB_CHUNK points, default
+    #       the method's own default).
+    # (a) and (b) alternate in this one process after a warm-up of each; device events around synchronised work; `reps` rounds; a row
+    # is the median with min / max, the peak is the rise of allocated memory over the inputs.  Kept in
+    # profiles/decoder_sample_microbench.txt.
+    from gaot_3d_amd.data import latent_grid
+    from gaot_3d_amd.model.layers.magno import MAGNOConfig, MAGNODecoder
+    latent = (64, 64, 32)
+    cfg = MAGNOConfig(gno_coord_dim=3, lifting_channels=32, mlp_type="linear", use_geoembed=[True, False], neighbor_strategy="knn",
+                      k_neighbors=8, out_gno_channel_mlp_hidden_layers=[64, 64], precompute_edges=False)
+    dec = MAGNODecoder(in_channels=32, out_channels=1, gno_config=cfg).to(dev).eval()
+    dec.latent_dims = latent
+    tokens = latent_grid(latent).to(dev)
+    m = tokens.shape[0]
+    rn = torch.randn(m, 32, device=dev)
+    lat_bidx = torch.zeros(m, dtype=torch.long, device=dev)
+    chunk = int(os.environ["MB_CHUNK"]) if os.environ.get("MB_CHUNK") else None
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); out = fn(); e1.record()
+        torch.cuda.synchronize()
+        peak = torch.cuda.max_memory_allocated() - base
+        return e0.elapsed_time(e1), peak, out
+
+    for nq in (500000, 8000000):
+        q = torch.rand(nq, 3, device=dev) * 2 - 1
+        q_bidx = torch.zeros(nq, dtype=torch.long, device=dev)
+        for prec in ("fp32", "bf16"):
+            gaot_3d_amd.set_precision(prec)
+            with torch.no_grad():
+                route_a = lambda: dec._decode(rn, q, q_bidx, tokens, lat_bidx, None, False)
+                route_b = lambda: dec.sample(rn, q, tokens, chunk_points=chunk)
+                ra, rb = timed(route_a)[2], timed(route_b)[2]          # warm-up, and the two routes agree
+                diff = (ra - rb).abs().max().item()
+                del ra, rb
+                ta, tb, pa, pb = [], [], 0, 0
+                for _ in range(reps):
+                    t, p, _o = timed(route_a); ta.append(t); pa = max(pa, p); del _o
+                    t, p, _o = timed(route_b); tb.append(t); pb = max(pb, p); del _o
+            ta.sort(); tb.sort()
+            ma, mb = ta[len(ta) // 2], tb[len(tb) // 2]
+            print(f"Nq={nq} {prec}: (a) strategy + build_graph + decoder {ma:9.3f} ms (min {ta[0]:.3f}, max {ta[-1]:.3f}, spread "
+                  f"{100 * (ta[-1] - ta[0]) / ma:.1f} %), peak {pa / 2**20:9.1f} MiB")
+            print(f"Nq={nq} {prec}: (b) sample (chunk {chunk or dec.SAMPLE_CHUNK})      {mb:9.3f} ms (min {tb[0]:.3f}, max {tb[-1]:.3f}, spread "
+                  f"{100 * (tb[-1] - tb[0]) / mb:.1f} %), peak {pb / 2**20:9.1f} MiB  = {mb / ma:.3f} x (a) in time, {pb / max(pa, 1):.3f} x in "
+                  f"peak memory; max|a - b| = {diff:.1e}", flush=True)
+        del q, q_bidx
