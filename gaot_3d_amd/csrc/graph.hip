@@ -8,6 +8,8 @@
 //                                                   enumerate per point, stable-sort by token (csr_impl.h), keep the
 //                                                   first cap points of every token, compact
 //   'bidirectional' = coalesce(cat(knn, radius)) (219-220, 292-293): two stable sorts + adjacent-unique + compact.
+//            On the DECODER side both sets belong to the query, so the by-query list of that graph can also be written row by
+//            row (k_nbr_union_grid: sorted union of a query's two sets) -- the forward-only route of MAGNODecoder.sample.
 // Distances use the ACTUAL token coordinates (gathered from the token array), the grid descriptor only bounds the
 // search window; the window grows until the k-th distance is provably inside it, so the result is exact.
 // Tie rules (torch_cluster leaves them to the implementation): knn orders by (distance, token index); radius keeps the
@@ -30,14 +32,17 @@ __device__ __forceinline__ float dist2(const float* __restrict__ tok, int lin, f
     return dx * dx + dy * dy + dz * dz;
 }
 
+// ---- the two per-point searches as device functions: k_knn_grid / k_radius_grid and the per-query union (k_nbr_union_grid) run
+// the SAME window, distance and tie code, so a pair is in or out of every list by one floating-point comparison ----
+
+// ids[0 .. K) = the K nearest tokens of point p, ascending by (distance, token index).  K = capacity of the register lists (an
+// instantiated size >= kout); the first kout entries of the sorted top-K list ARE the top-kout list, so any k <= 64 runs on the
+// next instantiated capacity (torch_cluster takes any k, magno.py:183-189)
 template <int K>
-__global__ __launch_bounds__(256) void k_knn_grid(const float* __restrict__ pos, int64_t N, GridDesc g,
-                                                  const float* __restrict__ tok, int* __restrict__ out, int kout) {
-    // K = capacity of the register list (an instantiated size >= kout); the first kout entries of the sorted top-K list ARE
-    // the top-kout list, so any k <= 64 runs on the next instantiated capacity (torch_cluster takes any k, magno.py:183-189)
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    const float p[3] = {pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]};
+__device__ __forceinline__ void knn_grid_select(const float (&p)[3], const GridDesc& g, const float* __restrict__ tok, int kout,
+                                                int (&ids)[K]) {
+    float bd[K];
+    int bi[K];
     float f[3];
     int base[3];
 #pragma unroll
@@ -45,8 +50,6 @@ __global__ __launch_bounds__(256) void k_knn_grid(const float* __restrict__ pos,
         f[a] = (p[a] - g.lo[a]) * g.inv_step[a];
         base[a] = clampi((int)rintf(f[a]), 0, g.dim[a] - 1);
     }
-    float bd[K];
-    int bi[K];
     for (int w = 1;; ++w) {
 #pragma unroll
         for (int j = 0; j < K; ++j) { bd[j] = FLT_MAX; bi[j] = 0x7fffffff; }
@@ -60,6 +63,12 @@ __global__ __launch_bounds__(256) void k_knn_grid(const float* __restrict__ pos,
             if (c0[a] > 0) { whole = false; bound = fminf(bound, (f[a] - (float)(c0[a] - 1)) * g.step[a]); }
             if (c1[a] < g.dim[a] - 1) { whole = false; bound = fminf(bound, ((float)(c1[a] + 1) - f[a]) * g.step[a]); }
         }
+        // `bound` is read after the search only; left alone the compiler sinks its arithmetic below the loops and keeps the six
+        // base -/+ w values alive across them for it: 6 more VGPRs, a wave per SIMD less at K = 8, 16 and 64.  Pinned here it is
+        // one live register, and so is each base[a] instead of the values derived from it (empty statements: no instruction, the
+        // values are unchanged; K = 64 stays at three waves per SIMD without scratch)
+        asm volatile("" : "+v"(bound));
+        asm volatile("" : "+v"(base[0]), "+v"(base[1]), "+v"(base[2]));
         for (int cd = c0[0]; cd <= c1[0]; ++cd)
             for (int ch = c0[1]; ch <= c1[1]; ++ch)
                 for (int cw = c0[2]; cw <= c1[2]; ++cw) {
@@ -87,21 +96,27 @@ __global__ __launch_bounds__(256) void k_knn_grid(const float* __restrict__ pos,
         if (whole || (bound > 0.f && kth < b * b)) break;
     }
 #pragma unroll
+    for (int j = 0; j < K; ++j) ids[j] = bi[j];
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void k_knn_grid(const float* __restrict__ pos, int64_t N, GridDesc g,
+                                                  const float* __restrict__ tok, int* __restrict__ out, int kout) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const float p[3] = {pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]};
+    int bi[K];
+    knn_grid_select<K>(p, g, tok, kout, bi);
+#pragma unroll
     for (int j = 0; j < K; ++j)
         if (j < kout) out[i * kout + j] = bi[j];
 }
 
-// tokens within `radius` of point i, ascending token index; FILL == false: counts[i] = min(count, cap);
-// FILL == true: writes (i, token) pairs at offsets[i]
-template <bool FILL>
-__global__ __launch_bounds__(256) void k_radius_grid(const float* __restrict__ pos, int64_t N, GridDesc g,
-                                                     const float* __restrict__ tok, float radius, int cap,
-                                                     int* __restrict__ counts, const int* __restrict__ offsets,
-                                                     int* __restrict__ out_center, int* __restrict__ out_other) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    const float px = pos[3 * i], py = pos[3 * i + 1], pz = pos[3 * i + 2];
-    const float p[3] = {px, py, pz};
+// the tokens with d <= radius of point p in ascending token index, the first `cap` of them: emit(n, token) for the n-th; -> how many
+template <class Emit>
+__device__ __forceinline__ int radius_grid_visit(const float (&p)[3], const GridDesc& g, const float* __restrict__ tok, float radius,
+                                                 int cap, Emit&& emit) {
+    const float px = p[0], py = p[1], pz = p[2];
     int c0[3], c1[3];
     const float rr = radius * (1.0f + 1e-4f);
 #pragma unroll
@@ -114,16 +129,79 @@ __global__ __launch_bounds__(256) void k_radius_grid(const float* __restrict__ p
     }
     const float r2 = radius * radius;
     int n = 0;
-    const int o = FILL ? offsets[i] : 0;
     for (int cd = c0[0]; cd <= c1[0] && n < cap; ++cd)
         for (int ch = c0[1]; ch <= c1[1] && n < cap; ++ch)
             for (int cw = c0[2]; cw <= c1[2] && n < cap; ++cw) {
                 const int lin = (cd * g.dim[1] + ch) * g.dim[2] + cw;
                 if (dist2(tok, lin, px, py, pz) <= r2) {
-                    if (FILL) { out_center[o + n] = (int)i; out_other[o + n] = lin; }
+                    emit(n, lin);
                     ++n;
                 }
             }
+    return n;
+}
+
+// tokens within `radius` of point i, ascending token index; FILL == false: counts[i] = min(count, cap);
+// FILL == true: writes (i, token) pairs at offsets[i]
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_radius_grid(const float* __restrict__ pos, int64_t N, GridDesc g,
+                                                     const float* __restrict__ tok, float radius, int cap,
+                                                     int* __restrict__ counts, const int* __restrict__ offsets,
+                                                     int* __restrict__ out_center, int* __restrict__ out_other) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const float p[3] = {pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]};
+    const int o = FILL ? offsets[i] : 0;
+    const int n = radius_grid_visit(p, g, tok, radius, cap, [&](int at, int lin) {
+        if (FILL) { out_center[o + at] = (int)i; out_other[o + at] = lin; }
+    });
+    if (!FILL) counts[i] = n;
+}
+
+// The by-query row of a 'bidirectional' decoder graph (coalesce(cat(knn, radius)) sorted by query, magno.py:292-293) written
+// directly: the kout nearest tokens of query i (knn_grid_select) united with its radius tokens (radius_grid_visit: d <= radius, the
+// `cap` lowest indices), every token once, ascending token index.  FILL == false: counts[i] = row length (<= kout + cap);
+// FILL == true: (i, token) pairs at offsets[i].  The radius tokens arrive in ascending order; the knn tokens are sorted by index in
+// registers (odd-even transposition network, unused capacity = INT_MAX behind every index) and merged in front of them: bi[0] is
+// always the lowest knn token not yet written, taking it shifts the list down -- every index into bi is a compile-time one.
+template <int K, bool FILL>
+__global__ __launch_bounds__(256) void k_nbr_union_grid(const float* __restrict__ pos, int64_t N, GridDesc g,
+                                                        const float* __restrict__ tok, int kout, float radius, int cap,
+                                                        int* __restrict__ counts, const int* __restrict__ offsets,
+                                                        int* __restrict__ out_query, int* __restrict__ out_token) {
+    constexpr int NONE = 0x7fffffff;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const float p[3] = {pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]};
+    int bi[K];
+    knn_grid_select<K>(p, g, tok, kout, bi);
+#pragma unroll
+    for (int j = 0; j < K; ++j) bi[j] = j < kout ? bi[j] : NONE;
+#pragma unroll
+    for (int pass = 0; pass < K; ++pass)
+#pragma unroll
+        for (int j = pass & 1; j + 1 < K; j += 2) {
+            const int lo = min(bi[j], bi[j + 1]), hi = max(bi[j], bi[j + 1]);
+            bi[j] = lo;
+            bi[j + 1] = hi;
+        }
+    const int o = FILL ? offsets[i] : 0;
+    int n = 0;
+    auto put = [&](int t) {
+        if (FILL) { out_query[o + n] = (int)i; out_token[o + n] = t; }
+        ++n;
+    };
+    auto take = [&]() {
+#pragma unroll
+        for (int j = 0; j + 1 < K; ++j) bi[j] = bi[j + 1];
+        bi[K - 1] = NONE;
+    };
+    radius_grid_visit(p, g, tok, radius, cap, [&](int, int lin) {
+        while (bi[0] < lin) { put(bi[0]); take(); }
+        if (bi[0] == lin) take();       // also a radius token: written once
+        put(lin);
+    });
+    while (bi[0] != NONE) { put(bi[0]); take(); }
     if (!FILL) counts[i] = n;
 }
 
@@ -470,6 +548,68 @@ extern "C" int gaot_radius_grid_fill(const float* pos, int64_t num_points, const
                        num_points, g, token_pos, radius, cap, (int*)nullptr, offsets, out_point, out_token);
     GAOT_LAUNCH_CHECK();
     return GAOT_OK;
+}
+
+// count or fill pass of the per-query union (k_nbr_union_grid); `fn` names the entry point in the error message
+static int nbr_union_grid(const char* fn, const float* pos, int64_t num_points, const gaot_grid_t* grid, const float* token_pos,
+                          int k, float radius, int cap, int32_t* counts, const int32_t* offsets, int32_t* out_query,
+                          int32_t* out_token, bool fill, gaot_stream_t stream) {
+#define UNION_CHECK(cond, msg)                       \
+    do {                                             \
+        if (!(cond)) {                               \
+            gaot_set_error("%s: %s", fn, msg);       \
+            return GAOT_ERR_ARG;                     \
+        }                                            \
+    } while (0)
+    GridDesc g;
+    UNION_CHECK(make_grid(grid, g) == 0, "bad grid descriptor");
+    UNION_CHECK(num_points >= 0, "negative size");
+    const int64_t m = (int64_t)g.dim[0] * g.dim[1] * g.dim[2];
+    UNION_CHECK(k >= 1 && k <= m, "k must be in [1, number of tokens]");
+    UNION_CHECK(k <= 32, "k beyond 32: build the edge list (gaot_knn_grid, gaot_radius_grid_*, coalesce)");
+    UNION_CHECK(radius > 0.f, "radius must be positive");
+    UNION_CHECK(cap >= 1, "cap must be at least 1");
+    UNION_CHECK(num_points <= (int64_t)INT32_MAX / ((int64_t)k + cap), "num_points * (k + cap) beyond int32 (take the queries in chunks)");
+    UNION_CHECK(pos && token_pos && (fill ? (offsets && out_query && out_token) : counts != nullptr), "null pointer");
+#undef UNION_CHECK
+    if (num_points == 0) return GAOT_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grd((unsigned)ceil_div(num_points, 256)), blk(256);
+#define GAOT_UNION(KK)                                                                                                              \
+    case KK:                                                                                                                        \
+        if (fill)                                                                                                                   \
+            GAOT_KLAUNCH((k_nbr_union_grid<KK, true>), grd, blk, 0, st, pos, num_points, g, token_pos, k, radius, cap, (int*)nullptr, \
+                         offsets, out_query, out_token);                                                                            \
+        else                                                                                                                        \
+            GAOT_KLAUNCH((k_nbr_union_grid<KK, false>), grd, blk, 0, st, pos, num_points, g, token_pos, k, radius, cap, counts,      \
+                         (const int*)nullptr, (int*)nullptr, (int*)nullptr);                                                        \
+        break;
+    switch (k <= 8 ? k : k <= 12 ? 12 : k <= 16 ? 16 : k <= 24 ? 24 : 32) {      // the capacities of gaot_knn_grid, up to 32
+        GAOT_UNION(1) GAOT_UNION(2) GAOT_UNION(3) GAOT_UNION(4) GAOT_UNION(5) GAOT_UNION(6) GAOT_UNION(7) GAOT_UNION(8)
+        GAOT_UNION(12) GAOT_UNION(16) GAOT_UNION(24) GAOT_UNION(32)
+    }
+#undef GAOT_UNION
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        gaot_set_error("%s: launch failed: %s", fn, hipGetErrorString(e));
+        return GAOT_ERR_LAUNCH;
+    }
+    return GAOT_OK;
+}
+
+extern "C" int gaot_nbr_union_grid_count(const float* pos, int64_t num_points, const gaot_grid_t* grid, const float* token_pos, int k,
+                                         float radius, int cap, int32_t* counts, gaot_stream_t stream) {
+    GAOT_ENTER();
+    return nbr_union_grid("gaot_nbr_union_grid_count", pos, num_points, grid, token_pos, k, radius, cap, counts, nullptr, nullptr,
+                          nullptr, false, stream);
+}
+
+extern "C" int gaot_nbr_union_grid_fill(const float* pos, int64_t num_points, const gaot_grid_t* grid, const float* token_pos, int k,
+                                        float radius, int cap, const int32_t* offsets, int32_t* out_query, int32_t* out_token,
+                                        gaot_stream_t stream) {
+    GAOT_ENTER();
+    return nbr_union_grid("gaot_nbr_union_grid_fill", pos, num_points, grid, token_pos, k, radius, cap, nullptr, offsets, out_query,
+                          out_token, true, stream);
 }
 
 extern "C" size_t gaot_exclusive_scan_workspace_bytes(int64_t n) { return sizeof(int) * (size_t)(ceil_div(n, SCAN_TILE) + 2) + 64; }

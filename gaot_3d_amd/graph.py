@@ -257,6 +257,58 @@ def _decoder_edges(strategy: str, p: Tensor, grid: LatentGrid, radius: float, k:
     raise ValueError(f"Unknown decoder strategy: {strategy}")
 
 
+QUERY_LIST_STRATEGIES = ("radius", "bidirectional")
+QUERY_LIST_MAX_K = 32     # the register-list capacities gaot_nbr_union_grid_* is instantiated for
+
+
+def query_lists(strategy: str, query_pos: Tensor, grid: LatentGrid, radius: float, k: int) -> ops.BipartiteGraph:
+    """The by-query neighbour list of a 'radius' or 'bidirectional' DECODER graph for one regular token grid, written row by row --
+    what ``ops.csr_build(_decoder_edges(strategy, ...), 1, Nq)`` holds in ``rowptr`` / ``key`` / ``other``, without the edge list,
+    ``coalesce`` or a sort.  Both neighbourhoods are defined per query ('radius': the tokens within ``radius``, the ``RADIUS_CAP``
+    lowest ids; 'bidirectional': those united with the ``k`` nearest tokens), and ``coalesce`` followed by the stable sort by query
+    leaves every query's tokens ascending without duplicates, so a row does not depend on the other queries.
+
+    FORWARD ONLY: ``by_dst`` is ``SortedEdges(rowptr=offsets, perm=None, key=query ids, other=token ids)`` -- the three arrays the
+    fused forward (``ops.gno_forward`` / ``ops.gno_nl_forward``) reads -- and ``by_src`` is None; a backward needs ``build_graph``.
+    One host read of the total (it sizes the two id lists), as in ``radius_pairs``: raises while a stream is being captured."""
+    if strategy not in QUERY_LIST_STRATEGIES:
+        raise ValueError(f"query_lists: strategy must be one of {QUERY_LIST_STRATEGIES}, got {strategy!r}")
+    _need_cuda(query_pos, "query_lists")
+    if isinstance(grid, TokenSet):
+        raise GaotError("query_lists: the tokens are not a regular grid (TokenSet); build the edge list (get_neighbor_strategy)")
+    if torch.cuda.is_current_stream_capturing():
+        raise GaotError(f"query_lists: a '{strategy}' neighbour list is sized by a host read of its length, which is illegal while a "
+                        "stream is being captured; sample eagerly")
+    union = strategy == "bidirectional"
+    p = query_pos.detach().to(torch.float32).contiguous()
+    if p.dim() != 2 or p.shape[1] != 3:
+        raise GaotError(f"query_lists: query_pos must be [Nq, 3], got {tuple(p.shape)}")
+    n, k = int(p.shape[0]), int(k)
+    if not float(radius) > 0.0:
+        raise GaotError(f"query_lists: radius must be positive, got {radius}")
+    if union and not 1 <= k <= min(QUERY_LIST_MAX_K, grid.num_tokens):
+        raise GaotError(f"query_lists: k must be in [1, min({QUERY_LIST_MAX_K}, number of tokens = {grid.num_tokens})], got {k}")
+    if n * ((k if union else 0) + RADIUS_CAP) > 0x7fffffff:
+        raise GaotError(f"query_lists: {n} queries x up to {(k if union else 0) + RADIUS_CAP} tokens is beyond int32; take the "
+                        "queries in chunks")
+    lib = _lib.load()
+    counts = torch.empty(n, dtype=torch.int32, device=p.device)
+    gs = grid.c_struct()
+    head = (ops._ptr(p), n, C.byref(gs), ops._ptr(grid.pos)) + ((k,) if union else ()) + (float(radius), RADIUS_CAP)
+    count, fill = (lib.gaot_nbr_union_grid_count, lib.gaot_nbr_union_grid_fill) if union else \
+        (lib.gaot_radius_grid_count, lib.gaot_radius_grid_fill)
+    what = "gaot_nbr_union_grid" if union else "gaot_radius_grid"
+    if n:
+        check(count(*head, ops._ptr(counts), ops._stream()), what + "_count")
+    offs = exclusive_scan(counts)
+    total = int(offs[-1])     # host sync: sizes the lists
+    qi = torch.empty(total, dtype=torch.int32, device=p.device)
+    tk = torch.empty(total, dtype=torch.int32, device=p.device)
+    if total:
+        check(fill(*head, ops._ptr(offs), ops._ptr(qi), ops._ptr(tk), ops._stream()), what + "_fill")
+    return ops.BipartiteGraph(ops.SortedEdges(offs, None, qi, tk, n), None, grid.num_tokens, n)
+
+
 def get_neighbor_strategy(neighbor_strategy: str, phys_pos: Tensor, batch_idx_phys: Optional[Tensor], latent_tokens_pos: Tensor,
                           batch_idx_latent: Optional[Tensor], radius: float, k_neighbors: int = 1, is_decoder: bool = False,
                           latent_dims: Optional[Sequence[int]] = None) -> Tensor:

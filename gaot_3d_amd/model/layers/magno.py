@@ -414,6 +414,12 @@ class MAGNODecoder(nn.Module):
         32-channel pass, the scale mix and the projection MLP.  No edge_index, no sorted lists, nothing sized by Nq but the result.
         (The knn lists do not depend on the scale, so a multi-scale decoder evaluates the transform once and mixes that one result
         with itself, as ``forward`` does with equal operands.)
+        Decoder strategies 'radius' and 'bidirectional' (k_neighbors <= 32) stream under the same conditions on ROW lists: per chunk
+        and scale ``graph.query_lists`` writes every query's tokens (within the scale's radius, the 32 lowest ids; united with its k
+        nearest for 'bidirectional') in ascending order straight into the by-query list -- the list ``forward``'s route reaches
+        through cat, coalesce and two CSR builds -- and the fused forward (``gaot_gno_fwd`` / ``gaot_gno_fwd_nl``) reads it as it
+        stands: no edge_index, no sort, no by-source list.  The list's length is read on the host once per chunk and scale (it
+        sizes the two id arrays), so this route cannot be captured in a graph: it raises GaotError before any launch.
         Every other configuration FALLS BACK to ``forward``'s route -- ``get_neighbor_strategy`` + ``build_graph`` + the general
         decoder -- chunked in the same way.  The exception is a 'statistical' decoder GeoEmbed: its z-score runs over ALL query rows
         (geoembed.py:177-180), so it takes the queries in one piece whatever ``chunk_points`` says.
@@ -430,7 +436,9 @@ class MAGNODecoder(nn.Module):
         lat = latent_tokens_pos
         k = int(self.k_neighbors)
         grid = None
-        if (self.decoder_strategy == "knn" and k in ops.GNO_KNN_K and self.sampling_strategy is None and not self.use_geoembed
+        strategy = self.decoder_strategy
+        by_rows = strategy == "radius" or (strategy == "bidirectional" and k <= device_graph.QUERY_LIST_MAX_K)
+        if (((strategy == "knn" and k in ops.GNO_KNN_K) or by_rows) and self.sampling_strategy is None and not self.use_geoembed
                 and rndata_flat.is_cuda and query_pos.dim() == 2 and query_pos.shape[1] == 3 and query_pos.dtype == torch.float32
                 and lat.dtype == torch.float32 and lat.is_contiguous() and rndata_flat.shape[0] == lat.shape[0]
                 and self.gno._fused_plan(list(self.gno.channel_mlp.fcs), rndata_flat, lat, query_pos) is not None):
@@ -438,6 +446,15 @@ class MAGNODecoder(nn.Module):
             if grid is not None and grid.num_tokens != lat.shape[0]:
                 grid = None                                   # a batch of several graphs: no streaming
         out = torch.empty(nq, self.out_channels, dtype=rndata_flat.dtype, device=rndata_flat.device)
+        if grid is not None and by_rows:
+            for i in range(0, nq, chunk):
+                q = query_pos[i:i + chunk]
+                outs = []
+                for scale in self.scales:                     # the radius, hence the rows, of every scale as ``_decode`` derives it
+                    rows = device_graph.query_lists(strategy, q, grid, self.gno_radius * scale, k)
+                    outs.append(self.gno(y_pos=lat, x_pos=q, edge_index=None, f_y=rndata_flat, graph=rows))
+                self._project_into(_mix_scales(self, outs, q), out[i:i + chunk])
+            return out
         if grid is not None:
             for i in range(0, nq, chunk):
                 q = query_pos[i:i + chunk]

@@ -107,7 +107,7 @@ def timing_summary():
 class SortedEdges:
     """Edge list sorted (stably) by one endpoint.  ``key`` = the sort endpoint, ``other`` = the other."""
     rowptr: Tensor   # int32 [num_rows+1]
-    perm: Tensor     # int32 [E]
+    perm: Optional[Tensor]     # int32 [E]; None for a list written directly in sorted order (graph.query_lists: no edge_index)
     key: Tensor      # int32 [E]
     other: Tensor    # int32 [E]
     num_rows: int
@@ -141,7 +141,8 @@ def csr_build(edge_index: Tensor, sort_row: int, num_rows: int) -> SortedEdges:
 class BipartiteGraph:
     """Both orderings of one reference ``edge_index`` (row 0 = source, row 1 = query)."""
     by_dst: SortedEdges   # key = query,  other = source
-    by_src: SortedEdges   # key = source, other = query
+    by_src: Optional[SortedEdges]   # key = source, other = query; None for forward-only lists (graph.query_lists): the fused
+                                    # forward reads by_dst alone, every backward needs both
     num_src: int
     num_dst: int
 

@@ -6,7 +6,8 @@
  * otherwise an error code; gaot_last_error() gives the message (thread local).
  *
  * Forward-only use of a trained model (sampling the decoded field at arbitrary points) needs no edge list:
- * gaot_knn_grid writes the regular k-neighbour list that gaot_gno_fwd_knn consumes as it stands.
+ * gaot_knn_grid writes the regular k-neighbour list that gaot_gno_fwd_knn consumes as it stands; for 'radius' / 'bidirectional'
+ * decoders gaot_radius_grid_* / gaot_nbr_union_grid_* write the by-query list that gaot_gno_fwd / gaot_gno_fwd_nl read.
  *
  * Each entry point names the reference interface it stands in for (paths relative to the
  * reference repo Shizheng-Wen/GAOT-3D); the Python host side (gaot_3d_amd/model) mirrors the
@@ -582,6 +583,19 @@ int gaot_radius_grid_count(const float* pos, int64_t num_points, const gaot_grid
 int gaot_radius_grid_fill(const float* pos, int64_t num_points, const gaot_grid_t* grid, const float* token_pos,
                           float radius, int cap, const int32_t* offsets, int32_t* out_point, int32_t* out_token,
                           gaot_stream_t stream);
+/* The by-query neighbour list of a 'bidirectional' DECODER graph, written row by row without an edge list or a sort (forward-only
+ * sampling of a decoded field: gaot_gno_fwd / gaot_gno_fwd_nl read a by-query list and nothing else).  One lane per query: its k
+ * nearest tokens, selected as gaot_knn_grid selects them, united with its tokens within `radius`, selected as gaot_radius_grid_*
+ * selects them (d <= radius, the `cap` lowest indices); every token once, ascending token index -- the row that
+ * coalesce(cat(knn, radius)) sorted by query holds (magno.py:292-293), whatever the chunk of queries it is built in.
+ *   count : counts[i] = length of row i (<= k + cap); gaot_exclusive_scan_i32 turns them into offsets[n+1], which is the rowptr
+ *   fill  : out_query[offsets[i] + j] = i, out_token[offsets[i] + j] = the j-th token of row i
+ * 1 <= k <= min(32, number of tokens), radius > 0, cap >= 1, num_points * (k + cap) within int32; a null pointer is an error. */
+int gaot_nbr_union_grid_count(const float* pos, int64_t num_points, const gaot_grid_t* grid, const float* token_pos, int k,
+                              float radius, int cap, int32_t* counts, gaot_stream_t stream);
+int gaot_nbr_union_grid_fill(const float* pos, int64_t num_points, const gaot_grid_t* grid, const float* token_pos, int k,
+                             float radius, int cap, const int32_t* offsets, int32_t* out_query, int32_t* out_token,
+                             gaot_stream_t stream);
 /* The same searches against token coordinates that are NOT a regular grid (custom `tokens_pos`; the reference's
  * get_neighbor_strategy takes any latent coordinates, magno.py:116-124): every point scans all tokens, staged through LDS
  * -- O(N M) on the device, no N x M distance matrix.  Same order and tie rules as the grid forms. */

@@ -10,7 +10,7 @@ import gaot_3d_amd
 from gaot_3d_amd import ops, functional as GF
 
 what = sys.argv[1] if len(sys.argv) > 1 else "attn"
-reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+reps = int(sys.argv[2]) if len(sys.argv) > 2 and sys.argv[2].isdigit() else 5
 dev = "cuda:0"
 gaot_3d_amd.set_precision(os.environ.get("GAOT_PRECISION", "bf16"))
 torch.manual_seed(0)
@@ -452,11 +452,22 @@ elif what == "decoder_sample":
     # (a) and (b) alternate in this one process after a warm-up of each; device events around synchronised work; `reps` rounds; a row
     # is the median with min / max, the peak is the rise of allocated memory over the inputs.  Kept in
     # profiles/decoder_sample_microbench.txt.
+    # `--strategy radius|bidirectional`: the reference YAML's decoder instead (config/examples/drivaernet/pressure.yaml: r = 0.033,
+    # k_neighbors at its default 1, neighbor_strategy 'bidirectional'; 'radius' = the same decoder on the radius graph alone) with
+    #   (a) the route sample fell back to for these strategies: per chunk get_neighbor_strategy (knn_to_grid, radius_pairs, cat,
+    #       coalesce) -> build_graph -> decoder, into one preallocated result;
+    #   (b) MAGNODecoder.sample: per chunk graph.query_lists (rows written in place, no sort) -> gaot_gno_fwd -> projection.
+    # Kept in profiles/decoder_sample_radius_microbench.txt.
     from gaot_3d_amd.data import latent_grid
     from gaot_3d_amd.model.layers.magno import MAGNOConfig, MAGNODecoder
     latent = (64, 64, 32)
-    cfg = MAGNOConfig(gno_coord_dim=3, lifting_channels=32, mlp_type="linear", use_geoembed=[True, False], neighbor_strategy="knn",
-                      k_neighbors=8, out_gno_channel_mlp_hidden_layers=[64, 64], precompute_edges=False)
+    strategy = sys.argv[sys.argv.index("--strategy") + 1] if "--strategy" in sys.argv else "knn"
+    if strategy not in ("knn", "radius", "bidirectional"):
+        sys.exit(f"--strategy must be radius or bidirectional, got {strategy}")
+    rows = strategy != "knn"
+    cfg = MAGNOConfig(gno_coord_dim=3, lifting_channels=32, mlp_type="linear", use_geoembed=[True, False],
+                      neighbor_strategy=["knn", strategy] if rows else "knn", k_neighbors=1 if rows else 8, gno_radius=0.033,
+                      out_gno_channel_mlp_hidden_layers=[64, 64], precompute_edges=False)
     dec = MAGNODecoder(in_channels=32, out_channels=1, gno_config=cfg).to(dev).eval()
     dec.latent_dims = latent
     tokens = latent_grid(latent).to(dev)
@@ -481,7 +492,13 @@ elif what == "decoder_sample":
         for prec in ("fp32", "bf16"):
             gaot_3d_amd.set_precision(prec)
             with torch.no_grad():
-                route_a = lambda: dec._decode(rn, q, q_bidx, tokens, lat_bidx, None, False)
+                def route_a():
+                    if not rows:
+                        return dec._decode(rn, q, q_bidx, tokens, lat_bidx, None, False)
+                    out, step = torch.empty(nq, 1, device=dev), chunk or dec.SAMPLE_CHUNK      # sample's fall-back loop
+                    for i in range(0, nq, step):
+                        out[i:i + step] = dec._decode(rn, q[i:i + step], q_bidx[i:i + step], tokens, lat_bidx, None, False)
+                    return out
                 route_b = lambda: dec.sample(rn, q, tokens, chunk_points=chunk)
                 ra, rb = timed(route_a)[2], timed(route_b)[2]          # warm-up, and the two routes agree
                 diff = (ra - rb).abs().max().item()
@@ -492,6 +509,9 @@ elif what == "decoder_sample":
                     t, p, _o = timed(route_b); tb.append(t); pb = max(pb, p); del _o
             ta.sort(); tb.sort()
             ma, mb = ta[len(ta) // 2], tb[len(tb) // 2]
+            if rows:
+                print(f"Nq={nq} {prec} {strategy}: max - min of the rounds (a) {ta[-1] - ta[0]:.3f} ms, (b) {tb[-1] - tb[0]:.3f} ms; (b) - (a) "
+                      f"medians {mb - ma:+.3f} ms; (b) peak < (a) peak: {pb < pa}")
             print(f"Nq={nq} {prec}: (a) strategy + build_graph + decoder {ma:9.3f} ms (min {ta[0]:.3f}, max {ta[-1]:.3f}, spread "
                   f"{100 * (ta[-1] - ta[0]) / ma:.1f} %), peak {pa / 2**20:9.1f} MiB")
             print(f"Nq={nq} {prec}: (b) sample (chunk {chunk or dec.SAMPLE_CHUNK})      {mb:9.3f} ms (min {tb[0]:.3f}, max {tb[-1]:.3f}, spread "
