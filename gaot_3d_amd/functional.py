@@ -306,6 +306,32 @@ def linear(x, weight, bias=None, act: Optional[str] = None, precision: Optional[
     return LinearFn.apply(x, weight, bias, ops.ACT[act], precision, residual)
 
 
+def linear_with_preact(x, weight, bias=None, act: Optional[str] = None, precision: Optional[int] = None):
+    """(y, z) = (act(x W^T + b), a tensor whose activation derivative is that of x W^T + b), outside autograd: the kernels of
+    ``LinearFn.forward`` in its dispatch order, so y is ``linear``'s result bit for bit.  z is the pre-activation itself, except on
+    the single-pass ReLU kernel, which keeps none: there z is y, and relu'(y) = relu'(z).  For forward-mode tangents
+    (``LinearChannelMLP.jvp_rows``)."""
+    a = ops.ACT[act]
+    w = _w2d(weight)
+    n, k = w.shape
+    if x.shape[-1] != k:
+        raise GaotError(f"linear: input has {x.shape[-1]} features, weight expects {k}")
+    x2 = _rows2d(x, k)
+    m = x2.shape[0]
+    with torch.no_grad():
+        if ops.rowlin_ok((x2,), w, bias, a, precision):
+            y = ops.rowlin_forward((x2,), w, bias, a == 2)
+            return y, y
+        w = _wb(w, precision)
+        if a > 3:
+            z = ops.gemm(x2, w, m, n, k, k, k, False, True, bias, 0, precision=precision)
+            return ops.act_fwd(z, a), z
+        if a:
+            return ops.gemm(x2, w, m, n, k, k, k, False, True, bias, a, want_preact=True, precision=precision)
+        y = ops.gemm(x2, w, m, n, k, k, k, False, True, bias, 0, precision=precision)
+        return y, y
+
+
 class GnoFn(Function):
     """Fused IntegralTransform (transform_type='linear', mean reduction)."""
 

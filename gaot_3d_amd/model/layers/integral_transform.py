@@ -18,7 +18,9 @@ runs the general path: per-edge tensors in dst-sorted order, the MLP on the GEMM
 element-wise glue and its autograd in csrc/edgeops.hip (gaot_3d_amd/edgeops.py), with the same ``_attn_weights`` under use_attn.
 ``forward_knn`` is the forward alone on a regular k-neighbour list (the [n, k] ids of ``graph.knn_to_grid`` as they stand, k | 32):
 the same operands, one ``gaot_gno_fwd_knn`` launch per 32-channel pass, no edge list or sorted lists, bit-identical to ``forward`` on
-the graph of those lists -- what ``MAGNODecoder.sample`` streams query chunks through.
+the graph of those lists -- what ``MAGNODecoder.sample`` streams query chunks through.  ``jacobian_knn`` is ``forward_knn`` with the
+derivative of its result with respect to the query coordinates, in forward mode (``gaot_gno_fwd_knn_jac``: three tangents through the
+per-edge MLP beside the value, exact fp32) -- what ``MAGNODecoder.sample_jacobian`` streams.
 HIP only, no CPU fallback."""
 from typing import Optional
 
@@ -162,6 +164,25 @@ class IntegralTransform(nn.Module):
                                           f"on lists of k in {ops.GNO_KNN_K} neighbours per query; use forward() with an edge_index")
             return self._forward_fused(fcs, y_pos, x_pos, f_y, None, *plan, knn=(nbr, int(k)))
 
+    def jacobian_knn(self, y_pos, x_pos, nbr, k: int, f_y: Optional[torch.Tensor] = None):
+        """``forward_knn`` with the spatial derivative of its result: -> (out [N_x, C], jac [3, N_x, C]) with
+        jac[d, q, c] = d out[q, c] / d x_pos[q, d], every query's neighbour list held fixed -- the derivative autograd returns through
+        ``forward`` on the graph of these lists (edges are built once and not differentiated).  It is valid almost everywhere and NOT
+        defined across the surfaces where a query's k nearest sources change.  Forward mode, one ``ops.gno_forward_knn_jac`` launch per
+        32-channel pass (three tangents carried through the per-edge MLP beside the value), exact fp32 in both precision modes: ``out``
+        is ``forward_knn``'s fp32-mode result bit for bit.  The operands are prepared exactly as in ``forward_knn``; the planes of the
+        directions a coordinate dimension of 1 / 2 is padded with are exact zeros.  Runs exactly when ``_fused_plan`` is not None and
+        k is in ``ops.GNO_KNN_K`` and raises NotImplementedError otherwise.  Nothing is recorded for autograd."""
+        if self.transform_type not in ("linear", "nonlinear", "nonlinear_kernelonly"):
+            raise ValueError(f"Invalid transform_type: {self.transform_type}")
+        fcs = list(self.channel_mlp.fcs)
+        with torch.no_grad():
+            plan = self._fused_plan(fcs, f_y, y_pos, x_pos)
+            if plan is None or int(k) not in ops.GNO_KNN_K:
+                raise NotImplementedError("IntegralTransform.jacobian_knn: only the transforms the fused kernels evaluate (_fused_plan) "
+                                          f"on lists of k in {ops.GNO_KNN_K} neighbours per query")
+            return self._forward_fused(fcs, y_pos, x_pos, f_y, None, *plan, knn=(nbr, int(k)), jac=True)
+
     @staticmethod
     def _pad3(pos):
         """coordinates of dimension 1 / 2 padded with zeros to the kernels' 3-D rows"""
@@ -232,17 +253,19 @@ class IntegralTransform(nn.Module):
         return (not self.use_attn and self.transform_type == "linear" and f_y is not None and dims[0] == (64, 6)
                 and dims[-1] == (32, 64) and f_y.shape[1] == 32)
 
-    def _forward_fused(self, fcs, y_pos, x_pos, f_y, graph, cd: int, c: int, edge_w=None, knn=None):
+    def _forward_fused(self, fcs, y_pos, x_pos, f_y, graph, cd: int, c: int, edge_w=None, knn=None, jac=False):
         """``edge_w`` [E] (dst-sorted order): the weighted transform of use_attn -- every pass runs ``GnoWFn`` with the same weights and
         autograd adds the passes' gradients with respect to them (padded channels carry zero grad_out and zero f: exact zeros).
         ``knn`` = (nbr, k) (``forward_knn``; ``graph`` is None, no autograd): the passes run ``ops.gno_forward_knn`` on the regular
-        list instead of the autograd Functions."""
+        list instead of the autograd Functions; with ``jac`` (``jacobian_knn``) they run ``ops.gno_forward_knn_jac`` and the result is
+        (out [N_x, c], jac [3, N_x, c])."""
         w2 = lambda fc: fc.weight[:, :, 0] if fc.weight.dim() == 3 else fc.weight    # Conv1d(k=1) storage of mlp_type='channel'
         pad_hidden = any(fc.weight.shape[0] != 64 for fc in fcs[:-1])
         tt = self.transform_type
         if tt == "linear" and cd == 3 and c == 32 and not pad_hidden and edge_w is None:   # the shipped shape: straight through
             if knn is not None:
-                return ops.gno_forward_knn(0, [w2(fc) for fc in fcs], [fc.bias for fc in fcs], y_pos, x_pos, f_y, None, *knn)
+                fwd = ops.gno_forward_knn_jac if jac else ops.gno_forward_knn
+                return fwd(0, [w2(fc) for fc in fcs], [fc.bias for fc in fcs], y_pos, x_pos, f_y, None, *knn)
             params = []
             for fc in fcs:
                 params += [fc.weight, fc.bias]
@@ -284,8 +307,12 @@ class IntegralTransform(nn.Module):
                 bb = torch.nn.functional.pad(bb, (0, 32 - n))
                 fb = None if fb is None else torch.nn.functional.pad(fb, (0, 32 - n))
             if knn is not None:
-                o = ops.gno_forward_knn(tt, [w0.contiguous(), *mid[0::2], wb.contiguous()], [b0, *mid[1::2], bb.contiguous()], y3, x3,
-                                        None if fb is None else fb.contiguous(), t, *knn)
+                fwd = ops.gno_forward_knn_jac if jac else ops.gno_forward_knn
+                o = fwd(tt, [w0.contiguous(), *mid[0::2], wb.contiguous()], [b0, *mid[1::2], bb.contiguous()], y3, x3,
+                        None if fb is None else fb.contiguous(), t, *knn)
+                if jac:
+                    outs.append((o[0][:, :n], o[1][:, :, :n]) if n < 32 else o)
+                    continue
             elif edge_w is not None:
                 o = GF.GnoWFn.apply(tt, None if fb is None else fb.contiguous(), t, edge_w, y3, x3, graph, w0.contiguous(), b0, *mid,
                                     wb.contiguous(), bb.contiguous())
@@ -295,6 +322,10 @@ class IntegralTransform(nn.Module):
                 o = GF.GnoNlFn.apply(tt, None if fb is None else fb.contiguous(), t, y3, x3, graph, w0.contiguous(), b0, *mid,
                                      wb.contiguous(), bb.contiguous())
             outs.append(o[:, :n] if n < 32 else o)
+        if jac:
+            if len(outs) == 1:
+                return outs[0][0].contiguous(), outs[0][1].contiguous()
+            return torch.cat([o[0] for o in outs], dim=1), torch.cat([o[1] for o in outs], dim=2)
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
 
     def _forward_general(self, fcs, y_pos, x_pos, f_y, g):

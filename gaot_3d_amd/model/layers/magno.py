@@ -389,6 +389,20 @@ class MAGNODecoder(nn.Module):
         self.__dict__["_gaot_sample_grid"] = (latent_tokens_pos, latent_tokens_pos._version, grid)
         return grid
 
+    def _stream_grid(self, rndata_flat, query_pos, lat):
+        """the token grid's descriptor when the operands allow a streaming path of ``sample`` / ``sample_jacobian`` (the decoder
+        strategy is the caller's condition): no neighbour sampling, no decoder GeoEmbed, fp32 3-D coordinates on the device, ONE
+        graph's tokens on the model's regular grid, a transform the fused kernels evaluate; None otherwise"""
+        if not (self.sampling_strategy is None and not self.use_geoembed
+                and rndata_flat.is_cuda and query_pos.dim() == 2 and query_pos.shape[1] == 3 and query_pos.dtype == torch.float32
+                and lat.dtype == torch.float32 and lat.is_contiguous() and rndata_flat.shape[0] == lat.shape[0]
+                and self.gno._fused_plan(list(self.gno.channel_mlp.fcs), rndata_flat, lat, query_pos) is not None):
+            return None
+        grid = self._sample_grid(lat)
+        if grid is not None and grid.num_tokens != lat.shape[0]:
+            grid = None                                   # a batch of several graphs: no streaming
+        return grid
+
     def _project_into(self, x, out) -> None:
         """out[:] = projection(x), rows in blocks.  Unless the projection MLP runs as one fused launch (``Mlp2Fn``, bf16 mode) its
         hidden layer [rows, projection_channels] goes through memory, 8 x the size of x at the shipped 32 -> 256: the blocks keep
@@ -438,13 +452,8 @@ class MAGNODecoder(nn.Module):
         grid = None
         strategy = self.decoder_strategy
         by_rows = strategy == "radius" or (strategy == "bidirectional" and k <= device_graph.QUERY_LIST_MAX_K)
-        if (((strategy == "knn" and k in ops.GNO_KNN_K) or by_rows) and self.sampling_strategy is None and not self.use_geoembed
-                and rndata_flat.is_cuda and query_pos.dim() == 2 and query_pos.shape[1] == 3 and query_pos.dtype == torch.float32
-                and lat.dtype == torch.float32 and lat.is_contiguous() and rndata_flat.shape[0] == lat.shape[0]
-                and self.gno._fused_plan(list(self.gno.channel_mlp.fcs), rndata_flat, lat, query_pos) is not None):
-            grid = self._sample_grid(lat)
-            if grid is not None and grid.num_tokens != lat.shape[0]:
-                grid = None                                   # a batch of several graphs: no streaming
+        if (strategy == "knn" and k in ops.GNO_KNN_K) or by_rows:
+            grid = self._stream_grid(rndata_flat, query_pos, lat)
         out = torch.empty(nq, self.out_channels, dtype=rndata_flat.dtype, device=rndata_flat.device)
         if grid is not None and by_rows:
             for i in range(0, nq, chunk):
@@ -470,3 +479,78 @@ class MAGNODecoder(nn.Module):
             q_bidx = torch.zeros(q.shape[0], dtype=torch.long, device=q.device)
             out[i:i + chunk] = self._decode(rndata_flat, q, q_bidx, lat, lat_bidx, None, False)
         return out
+
+    def sample_jacobian(self, rndata_flat, query_pos, latent_tokens_pos, chunk_points: Optional[int] = None):
+        """``sample`` with the spatial derivative of the field: -> (pred [Nq, out_channels], jac [Nq, out_channels, coord_dim]) with
+        jac[q, o, d] = d pred[q, o] / d query_pos[q, d], every query's neighbour list held fixed -- the derivative autograd returns
+        through ``forward(query_coord_pos=...)``, where edges are built once and not differentiated.  It is valid almost everywhere
+        and NOT defined across the surfaces where a query's neighbour list (its k nearest tokens, the tokens within its radius)
+        changes.  ``chunk_points`` queries at a time into two preallocated results; neither ever requires grad.  Argument rules are
+        ``sample``'s: 'reverse' and a non-positive ``chunk_points`` raise ValueError.
+
+        STREAMING path -- the conditions of ``sample``'s 'knn' route (strategy 'knn', k_neighbors in ``ops.GNO_KNN_K``, tokens on the
+        model's regular grid, no neighbour sampling, no decoder GeoEmbed, a transform ``_fused_plan`` accepts): forward mode.  Per chunk
+        one ``knn_to_grid`` launch, one ``jacobian_knn`` launch per 32-channel pass (value and three tangent planes), the scale mix
+        applied to the value and to every tangent plane with the same weights, and the projection MLP's tangent
+        (``jvp_rows``).  Every scale sees the same list, so the mix is of EQUAL operands: the derivative of the softmax weights
+        themselves multiplies sum_s dw_s = 0 and drops out.  No edge_index, no sorted lists, no autograd graph, no backward pass, no
+        host synchronisation (capturable in a graph after one eager call, as ``sample``).  Everything on this path is exact fp32 in
+        both precision modes: in bf16 mode ``pred`` is the fp32-kernel value and differs from ``sample``'s by bf16 rounding.
+        Every other configuration ('radius' / 'bidirectional' decoders included) takes the AUTOGRAD route: per chunk ``forward``'s
+        decoder on a detached copy of the chunk that requires grad, then one backward pass per output channel.  use_attn raises the
+        NotImplementedError ``IntegralTransform`` raises for coordinate gradients; a 'statistical' decoder GeoEmbed couples all
+        queries through its z-score, so a per-query Jacobian is not what that route returns: NotImplementedError."""
+        from ... import graph as device_graph
+        from ... import ops
+        if self.decoder_strategy == "reverse":
+            raise ValueError("MAGNODecoder.sample_jacobian: decoder strategy 'reverse' is the flip of the encoder's graph of the "
+                             "sample's own points and is undefined for other query points")
+        if chunk_points is not None and int(chunk_points) < 1:
+            raise ValueError(f"chunk_points must be positive, got {chunk_points}")
+        if self.use_geoembed and self.geoembed.method == "statistical":
+            raise NotImplementedError("MAGNODecoder.sample_jacobian: a 'statistical' decoder GeoEmbed normalises over ALL query rows, "
+                                      "which couples the queries; there is no per-query Jacobian")
+        nq = int(query_pos.shape[0])
+        chunk = int(chunk_points) if chunk_points is not None else self.SAMPLE_CHUNK
+        lat = latent_tokens_pos
+        k = int(self.k_neighbors)
+        cd = int(query_pos.shape[1])
+        rndata_flat = rndata_flat.detach()
+        query_pos = query_pos.detach()
+        pred = torch.empty(nq, self.out_channels, dtype=rndata_flat.dtype, device=rndata_flat.device)
+        jac = torch.empty(nq, self.out_channels, cd, dtype=rndata_flat.dtype, device=rndata_flat.device)
+        grid = None
+        if self.decoder_strategy == "knn" and k in ops.GNO_KNN_K:
+            with torch.no_grad():           # the plan of the forward alone, as ``sample`` asks for it (four hidden layers stream in fp32 mode)
+                grid = self._stream_grid(rndata_flat, query_pos, lat)
+        if grid is not None:
+            ns = len(self.scales)
+            with torch.no_grad():
+                for i in range(0, nq, chunk):
+                    q = query_pos[i:i + chunk]
+                    nbr = device_graph.knn_to_grid(q, grid, k)
+                    dec, dj = self.gno.jacobian_knn(lat, q, nbr, k, rndata_flat)
+                    planes = [dec, *dj.unbind(0)]
+                    if ns > 1 and self.use_scale_weights:
+                        sw = self.scale_weighting
+                        h = GF.linear(q, sw[0].weight, sw[0].bias, act="relu", precision=0)
+                        logits = GF.linear(h, sw[2].weight, sw[2].bias, precision=0)
+                        planes = [GF.ScaleMixFn.apply(logits, *([p] * ns)) for p in planes]
+                    elif ns > 1:
+                        planes = [_sum_scales([p] * ns) for p in planes]
+                    y, dys = self.projection.jvp_rows(planes[0], planes[1:])
+                    pred[i:i + chunk] = y
+                    for d in range(cd):
+                        jac[i:i + chunk, :, d] = dys[d]
+            return pred, jac
+        lat_bidx = torch.zeros(lat.shape[0], dtype=torch.long, device=lat.device)
+        for i in range(0, nq, chunk):
+            with torch.enable_grad():
+                q = query_pos[i:i + chunk].clone().requires_grad_(True)
+                q_bidx = torch.zeros(q.shape[0], dtype=torch.long, device=q.device)
+                p = self._decode(rndata_flat, q, q_bidx, lat, lat_bidx, None, False)
+                for o in range(self.out_channels):
+                    (g,) = torch.autograd.grad(p[:, o].sum(), q, retain_graph=o + 1 < self.out_channels)
+                    jac[i:i + chunk, o, :] = g
+            pred[i:i + chunk] = p.detach()
+        return pred, jac

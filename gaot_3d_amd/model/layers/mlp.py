@@ -46,6 +46,37 @@ def activation_name(fn) -> str:
     return name
 
 
+def _jvp_rows(self, x, dxs):
+    """Forward-mode tangents of the MLP on rows: -> (y [N, out], [dy_d [N, out] for dx_d in dxs]) with y = ``forward_rows(x)`` in
+    fp32 mode (bit for bit: the same kernels) and dy_d the directional derivative of y along dx_d [N, C].  Per layer z = linear(x),
+    u_d = linear(dx_d) without bias, h = act(z), v_d = act'(z) * u_d (``ops.act_bwd``); precision-0 linears in both precision modes,
+    no dropout (evaluation), nothing recorded for autograd.  Rows are taken in blocks so that no hidden tensor exceeds the
+    input's size (the rule of ``MAGNODecoder._project_into``)."""
+    from ... import ops
+    fcs = list(self.fcs)
+    act = self.non_linearity
+    n = x.shape[0]
+    cout = fcs[-1].weight.shape[0]
+    hid = max([fc.weight.shape[0] for fc in fcs[:-1]], default=0)
+    step = max(n, 1) if hid <= x.shape[1] else max(1024, n * x.shape[1] // hid)
+    with torch.no_grad():
+        y = torch.empty(n, cout, dtype=x.dtype, device=x.device)
+        dys = [torch.empty(n, cout, dtype=x.dtype, device=x.device) for _ in dxs]
+        for j in range(0, n, step):
+            h = x[j:j + step]
+            ds = [d[j:j + step] for d in dxs]
+            for i, fc in enumerate(fcs):
+                last = i == len(fcs) - 1
+                h, z = GF.linear_with_preact(h, fc.weight, fc.bias, act=None if last else act, precision=_FP32)
+                ds = [GF.linear(d, fc.weight, None, precision=_FP32) for d in ds]
+                if not last and ops.ACT[act]:
+                    ds = [ops.act_bwd(z, d, ops.ACT[act]) for d in ds]
+            y[j:j + step] = h
+            for o, d in zip(dys, ds):
+                o[j:j + step] = d
+    return y, dys
+
+
 class LinearChannelMLP(nn.Module):
     """Stack of nn.Linear parameters [layers[j] -> layers[j+1]], activation (default erf-GELU) between, none after the
     last, nn.Dropout after every layer when ``dropout`` > 0 (reference mlp.py:308-335)."""
@@ -69,6 +100,7 @@ class LinearChannelMLP(nn.Module):
         return x
 
     forward_rows = forward      # [N, C] rows in, rows out (what the encoder / decoder hand over)
+    jvp_rows = _jvp_rows
 
 
 class ChannelMLP(nn.Module):
@@ -102,6 +134,8 @@ class ChannelMLP(nn.Module):
                           precision=_FP32)
             x = GF.dropout(x, p, self.training)
         return x
+
+    jvp_rows = _jvp_rows
 
     def forward(self, x):
         size = list(x.shape)

@@ -284,18 +284,11 @@ def gno_nl_forward(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Opt
 GNO_KNN_K = (1, 2, 4, 8, 16, 32)      # the divisors of the kernels' 32-edge tile (gaot_gno_fwd_knn)
 
 
-def gno_forward_knn(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], src_table: Optional[Tensor],
-                    nbr: Tensor, k: int, precision: Optional[int] = None) -> Tensor:
-    """the fused transform's FORWARD on a regular neighbour list (gaot_gno_fwd_knn): ``nbr`` int32 [n_query * k] with
-    nbr[q*k + j] = the j-th source of query q (``knn_grid``'s output as it stands), k in ``GNO_KNN_K``.  ``mode``: 0 / 'linear'
-    (``src_table`` None), 'nonlinear', 'nonlinear_kernelonly' (``f_y`` None), operands as in ``gno_forward`` / ``gno_nl_forward``.
-    One launch, no edge list, no sorted lists, no workspace; bit-identical to those two on ``build_graph`` of the same lists.  No
-    backward."""
-    lib = _lib.load()
-    prec = _PRECISION["mode"] if precision is None else precision
+def _gno_knn_args(fn, mode, weights, biases, y_pos, x_pos, f_y, src_table, nbr, k):
+    """the operand checks shared by ``gno_forward_knn`` and ``gno_forward_knn_jac``"""
     md = {"linear": 0, **GNO_MODES}.get(mode, mode)
     if md not in (0, 1, 2):
-        raise GaotError(f"gno_forward_knn: mode must be 'linear' or one of {tuple(GNO_MODES)}, got {mode!r}")
+        raise GaotError(f"{fn}: mode must be 'linear' or one of {tuple(GNO_MODES)}, got {mode!r}")
     m, keep = _mlp_struct(weights, biases)
     y_pos = _req(y_pos, torch.float32, "y_pos")
     x_pos = _req(x_pos, torch.float32, "x_pos")
@@ -319,11 +312,44 @@ def gno_forward_knn(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Op
             raise GaotError(f"src_table must be [{n_src}, 64], got {tuple(src_table.shape)}")
     else:
         src_table = None
+    return md, m, keep, y_pos, x_pos, f_y, src_table, nbr, k, q
+
+
+def gno_forward_knn(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], src_table: Optional[Tensor],
+                    nbr: Tensor, k: int, precision: Optional[int] = None) -> Tensor:
+    """the fused transform's FORWARD on a regular neighbour list (gaot_gno_fwd_knn): ``nbr`` int32 [n_query * k] with
+    nbr[q*k + j] = the j-th source of query q (``knn_grid``'s output as it stands), k in ``GNO_KNN_K``.  ``mode``: 0 / 'linear'
+    (``src_table`` None), 'nonlinear', 'nonlinear_kernelonly' (``f_y`` None), operands as in ``gno_forward`` / ``gno_nl_forward``.
+    One launch, no edge list, no sorted lists, no workspace; bit-identical to those two on ``build_graph`` of the same lists.  No
+    backward."""
+    lib = _lib.load()
+    prec = _PRECISION["mode"] if precision is None else precision
+    md, m, keep, y_pos, x_pos, f_y, src_table, nbr, k, q = _gno_knn_args("gno_forward_knn", mode, weights, biases, y_pos, x_pos, f_y,
+                                                                         src_table, nbr, k)
     out = torch.empty(q, m.channels, dtype=torch.float32, device=x_pos.device)
     with _timed(f"gno_fwd_knn{f'_nl{md}' if md else ''}_nh{m.n_hidden}"):
         check(lib.gaot_gno_fwd_knn(C.byref(m), md, _ptr(y_pos), _ptr(x_pos), _ptr(f_y), _ptr(src_table), _ptr(nbr), k, q, _ptr(out),
                                    prec, _stream()), "gaot_gno_fwd_knn")
     return out
+
+
+def gno_forward_knn_jac(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], src_table: Optional[Tensor],
+                        nbr: Tensor, k: int):
+    """``gno_forward_knn`` with the spatial derivative of its result (gaot_gno_fwd_knn_jac): -> (out [n_query, 32],
+    jac [3, n_query, 32]) with jac[d, q, c] = d out[q, c] / d x_pos[q, d], the neighbour list of every query held fixed (the derivative
+    autograd returns through ``gno_forward`` on the graph of these lists; valid almost everywhere, not across the surfaces where a
+    query's k nearest sources change).  Forward mode: three tangents ride through the per-edge MLP beside the value, one launch,
+    nothing stored, no backward.  Exact fp32 whatever the precision mode: ``out`` is ``gno_forward_knn(..., precision=0)`` bit for
+    bit.  Operands and their checks are those of ``gno_forward_knn``."""
+    lib = _lib.load()
+    md, m, keep, y_pos, x_pos, f_y, src_table, nbr, k, q = _gno_knn_args("gno_forward_knn_jac", mode, weights, biases, y_pos, x_pos,
+                                                                         f_y, src_table, nbr, k)
+    out = torch.empty(q, m.channels, dtype=torch.float32, device=x_pos.device)
+    jac = torch.empty(3, q, m.channels, dtype=torch.float32, device=x_pos.device)
+    with _timed(f"gno_fwd_knn_jac{f'_nl{md}' if md else ''}_nh{m.n_hidden}"):
+        check(lib.gaot_gno_fwd_knn_jac(C.byref(m), md, _ptr(y_pos), _ptr(x_pos), _ptr(f_y), _ptr(src_table), _ptr(nbr), k, q,
+                                       _ptr(out), _ptr(jac), _stream()), "gaot_gno_fwd_knn_jac")
+    return out, jac
 
 
 def gno_nl_backward(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], src_table: Tensor, grad_out: Tensor,

@@ -160,6 +160,22 @@ int gaot_gno_fwd_knn(const gaot_mlp_t* mlp /* host */, int mode, const float* y_
                      const float* src_table, const int32_t* nbr /* [num_queries * k] */, int k, int64_t num_queries,
                      float* out /* [num_queries, channels] */, int precision, gaot_stream_t stream);
 
+/* gaot_gno_fwd_knn with the spatial derivative of its result, for the gradient / Jacobian of a sampled field at the query points:
+ *   jac[d][q][c] = d out[q][c] / d x_pos[q][d],  d = 0..2        (direction-major: each direction is a plain [num_queries, channels]
+ * row matrix), the neighbour list of every query held fixed -- the derivative autograd returns through gaot_gno_fwd / gaot_gno_bwd_coords
+ * on the graph of these lists.  It is valid almost everywhere and not defined across the surfaces where a query's k nearest sources
+ * change.  Forward mode in ONE launch: only the three query columns of the first layer see x_pos, so three tangents ride through
+ * the per-edge MLP beside the value (dh_0 = gelu'(z_0) W_0[:, 3+d], dh_l = gelu'(z_l) (W_l dh_{l-1}), dk = W_L dh) and are reduced by
+ * the same fixed-k row means; src_table and f_y do not depend on x_pos.  Nothing is stored, no backward runs, no workspace, no
+ * atomics.  Operands and argument rules are gaot_gno_fwd_knn's (k in {1, 2, 4, 8, 16, 32}, 1 <= n_hidden <= 4, hidden 64, channels
+ * 32, the three modes, num_queries * k within int32); both outputs are required.  There is no precision argument: the kernel is exact
+ * fp32 (v_mfma_f32_32x32x2_f32) in both precision modes of the library, and `out` is what gaot_gno_fwd_knn writes at precision 0,
+ * bit for bit. */
+int gaot_gno_fwd_knn_jac(const gaot_mlp_t* mlp /* host */, int mode, const float* y_pos, const float* x_pos, const float* f_y,
+                         const float* src_table, const int32_t* nbr /* [num_queries * k] */, int k, int64_t num_queries,
+                         float* out /* [num_queries, channels] */, float* jac /* [3, num_queries, channels] */,
+                         gaot_stream_t stream);
+
 /* Dot-product attention scores of the attention-weighted transform (reference integral_transform.py:128-137, use_attn with
  * attention_type "dot_product") as a bilinear form of the homogeneous endpoint coordinates (csrc/gno_attn.hip):
  *   scores[e] = scale * [x_pos[dst[e]], 1]^T M [y_pos[src[e]], 1]        x_pos / y_pos: [*, 3] rows, m: DEVICE [4][4] fp32

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Kernel microbenchmarks at the configs[1] shapes (for rocprofv3 / quick A-B): attention fwd+bwd, GEMM shapes, GNO, PointNet GeoEmbed,
-the attention-weighted GNO, the forward-only decoder (decoder_sample)."""
+the attention-weighted GNO, the forward-only decoder (decoder_sample), the sampled field's Jacobian (decoder_jacobian)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 if os.environ.get("MB_TREE"):      # measure another checkout's package (gno_weighted: the parent commit's) with this script
@@ -518,3 +518,86 @@ elif what == "decoder_sample":
                   f"{100 * (tb[-1] - tb[0]) / mb:.1f} %), peak {pb / 2**20:9.1f} MiB  = {mb / ma:.3f} x (a) in time, {pb / max(pa, 1):.3f} x in "
                   f"peak memory; max|a - b| = {diff:.1e}", flush=True)
         del q, q_bidx
+elif what == "decoder_jacobian":
+    # From query coordinates to predictions AND their spatial Jacobian on the configs[1] decoder (latent 64x64x32 tokens, C = 32, knn
+    # k = 8, kernel MLP hidden [64, 64], projection 32 -> 256 -> 1) at 500 K and 8 M random query points, fp32 mode:
+    #   (a) the autograd route: neighbour strategy (knn_to_grid + edge_index) -> build_graph (two radix sorts) -> decoder on queries
+    #       that require grad -> one backward per output channel, in one piece (MAGNODecoder.sample_jacobian's fall-back route);
+    #   (b) MAGNODecoder.sample_jacobian's streaming route: per chunk knn_to_grid -> gaot_gno_fwd_knn_jac -> scale mix -> projection
+    #       tangent (MB_CHUNK points, default the method's own default).
+    # (a) and (b) alternate in this one process after a warm-up of each; device events around synchronised work; `reps` rounds; a row
+    # is the median with min / max, the peak is the rise of allocated memory over the inputs.  Then the split of (b) -- each stage
+    # timed over all chunks on its own -- and the tangent kernel against gaot_gno_fwd_knn (precision 0) on the same list.  Kept in
+    # profiles/decoder_jacobian_microbench.txt.
+    from gaot_3d_amd import graph as device_graph
+    from gaot_3d_amd.data import latent_grid
+    from gaot_3d_amd.model.layers.magno import MAGNOConfig, MAGNODecoder
+    gaot_3d_amd.set_precision("fp32")
+    latent = (64, 64, 32)
+    cfg = MAGNOConfig(gno_coord_dim=3, lifting_channels=32, mlp_type="linear", use_geoembed=[True, False], neighbor_strategy="knn",
+                      k_neighbors=8, gno_radius=0.033, out_gno_channel_mlp_hidden_layers=[64, 64], precompute_edges=False)
+    dec = MAGNODecoder(in_channels=32, out_channels=1, gno_config=cfg).to(dev).eval()
+    dec.latent_dims = latent
+    tokens = latent_grid(latent).to(dev)
+    rn = torch.randn(tokens.shape[0], 32, device=dev)
+    chunk = int(os.environ["MB_CHUNK"]) if os.environ.get("MB_CHUNK") else None
+    step = chunk or dec.SAMPLE_CHUNK
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); out = fn(); e1.record()
+        torch.cuda.synchronize()
+        peak = torch.cuda.max_memory_allocated() - base
+        return e0.elapsed_time(e1), peak, out
+
+    def median(ts):
+        ts = sorted(ts)
+        return ts[len(ts) // 2], ts[0], ts[-1]
+
+    for nq in (500000, 8000000):
+        q = torch.rand(nq, 3, device=dev) * 2 - 1
+
+        def route_a():
+            dec._stream_grid = lambda *a: None          # the autograd route, the queries in one piece
+            try:
+                return dec.sample_jacobian(rn, q, tokens, chunk_points=nq)
+            finally:
+                del dec._stream_grid
+        route_b = lambda: dec.sample_jacobian(rn, q, tokens, chunk_points=chunk)
+        ra, rb = timed(route_a)[2], timed(route_b)[2]          # warm-up, and the two routes agree
+        dp = (ra[0] - rb[0]).abs().max().item()
+        dj = (ra[1] - rb[1]).abs().max().item() / ra[1].abs().max().item()
+        del ra, rb
+        ta, tb, pa, pb = [], [], 0, 0
+        for _ in range(reps):
+            t, p, _o = timed(route_a); ta.append(t); pa = max(pa, p); del _o
+            t, p, _o = timed(route_b); tb.append(t); pb = max(pb, p); del _o
+        (ma, lo_a, hi_a), (mb, lo_b, hi_b) = median(ta), median(tb)
+        print(f"Nq={nq} fp32: (a) autograd route, one piece       {ma:9.3f} ms (min {lo_a:.3f}, max {hi_a:.3f}, spread "
+              f"{100 * (hi_a - lo_a) / ma:.1f} %), peak {pa / 2**20:9.1f} MiB")
+        print(f"Nq={nq} fp32: (b) sample_jacobian (chunk {step}) {mb:9.3f} ms (min {lo_b:.3f}, max {hi_b:.3f}, spread "
+              f"{100 * (hi_b - lo_b) / mb:.1f} %), peak {pb / 2**20:9.1f} MiB  = {mb / ma:.3f} x (a) in time, {pb / max(pa, 1):.3f} x in "
+              f"peak memory; (a) - (b) = {ma - mb:.3f} ms against a spread of {max(hi_a - lo_a, hi_b - lo_b):.3f} ms; "
+              f"max|pred_a - pred_b| = {dp:.1e}, max|jac_a - jac_b| / peak = {dj:.1e}", flush=True)
+        # the split of (b): every stage over all chunks on its own (the stages' inputs kept from the stage before)
+        grid = dec._stream_grid(rn, q, tokens)
+        with torch.no_grad():
+            chunks = [q[i:i + step] for i in range(0, nq, step)]
+            t_nbr, t_jac, t_fwd, t_proj = [], [], [], []
+            for _ in range(reps + 1):                                      # the first round warms up and is dropped
+                t, _p, nbrs = timed(lambda: [device_graph.knn_to_grid(c, grid, 8) for c in chunks]); t_nbr.append(t)
+                t, _p, outs = timed(lambda: [dec.gno.jacobian_knn(tokens, c, n, 8, rn) for c, n in zip(chunks, nbrs)]); t_jac.append(t)
+                t, _p, vals = timed(lambda: [dec.gno.forward_knn(tokens, c, n, 8, rn) for c, n in zip(chunks, nbrs)]); t_fwd.append(t)
+                del vals
+                t, _p, prj = timed(lambda: [dec.projection.jvp_rows(o, list(j.unbind(0))) for o, j in outs]); t_proj.append(t)
+                del nbrs, outs, prj
+            (mn, _, _), (mj, lo_j, hi_j), (mf, lo_f, hi_f), (mp, _, _) = (median(t[1:]) for t in (t_nbr, t_jac, t_fwd, t_proj))
+            tot = mn + mj + mp
+            print(f"Nq={nq} fp32: split of (b): neighbour search {mn:.3f} ms ({100 * mn / tot:.0f} %), GNO tangent kernel {mj:.3f} ms "
+                  f"({100 * mj / tot:.0f} %), mix + projection tangent {mp:.3f} ms ({100 * mp / tot:.0f} %); stages sum to {tot:.3f} ms")
+            print(f"Nq={nq} fp32: gaot_gno_fwd_knn_jac {mj:.3f} ms (min {lo_j:.3f}, max {hi_j:.3f}) against gaot_gno_fwd_knn at precision 0 "
+                  f"{mf:.3f} ms (min {lo_f:.3f}, max {hi_f:.3f}) on the same lists: {mj / mf:.2f} x", flush=True)
+        del q, chunks
