@@ -42,9 +42,39 @@ class LatentGrid:
         return _Grid((C.c_int32 * 3)(*self.dims), (C.c_float * 3)(*self.lo), (C.c_float * 3)(*self.hi))
 
 
-def as_latent_grid(latent_pos: Tensor, dims: Sequence[int], rtol: float = 1e-4) -> LatentGrid:
+WINDOW_SLACK = 1e-4      # the relative slack of knn_grid_select's window test (csrc/graph.hip: bound * (1 - 1e-4))
+_U = 2.0 ** -24          # fp32 unit roundoff
+
+
+def grid_deviation_bound(dims: Sequence[int], slack: float = WINDOW_SLACK) -> float:
+    """The largest distance, in units of the grid's smallest step, a stored token coordinate may lie from its ideal node
+    ``lo + i * (hi - lo) / (n - 1)`` (exact arithmetic on the stored corner coordinates) for the grid kernels' lists to be exact.
+
+    knn_grid_select stops at a window once ``kth < (bound * (1 - slack))^2``, where ``bound`` is the kernel's fp32 value of the
+    distance D from the query to the nearest excluded grid PLANE (axis a, ideal position).  A token of that plane is at least
+    ``D - delta`` away (delta: its deviation along axis a), and the kernel's value is at most ``(D + 5u |f| step_a)(1 + 4u)``:
+    f = (p - lo) / step carries five roundings (p - lo; hi - lo, / (n - 1) and 1 / step behind inv_step; the product), the
+    subtraction of the plane index and the product with step (two roundings behind it) four more.  dist2, bound * (1 - slack) and
+    its square round too: another 4u relative.  The stop is therefore sound when
+        delta + 5u |f| step_a <= (slack - 8u) D.
+    Inside the box |f| <= C = n - 1 cells and D >= (1.5 - 5u C) step_a at the first window (w = 1; rint puts the query within half a
+    cell of the base node, the excluded plane is two nodes from it); wider windows and queries outside the box raise D by at least
+    as many cells as |f|, and slack - 8u > 5u.  With step_a >= step_min:
+        delta / step_min <= (1.5 - 5u C)(slack - 8u) - 5u C,       C = the largest number of cells along one axis.
+    At slack = 1e-4 that is 1.30e-4 for 64 nodes, 7.3e-5 for 256 and no longer positive beyond C = 500 cells: larger grids are
+    not accepted.  (radius_grid_visit floors / ceils its window outwards: a whole cell of margin, nothing to add here.)"""
+    c = max(int(v) for v in dims) - 1
+    return (1.5 - 5 * _U * c) * (slack - 8 * _U) - 5 * _U * c
+
+
+def as_latent_grid(latent_pos: Tensor, dims: Sequence[int], rtol: float = WINDOW_SLACK) -> LatentGrid:
     """Check that ``latent_pos [D*H*W, 3]`` is the reference's ``meshgrid(linspace, indexing='ij')`` grid (possibly
-    rescaled per axis) and describe it.  Raises GaotError otherwise (no tree search on this path)."""
+    rescaled per axis) and describe it.  Raises GaotError otherwise (no tree search on this path).
+
+    Accepted: every stored coordinate within ``grid_deviation_bound(dims, rtol) * step_min`` of its ideal node, measured in fp64
+    against the exact subdivision of the stored corners (``step_min``: the smallest step of an axis with more than one node).
+    ``rtol`` is the slack the deviation budget is derived from; the kernels' own is WINDOW_SLACK, so a larger value is cut to
+    it -- every grid accepted here gives exact lists."""
     d, h, w = (int(v) for v in dims)
     if latent_pos.dim() != 2 or latent_pos.shape[1] != 3 or latent_pos.shape[0] != d * h * w:
         raise GaotError(f"latent tokens {tuple(latent_pos.shape)} do not form a {d}x{h}x{w} grid")
@@ -52,10 +82,15 @@ def as_latent_grid(latent_pos: Tensor, dims: Sequence[int], rtol: float = 1e-4) 
     g = p.view(d, h, w, 3)
     lo = [float(g[0, 0, 0, a]) for a in range(3)]
     hi = [float(g[-1, -1, -1, a]) for a in range(3)]
-    span = max(max(abs(hi[a] - lo[a]) for a in range(3)), 1e-30)
-    ref = torch.stack(torch.meshgrid(*[torch.linspace(lo[a], hi[a], n, device=p.device) for a, n in enumerate((d, h, w))],
-                                     indexing="ij"), dim=-1)
-    if float((g - ref).abs().max()) > rtol * span or any((n > 1 and not hi[a] > lo[a]) for a, n in enumerate((d, h, w))):
+    bad = any((n > 1 and not hi[a] > lo[a]) for a, n in enumerate((d, h, w)))
+    steps = [(hi[a] - lo[a]) / (n - 1) for a, n in enumerate((d, h, w)) if n > 1]
+    step_min = min(steps) if steps and not bad else 1.0      # a one-token grid has no step: the three coordinates must just agree
+    tol = grid_deviation_bound((d, h, w), min(float(rtol), WINDOW_SLACK)) * step_min
+    if not bad and tol > 0.0:
+        ref = torch.stack(torch.meshgrid(*[lo[a] + torch.arange(n, device=p.device, dtype=torch.float64) * ((hi[a] - lo[a]) / max(n - 1, 1))
+                                           for a, n in enumerate((d, h, w))], indexing="ij"), dim=-1)
+        bad = not float((g.double() - ref).abs().max()) <= tol
+    if bad or not tol > 0.0:
         raise GaotError("latent tokens are not a regular ascending meshgrid(linspace) grid: device graph construction "
                         "needs the reference's regular token grid")
     return LatentGrid((d, h, w), tuple(lo), tuple(hi), p)
