@@ -296,7 +296,7 @@ QUERY_LIST_STRATEGIES = ("radius", "bidirectional")
 QUERY_LIST_MAX_K = 32     # the register-list capacities gaot_nbr_union_grid_* is instantiated for
 
 
-def query_lists(strategy: str, query_pos: Tensor, grid: LatentGrid, radius: float, k: int) -> ops.BipartiteGraph:
+def query_lists(strategy: str, query_pos: Tensor, grid: LatentGrid, radius: float, k: int, lead: int = 0) -> ops.BipartiteGraph:
     """The by-query neighbour list of a 'radius' or 'bidirectional' DECODER graph for one regular token grid, written row by row --
     what ``ops.csr_build(_decoder_edges(strategy, ...), 1, Nq)`` holds in ``rowptr`` / ``key`` / ``other``, without the edge list,
     ``coalesce`` or a sort.  Both neighbourhoods are defined per query ('radius': the tokens within ``radius``, the ``RADIUS_CAP``
@@ -305,7 +305,10 @@ def query_lists(strategy: str, query_pos: Tensor, grid: LatentGrid, radius: floa
 
     FORWARD ONLY: ``by_dst`` is ``SortedEdges(rowptr=offsets, perm=None, key=query ids, other=token ids)`` -- the three arrays the
     fused forward (``ops.gno_forward`` / ``ops.gno_nl_forward``) reads -- and ``by_src`` is None; a backward needs ``build_graph``.
-    One host read of the total (it sizes the two id lists), as in ``radius_pairs``: raises while a stream is being captured."""
+    One host read of the total (it sizes the two id lists), as in ``radius_pairs``: raises while a stream is being captured.
+    ``lead`` > 0 (``ops.gno_forward_jac`` alone reads such a list): the lists begin with ``lead`` PADDING edges (query id -1, token 0)
+    and ``rowptr`` starts at ``lead``, so that a piece of a longer list can lie against the kernels' 32-edge tiles as it does there
+    (``lead`` = the edges before it, modulo 32); the rows are written at their shifted offsets, nothing is copied."""
     if strategy not in QUERY_LIST_STRATEGIES:
         raise ValueError(f"query_lists: strategy must be one of {QUERY_LIST_STRATEGIES}, got {strategy!r}")
     _need_cuda(query_pos, "query_lists")
@@ -337,8 +340,15 @@ def query_lists(strategy: str, query_pos: Tensor, grid: LatentGrid, radius: floa
         check(count(*head, ops._ptr(counts), ops._stream()), what + "_count")
     offs = exclusive_scan(counts)
     total = int(offs[-1])     # host sync: sizes the lists
-    qi = torch.empty(total, dtype=torch.int32, device=p.device)
-    tk = torch.empty(total, dtype=torch.int32, device=p.device)
+    lead = int(lead)
+    if lead < 0:
+        raise GaotError(f"query_lists: lead must not be negative, got {lead}")
+    qi = torch.empty(lead + total, dtype=torch.int32, device=p.device)
+    tk = torch.empty(lead + total, dtype=torch.int32, device=p.device)
+    if lead:
+        offs = offs + lead
+        qi[:lead] = -1
+        tk[:lead] = 0
     if total:
         check(fill(*head, ops._ptr(offs), ops._ptr(qi), ops._ptr(tk), ops._stream()), what + "_fill")
     return ops.BipartiteGraph(ops.SortedEdges(offs, None, qi, tk, n), None, grid.num_tokens, n)

@@ -149,18 +149,21 @@ class GAOT3D(nn.Module):
         return self.decoder.sample(latent, query_pos.to(latent.device), lat, chunk_points=chunk_points)
 
     def sample_jacobian(self, latent: torch.Tensor, query_pos: torch.Tensor, tokens_pos: Optional[torch.Tensor] = None,
-                        chunk_points: Optional[int] = None):
+                        chunk_points: Optional[int] = None, row_lists: bool = False):
         """``sample`` with the field's spatial derivative: -> (pred [Nq, output_size], jac [Nq, output_size, coord_dim]) with
         jac[q, o, d] = d pred[q, o] / d query_pos[q, d] (pressure gradient, wall-normal derivative, velocity Jacobian), every query's
         neighbour list held fixed: the derivative autograd returns through ``forward(query_coord_pos=...)``, valid almost everywhere
         and not defined across the surfaces where a query's nearest tokens change.  ``MAGNODecoder.sample_jacobian``: the shipped 'knn'
         decoder streams it in forward mode (no edge list, no autograd graph, no backward); neither result requires grad.  That path
-        is exact fp32 in both precision modes, so in bf16 mode ``pred`` differs from ``sample``'s by bf16 rounding."""
+        is exact fp32 in both precision modes, so in bf16 mode ``pred`` differs from ``sample``'s by bf16 rounding.
+        ``row_lists=True`` streams 'radius' / 'bidirectional' decoders in the same way on row lists (``graph.query_lists`` and the
+        tangent kernel on ragged rows) instead of the autograd route; it changes nothing for other decoders."""
         if latent.dim() != 2 or latent.shape[0] != self.num_latent_tokens:
             raise ValueError(f"sample_jacobian: latent {tuple(latent.shape)} is not ONE sample's [{self.num_latent_tokens}, "
                              f"{self.node_latent_size}] token rows (sample the graphs of a batch one by one)")
         lat, _ = self._tokens(1, latent.device, tokens_pos, None)
-        return self.decoder.sample_jacobian(latent, query_pos.to(latent.device), lat, chunk_points=chunk_points)
+        return self.decoder.sample_jacobian(latent, query_pos.to(latent.device), lat, chunk_points=chunk_points,
+                                            row_lists=row_lists)
 
     def forward(self, batch, tokens_pos: Optional[torch.Tensor] = None, tokens_batch_idx: Optional[torch.Tensor] = None,
                 query_coord_pos: Optional[torch.Tensor] = None, query_coord_batch_idx: Optional[torch.Tensor] = None,

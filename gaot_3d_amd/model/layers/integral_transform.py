@@ -20,7 +20,9 @@ element-wise glue and its autograd in csrc/edgeops.hip (gaot_3d_amd/edgeops.py),
 the same operands, one ``gaot_gno_fwd_knn`` launch per 32-channel pass, no edge list or sorted lists, bit-identical to ``forward`` on
 the graph of those lists -- what ``MAGNODecoder.sample`` streams query chunks through.  ``jacobian_knn`` is ``forward_knn`` with the
 derivative of its result with respect to the query coordinates, in forward mode (``gaot_gno_fwd_knn_jac``: three tangents through the
-per-edge MLP beside the value, exact fp32) -- what ``MAGNODecoder.sample_jacobian`` streams.
+per-edge MLP beside the value, exact fp32) -- what ``MAGNODecoder.sample_jacobian`` streams.  ``jacobian_rows`` is the same on the
+ragged by-query list of any graph (``gaot_gno_fwd_jac``: the tangent kernel finished by the forward's segmented walk and one fix-up
+launch) -- what ``sample_jacobian(row_lists=True)`` streams for 'radius' / 'bidirectional' decoders.
 HIP only, no CPU fallback."""
 from typing import Optional
 
@@ -183,6 +185,22 @@ class IntegralTransform(nn.Module):
                                           f"on lists of k in {ops.GNO_KNN_K} neighbours per query")
             return self._forward_fused(fcs, y_pos, x_pos, f_y, None, *plan, knn=(nbr, int(k)), jac=True)
 
+    def jacobian_rows(self, y_pos, x_pos, f_y: Optional[torch.Tensor], graph):
+        """``jacobian_knn`` on RAGGED rows: ``graph`` holds the by-query list of any graph (``graph.by_dst``; ``by_src`` may be None, as
+        ``graph.query_lists`` leaves it) -> (out [N_x, C], jac [3, N_x, C]), every query's list held fixed, empty rows exact zeros.
+        Forward mode, one ``ops.gno_forward_jac`` call (the tangent kernel and its fix-up) per 32-channel pass, exact fp32 in both
+        precision modes: ``out`` is ``forward``'s fp32-mode result on the same graph bit for bit.  The operands are prepared exactly
+        as in ``forward``; the planes of the directions a coordinate dimension of 1 / 2 is padded with are exact zeros.  Runs exactly
+        when ``_fused_plan`` is not None and raises NotImplementedError otherwise.  Nothing is recorded for autograd."""
+        if self.transform_type not in ("linear", "nonlinear", "nonlinear_kernelonly"):
+            raise ValueError(f"Invalid transform_type: {self.transform_type}")
+        fcs = list(self.channel_mlp.fcs)
+        with torch.no_grad():
+            plan = self._fused_plan(fcs, f_y, y_pos, x_pos)
+            if plan is None:
+                raise NotImplementedError("IntegralTransform.jacobian_rows: only the transforms the fused kernels evaluate (_fused_plan)")
+            return self._forward_fused(fcs, y_pos, x_pos, f_y, graph, *plan, jac=True)
+
     @staticmethod
     def _pad3(pos):
         """coordinates of dimension 1 / 2 padded with zeros to the kernels' 3-D rows"""
@@ -258,7 +276,8 @@ class IntegralTransform(nn.Module):
         autograd adds the passes' gradients with respect to them (padded channels carry zero grad_out and zero f: exact zeros).
         ``knn`` = (nbr, k) (``forward_knn``; ``graph`` is None, no autograd): the passes run ``ops.gno_forward_knn`` on the regular
         list instead of the autograd Functions; with ``jac`` (``jacobian_knn``) they run ``ops.gno_forward_knn_jac`` and the result is
-        (out [N_x, c], jac [3, N_x, c])."""
+        (out [N_x, c], jac [3, N_x, c]).  ``jac`` with a ``graph`` (``jacobian_rows``; no autograd either): the passes run
+        ``ops.gno_forward_jac`` on the graph's by-query list, with the same result shapes."""
         w2 = lambda fc: fc.weight[:, :, 0] if fc.weight.dim() == 3 else fc.weight    # Conv1d(k=1) storage of mlp_type='channel'
         pad_hidden = any(fc.weight.shape[0] != 64 for fc in fcs[:-1])
         tt = self.transform_type
@@ -266,6 +285,8 @@ class IntegralTransform(nn.Module):
             if knn is not None:
                 fwd = ops.gno_forward_knn_jac if jac else ops.gno_forward_knn
                 return fwd(0, [w2(fc) for fc in fcs], [fc.bias for fc in fcs], y_pos, x_pos, f_y, None, *knn)
+            if jac:
+                return ops.gno_forward_jac(0, [w2(fc) for fc in fcs], [fc.bias for fc in fcs], y_pos, x_pos, f_y, None, graph)
             params = []
             for fc in fcs:
                 params += [fc.weight, fc.bias]
@@ -306,10 +327,10 @@ class IntegralTransform(nn.Module):
                 wb = torch.nn.functional.pad(wb, (0, 0, 0, 32 - n))
                 bb = torch.nn.functional.pad(bb, (0, 32 - n))
                 fb = None if fb is None else torch.nn.functional.pad(fb, (0, 32 - n))
-            if knn is not None:
-                fwd = ops.gno_forward_knn_jac if jac else ops.gno_forward_knn
+            if knn is not None or jac:
+                fwd = ops.gno_forward_jac if knn is None else ops.gno_forward_knn_jac if jac else ops.gno_forward_knn
                 o = fwd(tt, [w0.contiguous(), *mid[0::2], wb.contiguous()], [b0, *mid[1::2], bb.contiguous()], y3, x3,
-                        None if fb is None else fb.contiguous(), t, *knn)
+                        None if fb is None else fb.contiguous(), t, *(knn if knn is not None else (graph,)))
                 if jac:
                     outs.append((o[0][:, :n], o[1][:, :, :n]) if n < 32 else o)
                     continue

@@ -192,6 +192,51 @@ def _mix_scales(module, outs, pos):
     return GF.ScaleMixFn.apply(logits, *outs)
 
 
+def _softmax_weight_tangents(w, active, w1, w2, rows_matmul):
+    """The derivative of the scale weights w = softmax(l), l = W_2 relu(W_1 pos + b_1) + b_2, with respect to the position:
+        d_d l = W_2 (1[z > 0] * W_1[:, d]),    d_d w_s = w_s (d_d l_s - sum_t w_t d_d l_t)
+    ``w`` [n, scales], ``active`` = 1[z > 0] [n, hidden], ``w1`` [hidden, dims], ``w2`` [scales, hidden];
+    ``rows_matmul(x, W)`` = x W^T row by row.  -> one [n, scales] tensor per direction.  The sum over the scales is written term by
+    term: a row's result does not depend on how many rows there are."""
+    ns = w.shape[1]
+    dws = []
+    for d in range(w1.shape[1]):
+        dl = rows_matmul(active * w1[:, d], w2)
+        mean = w[:, 0] * dl[:, 0]
+        for s in range(1, ns):
+            mean = mean + w[:, s] * dl[:, s]
+        dws.append(torch.stack([w[:, s] * (dl[:, s] - mean) for s in range(ns)], dim=1))
+    return dws
+
+
+def _mix_scales_jvp(module, outs, jacs, pos):
+    """``_mix_scales`` with its tangent along the three query directions: ``outs[s]`` [n, C] and ``jacs[s]`` [3, n, C] of every scale
+    -> [value, d/dx, d/dy, d/dz], [n, C] each.  The value is ``_mix_scales``'s (bit for bit).  Summed scales: the sum of each plane.
+    Softmax weights w = softmax(l), l = W_2 relu(W_1 pos + b_1) + b_2, depend on the query position themselves:
+        d_d mix = sum_s w_s d_d out_s + sum_s (d_d w_s) out_s          (d_d w: ``_softmax_weight_tangents``)
+    -- with different lists per scale the second sum does not vanish.  Per-row fp32 operations only (the row kernels and
+    elementwise torch ops), so a row's result does not depend on the chunk it is in."""
+    ns = len(outs)
+    if ns == 1:
+        return [outs[0], *jacs[0].unbind(0)]
+    if not module.use_scale_weights:
+        return [_sum_scales(outs)] + [_sum_scales([j[d] for j in jacs]) for d in range(3)]
+    sw = module.scale_weighting
+    h = GF.linear(pos, sw[0].weight, sw[0].bias, act="relu", precision=0)
+    logits = GF.linear(h, sw[2].weight, sw[2].bias, precision=0)
+    planes = [GF.ScaleMixFn.apply(logits, *outs)]
+    w = torch.softmax(logits, dim=1)                       # [n, scales]
+    active = (h > 0).to(h.dtype)                           # relu'(z): [n, 16]
+    dws = _softmax_weight_tangents(w, active, sw[0].weight, sw[2].weight, lambda x, wt: GF.linear(x, wt, None, precision=0))
+    for d in range(3):
+        acc = None
+        for s in range(ns):
+            term = w[:, s:s + 1] * jacs[s][d] + dws[d][:, s:s + 1] * outs[s]
+            acc = term if acc is None else acc + term
+        planes.append(acc)
+    return planes
+
+
 class MAGNOEncoder(nn.Module):
     def __init__(self, in_channels, out_channels, gno_config: MAGNOConfig):
         super().__init__()
@@ -480,7 +525,8 @@ class MAGNODecoder(nn.Module):
             out[i:i + chunk] = self._decode(rndata_flat, q, q_bidx, lat, lat_bidx, None, False)
         return out
 
-    def sample_jacobian(self, rndata_flat, query_pos, latent_tokens_pos, chunk_points: Optional[int] = None):
+    def sample_jacobian(self, rndata_flat, query_pos, latent_tokens_pos, chunk_points: Optional[int] = None,
+                        row_lists: bool = False):
         """``sample`` with the spatial derivative of the field: -> (pred [Nq, out_channels], jac [Nq, out_channels, coord_dim]) with
         jac[q, o, d] = d pred[q, o] / d query_pos[q, d], every query's neighbour list held fixed -- the derivative autograd returns
         through ``forward(query_coord_pos=...)``, where edges are built once and not differentiated.  It is valid almost everywhere
@@ -496,7 +542,18 @@ class MAGNODecoder(nn.Module):
         themselves multiplies sum_s dw_s = 0 and drops out.  No edge_index, no sorted lists, no autograd graph, no backward pass, no
         host synchronisation (capturable in a graph after one eager call, as ``sample``).  Everything on this path is exact fp32 in
         both precision modes: in bf16 mode ``pred`` is the fp32-kernel value and differs from ``sample``'s by bf16 rounding.
-        Every other configuration ('radius' / 'bidirectional' decoders included) takes the AUTOGRAD route: per chunk ``forward``'s
+        ``row_lists=True`` (opt-in; without it every configuration runs the route it ran before the argument existed) streams the
+        'radius' and 'bidirectional' decoders too, under exactly the conditions of ``sample``'s row-list route ('bidirectional':
+        k_neighbors <= ``graph.QUERY_LIST_MAX_K``): per chunk and scale ``graph.query_lists`` writes the by-query list and
+        ``jacobian_rows`` runs the tangent kernel on its ragged rows (two launches per 32-channel pass), then the scale mix WITH the
+        tangent of its weights -- the scales see different lists, so sum_s (dw_s) out_s does not vanish (``_mix_scales_jvp``) -- and
+        ``jvp_rows``.  Exact fp32 in both precision modes; ``pred`` is the fp32-mode result of ``sample`` with the queries
+        in one piece, bit for bit.  The results do not depend on ``chunk_points``: a row that straddles two of the kernel's 32-edge
+        tiles is summed from two partial sums, so every chunk's list is led by as many padding edges as put its rows against the
+        tiles where the list of ALL queries would have them (``query_lists(..., lead=)``).  The lists are sized by a host read, so
+        this route raises GaotError inside a stream capture, before any launch.  It differs from the autograd route by fp32
+        rounding (forward against reverse mode).  The flag changes nothing for any other configuration.
+        Every other configuration ('radius' / 'bidirectional' decoders without ``row_lists``) takes the AUTOGRAD route: per chunk ``forward``'s
         decoder on a detached copy of the chunk that requires grad, then one backward pass per output channel.  use_attn raises the
         NotImplementedError ``IntegralTransform`` raises for coordinate gradients; a 'statistical' decoder GeoEmbed couples all
         queries through its z-score, so a per-query Jacobian is not what that route returns: NotImplementedError."""
@@ -523,6 +580,32 @@ class MAGNODecoder(nn.Module):
         if self.decoder_strategy == "knn" and k in ops.GNO_KNN_K:
             with torch.no_grad():           # the plan of the forward alone, as ``sample`` asks for it (four hidden layers stream in fp32 mode)
                 grid = self._stream_grid(rndata_flat, query_pos, lat)
+        strategy = self.decoder_strategy
+        by_rows = bool(row_lists) and (strategy == "radius" or (strategy == "bidirectional" and k <= device_graph.QUERY_LIST_MAX_K))
+        if by_rows:
+            with torch.no_grad():
+                grid = self._stream_grid(rndata_flat, query_pos, lat)
+        if grid is not None and by_rows:
+            with torch.no_grad():
+                before = [0] * len(self.scales)           # edges of the earlier chunks, per scale
+                for i in range(0, nq, chunk):
+                    q = query_pos[i:i + chunk]
+                    outs, jacs = [], []
+                    for si, scale in enumerate(self.scales):  # the radius, hence the rows, of every scale as ``_decode`` derives it
+                        # the chunk's rows lie against the kernel's 32-edge tiles as they would in the list of ALL queries (so many
+                        # padding edges lead the list): a row is summed in the same order whatever the chunking
+                        lead = before[si] % 32
+                        rows = device_graph.query_lists(strategy, q, grid, self.gno_radius * scale, k, lead=lead)
+                        before[si] += rows.by_dst.num_edges - lead
+                        o, j = self.gno.jacobian_rows(lat, q, rndata_flat, rows)
+                        outs.append(o)
+                        jacs.append(j)
+                    planes = _mix_scales_jvp(self, outs, jacs, q)
+                    y, dys = self.projection.jvp_rows(planes[0], planes[1:])
+                    pred[i:i + chunk] = y
+                    for d in range(cd):
+                        jac[i:i + chunk, :, d] = dys[d]
+            return pred, jac
         if grid is not None:
             ns = len(self.scales)
             with torch.no_grad():

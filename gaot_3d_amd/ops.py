@@ -284,21 +284,17 @@ def gno_nl_forward(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Opt
 GNO_KNN_K = (1, 2, 4, 8, 16, 32)      # the divisors of the kernels' 32-edge tile (gaot_gno_fwd_knn)
 
 
-def _gno_knn_args(fn, mode, weights, biases, y_pos, x_pos, f_y, src_table, nbr, k):
-    """the operand checks shared by ``gno_forward_knn`` and ``gno_forward_knn_jac``"""
+def _gno_mode_args(fn, mode, weights, biases, y_pos, x_pos, f_y, src_table):
+    """the operand checks of the entry points that take the transform type as ``mode`` (0 / 'linear', 'nonlinear',
+    'nonlinear_kernelonly'): ``gno_forward_knn``, ``gno_forward_knn_jac``, ``gno_forward_jac``"""
     md = {"linear": 0, **GNO_MODES}.get(mode, mode)
     if md not in (0, 1, 2):
         raise GaotError(f"{fn}: mode must be 'linear' or one of {tuple(GNO_MODES)}, got {mode!r}")
     m, keep = _mlp_struct(weights, biases)
     y_pos = _req(y_pos, torch.float32, "y_pos")
     x_pos = _req(x_pos, torch.float32, "x_pos")
-    nbr = _req(nbr, torch.int32, "nbr")
-    k = int(k)
-    q = int(x_pos.shape[0])
     if y_pos.dim() != 2 or x_pos.dim() != 2 or y_pos.shape[1] != 3 or x_pos.shape[1] != 3:
         raise GaotError(f"y_pos / x_pos must be [*, 3], got {tuple(y_pos.shape)} / {tuple(x_pos.shape)}")
-    if nbr.numel() != q * k:
-        raise GaotError(f"nbr must hold {q} x {k} ids, got {nbr.numel()}")
     n_src = int(y_pos.shape[0])
     if md != 2:
         f_y = _req(f_y, torch.float32, "f_y")
@@ -312,6 +308,17 @@ def _gno_knn_args(fn, mode, weights, biases, y_pos, x_pos, f_y, src_table, nbr, 
             raise GaotError(f"src_table must be [{n_src}, 64], got {tuple(src_table.shape)}")
     else:
         src_table = None
+    return md, m, keep, y_pos, x_pos, f_y, src_table
+
+
+def _gno_knn_args(fn, mode, weights, biases, y_pos, x_pos, f_y, src_table, nbr, k):
+    """the operand checks shared by ``gno_forward_knn`` and ``gno_forward_knn_jac``"""
+    md, m, keep, y_pos, x_pos, f_y, src_table = _gno_mode_args(fn, mode, weights, biases, y_pos, x_pos, f_y, src_table)
+    nbr = _req(nbr, torch.int32, "nbr")
+    k = int(k)
+    q = int(x_pos.shape[0])
+    if nbr.numel() != q * k:
+        raise GaotError(f"nbr must hold {q} x {k} ids, got {nbr.numel()}")
     return md, m, keep, y_pos, x_pos, f_y, src_table, nbr, k, q
 
 
@@ -349,6 +356,29 @@ def gno_forward_knn_jac(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y
     with _timed(f"gno_fwd_knn_jac{f'_nl{md}' if md else ''}_nh{m.n_hidden}"):
         check(lib.gaot_gno_fwd_knn_jac(C.byref(m), md, _ptr(y_pos), _ptr(x_pos), _ptr(f_y), _ptr(src_table), _ptr(nbr), k, q,
                                        _ptr(out), _ptr(jac), _stream()), "gaot_gno_fwd_knn_jac")
+    return out, jac
+
+
+def gno_forward_jac(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], src_table: Optional[Tensor],
+                    g: BipartiteGraph):
+    """``gno_forward_knn_jac`` on RAGGED rows (gaot_gno_fwd_jac): the value and the Jacobian of the fused transform on the by-query list
+    of any graph -> (out [n_query, 32], jac [3, n_query, 32]), every query's list held fixed, rows of any length (an empty row gives
+    exact zeros in all four planes).  Reads ``g.by_dst.{other, key, rowptr}`` alone: ``g.by_src`` may be None (``graph.query_lists``).
+    Two launches (the tangent kernel and one fix-up over the four planes), exact fp32 whatever the precision mode: ``out`` is
+    ``gno_forward`` / ``gno_nl_forward(..., precision=0)`` on the same graph bit for bit, and on a list of equal rows of k in
+    ``GNO_KNN_K`` edges both results are ``gno_forward_knn_jac``'s.  ``mode`` and the operands as in ``gno_forward_knn``."""
+    lib = _lib.load()
+    md, m, keep, y_pos, x_pos, f_y, src_table = _gno_mode_args("gno_forward_jac", mode, weights, biases, y_pos, x_pos, f_y, src_table)
+    if y_pos.shape[0] != g.num_src or x_pos.shape[0] != g.num_dst:
+        raise GaotError(f"y_pos / x_pos have {y_pos.shape[0]} / {x_pos.shape[0]} rows, the graph {g.num_src} / {g.num_dst}")
+    q, e = g.num_dst, g.by_dst.num_edges
+    out = torch.empty(q, m.channels, dtype=torch.float32, device=x_pos.device)
+    jac = torch.empty(3, q, m.channels, dtype=torch.float32, device=x_pos.device)
+    ws = _ws(lib.gaot_gno_fwd_jac_workspace_bytes(e), x_pos.device)
+    with _timed(f"gno_fwd_jac{f'_nl{md}' if md else ''}_nh{m.n_hidden}"):
+        check(lib.gaot_gno_fwd_jac(C.byref(m), md, _ptr(y_pos), _ptr(x_pos), _ptr(f_y), _ptr(src_table), _ptr(g.by_dst.other),
+                                   _ptr(g.by_dst.key), _ptr(g.by_dst.rowptr), e, q, _ptr(out), _ptr(jac), _ptr(ws), ws.numel(),
+                                   _stream()), "gaot_gno_fwd_jac")
     return out, jac
 
 

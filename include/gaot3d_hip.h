@@ -176,6 +176,26 @@ int gaot_gno_fwd_knn_jac(const gaot_mlp_t* mlp /* host */, int mode, const float
                          float* out /* [num_queries, channels] */, float* jac /* [3, num_queries, channels] */,
                          gaot_stream_t stream);
 
+/* The same value and Jacobian on RAGGED rows: the by-query list of any graph (gaot_gno_fwd's src_sorted / dst_sorted / rowptr_dst, e.g.
+ * the row lists gaot_radius_grid_fill / gaot_nbr_union_grid_fill write for 'radius' / 'bidirectional' decoders), rows of any length,
+ * empty rows included:
+ *   out[q,:] = (1/deg_q) sum_{e -> q} k_e * f_y[src_e,:],   jac[d][q][:] = (1/deg_q) sum_{e -> q} (d k_e / d x_pos[q][d]) * f_y[src_e,:]
+ * (deg_q = 0: exact zeros in all four planes; mode 2 without f_y).  Per edge the arithmetic of gaot_gno_fwd_knn_jac; every plane is
+ * reduced as gaot_gno_fwd reduces its rows (a walk over the 32-edge tile, rows that straddle tiles through two partial slots per
+ * tile and plane, combined in tile order), so `out` is what gaot_gno_fwd / gaot_gno_fwd_nl write at precision 0 on the same lists,
+ * bit for bit, and on a list whose rows all have k in {1, 2, 4, 8, 16, 32} edges all four planes are gaot_gno_fwd_knn_jac's.  Two
+ * launches: the tangent kernel and one fix-up over the four planes (num_edges == 0: the fix-up alone; num_queries == 0: none).  No
+ * atomics, exact fp32 in both precision modes.  workspace: gaot_gno_fwd_jac_workspace_bytes(num_edges) bytes (1 KiB per tile; may
+ * be null when that is 0).  num_edges must fit int32.  f_y may be null in mode 2, src_table in mode 0.
+ * PADDING edges: an edge with dst_sorted[e] = -1 (and any valid source id) that lies outside every row of rowptr_dst is computed and
+ * dropped.  A list may begin with some (rowptr_dst[0] = their number, counted in num_edges), so that a piece of a longer list has its
+ * rows against the 32-edge tiles where the longer list has them and gives that list's rows bit for bit, whatever the piece. */
+size_t gaot_gno_fwd_jac_workspace_bytes(int64_t num_edges);
+int gaot_gno_fwd_jac(const gaot_mlp_t* mlp /* host */, int mode, const float* y_pos, const float* x_pos, const float* f_y,
+                     const float* src_table, const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr_dst,
+                     int64_t num_edges, int64_t num_queries, float* out /* [num_queries, channels] */,
+                     float* jac /* [3, num_queries, channels] */, void* workspace, size_t workspace_bytes, gaot_stream_t stream);
+
 /* Dot-product attention scores of the attention-weighted transform (reference integral_transform.py:128-137, use_attn with
  * attention_type "dot_product") as a bilinear form of the homogeneous endpoint coordinates (csrc/gno_attn.hip):
  *   scores[e] = scale * [x_pos[dst[e]], 1]^T M [y_pos[src[e]], 1]        x_pos / y_pos: [*, 3] rows, m: DEVICE [4][4] fp32

@@ -529,13 +529,26 @@ elif what == "decoder_jacobian":
     # is the median with min / max, the peak is the rise of allocated memory over the inputs.  Then the split of (b) -- each stage
     # timed over all chunks on its own -- and the tangent kernel against gaot_gno_fwd_knn (precision 0) on the same list.  Kept in
     # profiles/decoder_jacobian_microbench.txt.
+    # `--strategy radius|bidirectional`: the reference YAML's decoder instead (config/examples/drivaernet/pressure.yaml: r = 0.033,
+    # k_neighbors at its default 1, neighbor_strategy 'bidirectional'; 'radius' = the same decoder on the radius graph alone) with
+    #   (a) sample_jacobian's default route for these strategies: per chunk get_neighbor_strategy -> build_graph -> decoder on queries
+    #       that require grad -> one backward per output channel;
+    #   (b) sample_jacobian(row_lists=True): per chunk graph.query_lists -> gaot_gno_fwd_jac (tangent kernel + fix-up) -> scale mix
+    #       -> projection tangent;
+    # both with the same chunk (MB_CHUNK points, default the method's own default), then the split of (b) into lists, tangent kernel
+    # + fix-up, and mix + projection tangent.  Kept in profiles/decoder_jacobian_rows_microbench.txt.
     from gaot_3d_amd import graph as device_graph
     from gaot_3d_amd.data import latent_grid
     from gaot_3d_amd.model.layers.magno import MAGNOConfig, MAGNODecoder
     gaot_3d_amd.set_precision("fp32")
     latent = (64, 64, 32)
-    cfg = MAGNOConfig(gno_coord_dim=3, lifting_channels=32, mlp_type="linear", use_geoembed=[True, False], neighbor_strategy="knn",
-                      k_neighbors=8, gno_radius=0.033, out_gno_channel_mlp_hidden_layers=[64, 64], precompute_edges=False)
+    strategy = sys.argv[sys.argv.index("--strategy") + 1] if "--strategy" in sys.argv else "knn"
+    if strategy not in ("knn", "radius", "bidirectional"):
+        sys.exit(f"--strategy must be radius or bidirectional, got {strategy}")
+    rows = strategy != "knn"
+    cfg = MAGNOConfig(gno_coord_dim=3, lifting_channels=32, mlp_type="linear", use_geoembed=[True, False],
+                      neighbor_strategy=["knn", strategy] if rows else "knn", k_neighbors=1 if rows else 8, gno_radius=0.033,
+                      out_gno_channel_mlp_hidden_layers=[64, 64], precompute_edges=False)
     dec = MAGNODecoder(in_channels=32, out_channels=1, gno_config=cfg).to(dev).eval()
     dec.latent_dims = latent
     tokens = latent_grid(latent).to(dev)
@@ -561,12 +574,14 @@ elif what == "decoder_jacobian":
         q = torch.rand(nq, 3, device=dev) * 2 - 1
 
         def route_a():
+            if rows:
+                return dec.sample_jacobian(rn, q, tokens, chunk_points=chunk)       # the default route of these strategies
             dec._stream_grid = lambda *a: None          # the autograd route, the queries in one piece
             try:
                 return dec.sample_jacobian(rn, q, tokens, chunk_points=nq)
             finally:
                 del dec._stream_grid
-        route_b = lambda: dec.sample_jacobian(rn, q, tokens, chunk_points=chunk)
+        route_b = lambda: dec.sample_jacobian(rn, q, tokens, chunk_points=chunk, row_lists=rows)
         ra, rb = timed(route_a)[2], timed(route_b)[2]          # warm-up, and the two routes agree
         dp = (ra[0] - rb[0]).abs().max().item()
         dj = (ra[1] - rb[1]).abs().max().item() / ra[1].abs().max().item()
@@ -576,7 +591,11 @@ elif what == "decoder_jacobian":
             t, p, _o = timed(route_a); ta.append(t); pa = max(pa, p); del _o
             t, p, _o = timed(route_b); tb.append(t); pb = max(pb, p); del _o
         (ma, lo_a, hi_a), (mb, lo_b, hi_b) = median(ta), median(tb)
-        print(f"Nq={nq} fp32: (a) autograd route, one piece       {ma:9.3f} ms (min {lo_a:.3f}, max {hi_a:.3f}, spread "
+        if rows:
+            print(f"Nq={nq} fp32 {strategy}: max - min of the rounds (a) {hi_a - lo_a:.3f} ms, (b) {hi_b - lo_b:.3f} ms; (b) - (a) medians "
+                  f"{mb - ma:+.3f} ms; (b) not slower beyond the spread: {mb - ma <= max(hi_a - lo_a, hi_b - lo_b)}; (b) peak < (a) peak: "
+                  f"{pb < pa}")
+        print(f"Nq={nq} fp32: (a) autograd route, {f'chunk {step}' if rows else 'one piece'}       {ma:9.3f} ms (min {lo_a:.3f}, max {hi_a:.3f}, spread "
               f"{100 * (hi_a - lo_a) / ma:.1f} %), peak {pa / 2**20:9.1f} MiB")
         print(f"Nq={nq} fp32: (b) sample_jacobian (chunk {step}) {mb:9.3f} ms (min {lo_b:.3f}, max {hi_b:.3f}, spread "
               f"{100 * (hi_b - lo_b) / mb:.1f} %), peak {pb / 2**20:9.1f} MiB  = {mb / ma:.3f} x (a) in time, {pb / max(pa, 1):.3f} x in "
@@ -584,6 +603,24 @@ elif what == "decoder_jacobian":
               f"max|pred_a - pred_b| = {dp:.1e}, max|jac_a - jac_b| / peak = {dj:.1e}", flush=True)
         # the split of (b): every stage over all chunks on its own (the stages' inputs kept from the stage before)
         grid = dec._stream_grid(rn, q, tokens)
+        if rows:
+            with torch.no_grad():
+                chunks = [q[i:i + step] for i in range(0, nq, step)]
+                t_nbr, t_jac, t_proj = [], [], []
+                for _ in range(reps + 1):                                  # the first round warms up and is dropped
+                    t, _p, lists = timed(lambda: [device_graph.query_lists(strategy, c, grid, dec.gno_radius, 1) for c in chunks])
+                    t_nbr.append(t)
+                    edges = sum(g.by_dst.num_edges for g in lists)
+                    t, _p, outs = timed(lambda: [dec.gno.jacobian_rows(tokens, c, rn, g) for c, g in zip(chunks, lists)]); t_jac.append(t)
+                    t, _p, prj = timed(lambda: [dec.projection.jvp_rows(o, list(j.unbind(0))) for o, j in outs]); t_proj.append(t)
+                    del lists, outs, prj
+                (mn, _, _), (mj, lo_j, hi_j), (mp, _, _) = (median(t[1:]) for t in (t_nbr, t_jac, t_proj))
+                tot = mn + mj + mp
+                print(f"Nq={nq} fp32: split of (b): query_lists {mn:.3f} ms ({100 * mn / tot:.0f} %), GNO tangent kernel + fix-up {mj:.3f} ms "
+                      f"({100 * mj / tot:.0f} %; min {lo_j:.3f}, max {hi_j:.3f}; {edges} edges), mix + projection tangent {mp:.3f} ms "
+                      f"({100 * mp / tot:.0f} %); stages sum to {tot:.3f} ms", flush=True)
+            del q, chunks
+            continue
         with torch.no_grad():
             chunks = [q[i:i + step] for i in range(0, nq, step)]
             t_nbr, t_jac, t_fwd, t_proj = [], [], [], []
