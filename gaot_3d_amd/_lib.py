@@ -108,6 +108,8 @@ SIGNATURES = {
     "gaot_mlp2_fwd": (_i, [_p, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "gaot_mlp2_bwd_workspace_bytes": (_sz, [_i, _i]),
     "gaot_mlp2_bwd_parts": (_i64, [_i64]),
+    "gaot_mlp2_jvp_supported": (_i, [_i, _i, _i, _i, _i]),
+    "gaot_mlp2_jvp": (_i, [_p, _p, _p, _p, _i, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _p]),
     "gaot_rowlin_supported": (_i, [_p, _i, _i]),
     "gaot_rowlin_plan": (_i, [_i64, _i, _p, _p, _p]),
     "gaot_rowlin_fwd": (_i, [_p, _p, _i, _p, _p, _i64, _i, _i, _p, _p]),

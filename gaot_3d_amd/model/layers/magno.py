@@ -601,10 +601,8 @@ class MAGNODecoder(nn.Module):
                         outs.append(o)
                         jacs.append(j)
                     planes = _mix_scales_jvp(self, outs, jacs, q)
-                    y, dys = self.projection.jvp_rows(planes[0], planes[1:])
-                    pred[i:i + chunk] = y
-                    for d in range(cd):
-                        jac[i:i + chunk, :, d] = dys[d]
+                    # the planes of the real directions only (a padded direction's plane is zero and has no column in ``jac``)
+                    self.projection.jvp_rows(planes[0], planes[1:1 + cd], out=(pred[i:i + chunk], jac[i:i + chunk]))
             return pred, jac
         if grid is not None:
             ns = len(self.scales)
@@ -621,10 +619,7 @@ class MAGNODecoder(nn.Module):
                         planes = [GF.ScaleMixFn.apply(logits, *([p] * ns)) for p in planes]
                     elif ns > 1:
                         planes = [_sum_scales([p] * ns) for p in planes]
-                    y, dys = self.projection.jvp_rows(planes[0], planes[1:])
-                    pred[i:i + chunk] = y
-                    for d in range(cd):
-                        jac[i:i + chunk, :, d] = dys[d]
+                    self.projection.jvp_rows(planes[0], planes[1:1 + cd], out=(pred[i:i + chunk], jac[i:i + chunk]))
             return pred, jac
         lat_bidx = torch.zeros(lat.shape[0], dtype=torch.long, device=lat.device)
         for i in range(0, nq, chunk):

@@ -46,22 +46,61 @@ def activation_name(fn) -> str:
     return name
 
 
-def _jvp_rows(self, x, dxs):
+def _jvp_fused_eligible(self, x, dxs) -> bool:
+    """may ``jvp_rows`` run as one ``ops.mlp2_jvp`` launch?  Two layers with erf-GELU between them, 32 -> {64, 128, 256} -> <= 4 with
+    a first bias, x and at most three tangent planes dense fp32 [N, 32] on the GPU (independent of the precision mode: the kernel is
+    exact fp32)"""
+    from ... import ops
+    fcs = list(self.fcs)
+    if len(fcs) != 2 or self.non_linearity != "gelu" or fcs[0].bias is None or not torch.is_tensor(x) or x.dim() != 2:
+        return False
+    ok = lambda t: t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape == x.shape and t.is_contiguous()
+    w1, w2 = GF._w2d(fcs[0].weight), GF._w2d(fcs[1].weight)
+    if not ok(x) or x.shape[1] != w1.shape[1] or w2.shape[1] != w1.shape[0] or not all(torch.is_tensor(d) and ok(d) for d in dxs):
+        return False
+    if any(p.dtype != torch.float32 or not p.is_cuda for p in (w1, w2, fcs[0].bias)):
+        return False
+    return len(dxs) <= 3 and ops.mlp2_jvp_supported(x.shape[1], w1.shape[0], w2.shape[0], len(dxs), ops.ACT["gelu"])
+
+
+def _jvp_rows(self, x, dxs, fused=None, out=None):
     """Forward-mode tangents of the MLP on rows: -> (y [N, out], [dy_d [N, out] for dx_d in dxs]) with y = ``forward_rows(x)`` in
-    fp32 mode (bit for bit: the same kernels) and dy_d the directional derivative of y along dx_d [N, C].  Per layer z = linear(x),
-    u_d = linear(dx_d) without bias, h = act(z), v_d = act'(z) * u_d (``ops.act_bwd``); precision-0 linears in both precision modes,
-    no dropout (evaluation), nothing recorded for autograd.  Rows are taken in blocks so that no hidden tensor exceeds the
-    input's size (the rule of ``MAGNODecoder._project_into``)."""
+    fp32 mode (bit for bit) and dy_d the directional derivative of y along dx_d [N, C]; exact fp32 in both precision modes, no
+    dropout (evaluation), nothing recorded for autograd.
+    ``fused`` None: one ``ops.mlp2_jvp`` launch with the hidden layer in registers when ``_jvp_fused_eligible``, else the chain;
+    True: that launch, GaotError when the module or the operands are not eligible; False: the chain.
+    The chain, per layer: z = linear(x), u_d = linear(dx_d) without bias, h = act(z), v_d = act'(z) * u_d (``ops.act_bwd``), with
+    precision-0 linears; rows are taken in blocks so that no hidden tensor exceeds the input's size (the rule of
+    ``MAGNODecoder._project_into``).
+    ``out`` = (pred_view [N, out], jac_view [N, out, len(dxs)]): the results are written there (by the fused kernel directly) and
+    the returned tangents are the views jac_view[:, :, d]."""
     from ... import ops
     fcs = list(self.fcs)
     act = self.non_linearity
     n = x.shape[0]
     cout = fcs[-1].weight.shape[0]
+    if out is not None:
+        pv, jv = out
+        if tuple(pv.shape) != (n, cout) or tuple(jv.shape) != (n, cout, len(dxs)):
+            raise ops.GaotError(f"jvp_rows: out must be ([{n}, {cout}], [{n}, {cout}, {len(dxs)}]), got {tuple(pv.shape)}, {tuple(jv.shape)}")
+    eligible = fused is not False and _jvp_fused_eligible(self, x, dxs)
+    if fused and not eligible:
+        raise ops.GaotError("jvp_rows(fused=True): the fused kernel takes a two-layer erf-GELU MLP 32 -> {64, 128, 256} -> <= 4 with a "
+                            "first bias, and x and at most three tangent planes as contiguous float32 [N, 32] on the GPU")
+    if eligible:
+        with torch.no_grad():
+            # without ``out`` the planes are laid out [T, N, out], so that every returned tangent is a dense [N, out] tensor
+            dst = out if out is not None else (None, torch.empty(len(dxs), n, cout, dtype=x.dtype, device=x.device).permute(1, 2, 0))
+            y, jac = ops.mlp2_jvp(x, list(dxs), GF._w2d(fcs[0].weight), fcs[0].bias, GF._w2d(fcs[1].weight), fcs[1].bias, *dst)
+        return y, [jac[:, :, d] for d in range(len(dxs))]
     hid = max([fc.weight.shape[0] for fc in fcs[:-1]], default=0)
     step = max(n, 1) if hid <= x.shape[1] else max(1024, n * x.shape[1] // hid)
     with torch.no_grad():
-        y = torch.empty(n, cout, dtype=x.dtype, device=x.device)
-        dys = [torch.empty(n, cout, dtype=x.dtype, device=x.device) for _ in dxs]
+        if out is not None:
+            y, dys = out[0], [out[1][:, :, d] for d in range(len(dxs))]
+        else:
+            y = torch.empty(n, cout, dtype=x.dtype, device=x.device)
+            dys = [torch.empty(n, cout, dtype=x.dtype, device=x.device) for _ in dxs]
         for j in range(0, n, step):
             h = x[j:j + step]
             ds = [d[j:j + step] for d in dxs]

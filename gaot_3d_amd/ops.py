@@ -1702,6 +1702,41 @@ def mlp2_forward(x: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Optional[Ten
     return out
 
 
+def mlp2_jvp_supported(in_dim: int, hidden: int, out_dim: int, num_tangents: int, act: int) -> bool:
+    return bool(_lib.load().gaot_mlp2_jvp_supported(int(in_dim), int(hidden), int(out_dim), int(num_tangents), int(act)))
+
+
+def mlp2_jvp(x: Tensor, dxs: Sequence[Tensor], w1: Tensor, b1: Tensor, w2: Tensor, b2: Optional[Tensor], y: Optional[Tensor] = None,
+             jac: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """-> (y [rows, out], jac [rows, out, T]): y = w2 gelu(w1 x + b1) + b2 and jac[:, :, d] its tangent along dxs[d], exact fp32 in
+    one launch (include/gaot3d_hip.h: gaot_mlp2_jvp).  x and the T <= 3 planes dense fp32 [rows, 32]; ``y`` / ``jac`` name the
+    destinations (fp32 views with any positive strides, y with unit column stride), else both are allocated"""
+    lib = _lib.load()
+    rows, hid, oc, t = _req_rows(x, torch.float32, 32, "mlp2_jvp: x"), int(w1.shape[0]), int(w2.shape[0]), len(dxs)
+    if t > 3:
+        raise GaotError(f"mlp2_jvp: at most 3 tangent planes, got {t}")
+    for d in dxs:
+        _req_rows(d, torch.float32, 32, "mlp2_jvp: tangent plane", rows=rows)
+    for name, w, shape in (("w1", w1, (hid, 32)), ("b1", b1, (hid,)), ("w2", w2, (oc, hid))) + ((("b2", b2, (oc,)),) if b2 is not None else ()):
+        if w.dtype != torch.float32 or tuple(w.shape) != shape or not w.is_contiguous():
+            raise GaotError(f"mlp2_jvp: {name}: contiguous float32 {shape} expected, got {w.dtype} {tuple(w.shape)}")
+    if y is None:
+        y = torch.empty(rows, oc, dtype=torch.float32, device=x.device)
+    if jac is None:
+        jac = torch.empty(rows, oc, t, dtype=torch.float32, device=x.device)
+    _req_rows(y, torch.float32, oc, "mlp2_jvp: y", dense=False, rows=rows)
+    if jac.dtype != torch.float32 or tuple(jac.shape) != (rows, oc, t) or not jac.is_cuda:
+        raise GaotError(f"mlp2_jvp: jac: float32 [{rows}, {oc}, {t}] on the GPU expected, got {jac.dtype} {tuple(jac.shape)} on {jac.device}")
+    # the stride of a dimension of extent <= 1 is never used (torch reports anything there); the library checks the others
+    ldy = int(y.stride(0)) if rows > 1 else oc
+    js = [int(s) if n > 1 else 1 for s, n in zip(jac.stride(), jac.shape)]
+    p = [_ptr(d) for d in dxs] + [None] * (3 - t)
+    with _timed(f"mlp2_jvp_h{hid}_t{t}"):
+        check(lib.gaot_mlp2_jvp(_ptr(x), p[0], p[1], p[2], t, rows, 32, hid, oc, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(y), ldy,
+                                _ptr(jac) if t else None, js[0], js[1], js[2], _stream()), "gaot_mlp2_jvp")
+    return y, jac
+
+
 def _finish_tables(ws: Tensor, outs, parts, lanes, defer: bool) -> None:
     """the fixed-order sums of the [parts][n] partial tables that lie one behind the other in ``ws`` (fp32) into ``outs``: left
     to flush_deferred (defer) or ONE gaot_reduce_multi launch now -- the same kernel, the same order, the same bits.  ``parts`` /

@@ -682,6 +682,20 @@ int gaot_mlp2_bwd(const float* x, int64_t num_rows, int in_dim, int hidden, int 
                   size_t workspace_bytes, gaot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Forward-mode tangents of the same two-layer MLP in one pass, exact fp32 (csrc/mlp2_jvp.hip; the projection under
+ * sample_jacobian):  y = W2 gelu(W1 x + b1) + b2  and, for num_tangents = 0..3 planes dx_d [rows, 32],
+ * dy_d = W2 (gelu'(W1 x + b1) * (W1 dx_d)).  in_dim = 32, hidden in {64, 128, 256}, out_dim in 1..4, erf-GELU
+ * (gaot_mlp2_jvp_supported: 1 for exactly this family, act being the activation id 1 = GELU).  x and the planes are dense
+ * row-major, 16-byte aligned; b2 may be NULL.  y[n * ldy + c]; the tangents go to jac[n * jac_row_stride + c * jac_chan_stride +
+ * d * jac_dir_stride] (jac may be NULL when num_tangents == 0).  y is what gaot_gemm (precision 0) gives for the two layers, bit
+ * for bit; a row's result depends on that row alone, a plane's on that plane alone.  No workspace; num_rows == 0 is a no-op.
+ * ------------------------------------------------------------------------------------------- */
+int gaot_mlp2_jvp_supported(int in_dim, int hidden, int out_dim, int num_tangents, int act);
+int gaot_mlp2_jvp(const float* x, const float* dx0, const float* dx1, const float* dx2, int num_tangents, int64_t num_rows, int in_dim,
+                  int hidden, int out_dim, const float* w1, const float* b1, const float* w2, const float* b2, float* y, int64_t ldy,
+                  float* jac, int64_t jac_row_stride, int64_t jac_chan_stride, int64_t jac_dir_stride, gaot_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Thin fp32 linears over many rows in one pass (csrc/rowlinear.hip):  y = act([x_0 | x_1 | ...] W^T + b),
  * act none or ReLU (ReLU: one input only) -- the per-point / per-token linears around the GNOs (reference magno.py:494,571-575,
  * 771-775: torch.cat + nn.Linear; geoembed.py: the statistics MLP).  nin = 1..4 dense row-major inputs

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Kernel microbenchmarks at the configs[1] shapes (for rocprofv3 / quick A-B): attention fwd+bwd, GEMM shapes, GNO, PointNet GeoEmbed,
-the attention-weighted GNO, the forward-only decoder (decoder_sample), the sampled field's Jacobian (decoder_jacobian)."""
+the attention-weighted GNO, the forward-only decoder (decoder_sample), the sampled field's Jacobian (decoder_jacobian), the projection MLP's tangent alone (projection_jvp)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 if os.environ.get("MB_TREE"):      # measure another checkout's package (gno_weighted: the parent commit's) with this script
@@ -638,3 +638,63 @@ elif what == "decoder_jacobian":
             print(f"Nq={nq} fp32: gaot_gno_fwd_knn_jac {mj:.3f} ms (min {lo_j:.3f}, max {hi_j:.3f}) against gaot_gno_fwd_knn at precision 0 "
                   f"{mf:.3f} ms (min {lo_f:.3f}, max {hi_f:.3f}) on the same lists: {mj / mf:.2f} x", flush=True)
         del q, chunks
+elif what == "projection_jvp":
+    # The projection MLP's forward-mode tangent on its own (LinearChannelMLP 32 -> 256 -> out, out in {1, 4}, three tangent planes, fp32
+    # mode, random rows), as MAGNODecoder.sample_jacobian calls it: SAMPLE_CHUNK rows at a time into preallocated pred [N, out] and
+    # jac [N, out, 3] through ``out=``.
+    #   (a) jvp_rows(fused=False): the chain of gaot_gemm / gaot_act_bwd launches with the hidden tensors in memory;
+    #   (b) jvp_rows(fused=True): one gaot_mlp2_jvp launch per chunk, the hidden layer in registers.
+    # (a) and (b) alternate in this one process after a warm-up of each; device events around synchronised work; a window is `inner`
+    # passes over all rows (10 at 500 K rows, 1 at 8 M) and the figures are per pass; `reps` windows; a row is the median with min / max,
+    # the peak is the rise of allocated memory over the operands and the results.  Kept in profiles/projection_jvp_microbench.txt.
+    from gaot_3d_amd.model.layers.magno import MAGNODecoder
+    from gaot_3d_amd.model.layers.mlp import LinearChannelMLP
+    gaot_3d_amd.set_precision("fp32")
+    step = MAGNODecoder.SAMPLE_CHUNK
+
+    def timed(fn, inner):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(inner):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / inner, torch.cuda.max_memory_allocated() - base
+
+    def median(ts):
+        ts = sorted(ts)
+        return ts[len(ts) // 2], ts[0], ts[-1]
+
+    for oc in (1, 4):
+        mlp = LinearChannelMLP([32, 256, oc]).to(dev).eval()
+        for n in (500000, 8000000):
+            inner = 10 if n <= 1000000 else 1
+            x = torch.randn(n, 32, device=dev)
+            dxs = [torch.randn(n, 32, device=dev) for _ in range(3)]
+            pred, jac = torch.empty(n, oc, device=dev), torch.empty(n, oc, 3, device=dev)
+
+            def run(fused):
+                for i in range(0, n, step):
+                    mlp.jvp_rows(x[i:i + step], [d[i:i + step] for d in dxs], fused=fused, out=(pred[i:i + step], jac[i:i + step]))
+            timed(lambda: run(False), 1)                        # warm-up, and the two agree
+            pc, jc = pred.clone(), jac.clone()
+            timed(lambda: run(True), 1)
+            same = torch.equal(pred, pc)
+            dj = (jac - jc).abs().max().item() / jc.abs().max().item()
+            del pc, jc
+            ta, tb, pa, pb = [], [], 0, 0
+            for _ in range(reps):
+                t, p = timed(lambda: run(False), inner); ta.append(t); pa = max(pa, p)
+                t, p = timed(lambda: run(True), inner); tb.append(t); pb = max(pb, p)
+            (ma, lo_a, hi_a), (mb, lo_b, hi_b) = median(ta), median(tb)
+            spread = max(hi_a - lo_a, hi_b - lo_b)
+            print(f"N={n} out={oc} fp32: (a) jvp_rows(fused=False), chunk {step} {ma:9.3f} ms (min {lo_a:.3f}, max {hi_a:.3f}, spread "
+                  f"{100 * (hi_a - lo_a) / ma:.1f} %), peak {pa / 2**20:9.1f} MiB")
+            print(f"N={n} out={oc} fp32: (b) jvp_rows(fused=True),  chunk {step} {mb:9.3f} ms (min {lo_b:.3f}, max {hi_b:.3f}, spread "
+                  f"{100 * (hi_b - lo_b) / mb:.1f} %), peak {pb / 2**20:9.1f} MiB  = {mb / ma:.3f} x (a) in time; (a) - (b) = {ma - mb:.3f} ms "
+                  f"against a spread of {spread:.3f} ms; (b) faster beyond the spread: {ma - mb > spread}; y_a == y_b bit for bit: {same}, "
+                  f"max|jac_a - jac_b| / peak = {dj:.1e}", flush=True)
+            del x, dxs, pred, jac
