@@ -57,6 +57,7 @@ SIGNATURES = {
                             C.POINTER(MlpGradT), _p, _i, _p, _sz, _p]),
     "gaot_gno_fwd_knn": (_i, [C.POINTER(MlpT), _i, _p, _p, _p, _p, _p, _i, _i64, _p, _i, _p]),
     "gaot_gno_fwd_knn_jac": (_i, [C.POINTER(MlpT), _i, _p, _p, _p, _p, _p, _i, _i64, _p, _p, _p]),
+    "gaot_gno_fwd_knn_jet2": (_i, [C.POINTER(MlpT), _i, _p, _p, _p, _p, _p, _i, _i64, _p, _i, _p, _p, _p, _p]),
     "gaot_gno_fwd_jac_workspace_bytes": (_sz, [_i64]),
     "gaot_gno_fwd_jac": (_i, [C.POINTER(MlpT), _i, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _sz, _p]),
     "gaot_edge_bilinear_fwd": (_i, [_p, _p, _p, _p, _i64, _p, _f, _p, _p]),
@@ -110,6 +111,8 @@ SIGNATURES = {
     "gaot_mlp2_bwd_parts": (_i64, [_i64]),
     "gaot_mlp2_jvp_supported": (_i, [_i, _i, _i, _i, _i]),
     "gaot_mlp2_jvp": (_i, [_p, _p, _p, _p, _i, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _p]),
+    "gaot_mlp2_jet2_supported": (_i, [_i, _i, _i, _i, _i]),
+    "gaot_mlp2_jet2": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _i64, _p, _p, _i64, _i64, _i64, _p]),
     "gaot_rowlin_supported": (_i, [_p, _i, _i]),
     "gaot_rowlin_plan": (_i, [_i64, _i, _p, _p, _p]),
     "gaot_rowlin_fwd": (_i, [_p, _p, _i, _p, _p, _i64, _i, _i, _p, _p]),

@@ -61,6 +61,11 @@ __device__ __forceinline__ float gelu_grad_f(float x) {
     const float pdf = 0.39894228040143267794f * __expf(-0.5f * x * x);
     return cdf + x * pdf;
 }
+// gelu''(x) = phi(x) (2 - x^2), gelu_grad_f's pdf
+__device__ __forceinline__ float gelu_grad2_f(float x) {
+    const float pdf = 0.39894228040143267794f * __expf(-0.5f * x * x);
+    return pdf * (2.0f - x * x);
+}
 
 // Activation ids of the GEMM epilogues and gaot_act_bwd.  0-3 are the shipped configurations' (mlp.py:330-331 F.gelu,
 // geoembed.py:37 ReLU, attn.py:156 SiLU); 4.. cover the rest of the reference's `activation_fn(name)` surface

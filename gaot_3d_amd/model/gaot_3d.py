@@ -165,6 +165,31 @@ class GAOT3D(nn.Module):
         return self.decoder.sample_jacobian(latent, query_pos.to(latent.device), lat, chunk_points=chunk_points,
                                             row_lists=row_lists)
 
+    def _one_sample(self, fn, latent, tokens_pos):
+        if latent.dim() != 2 or latent.shape[0] != self.num_latent_tokens:
+            raise ValueError(f"{fn}: latent {tuple(latent.shape)} is not ONE sample's [{self.num_latent_tokens}, "
+                             f"{self.node_latent_size}] token rows (sample the graphs of a batch one by one)")
+        return self._tokens(1, latent.device, tokens_pos, None)[0]
+
+    def sample_hessian(self, latent: torch.Tensor, query_pos: torch.Tensor, tokens_pos: Optional[torch.Tensor] = None,
+                       chunk_points: Optional[int] = None):
+        """``sample_jacobian`` with the field's SECOND spatial derivatives: -> (pred [Nq, output_size], jac [Nq, output_size, 3],
+        hess [Nq, output_size, 3, 3]) with hess[q, o, i, j] = d^2 pred[q, o] / d query_pos[q, i] d query_pos[q, j] (curvature and
+        smoothness of the decoded field, the derivative of a wall-shear component), every query's neighbour list held fixed: valid
+        almost everywhere, not defined across the surfaces where a query's nearest tokens change.  ``MAGNODecoder.sample_hessian``:
+        forward-mode directional 2-jets on the shipped 'knn' decoder, exact fp32 in both precision modes, no autograd graph;
+        ``pred`` and ``jac`` are ``sample_jacobian``'s bit for bit.  Configurations that do not stream raise NotImplementedError."""
+        lat = self._one_sample("sample_hessian", latent, tokens_pos)
+        return self.decoder.sample_hessian(latent, query_pos.to(latent.device), lat, chunk_points=chunk_points)
+
+    def sample_laplacian(self, latent: torch.Tensor, query_pos: torch.Tensor, tokens_pos: Optional[torch.Tensor] = None,
+                         chunk_points: Optional[int] = None):
+        """-> (pred [Nq, output_size], lap [Nq, output_size]): the Laplacian of the field at the query points (a Poisson or momentum
+        residual), the trace of ``sample_hessian``'s result bit for bit from three directions instead of six.
+        ``MAGNODecoder.sample_laplacian``; conditions as for ``sample_hessian``."""
+        lat = self._one_sample("sample_laplacian", latent, tokens_pos)
+        return self.decoder.sample_laplacian(latent, query_pos.to(latent.device), lat, chunk_points=chunk_points)
+
     def forward(self, batch, tokens_pos: Optional[torch.Tensor] = None, tokens_batch_idx: Optional[torch.Tensor] = None,
                 query_coord_pos: Optional[torch.Tensor] = None, query_coord_batch_idx: Optional[torch.Tensor] = None,
                 condition: Optional[float] = None) -> torch.Tensor:

@@ -185,6 +185,24 @@ class IntegralTransform(nn.Module):
                                           f"on lists of k in {ops.GNO_KNN_K} neighbours per query")
             return self._forward_fused(fcs, y_pos, x_pos, f_y, None, *plan, knn=(nbr, int(k)), jac=True)
 
+    def jet2_knn(self, y_pos, x_pos, nbr, k: int, f_y: Optional[torch.Tensor] = None, dirs=((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0))):
+        """``forward_knn`` with a directional 2-jet of its result: -> (out [N_x, C], d1 [nd, N_x, C], d2 [nd, N_x, C]), the first and
+        second directional derivative of out with respect to x_pos along each of the 1..6 directions ``dirs`` (host values [nd][3];
+        components beyond the coordinate dimension meet zero weight columns), every query's neighbour list held fixed as in
+        ``jacobian_knn``.  One ``ops.gno_forward_knn_jet2`` launch per 32-channel pass, exact fp32 in both precision modes: ``out`` is
+        ``forward_knn``'s fp32-mode result and, for an axis direction, d1 is ``jacobian_knn``'s plane, bit for bit.  The operands are
+        prepared exactly as in ``jacobian_knn``.  Runs exactly when ``_fused_plan`` is not None and k is in ``ops.GNO_KNN_K`` and raises
+        NotImplementedError otherwise.  Nothing is recorded for autograd."""
+        if self.transform_type not in ("linear", "nonlinear", "nonlinear_kernelonly"):
+            raise ValueError(f"Invalid transform_type: {self.transform_type}")
+        fcs = list(self.channel_mlp.fcs)
+        with torch.no_grad():
+            plan = self._fused_plan(fcs, f_y, y_pos, x_pos)
+            if plan is None or int(k) not in ops.GNO_KNN_K:
+                raise NotImplementedError("IntegralTransform.jet2_knn: only the transforms the fused kernels evaluate (_fused_plan) "
+                                          f"on lists of k in {ops.GNO_KNN_K} neighbours per query")
+            return self._forward_fused(fcs, y_pos, x_pos, f_y, None, *plan, knn=(nbr, int(k)), jet2=dirs)
+
     def jacobian_rows(self, y_pos, x_pos, f_y: Optional[torch.Tensor], graph):
         """``jacobian_knn`` on RAGGED rows: ``graph`` holds the by-query list of any graph (``graph.by_dst``; ``by_src`` may be None, as
         ``graph.query_lists`` leaves it) -> (out [N_x, C], jac [3, N_x, C]), every query's list held fixed, empty rows exact zeros.
@@ -271,17 +289,20 @@ class IntegralTransform(nn.Module):
         return (not self.use_attn and self.transform_type == "linear" and f_y is not None and dims[0] == (64, 6)
                 and dims[-1] == (32, 64) and f_y.shape[1] == 32)
 
-    def _forward_fused(self, fcs, y_pos, x_pos, f_y, graph, cd: int, c: int, edge_w=None, knn=None, jac=False):
+    def _forward_fused(self, fcs, y_pos, x_pos, f_y, graph, cd: int, c: int, edge_w=None, knn=None, jac=False, jet2=None):
         """``edge_w`` [E] (dst-sorted order): the weighted transform of use_attn -- every pass runs ``GnoWFn`` with the same weights and
         autograd adds the passes' gradients with respect to them (padded channels carry zero grad_out and zero f: exact zeros).
         ``knn`` = (nbr, k) (``forward_knn``; ``graph`` is None, no autograd): the passes run ``ops.gno_forward_knn`` on the regular
         list instead of the autograd Functions; with ``jac`` (``jacobian_knn``) they run ``ops.gno_forward_knn_jac`` and the result is
         (out [N_x, c], jac [3, N_x, c]).  ``jac`` with a ``graph`` (``jacobian_rows``; no autograd either): the passes run
-        ``ops.gno_forward_jac`` on the graph's by-query list, with the same result shapes."""
+        ``ops.gno_forward_jac`` on the graph's by-query list, with the same result shapes.  ``jet2`` = directions (``jet2_knn``; with
+        ``knn``): the passes run ``ops.gno_forward_knn_jet2`` and the result is (out [N_x, c], d1 [nd, N_x, c], d2 [nd, N_x, c])."""
         w2 = lambda fc: fc.weight[:, :, 0] if fc.weight.dim() == 3 else fc.weight    # Conv1d(k=1) storage of mlp_type='channel'
         pad_hidden = any(fc.weight.shape[0] != 64 for fc in fcs[:-1])
         tt = self.transform_type
         if tt == "linear" and cd == 3 and c == 32 and not pad_hidden and edge_w is None:   # the shipped shape: straight through
+            if jet2 is not None:
+                return ops.gno_forward_knn_jet2(0, [w2(fc) for fc in fcs], [fc.bias for fc in fcs], y_pos, x_pos, f_y, None, *knn, jet2)
             if knn is not None:
                 fwd = ops.gno_forward_knn_jac if jac else ops.gno_forward_knn
                 return fwd(0, [w2(fc) for fc in fcs], [fc.bias for fc in fcs], y_pos, x_pos, f_y, None, *knn)
@@ -327,7 +348,12 @@ class IntegralTransform(nn.Module):
                 wb = torch.nn.functional.pad(wb, (0, 0, 0, 32 - n))
                 bb = torch.nn.functional.pad(bb, (0, 32 - n))
                 fb = None if fb is None else torch.nn.functional.pad(fb, (0, 32 - n))
-            if knn is not None or jac:
+            if jet2 is not None:
+                o = ops.gno_forward_knn_jet2(tt, [w0.contiguous(), *mid[0::2], wb.contiguous()], [b0, *mid[1::2], bb.contiguous()], y3,
+                                             x3, None if fb is None else fb.contiguous(), t, *knn, jet2)
+                outs.append((o[0][:, :n], o[1][:, :, :n], o[2][:, :, :n]) if n < 32 else o)
+                continue
+            elif knn is not None or jac:
                 fwd = ops.gno_forward_jac if knn is None else ops.gno_forward_knn_jac if jac else ops.gno_forward_knn
                 o = fwd(tt, [w0.contiguous(), *mid[0::2], wb.contiguous()], [b0, *mid[1::2], bb.contiguous()], y3, x3,
                         None if fb is None else fb.contiguous(), t, *(knn if knn is not None else (graph,)))
@@ -343,6 +369,11 @@ class IntegralTransform(nn.Module):
                 o = GF.GnoNlFn.apply(tt, None if fb is None else fb.contiguous(), t, y3, x3, graph, w0.contiguous(), b0, *mid,
                                      wb.contiguous(), bb.contiguous())
             outs.append(o[:, :n] if n < 32 else o)
+        if jet2 is not None:
+            if len(outs) == 1:
+                return tuple(o.contiguous() for o in outs[0])
+            return (torch.cat([o[0] for o in outs], dim=1), torch.cat([o[1] for o in outs], dim=2),
+                    torch.cat([o[2] for o in outs], dim=2))
         if jac:
             if len(outs) == 1:
                 return outs[0][0].contiguous(), outs[0][1].contiguous()

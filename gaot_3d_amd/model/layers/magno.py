@@ -525,6 +525,120 @@ class MAGNODecoder(nn.Module):
             out[i:i + chunk] = self._decode(rndata_flat, q, q_bidx, lat, lat_bidx, None, False)
         return out
 
+    # the directions of a Hessian by polarisation: H_ii = D^2_{e_i}, H_ij = (D^2_{e_i + e_j} - D^2_{e_i} - D^2_{e_j}) / 2
+    HESSIAN_DIRS = ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0), (1.0, 1.0, 0.0), (0.0, 1.0, 1.0), (1.0, 0.0, 1.0))
+    HESSIAN_PAIRS = ((0, 1), (1, 2), (0, 2))      # the axes of directions 3, 4, 5
+
+    def _jet2_stream(self, fn, rndata_flat, query_pos, lat, chunk_points):
+        """the argument rules and streaming conditions shared by ``sample_hessian`` and ``sample_laplacian`` -> (grid, chunk); raises
+        for every configuration they do not stream, naming the condition"""
+        from ... import ops
+        if self.decoder_strategy == "reverse":
+            raise ValueError(f"MAGNODecoder.{fn}: decoder strategy 'reverse' is the flip of the encoder's graph of the sample's own "
+                             "points and is undefined for other query points")
+        if chunk_points is not None and int(chunk_points) < 1:
+            raise ValueError(f"chunk_points must be positive, got {chunk_points}")
+        no = lambda why: NotImplementedError(f"MAGNODecoder.{fn}: second derivatives stream on the regular k-neighbour lists only; {why}")
+        k = int(self.k_neighbors)
+        if self.decoder_strategy != "knn":
+            raise no(f"decoder strategy {self.decoder_strategy!r} is not 'knn'")
+        if k not in ops.GNO_KNN_K:
+            raise no(f"k_neighbors = {k} is not in {ops.GNO_KNN_K}")
+        if getattr(self.gno, "use_attn", False):
+            raise no("the attention-weighted transform (use_attn) is not supported")
+        if self.use_geoembed:
+            raise no("a decoder GeoEmbed is not supported")
+        if self.sampling_strategy is not None:
+            raise no(f"neighbour sampling ({self.sampling_strategy!r}) is not supported")
+        fcs = list(self.projection.fcs)
+        if not (len(fcs) == 2 and self.projection.non_linearity == "gelu" and fcs[0].bias is not None and ops.mlp2_jet2_supported(
+                fcs[0].weight.shape[1], fcs[0].weight.shape[0], fcs[1].weight.shape[0], 3, ops.ACT["gelu"])):
+            raise no("the projection is not a two-layer erf-GELU MLP 32 -> {64, 128, 256} -> 1..4 with a first bias (layers "
+                     f"{[tuple(fc.weight.shape[:2]) for fc in fcs]})")
+        grid = self._stream_grid(rndata_flat, query_pos, lat)
+        if grid is None:
+            raise no("the operands do not stream (fp32 3-D query coordinates on the device, ONE graph's tokens on the model's regular "
+                     "grid and a transform the fused kernels evaluate are needed)")
+        return grid, int(chunk_points) if chunk_points is not None else self.SAMPLE_CHUNK
+
+    def _mix_equal_scales(self, planes, q):
+        """the scale mix of the knn route applied to every plane with the same weights: every scale sees the same list, so the mix is
+        of equal operands and the derivatives of its softmax weights drop out (``sample_jacobian``); one scale: the planes as they are"""
+        ns = len(self.scales)
+        if ns > 1 and self.use_scale_weights:
+            sw = self.scale_weighting
+            h = GF.linear(q, sw[0].weight, sw[0].bias, act="relu", precision=0)
+            logits = GF.linear(h, sw[2].weight, sw[2].bias, precision=0)
+            return [GF.ScaleMixFn.apply(logits, *([p] * ns)) for p in planes]
+        if ns > 1:
+            return [_sum_scales([p] * ns) for p in planes]
+        return planes
+
+    def _jet2_chunk(self, rndata_flat, q, lat, grid, dirs, pred):
+        """one chunk of queries: -> (d1, d2) [n, out_channels, nd] of the prediction along ``dirs``, the value written into ``pred``"""
+        from ... import graph as device_graph
+        k = int(self.k_neighbors)
+        nbr = device_graph.knn_to_grid(q, grid, k)
+        dec, g1, g2 = self.gno.jet2_knn(lat, q, nbr, k, rndata_flat, dirs)
+        planes = self._mix_equal_scales([dec, *g1.unbind(0), *g2.unbind(0)], q)
+        nd = len(dirs)
+        d1 = torch.empty(q.shape[0], self.out_channels, nd, dtype=pred.dtype, device=pred.device)
+        d2 = torch.empty_like(d1)
+        self.projection.jet2_rows(planes[0], planes[1:1 + nd], planes[1 + nd:1 + 2 * nd], out=(pred, d1, d2))
+        return d1, d2
+
+    @torch.no_grad()
+    def sample_hessian(self, rndata_flat, query_pos, latent_tokens_pos, chunk_points: Optional[int] = None):
+        """``sample_jacobian`` with the SECOND spatial derivatives of the field: -> (pred [Nq, out_channels], jac [Nq, out_channels, 3],
+        hess [Nq, out_channels, 3, 3]) with hess[q, o, i, j] = d^2 pred[q, o] / d query_pos[q, i] d query_pos[q, j], every query's
+        neighbour list held fixed: valid almost everywhere, NOT defined across the surfaces where a query's k nearest tokens change.
+
+        The kernels carry directional 2-jets (value, D_v, D_v^2): per chunk one ``knn_to_grid`` launch, one ``jet2_knn`` launch per
+        32-channel pass with the six directions ``HESSIAN_DIRS``, the scale mix on every plane with the same weights, and the
+        projection's jets (``jet2_rows``, two launches).  The Hessian follows by polarisation, H_ii = D^2_{e_i} and
+        H_ij = (D^2_{e_i + e_j} - D^2_{e_i} - D^2_{e_j}) / 2, in plain tensor operations; hess[..., i, j] and hess[..., j, i] are written
+        from the same value.  ``jac`` is the D_v planes of the three axis directions: ``pred`` and ``jac`` are ``sample_jacobian``'s
+        bit for bit.  Exact fp32 in both precision modes, no autograd graph, no host synchronisation (capturable after one eager
+        call, as ``sample``), results independent of ``chunk_points``.
+
+        Streams under exactly the conditions of ``sample_jacobian``'s 'knn' route plus a projection in the fused family (two-layer
+        erf-GELU 32 -> {64, 128, 256} -> 1..4); every other configuration -- 'radius' / 'bidirectional' decoders, other k, use_attn, a
+        decoder GeoEmbed, neighbour sampling, tokens off the regular grid, other projections -- raises NotImplementedError naming the
+        condition.  'reverse' and a non-positive ``chunk_points`` raise ValueError."""
+        rndata_flat, query_pos = rndata_flat.detach(), query_pos.detach()
+        grid, chunk = self._jet2_stream("sample_hessian", rndata_flat, query_pos, latent_tokens_pos, chunk_points)
+        nq, oc = int(query_pos.shape[0]), self.out_channels
+        pred = torch.empty(nq, oc, dtype=rndata_flat.dtype, device=rndata_flat.device)
+        jac = torch.empty(nq, oc, 3, dtype=rndata_flat.dtype, device=rndata_flat.device)
+        hess = torch.empty(nq, oc, 3, 3, dtype=rndata_flat.dtype, device=rndata_flat.device)
+        for i in range(0, nq, chunk):
+            d1, d2 = self._jet2_chunk(rndata_flat, query_pos[i:i + chunk], latent_tokens_pos, grid, self.HESSIAN_DIRS, pred[i:i + chunk])
+            jac[i:i + chunk] = d1[:, :, :3]
+            hc = hess[i:i + chunk]
+            for a in range(3):
+                hc[:, :, a, a] = d2[:, :, a]
+            for n, (a, b) in enumerate(self.HESSIAN_PAIRS):
+                off = 0.5 * (d2[:, :, 3 + n] - d2[:, :, a] - d2[:, :, b])
+                hc[:, :, a, b] = off
+                hc[:, :, b, a] = off
+        return pred, jac, hess
+
+    @torch.no_grad()
+    def sample_laplacian(self, rndata_flat, query_pos, latent_tokens_pos, chunk_points: Optional[int] = None):
+        """``sample_hessian``'s trace without the off-diagonal work: -> (pred [Nq, out_channels], lap [Nq, out_channels]) with
+        lap = d^2 pred / dx^2 + d^2 pred / dy^2 + d^2 pred / dz^2, summed in that order from the D_v^2 planes of the three axis
+        directions -- bit for bit hess[..., 0, 0] + hess[..., 1, 1] + hess[..., 2, 2] of ``sample_hessian``.  Conditions, errors,
+        exactness and capture as there."""
+        rndata_flat, query_pos = rndata_flat.detach(), query_pos.detach()
+        grid, chunk = self._jet2_stream("sample_laplacian", rndata_flat, query_pos, latent_tokens_pos, chunk_points)
+        nq, oc = int(query_pos.shape[0]), self.out_channels
+        pred = torch.empty(nq, oc, dtype=rndata_flat.dtype, device=rndata_flat.device)
+        lap = torch.empty(nq, oc, dtype=rndata_flat.dtype, device=rndata_flat.device)
+        for i in range(0, nq, chunk):
+            _, d2 = self._jet2_chunk(rndata_flat, query_pos[i:i + chunk], latent_tokens_pos, grid, self.HESSIAN_DIRS[:3], pred[i:i + chunk])
+            torch.add(d2[:, :, 0] + d2[:, :, 1], d2[:, :, 2], out=lap[i:i + chunk])
+        return pred, lap
+
     def sample_jacobian(self, rndata_flat, query_pos, latent_tokens_pos, chunk_points: Optional[int] = None,
                         row_lists: bool = False):
         """``sample`` with the spatial derivative of the field: -> (pred [Nq, out_channels], jac [Nq, out_channels, coord_dim]) with

@@ -116,6 +116,41 @@ def _jvp_rows(self, x, dxs, fused=None, out=None):
     return y, dys
 
 
+def _jet2_rows(self, x, dxs, ddxs, out=None):
+    """Directional 2-jets of the MLP on rows: -> (y [N, out], d1 [N, out, nd], d2 [N, out, nd]) with y = ``forward_rows(x)`` in fp32
+    mode and, per direction d, d1[:, :, d] the first and d2[:, :, d] the second directional derivative of y, given the first-order
+    plane dxs[d] and the second-order plane ddxs[d] of x ([N, 32] each; any number of directions >= 1, three per ``ops.mlp2_jet2``
+    launch, the value stored by the first).  Exact fp32 in both precision modes, evaluation only, nothing recorded for autograd; y
+    and d1 are ``jvp_rows``'s bit for bit.  Only the fused family runs -- a two-layer erf-GELU MLP 32 -> {64, 128, 256} -> <= 4 with
+    a first bias on dense fp32 GPU rows; everything else raises NotImplementedError (there is no chain for second derivatives).
+    ``out`` = (pred_view [N, out], d1_view [N, out, nd], d2_view [N, out, nd]; the last two with the same strides): the results are
+    written there."""
+    from ... import ops
+    fcs = list(self.fcs)
+    nd = len(dxs)
+    if nd < 1 or len(ddxs) != nd:
+        raise ops.GaotError(f"jet2_rows: one dx and one ddx plane per direction, at least one direction (got {nd} and {len(ddxs)})")
+    plane_ok = lambda d: torch.is_tensor(d) and d.is_cuda and d.dtype == torch.float32 and d.shape == x.shape and d.is_contiguous()
+    # the module and x as for the fused tangent (no planes), then the planes and the jet kernel's own family
+    if not (_jvp_fused_eligible(self, x, []) and all(plane_ok(d) for d in list(dxs) + list(ddxs)) and ops.mlp2_jet2_supported(
+            x.shape[1], fcs[0].weight.shape[0], fcs[1].weight.shape[0], min(nd, 3), ops.ACT["gelu"])):
+        raise NotImplementedError("jet2_rows: the fused kernel takes a two-layer erf-GELU MLP 32 -> {64, 128, 256} -> <= 4 with a first "
+                                  "bias, and x and the direction planes as contiguous float32 [N, 32] on the GPU")
+    n, cout = x.shape[0], fcs[-1].weight.shape[0]
+    with torch.no_grad():
+        if out is None:
+            out = (torch.empty(n, cout, dtype=x.dtype, device=x.device), torch.empty(n, cout, nd, dtype=x.dtype, device=x.device),
+                   torch.empty(n, cout, nd, dtype=x.dtype, device=x.device))
+        y, d1, d2 = out
+        if tuple(y.shape) != (n, cout) or tuple(d1.shape) != (n, cout, nd) or tuple(d2.shape) != (n, cout, nd):
+            raise ops.GaotError(f"jet2_rows: out must be ([{n}, {cout}], [{n}, {cout}, {nd}], [{n}, {cout}, {nd}]), got "
+                                f"{tuple(y.shape)}, {tuple(d1.shape)}, {tuple(d2.shape)}")
+        for i in range(0, nd, 3):
+            ops.mlp2_jet2(x, list(dxs[i:i + 3]), list(ddxs[i:i + 3]), GF._w2d(fcs[0].weight), fcs[0].bias, GF._w2d(fcs[1].weight),
+                          fcs[1].bias, y, d1[:, :, i:i + 3], d2[:, :, i:i + 3], store_y=i == 0)
+    return y, d1, d2
+
+
 class LinearChannelMLP(nn.Module):
     """Stack of nn.Linear parameters [layers[j] -> layers[j+1]], activation (default erf-GELU) between, none after the
     last, nn.Dropout after every layer when ``dropout`` > 0 (reference mlp.py:308-335)."""
@@ -140,6 +175,7 @@ class LinearChannelMLP(nn.Module):
 
     forward_rows = forward      # [N, C] rows in, rows out (what the encoder / decoder hand over)
     jvp_rows = _jvp_rows
+    jet2_rows = _jet2_rows
 
 
 class ChannelMLP(nn.Module):
@@ -175,6 +211,7 @@ class ChannelMLP(nn.Module):
         return x
 
     jvp_rows = _jvp_rows
+    jet2_rows = _jet2_rows
 
     def forward(self, x):
         size = list(x.shape)

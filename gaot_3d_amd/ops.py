@@ -359,6 +359,40 @@ def gno_forward_knn_jac(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y
     return out, jac
 
 
+def _host_dirs(fn, dirs):
+    """directions as a host float array [nd][3] (a CPU tensor or nested sequences: never a device tensor, whose read would synchronise)"""
+    if isinstance(dirs, Tensor):
+        if dirs.is_cuda:
+            raise GaotError(f"{fn}: dirs must live on the host (the directions are passed to the kernel by value)")
+        dirs = dirs.tolist()
+    rows = [tuple(float(c) for c in d) for d in dirs]
+    if any(len(d) != 3 for d in rows):
+        raise GaotError(f"{fn}: dirs must be [nd][3]")
+    flat = [c for d in rows for c in d]
+    return (C.c_float * max(len(flat), 1))(*flat), len(rows)
+
+
+def gno_forward_knn_jet2(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], src_table: Optional[Tensor],
+                         nbr: Tensor, k: int, dirs):
+    """``gno_forward_knn`` with a directional 2-jet of its result (gaot_gno_fwd_knn_jet2): -> (out [n_query, 32], d1 [nd, n_query, 32],
+    d2 [nd, n_query, 32]) with d1[i] = D_v out and d2[i] = D_v^2 out along v = dirs[i] (1..6 directions, host values [nd][3]) with
+    respect to x_pos, the neighbour lists held fixed as in ``gno_forward_knn_jac``.  One launch, forward mode, exact fp32 whatever the
+    precision mode: ``out`` is ``gno_forward_knn(..., precision=0)`` and, for an axis direction e_d, d1[i] is ``gno_forward_knn_jac``'s
+    plane d, bit for bit; a direction's planes do not depend on the other directions.  Six directions e_x, e_y, e_z, e_x+e_y, e_y+e_z,
+    e_x+e_z give a Hessian by polarisation.  Operands and their checks are those of ``gno_forward_knn_jac``."""
+    lib = _lib.load()
+    md, m, keep, y_pos, x_pos, f_y, src_table, nbr, k, q = _gno_knn_args("gno_forward_knn_jet2", mode, weights, biases, y_pos, x_pos,
+                                                                         f_y, src_table, nbr, k)
+    hd, nd = _host_dirs("gno_forward_knn_jet2", dirs)
+    out = torch.empty(q, m.channels, dtype=torch.float32, device=x_pos.device)
+    d1 = torch.empty(max(nd, 1), q, m.channels, dtype=torch.float32, device=x_pos.device)
+    d2 = torch.empty_like(d1)
+    with _timed(f"gno_jet2_knn{f'_nl{md}' if md else ''}_nh{m.n_hidden}_d{nd}"):
+        check(lib.gaot_gno_fwd_knn_jet2(C.byref(m), md, _ptr(y_pos), _ptr(x_pos), _ptr(f_y), _ptr(src_table), _ptr(nbr), k, q, hd, nd,
+                                        _ptr(out), _ptr(d1), _ptr(d2), _stream()), "gaot_gno_fwd_knn_jet2")
+    return out, d1, d2
+
+
 def gno_forward_jac(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], src_table: Optional[Tensor],
                     g: BipartiteGraph):
     """``gno_forward_knn_jac`` on RAGGED rows (gaot_gno_fwd_jac): the value and the Jacobian of the fused transform on the by-query list
@@ -1735,6 +1769,55 @@ def mlp2_jvp(x: Tensor, dxs: Sequence[Tensor], w1: Tensor, b1: Tensor, w2: Tenso
         check(lib.gaot_mlp2_jvp(_ptr(x), p[0], p[1], p[2], t, rows, 32, hid, oc, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(y), ldy,
                                 _ptr(jac) if t else None, js[0], js[1], js[2], _stream()), "gaot_mlp2_jvp")
     return y, jac
+
+
+def mlp2_jet2_supported(in_dim: int, hidden: int, out_dim: int, nd: int, act: int) -> bool:
+    return bool(_lib.load().gaot_mlp2_jet2_supported(int(in_dim), int(hidden), int(out_dim), int(nd), int(act)))
+
+
+def mlp2_jet2(x: Tensor, dxs: Sequence[Tensor], ddxs: Sequence[Tensor], w1: Tensor, b1: Tensor, w2: Tensor, b2: Optional[Tensor],
+              y: Optional[Tensor] = None, d1: Optional[Tensor] = None, d2: Optional[Tensor] = None, store_y: bool = True):
+    """-> (y [rows, out], d1 [rows, out, nd], d2 [rows, out, nd]): y = w2 gelu(w1 x + b1) + b2 with its first and second directional
+    derivative along nd = 1..3 directions, given per direction the first-order plane dxs[d] and the second-order plane ddxs[d] of x
+    (dense fp32 [rows, 32]): d1 = w2 (gelu' * w1 dx), d2 = w2 (gelu'' * (w1 dx)^2 + gelu' * w1 ddx).  Exact fp32 in one launch
+    (include/gaot3d_hip.h: gaot_mlp2_jet2); y and d1 are ``mlp2_jvp``'s bit for bit.  ``y`` / ``d1`` / ``d2`` name the destinations
+    (fp32 views with positive strides, d1 and d2 with the SAME strides), else they are allocated; ``store_y=False`` skips the value
+    (y is returned as None)."""
+    lib = _lib.load()
+    rows, hid, oc, t = _req_rows(x, torch.float32, 32, "mlp2_jet2: x"), int(w1.shape[0]), int(w2.shape[0]), len(dxs)
+    if not 1 <= t <= 3 or len(ddxs) != t:
+        raise GaotError(f"mlp2_jet2: 1..3 directions with one dx and one ddx plane each, got {t} and {len(ddxs)}")
+    for d in list(dxs) + list(ddxs):
+        _req_rows(d, torch.float32, 32, "mlp2_jet2: direction plane", rows=rows)
+    for name, w, shape in (("w1", w1, (hid, 32)), ("b1", b1, (hid,)), ("w2", w2, (oc, hid))) + ((("b2", b2, (oc,)),) if b2 is not None else ()):
+        if w.dtype != torch.float32 or tuple(w.shape) != shape or not w.is_contiguous():
+            raise GaotError(f"mlp2_jet2: {name}: contiguous float32 {shape} expected, got {w.dtype} {tuple(w.shape)}")
+    if not store_y:
+        y = None
+    elif y is None:
+        y = torch.empty(rows, oc, dtype=torch.float32, device=x.device)
+    if d1 is None:
+        d1 = torch.empty(rows, oc, t, dtype=torch.float32, device=x.device)
+    if d2 is None:
+        d2 = torch.empty(rows, oc, t, dtype=torch.float32, device=x.device)
+    ldy = oc
+    if y is not None:
+        _req_rows(y, torch.float32, oc, "mlp2_jet2: y", dense=False, rows=rows)
+        ldy = int(y.stride(0)) if rows > 1 else oc
+    for name, j in (("d1", d1), ("d2", d2)):
+        if j.dtype != torch.float32 or tuple(j.shape) != (rows, oc, t) or not j.is_cuda:
+            raise GaotError(f"mlp2_jet2: {name}: float32 [{rows}, {oc}, {t}] on the GPU expected, got {j.dtype} {tuple(j.shape)} on {j.device}")
+    # the stride of a dimension of extent <= 1 is never used (torch reports anything there); the library checks the others
+    js = [int(s) if n > 1 else 1 for s, n in zip(d1.stride(), d1.shape)]
+    if js != [int(s) if n > 1 else 1 for s, n in zip(d2.stride(), d2.shape)]:
+        raise GaotError(f"mlp2_jet2: d1 and d2 must have the same strides, got {d1.stride()} and {d2.stride()}")
+    p = [_ptr(d) for d in dxs] + [None] * (3 - t)
+    pp = [_ptr(d) for d in ddxs] + [None] * (3 - t)
+    with _timed(f"mlp2_jet2_h{hid}_d{t}"):
+        check(lib.gaot_mlp2_jet2(_ptr(x), p[0], p[1], p[2], pp[0], pp[1], pp[2], t, rows, 32, hid, oc, _ptr(w1), _ptr(b1), _ptr(w2),
+                                 _ptr(b2), _ptr(y) if y is not None else None, ldy, _ptr(d1), _ptr(d2), js[0], js[1], js[2], _stream()),
+              "gaot_mlp2_jet2")
+    return y, d1, d2
 
 
 def _finish_tables(ws: Tensor, outs, parts, lanes, defer: bool) -> None:

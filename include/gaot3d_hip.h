@@ -176,6 +176,25 @@ int gaot_gno_fwd_knn_jac(const gaot_mlp_t* mlp /* host */, int mode, const float
                          float* out /* [num_queries, channels] */, float* jac /* [3, num_queries, channels] */,
                          gaot_stream_t stream);
 
+/* gaot_gno_fwd_knn with a DIRECTIONAL 2-JET of its result, for second spatial derivatives of a sampled field (csrc/gno_jet2.hip): for
+ * each of nd = 1..6 directions v_i = dirs[3 i .. 3 i + 2]
+ *   d1[i][q][c] = D_{v_i} out[q][c],   d2[i][q][c] = D^2_{v_i} out[q][c]      (direction-major planes [num_queries, channels])
+ * with respect to x_pos[q], the neighbour list of every query held fixed (valid almost everywhere, as gaot_gno_fwd_knn_jac's
+ * derivative).  Forward mode in ONE launch: z'_0 = W_0[:, 3:6] v, z''_0 = 0, then h' = gelu'(z) z', h'' = gelu''(z) z'^2 + gelu'(z) z''
+ * and z'_{l+1} = W h', z''_{l+1} = W h'' through the per-edge MLP, reduced by the same fixed-k row means.  A Hessian is six
+ * directions (e_x, e_y, e_z, e_x + e_y, e_y + e_z, e_x + e_z) polarised by the caller, H_ij = (D^2_{e_i + e_j} - D^2_{e_i} - D^2_{e_j}) / 2;
+ * a Laplacian the first three.  `dirs` is a HOST pointer: the directions are read during the call and passed to the kernel by value
+ * (no device read of host memory, no synchronisation, capturable).  Operands, argument rules and errors are gaot_gno_fwd_knn_jac's;
+ * nd outside 1..6 or null dirs: GAOT_ERR_ARG before any launch; num_queries == 0: OK without a launch.  Exact fp32 in both precision
+ * modes, no workspace, no atomics.  `out` is what gaot_gno_fwd_knn writes at precision 0, bit for bit; for an axis direction e_d plane
+ * d1 is plane d of gaot_gno_fwd_knn_jac, bit for bit; a direction's planes do not depend on the other directions in the list or on
+ * their order; a zero direction gives zero planes. */
+int gaot_gno_fwd_knn_jet2(const gaot_mlp_t* mlp /* host */, int mode, const float* y_pos, const float* x_pos, const float* f_y,
+                          const float* src_table, const int32_t* nbr /* [num_queries * k] */, int k, int64_t num_queries,
+                          const float* dirs /* HOST, [nd][3] */, int nd, float* out /* [num_queries, channels] */,
+                          float* d1 /* [nd, num_queries, channels] */, float* d2 /* [nd, num_queries, channels] */,
+                          gaot_stream_t stream);
+
 /* The same value and Jacobian on RAGGED rows: the by-query list of any graph (gaot_gno_fwd's src_sorted / dst_sorted / rowptr_dst, e.g.
  * the row lists gaot_radius_grid_fill / gaot_nbr_union_grid_fill write for 'radius' / 'bidirectional' decoders), rows of any length,
  * empty rows included:
@@ -694,6 +713,22 @@ int gaot_mlp2_jvp_supported(int in_dim, int hidden, int out_dim, int num_tangent
 int gaot_mlp2_jvp(const float* x, const float* dx0, const float* dx1, const float* dx2, int num_tangents, int64_t num_rows, int in_dim,
                   int hidden, int out_dim, const float* w1, const float* b1, const float* w2, const float* b2, float* y, int64_t ldy,
                   float* jac, int64_t jac_row_stride, int64_t jac_chan_stride, int64_t jac_dir_stride, gaot_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Directional 2-jets of the same two-layer MLP in one pass, exact fp32 (csrc/mlp2_jet2.hip; the projection under sample_hessian /
+ * sample_laplacian): for nd = 1..3 directions with a first-order plane dx_d and a second-order plane ddx_d [rows, 32],
+ *   d1_d = W2 (gelu'(z) * (W1 dx_d)),   d2_d = W2 (gelu''(z) * (W1 dx_d)^2 + gelu'(z) * (W1 ddx_d)),   z = W1 x + b1,
+ * gelu''(z) = phi(z) (2 - z^2).  The family, operands and strides are gaot_mlp2_jvp's (gaot_mlp2_jet2_supported: 1 for exactly
+ * 32 -> {64, 128, 256} -> 1..4, 1..3 directions, act 1 = GELU); unused plane pointers may be NULL.  d1 and d2 share their strides:
+ * element (n, c, d) at n * row_stride + c * chan_stride + d * dir_stride.  y may be NULL (the value is then not stored).  y is
+ * gaot_mlp2_jvp's value and d1 its tangents for the same dx, bit for bit; zero dx and ddx give exact zeros; a row's result depends
+ * on that row alone, a direction's on that direction alone.  No workspace, no atomics; num_rows == 0 is a no-op.
+ * ------------------------------------------------------------------------------------------- */
+int gaot_mlp2_jet2_supported(int in_dim, int hidden, int out_dim, int nd, int act);
+int gaot_mlp2_jet2(const float* x, const float* dx0, const float* dx1, const float* dx2, const float* ddx0, const float* ddx1,
+                   const float* ddx2, int nd, int64_t num_rows, int in_dim, int hidden, int out_dim, const float* w1, const float* b1,
+                   const float* w2, const float* b2, float* y, int64_t ldy, float* d1, float* d2, int64_t row_stride,
+                   int64_t chan_stride, int64_t dir_stride, gaot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Thin fp32 linears over many rows in one pass (csrc/rowlinear.hip):  y = act([x_0 | x_1 | ...] W^T + b),

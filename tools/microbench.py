@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Kernel microbenchmarks at the configs[1] shapes (for rocprofv3 / quick A-B): attention fwd+bwd, GEMM shapes, GNO, PointNet GeoEmbed,
-the attention-weighted GNO, the forward-only decoder (decoder_sample), the sampled field's Jacobian (decoder_jacobian), the projection MLP's tangent alone (projection_jvp)."""
+the attention-weighted GNO, the forward-only decoder (decoder_sample), the sampled field's Jacobian (decoder_jacobian), the projection MLP's tangent alone (projection_jvp), the sampled field's Hessian and Laplacian (decoder_hessian)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 if os.environ.get("MB_TREE"):      # measure another checkout's package (gno_weighted: the parent commit's) with this script
@@ -637,6 +637,99 @@ elif what == "decoder_jacobian":
                   f"({100 * mj / tot:.0f} %), mix + projection tangent {mp:.3f} ms ({100 * mp / tot:.0f} %); stages sum to {tot:.3f} ms")
             print(f"Nq={nq} fp32: gaot_gno_fwd_knn_jac {mj:.3f} ms (min {lo_j:.3f}, max {hi_j:.3f}) against gaot_gno_fwd_knn at precision 0 "
                   f"{mf:.3f} ms (min {lo_f:.3f}, max {hi_f:.3f}) on the same lists: {mj / mf:.2f} x", flush=True)
+        del q, chunks
+elif what == "decoder_hessian":
+    # Second spatial derivatives of the sampled field on the configs[1] decoder (latent 64x64x32 tokens, C = 32, knn k = 8, kernel MLP
+    # hidden [64, 64], projection 32 -> 256 -> 1) at 500 K and 8 M random query points, fp32 mode: MAGNODecoder.sample_jacobian (the
+    # yardstick: value + three tangent planes), sample_laplacian (three directional 2-jets) and sample_hessian (six), alternated in
+    # this one process after a warm-up of each; device events around synchronised work; `reps` rounds (7 for the kept output); a row
+    # is the median with max - min, the peak is the rise of allocated memory over the inputs.  Then the split of each -- neighbour
+    # search, GNO jet kernel, scale mix + projection, every stage timed over all chunks on its own.  Kept in
+    # profiles/decoder_hessian_microbench.txt.
+    from gaot_3d_amd import graph as device_graph
+    from gaot_3d_amd.data import latent_grid
+    from gaot_3d_amd.model.layers.magno import MAGNOConfig, MAGNODecoder
+    gaot_3d_amd.set_precision("fp32")
+    latent = (64, 64, 32)
+    cfg = MAGNOConfig(gno_coord_dim=3, lifting_channels=32, mlp_type="linear", use_geoembed=[True, False], neighbor_strategy="knn",
+                      k_neighbors=8, out_gno_channel_mlp_hidden_layers=[64, 64], precompute_edges=False)
+    dec = MAGNODecoder(in_channels=32, out_channels=1, gno_config=cfg).to(dev).eval()
+    dec.latent_dims = latent
+    tokens = latent_grid(latent).to(dev)
+    rn = torch.randn(tokens.shape[0], 32, device=dev)
+    chunk = int(os.environ["MB_CHUNK"]) if os.environ.get("MB_CHUNK") else None
+    step = chunk or dec.SAMPLE_CHUNK
+    DIRS = dec.HESSIAN_DIRS
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); out = fn(); e1.record()
+        torch.cuda.synchronize()
+        peak = torch.cuda.max_memory_allocated() - base
+        return e0.elapsed_time(e1), peak, out
+
+    def median(ts):
+        ts = sorted(ts)
+        return ts[len(ts) // 2], ts[0], ts[-1]
+
+    for nq in (500000, 8000000):
+        q = torch.rand(nq, 3, device=dev) * 2 - 1
+        routes = {"sample_jacobian": lambda: dec.sample_jacobian(rn, q, tokens, chunk_points=chunk),
+                  "sample_laplacian": lambda: dec.sample_laplacian(rn, q, tokens, chunk_points=chunk),
+                  "sample_hessian": lambda: dec.sample_hessian(rn, q, tokens, chunk_points=chunk)}
+        warm = {n: timed(f)[2] for n, f in routes.items()}            # warm-up, and the three agree where they must
+        same = (torch.equal(warm["sample_hessian"][0], warm["sample_jacobian"][0]) and torch.equal(warm["sample_hessian"][1], warm["sample_jacobian"][1])
+                and torch.equal(warm["sample_laplacian"][0], warm["sample_jacobian"][0]))
+        h = warm["sample_hessian"][2]
+        trace = torch.equal(warm["sample_laplacian"][1], h[..., 0, 0] + h[..., 1, 1] + h[..., 2, 2])
+        del warm, h
+        ts, pk = {n: [] for n in routes}, {n: 0 for n in routes}
+        for _ in range(reps):
+            for n, f in routes.items():
+                t, p, _o = timed(f); ts[n].append(t); pk[n] = max(pk[n], p); del _o
+        mj, lo_j, hi_j = median(ts["sample_jacobian"])
+        for n in routes:
+            m, lo, hi = median(ts[n])
+            print(f"Nq={nq} fp32: {n:16s} (chunk {step}) {m:9.3f} ms (max - min {hi - lo:.3f} ms = {100 * (hi - lo) / m:.1f} %), peak "
+                  f"{pk[n] / 2**20:9.1f} MiB  = {m / mj:.2f} x sample_jacobian in time, {pk[n] / max(pk['sample_jacobian'], 1):.2f} x in peak memory")
+        print(f"Nq={nq} fp32: pred / jac of sample_hessian and pred of sample_laplacian == sample_jacobian's bit for bit: {same}; "
+              f"lap == ordered trace of hess bit for bit: {trace}", flush=True)
+        # the split: every stage over all chunks on its own (the stages' inputs kept from the stage before)
+        grid = dec._stream_grid(rn, q, tokens)
+        with torch.no_grad():
+            chunks = [q[i:i + step] for i in range(0, nq, step)]
+            t_nbr, t_gno, t_prj = [], {"jac": [], "lap": [], "hess": []}, {"jac": [], "lap": [], "hess": []}
+            for _ in range(reps + 1):                                      # the first round warms up and is dropped
+                t, _p, nbrs = timed(lambda: [device_graph.knn_to_grid(c, grid, 8) for c in chunks]); t_nbr.append(t)
+                t, _p, outs = timed(lambda: [dec.gno.jacobian_knn(tokens, c, n, 8, rn) for c, n in zip(chunks, nbrs)]); t_gno["jac"].append(t)
+                def mix_jvp(c, o, j):
+                    p = dec._mix_equal_scales([o, *j.unbind(0)], c)
+                    return dec.projection.jvp_rows(p[0], p[1:])
+                t, _p, prj = timed(lambda: [mix_jvp(c, o, j) for c, (o, j) in zip(chunks, outs)]); t_prj["jac"].append(t)
+                del outs, prj
+                for name, nd in (("lap", 3), ("hess", 6)):
+                    t, _p, outs = timed(lambda: [dec.gno.jet2_knn(tokens, c, n, 8, rn, DIRS[:nd]) for c, n in zip(chunks, nbrs)])
+                    t_gno[name].append(t)
+                    def mix_jet(c, o, a, b, nd=nd):
+                        p = dec._mix_equal_scales([o, *a.unbind(0), *b.unbind(0)], c)
+                        return dec.projection.jet2_rows(p[0], p[1:1 + nd], p[1 + nd:])
+                    t, _p, prj = timed(lambda: [mix_jet(c, *oab) for c, oab in zip(chunks, outs)])
+                    t_prj[name].append(t)
+                    del outs, prj
+                del nbrs
+            mn = median(t_nbr[1:])[0]
+            gj = median(t_gno["jac"][1:])
+            for name, label, chains in (("jac", "sample_jacobian", 4), ("lap", "sample_laplacian", 7), ("hess", "sample_hessian", 13)):
+                mg, lo_g, hi_g = median(t_gno[name][1:])
+                mp = median(t_prj[name][1:])[0]
+                tot = mn + mg + mp
+                print(f"Nq={nq} fp32: split of {label}: neighbour search {mn:.3f} ms ({100 * mn / tot:.0f} %), GNO kernel {mg:.3f} ms "
+                      f"({100 * mg / tot:.0f} %; max - min {hi_g - lo_g:.3f}), mix + projection {mp:.3f} ms ({100 * mp / tot:.0f} %); stages sum to "
+                      f"{tot:.3f} ms; GNO kernel = {mg / gj[0]:.2f} x the Jacobian kernel's ({chains} plane-chains against 4 by count: "
+                      f"{chains / 4:.2f} x; yardstick's max - min {gj[2] - gj[1]:.3f} ms)", flush=True)
         del q, chunks
 elif what == "projection_jvp":
     # The projection MLP's forward-mode tangent on its own (LinearChannelMLP 32 -> 256 -> out, out in {1, 4}, three tangent planes, fp32
