@@ -30,6 +30,13 @@
 // The directions arrive BY VALUE in the kernel's arguments (read on the host from a host pointer): no device read of host memory, no
 // synchronisation, capturable.  LDS: up to 59.1 KiB of weights plus a 2-plane staging tile of 8 KiB per wave (91.6 KiB of 160 at four
 // hidden layers).  No scratch, no atomics, plain vector stores only.
+//
+// RAGGED rows (gaot_gno_fwd_jet2, the by-query list of a 'radius' / 'bidirectional' graph): k_gno_fwd_rows_jet2, the same kernel body
+// (gno_jet2_body.inc) with the list handling of gno_jac.hip's JacRows.  The per-edge arithmetic is untouched; the query of an edge
+// comes from dst_sorted, the wave keeps its 32 query ids in LDS (128 bytes more per wave) and every one of the 1 + 2 nd planes is
+// finished by segment_walk<32> -- complete rows stored as their mean, rows that straddle tiles left in the plane's partial buffer --
+// and by ONE fix-up launch over all planes (k_jet2_rows_fixup).  On a list whose rows all have k | 32 edges the two kernels perform
+// the same operations in the same order: bit-identical planes.
 #include "gno_common.h"
 
 namespace {
@@ -49,6 +56,8 @@ struct Jet2Lds {
     static constexpr int stage = weights_end;                    // [4 waves][2][32][C]
     static constexpr int ids = stage + 4 * 2 * 32 * C;           // [4 waves][32] (int)
     static constexpr size_t bytes = sizeof(float) * (size_t)(ids + 4 * 32);
+    static constexpr int qids = ids + 4 * 32;                    // row lists only: [4 waves][32] (int), the edges' queries
+    static constexpr size_t bytes_rows = sizeof(float) * (size_t)(qids + 4 * 32);
 };
 
 struct Jet2Dirs {
@@ -88,250 +97,89 @@ __device__ __forceinline__ void gelu_fast_jet2(float x, float& g, float& dg, flo
     ddg = 0.39894228040143267794f * e * fmaf(-x, x, 2.0f);
 }
 
+// ROW-LIST variant (gaot_gno_fwd_jet2, k_gno_fwd_rows_jet2): the kernel body (gno_jet2_body.inc) with R = true and a Jet2Rows as the
+// kernel's last argument.  As JacRows of gno_jac.hip: `nbr` is the by-query list's source ids (src_sorted), the
+// query of edge e is dst_s[e] (-1: no row -- an edge past E, or a PADDING edge of the list; such edges read row 0, are computed and
+// are dropped by the walk), lk is not read, and every plane is finished by segment_walk with its own partial buffer, two 32-float
+// slots per tile: plane 0 the value, 1 + d direction d's D_v, 1 + nd + d its D_v^2.
+struct Jet2Rows {
+    const int* dst_s;       // [E]
+    const int* rowptr;      // [Nq + 1]
+    float* part;            // [1 + 2 nd][n_tiles][2][32]
+    int64_t plane;          // Nq * 32: one plane of d1 / d2
+    int64_t part_plane;     // n_tiles * 2 * 32: one plane of part
+};
+
 template <int NH, int MODE>
 __global__ __launch_bounds__(256, 1) void k_gno_fwd_knn_jet2(MlpPtrs mlp, const float* __restrict__ y_pos,
                                                              const float* __restrict__ x_pos, const float* __restrict__ f_y,
                                                              const float* __restrict__ ttab, const int* __restrict__ nbr, int lk,
                                                              int64_t E, const Jet2Dirs dirs, float* __restrict__ out,
                                                              float* __restrict__ d1, float* __restrict__ d2) {
-    using L = Jet2Lds<NH>;
-    constexpr bool KEEP = NH <= 2;   // what the value path leaves for the direction passes (see the head of this file)
-    extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr bool R = false;
+    [[maybe_unused]] const Jet2Rows rows{};
+#include "gno_jet2_body.inc"
+}
 
-    // ---- weights -> LDS, transposed to [in][out] (k_gno_fwd's image) ---------------------------------
-    for (int i = threadIdx.x; i < IN0P * H; i += 256) {
-        const int k = i / H, j = i % H;
-        lds[L::w0 + i] = (k < IN0) ? mlp.w[0][j * IN0 + k] : 0.f;
-    }
-    for (int i = threadIdx.x; i < H; i += 256) lds[L::b0 + i] = mlp.b[0][i];
-#pragma unroll
-    for (int l = 1; l < NH; ++l) {
-        float* wt = lds + L::wl + (l - 1) * (H * H + H);
-        for (int i = threadIdx.x; i < H * H; i += 256) {
-            const int j = i / H, k = i % H;
-            wt[k * H + j] = mlp.w[l][i];
-        }
-        for (int i = threadIdx.x; i < H; i += 256) wt[H * H + i] = mlp.b[l][i];
-    }
-    for (int i = threadIdx.x; i < C * H; i += 256) {
-        const int c = i / H, k = i % H;
-        lds[L::wL + k * C + c] = mlp.w[NH][i];
-    }
-    for (int i = threadIdx.x; i < C; i += 256) lds[L::bL + i] = mlp.b[NH][i];
-    __syncthreads();
+// the same arithmetic on RAGGED rows (a name of its own: the regular-list kernels are counted by theirs)
+template <int NH, int MODE>
+__global__ __launch_bounds__(256, 1) void k_gno_fwd_rows_jet2(MlpPtrs mlp, const float* __restrict__ y_pos,
+                                                              const float* __restrict__ x_pos, const float* __restrict__ f_y,
+                                                              const float* __restrict__ ttab, const int* __restrict__ nbr, int64_t E,
+                                                              const Jet2Dirs dirs, float* __restrict__ out, float* __restrict__ d1,
+                                                              float* __restrict__ d2, const Jet2Rows rows) {
+    constexpr bool R = true;
+    [[maybe_unused]] constexpr int lk = 0;   // not read on row lists
+#include "gno_jet2_body.inc"
+}
 
-    const int wave = threadIdx.x >> 6;
-    const int lane = threadIdx.x & 63;
-    const int l31 = lane & 31, hf = lane >> 5;
-    float* stage = lds + L::stage + wave * (2 * 32 * C);
-    int* ids = (int*)(lds + L::ids) + wave * 32;
-    const int64_t plane = (E >> lk) * C;   // one [Nq][32] plane of d1 / d2
-
-    const int64_t n_tiles = (E + 31) / 32;
-    for (int64_t tile = (int64_t)blockIdx.x * 4 + wave; tile < n_tiles; tile += (int64_t)gridDim.x * 4) {
-        const int64_t base = tile * 32;
-        // MLP input k = 2i+hf of this lane's edge: [y.x y.y y.z x.x x.y x.z][2i+hf], i = 0..2 (edges past E: row 0, a valid row)
-        float bin[3];
-        int sid;
-        {
-            const int64_t e = base + l31;
-            const bool valid = e < E;
-            sid = valid ? nbr[e] : 0;
-            const int q = valid ? (int)(e >> lk) : 0;
-            const float* ys = y_pos + (int64_t)sid * 3;
-            const float* xq = x_pos + (int64_t)q * 3;
-            bin[0] = ys[hf];
-            bin[1] = hf ? xq[0] : ys[2];
-            bin[2] = xq[1 + hf];
-            if (hf == 0) ids[l31] = sid;
-        }
-        // ---- the value path, once per tile: gelu' and gelu'' of every hidden layer stay in registers -----
-        f32x16 h[KB], sa[NH][KB], sb[KEEP ? NH : 1][KB];   // KEEP: gelu'(z_l), gelu''(z_l); else z_l
-#pragma unroll
-        for (int ob = 0; ob < KB; ++ob) {
-            f32x16 z;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) z[r] = lds[L::b0 + 32 * ob + mfma32_row(r, hf)];
-            if constexpr (MODE != MODE_LINEAR) {
-                const float* tr = ttab + (int64_t)sid * NLH + 32 * ob + 4 * hf;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float4 v = *reinterpret_cast<const float4*>(tr + 8 * j);
-                    z[4 * j + 0] += v.x;
-                    z[4 * j + 1] += v.y;
-                    z[4 * j + 2] += v.z;
-                    z[4 * j + 3] += v.w;
-                }
+// The fix-up of all 1 + 2 nd planes in one pass over rowptr (k_jac_rows_fixup with a plane count): on each plane
+// k_segment_fixup<32>'s operations in its order -- rows with no edges -> 0, rows spanning several tiles -> the ordered sum of their
+// tile partials, then the division by the degree.
+__global__ void k_jet2_rows_fixup(const int* __restrict__ rowptr, int64_t Q, const float* __restrict__ part, int64_t part_plane, int nd,
+                                  float* __restrict__ out, float* __restrict__ d1, float* __restrict__ d2) {
+    constexpr int TPR = C / 4;                                   // threads per row, 16 bytes each
+    const int64_t n = Q * TPR, stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const int64_t q = i / TPR;
+        const int c = (int)(i % TPR) * 4;
+        const int rb = rowptr[q], re = rowptr[q + 1];
+        const int t0 = rb >> 5, t1 = (re - 1) >> 5;
+        if (re != rb && t0 == t1) continue;
+        for (int p = 0; p < 1 + 2 * nd; ++p) {
+            float* base = p == 0 ? out : p <= nd ? d1 + (int64_t)(p - 1) * Q * C : d2 + (int64_t)(p - 1 - nd) * Q * C;
+            float4* o = reinterpret_cast<float4*>(base + q * C + c);
+            if (re == rb) {
+                *o = make_float4(0.f, 0.f, 0.f, 0.f);
+                continue;
             }
-#pragma unroll
-            for (int i = 0; i < IN0 / 2; ++i) {
-                const float a = lds[L::w0 + (2 * i + hf) * H + 32 * ob + l31];
-                z = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bin[i], z, 0, 0, 0);
+            const float* pp = part + p * part_plane;
+            float4 s = *reinterpret_cast<const float4*>(pp + ((int64_t)t0 * 2 + 1) * C + c);
+            for (int t = t0 + 1; t <= t1; ++t) {
+                const float4 v = *reinterpret_cast<const float4*>(pp + ((int64_t)t * 2 + 0) * C + c);
+                s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
             }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                float g, a, b;
-                gelu_fast_jet2(z[r], g, a, b);
-                h[ob][r] = g;
-                if constexpr (KEEP) {
-                    sa[0][ob][r] = a;
-                    sb[0][ob][r] = b;
-                } else {
-                    sa[0][ob][r] = z[r];
-                }
-            }
-        }
-#pragma unroll
-        for (int l = 1; l < NH; ++l) {
-            const float* wt = lds + L::wl + (l - 1) * (H * H + H);
-            f32x16 zn[KB];
-#pragma unroll
-            for (int ob = 0; ob < KB; ++ob) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) zn[ob][r] = wt[H * H + 32 * ob + mfma32_row(r, hf)];
-#pragma unroll
-                for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const float a = wt[(32 * kb + mfma32_row(r, hf)) * H + 32 * ob + l31];
-                        zn[ob] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, h[kb][r], zn[ob], 0, 0, 0);
-                    }
-            }
-#pragma unroll
-            for (int ob = 0; ob < KB; ++ob)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    float g, a, b;
-                    gelu_fast_jet2(zn[ob][r], g, a, b);
-                    h[ob][r] = g;
-                    if constexpr (KEEP) {
-                        sa[l][ob][r] = a;
-                        sb[l][ob][r] = b;
-                    } else {
-                        sa[l][ob][r] = zn[ob][r];
-                    }
-                }
-        }
-        // ---- last layer, transposed: K'[e][c] = sum_k Hlast[k][e] * WL[c][k] + bL[c]; the value plane is finished by half 0 ----
-        wave_lds_fence();  // ids visible to the whole wave
-        [[maybe_unused]] float fv[16];
-        if constexpr (MODE != MODE_KERNELONLY) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) fv[r] = f_y[(int64_t)ids[mfma32_row(r, hf)] * C + l31];
-        }
-        {
-            f32x16 acc;
-            const float bl = lds[L::bL + l31];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = bl;
-#pragma unroll
-            for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float b = lds[L::wL + (32 * kb + mfma32_row(r, hf)) * C + l31];
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(h[kb][r], b, acc, 0, 0, 0);
-                }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int el = mfma32_row(r, hf);
-                if constexpr (MODE == MODE_KERNELONLY) stage[el * C + l31] = acc[r];
-                else stage[el * C + l31] = acc[r] * fv[r];
-            }
-        }
-        wave_lds_fence();
-        if (hf == 0) fixed_k_rows<C>(stage, C, l31, base, lk, E, out);
-        wave_lds_fence();
-
-        // ---- one pass per direction: h' and h'' through the layers, two planes staged, one finished by each half ----
-#pragma unroll 1
-        for (int d = 0; d < dirs.nd; ++d) {
-            const float vx = dir_at(dirs, d, 0), vy = dir_at(dirs, d, 1), vz = dir_at(dirs, d, 2);
-            f32x16 hd[KB], hdd[KB];
-#pragma unroll
-            for (int ob = 0; ob < KB; ++ob)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int j = 32 * ob + mfma32_row(r, hf);
-                    const float zd = fmaf(vz, lds[L::w0 + 5 * H + j], fmaf(vy, lds[L::w0 + 4 * H + j], vx * lds[L::w0 + 3 * H + j]));
-                    float dg, ddg;
-                    if constexpr (KEEP) {
-                        dg = sa[0][ob][r];
-                        ddg = sb[0][ob][r];
-                    } else {
-                        float g;
-                        gelu_fast_jet2(opaque(sa[0][ob][r]), g, dg, ddg);
-                    }
-                    hd[ob][r] = dg * zd;
-                    hdd[ob][r] = ddg * zd * zd;
-                }
-#pragma unroll
-            for (int l = 1; l < NH; ++l) {
-                const float* wt = lds + L::wl + (l - 1) * (H * H + H);
-                f32x16 u[KB], w[KB];
-#pragma unroll
-                for (int ob = 0; ob < KB; ++ob) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) u[ob][r] = 0.f;
-#pragma unroll
-                    for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            const float a = wt[(32 * kb + mfma32_row(r, hf)) * H + 32 * ob + l31];
-                            u[ob] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, hd[kb][r], u[ob], 0, 0, 0);
-                        }
-                }
-#pragma unroll
-                for (int ob = 0; ob < KB; ++ob) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) w[ob][r] = 0.f;
-#pragma unroll
-                    for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            const float a = wt[(32 * kb + mfma32_row(r, hf)) * H + 32 * ob + l31];
-                            w[ob] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, hdd[kb][r], w[ob], 0, 0, 0);
-                        }
-                }
-#pragma unroll
-                for (int ob = 0; ob < KB; ++ob)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        float dg, ddg;
-                        if constexpr (KEEP) {
-                            dg = sa[l][ob][r];
-                            ddg = sb[l][ob][r];
-                        } else {
-                            float g;
-                            gelu_fast_jet2(opaque(sa[l][ob][r]), g, dg, ddg);
-                        }
-                        hd[ob][r] = dg * u[ob][r];
-                        hdd[ob][r] = fmaf(dg, w[ob][r], ddg * u[ob][r] * u[ob][r]);
-                    }
-            }
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                f32x16 acc;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-                for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const float b = lds[L::wL + (32 * kb + mfma32_row(r, hf)) * C + l31];
-                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(p == 0 ? hd[kb][r] : hdd[kb][r], b, acc, 0, 0, 0);
-                    }
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int el = mfma32_row(r, hf);
-                    if constexpr (MODE == MODE_KERNELONLY) stage[(p * 32 + el) * C + l31] = acc[r];
-                    else stage[(p * 32 + el) * C + l31] = acc[r] * fv[r];
-                }
-            }
-            wave_lds_fence();
-            fixed_k_rows<C>(stage + hf * 32 * C, C, l31, base, lk, E, (hf ? d2 : d1) + (int64_t)d * plane);
-            wave_lds_fence();
+            const float d = (float)(re - rb);
+            s.x /= d; s.y /= d; s.z /= d; s.w /= d;
+            *o = s;
         }
     }
+}
+
+template <int NH, int MODE>
+int launch_jet2_rows(const MlpPtrs& p, const float* y_pos, const float* x_pos, const float* f_y, const float* ttab, const int* src_s,
+                     const Jet2Rows& rows, int64_t E, const Jet2Dirs& dirs, float* out, float* d1, float* d2, hipStream_t st) {
+    constexpr size_t lds = Jet2Lds<NH>::bytes_rows;
+    auto kern = k_gno_fwd_rows_jet2<NH, MODE>;
+    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) {
+        gaot_set_error("gaot_gno_fwd_jet2: cannot set dynamic LDS %zu: %s", lds, hipGetErrorString(e));
+        return GAOT_ERR_LAUNCH;
+    }
+    const int64_t n_tiles = ceil_div(E, 32);
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n_tiles, 4), 256));   // one workgroup per CU
+    GAOT_KLAUNCH(kern, dim3(grid), dim3(256), lds, st, p, y_pos, x_pos, f_y, ttab, src_s, E, dirs, out, d1, d2, rows);
+    return GAOT_OK;
 }
 
 template <int NH, int MODE>
@@ -397,6 +245,77 @@ extern "C" int gaot_gno_fwd_knn_jet2(const gaot_mlp_t* mlp, int mode, const floa
 #undef GNO_JET2_CASES
 #undef GNO_JET2_CASE
     if (rc != GAOT_OK) return rc;
+    GAOT_LAUNCH_CHECK();
+    return GAOT_OK;
+}
+
+// two 32-float slots per 32-edge tile and plane, 1 + 2 nd planes: 256 (1 + 2 nd) bytes per tile (3.25 KiB at six directions)
+extern "C" size_t gaot_gno_fwd_jet2_workspace_bytes(int64_t num_edges, int nd) {
+    return num_edges > 0 && nd >= 0 ? sizeof(float) * (size_t)(ceil_div(num_edges, 32) * (1 + 2 * nd) * 2 * C) : 0;
+}
+
+// The jet kernel on RAGGED rows (the by-query list of any graph) and the fix-up of its 1 + 2 nd planes: two launches
+extern "C" int gaot_gno_fwd_jet2(const gaot_mlp_t* mlp, int mode, const float* y_pos, const float* x_pos, const float* f_y,
+                                 const float* src_table, const int32_t* src_sorted, const int32_t* dst_sorted,
+                                 const int32_t* rowptr_dst, int64_t num_edges, int64_t num_queries, const float* dirs, int nd,
+                                 float* out, float* d1, float* d2, void* workspace, size_t workspace_bytes, gaot_stream_t stream) {
+    GAOT_ENTER();
+    GAOT_CHECK_ARG(mlp, "null mlp");
+    if (!(mlp->channels == C && mlp->hidden == H && mlp->n_hidden >= 1 && mlp->n_hidden <= 4)) {
+        gaot_set_error("gaot_gno_fwd_jet2: unsupported MLP shape (n_hidden=%d hidden=%d channels=%d)", mlp->n_hidden, mlp->hidden,
+                       mlp->channels);
+        return GAOT_ERR_UNSUPPORTED;
+    }
+    GAOT_CHECK_ARG(mode == MODE_LINEAR || mode == MODE_NONLINEAR || mode == MODE_KERNELONLY,
+                   "mode must be 0 (linear), 1 (nonlinear) or 2 (nonlinear_kernelonly)");
+    GAOT_CHECK_ARG(nd >= 1 && nd <= MAXD, "nd must be 1..6 directions");
+    GAOT_CHECK_ARG(dirs, "null dirs");
+    {
+        hipPointerAttribute_t attr;   // the directions are read here, on the host: a device pointer is an argument error
+        if (hipPointerGetAttributes(&attr, dirs) == hipSuccess)
+            GAOT_CHECK_ARG(attr.type != hipMemoryTypeDevice, "dirs must be a host pointer (the directions are passed to the kernel by value)");
+        else
+            (void)hipGetLastError();  // ordinary host memory the runtime has never seen
+    }
+    GAOT_CHECK_ARG(num_edges >= 0 && num_queries >= 0, "negative size");
+    GAOT_CHECK_ARG(num_edges <= (int64_t)INT32_MAX, "num_edges beyond int32 (sample the queries in chunks)");
+    GAOT_CHECK_ARG(rowptr_dst && (num_queries == 0 || (out && d1 && d2)), "null pointer");
+    if (num_edges > 0) {
+        GAOT_CHECK_ARG(y_pos && x_pos && src_sorted && dst_sorted && (f_y || mode == MODE_KERNELONLY), "null pointer");
+        GAOT_CHECK_ARG(mode == MODE_LINEAR || src_table, "null src_table");
+        GAOT_CHECK_ARG(workspace, "null workspace");
+    }
+    GAOT_CHECK_ARG(workspace_bytes >= gaot_gno_fwd_jet2_workspace_bytes(num_edges, nd), "workspace too small");
+    MlpPtrs p;
+    for (int l = 0; l <= mlp->n_hidden; ++l) {
+        p.w[l] = mlp->weight[l];
+        p.b[l] = mlp->bias[l];
+        GAOT_CHECK_ARG(p.w[l] && p.b[l], "null MLP parameter");
+    }
+    if (num_queries == 0) return GAOT_OK;
+    Jet2Dirs dv;   // read here, on the host: the kernel takes the directions by value
+    dv.nd = nd;
+    for (int d = 0; d < MAXD; ++d)
+        for (int c = 0; c < 3; ++c) dv.v[d][c] = d < nd ? dirs[d * 3 + c] : 0.f;
+    hipStream_t st = (hipStream_t)stream;
+    const Jet2Rows rows{dst_sorted, rowptr_dst, (float*)workspace, num_queries * C, ceil_div(num_edges, 32) * 2 * C};
+    if (num_edges > 0) {
+        int rc = GAOT_OK;
+#define GNO_JET2_CASE(NH_, MODE_)                                                                                               \
+    case NH_ * 3 + MODE_:                                                                                                       \
+        rc = launch_jet2_rows<NH_, MODE_>(p, y_pos, x_pos, f_y, src_table, src_sorted, rows, num_edges, dv, out, d1, d2, st);   \
+        break;
+#define GNO_JET2_CASES(NH_) GNO_JET2_CASE(NH_, MODE_LINEAR) GNO_JET2_CASE(NH_, MODE_NONLINEAR) GNO_JET2_CASE(NH_, MODE_KERNELONLY)
+        switch (mlp->n_hidden * 3 + mode) {
+            GNO_JET2_CASES(1) GNO_JET2_CASES(2) GNO_JET2_CASES(3) GNO_JET2_CASES(4)
+        }
+#undef GNO_JET2_CASES
+#undef GNO_JET2_CASE
+        if (rc != GAOT_OK) return rc;
+    }
+    // empty rows -> 0 and the rows that straddle tiles, all 1 + 2 nd planes (num_edges == 0: this launch alone)
+    GAOT_KLAUNCH(k_jet2_rows_fixup, dim3(segment_fixup_grid(num_queries * 8)), dim3(256), 0, st, rowptr_dst, num_queries, rows.part,
+                 rows.part_plane, nd, out, d1, d2);
     GAOT_LAUNCH_CHECK();
     return GAOT_OK;
 }

@@ -190,6 +190,23 @@ class GAOT3D(nn.Module):
         lat = self._one_sample("sample_laplacian", latent, tokens_pos)
         return self.decoder.sample_laplacian(latent, query_pos.to(latent.device), lat, chunk_points=chunk_points)
 
+    def sample_hessian_rows(self, latent: torch.Tensor, query_pos: torch.Tensor, tokens_pos: Optional[torch.Tensor] = None,
+                            chunk_points: Optional[int] = None):
+        """``sample_hessian`` for 'radius' / 'bidirectional' decoders (the reference's shipped configuration is 'bidirectional'): the
+        same results on ROW lists -- ``graph.query_lists``, the jet kernel on ragged rows and a scale mix that carries the first and
+        second derivative of its weights.  ``pred`` and ``jac`` are ``sample_jacobian(row_lists=True)``'s bit for bit.
+        ``MAGNODecoder.sample_hessian_rows``; on a 'knn' decoder the call is ``sample_hessian``."""
+        lat = self._one_sample("sample_hessian_rows", latent, tokens_pos)
+        return self.decoder.sample_hessian_rows(latent, query_pos.to(latent.device), lat, chunk_points=chunk_points)
+
+    def sample_laplacian_rows(self, latent: torch.Tensor, query_pos: torch.Tensor, tokens_pos: Optional[torch.Tensor] = None,
+                              chunk_points: Optional[int] = None):
+        """``sample_laplacian`` for 'radius' / 'bidirectional' decoders: -> (pred, lap), the trace of ``sample_hessian_rows``'s result
+        bit for bit from three directions.  ``MAGNODecoder.sample_laplacian_rows``; on a 'knn' decoder the call is
+        ``sample_laplacian``."""
+        lat = self._one_sample("sample_laplacian_rows", latent, tokens_pos)
+        return self.decoder.sample_laplacian_rows(latent, query_pos.to(latent.device), lat, chunk_points=chunk_points)
+
     def forward(self, batch, tokens_pos: Optional[torch.Tensor] = None, tokens_batch_idx: Optional[torch.Tensor] = None,
                 query_coord_pos: Optional[torch.Tensor] = None, query_coord_batch_idx: Optional[torch.Tensor] = None,
                 condition: Optional[float] = None) -> torch.Tensor:

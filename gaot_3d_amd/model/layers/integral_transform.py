@@ -22,7 +22,9 @@ the graph of those lists -- what ``MAGNODecoder.sample`` streams query chunks th
 derivative of its result with respect to the query coordinates, in forward mode (``gaot_gno_fwd_knn_jac``: three tangents through the
 per-edge MLP beside the value, exact fp32) -- what ``MAGNODecoder.sample_jacobian`` streams.  ``jacobian_rows`` is the same on the
 ragged by-query list of any graph (``gaot_gno_fwd_jac``: the tangent kernel finished by the forward's segmented walk and one fix-up
-launch) -- what ``sample_jacobian(row_lists=True)`` streams for 'radius' / 'bidirectional' decoders.
+launch) -- what ``sample_jacobian(row_lists=True)`` streams for 'radius' / 'bidirectional' decoders.  ``jet2_knn`` and ``jet2_rows``
+carry directional 2-jets (value, D_v, D_v^2) on the same two kinds of list (``gaot_gno_fwd_knn_jet2`` / ``gaot_gno_fwd_jet2``) -- what
+``sample_hessian`` / ``sample_laplacian`` and their ``_rows`` variants stream.
 HIP only, no CPU fallback."""
 from typing import Optional
 
@@ -219,6 +221,22 @@ class IntegralTransform(nn.Module):
                 raise NotImplementedError("IntegralTransform.jacobian_rows: only the transforms the fused kernels evaluate (_fused_plan)")
             return self._forward_fused(fcs, y_pos, x_pos, f_y, graph, *plan, jac=True)
 
+    def jet2_rows(self, y_pos, x_pos, f_y: Optional[torch.Tensor], graph, dirs):
+        """``jet2_knn`` on RAGGED rows: ``graph`` holds the by-query list of any graph (``graph.by_dst``; ``by_src`` may be None, as
+        ``graph.query_lists`` leaves it) -> (out [N_x, C], d1 [nd, N_x, C], d2 [nd, N_x, C]) along the 1..6 directions ``dirs`` (host
+        values [nd][3]), every query's list held fixed, empty rows exact zeros in every plane.  One ``ops.gno_forward_jet2`` call (the
+        jet kernel and its fix-up) per 32-channel pass, exact fp32 in both precision modes: ``out`` is ``jacobian_rows``'s and, for an
+        axis direction, d1 is its Jacobian plane, bit for bit.  The operands are prepared exactly as in ``jacobian_rows``.  Runs
+        exactly when ``_fused_plan`` is not None and raises NotImplementedError otherwise.  Nothing is recorded for autograd."""
+        if self.transform_type not in ("linear", "nonlinear", "nonlinear_kernelonly"):
+            raise ValueError(f"Invalid transform_type: {self.transform_type}")
+        fcs = list(self.channel_mlp.fcs)
+        with torch.no_grad():
+            plan = self._fused_plan(fcs, f_y, y_pos, x_pos)
+            if plan is None:
+                raise NotImplementedError("IntegralTransform.jet2_rows: only the transforms the fused kernels evaluate (_fused_plan)")
+            return self._forward_fused(fcs, y_pos, x_pos, f_y, graph, *plan, jet2=dirs)
+
     @staticmethod
     def _pad3(pos):
         """coordinates of dimension 1 / 2 padded with zeros to the kernels' 3-D rows"""
@@ -296,11 +314,14 @@ class IntegralTransform(nn.Module):
         list instead of the autograd Functions; with ``jac`` (``jacobian_knn``) they run ``ops.gno_forward_knn_jac`` and the result is
         (out [N_x, c], jac [3, N_x, c]).  ``jac`` with a ``graph`` (``jacobian_rows``; no autograd either): the passes run
         ``ops.gno_forward_jac`` on the graph's by-query list, with the same result shapes.  ``jet2`` = directions (``jet2_knn``; with
-        ``knn``): the passes run ``ops.gno_forward_knn_jet2`` and the result is (out [N_x, c], d1 [nd, N_x, c], d2 [nd, N_x, c])."""
+        ``knn``): the passes run ``ops.gno_forward_knn_jet2`` and the result is (out [N_x, c], d1 [nd, N_x, c], d2 [nd, N_x, c]);
+        ``jet2`` with a ``graph`` (``jet2_rows``): ``ops.gno_forward_jet2`` on the graph's by-query list, the same result shapes."""
         w2 = lambda fc: fc.weight[:, :, 0] if fc.weight.dim() == 3 else fc.weight    # Conv1d(k=1) storage of mlp_type='channel'
         pad_hidden = any(fc.weight.shape[0] != 64 for fc in fcs[:-1])
         tt = self.transform_type
         if tt == "linear" and cd == 3 and c == 32 and not pad_hidden and edge_w is None:   # the shipped shape: straight through
+            if jet2 is not None and knn is None:
+                return ops.gno_forward_jet2(0, [w2(fc) for fc in fcs], [fc.bias for fc in fcs], y_pos, x_pos, f_y, None, graph, jet2)
             if jet2 is not None:
                 return ops.gno_forward_knn_jet2(0, [w2(fc) for fc in fcs], [fc.bias for fc in fcs], y_pos, x_pos, f_y, None, *knn, jet2)
             if knn is not None:
@@ -349,8 +370,9 @@ class IntegralTransform(nn.Module):
                 bb = torch.nn.functional.pad(bb, (0, 32 - n))
                 fb = None if fb is None else torch.nn.functional.pad(fb, (0, 32 - n))
             if jet2 is not None:
-                o = ops.gno_forward_knn_jet2(tt, [w0.contiguous(), *mid[0::2], wb.contiguous()], [b0, *mid[1::2], bb.contiguous()], y3,
-                                             x3, None if fb is None else fb.contiguous(), t, *knn, jet2)
+                fwd = ops.gno_forward_jet2 if knn is None else ops.gno_forward_knn_jet2
+                o = fwd(tt, [w0.contiguous(), *mid[0::2], wb.contiguous()], [b0, *mid[1::2], bb.contiguous()], y3, x3,
+                        None if fb is None else fb.contiguous(), t, *(knn if knn is not None else (graph,)), jet2)
                 outs.append((o[0][:, :n], o[1][:, :, :n], o[2][:, :, :n]) if n < 32 else o)
                 continue
             elif knn is not None or jac:

@@ -198,15 +198,89 @@ def _softmax_weight_tangents(w, active, w1, w2, rows_matmul):
     ``w`` [n, scales], ``active`` = 1[z > 0] [n, hidden], ``w1`` [hidden, dims], ``w2`` [scales, hidden];
     ``rows_matmul(x, W)`` = x W^T row by row.  -> one [n, scales] tensor per direction.  The sum over the scales is written term by
     term: a row's result does not depend on how many rows there are."""
+    return [_softmax_weight_jets(w, dl)[0] for dl in _logit_tangents(active, w1, w2, rows_matmul)]
+
+
+def _logit_tangents(active, w1, w2, rows_matmul):
+    """d_d l = W_2 (1[z > 0] * W_1[:, d]) of ``_softmax_weight_tangents``, one [n, scales] tensor per coordinate axis"""
+    return [rows_matmul(active * w1[:, d], w2) for d in range(w1.shape[1])]
+
+
+def _softmax_weight_jets(w, dl, second=False):
+    """The first and second directional derivative of w = softmax(l) along a direction in which l' = ``dl`` [n, scales] and l'' = 0
+    (l is piecewise linear in the position):
+        m = sum_t w_t l'_t,   w'_s = w_s (l'_s - m),   m' = sum_t w'_t l'_t,   w''_s = w'_s (l'_s - m) - w_s m'
+    -> (w' [n, scales], w'' [n, scales] or None without ``second``); sum_s w'_s = sum_s w''_s = 0.  The sums over the scales are
+    written term by term: a row's result does not depend on how many rows there are."""
     ns = w.shape[1]
-    dws = []
-    for d in range(w1.shape[1]):
-        dl = rows_matmul(active * w1[:, d], w2)
-        mean = w[:, 0] * dl[:, 0]
-        for s in range(1, ns):
-            mean = mean + w[:, s] * dl[:, s]
-        dws.append(torch.stack([w[:, s] * (dl[:, s] - mean) for s in range(ns)], dim=1))
-    return dws
+    mean = w[:, 0] * dl[:, 0]
+    for s in range(1, ns):
+        mean = mean + w[:, s] * dl[:, s]
+    dw = torch.stack([w[:, s] * (dl[:, s] - mean) for s in range(ns)], dim=1)
+    if not second:
+        return dw, None
+    dmean = dw[:, 0] * dl[:, 0]
+    for s in range(1, ns):
+        dmean = dmean + dw[:, s] * dl[:, s]
+    ddw = torch.stack([dw[:, s] * (dl[:, s] - mean) - w[:, s] * dmean for s in range(ns)], dim=1)
+    return dw, ddw
+
+
+def _mix_jet2_planes(w, dls, outs, d1s, d2s, dirs):
+    """The softmax-weighted mix of the scales' 2-jets: ``w`` [n, scales], ``dls`` the logit tangents along the coordinate axes
+    (``_logit_tangents``), ``outs[s]`` [n, C] and ``d1s[s]`` / ``d2s[s]`` [nd, n, C] the value, D_v and D_v^2 planes of scale s along
+    ``dirs`` (host values [nd][3]) -> (D_v mix per direction, D_v^2 mix per direction, w' per direction, w'' per direction):
+        D_v mix = sum_s (w_s D_v o_s + w'_s o_s),     D_v^2 mix = sum_s (w_s D_v^2 o_s + 2 w'_s D_v o_s + w''_s o_s)
+    with l'_v = sum_c v_c d_c l formed from the axis tangents (an axis direction: that tangent itself; e_i + e_j: their sum).  Per-row
+    operations with the sums over the scales written term by term, in the dtype of the operands."""
+    ns = len(outs)
+    p1, p2, dws, ddws = [], [], [], []
+    for i, v in enumerate(dirs):
+        dl = None
+        for c, vc in enumerate(v):
+            if vc == 0.0 or c >= len(dls):
+                continue
+            term = dls[c] if vc == 1.0 else vc * dls[c]
+            dl = term if dl is None else dl + term
+        if dl is None:
+            dl = torch.zeros_like(w)
+        dw, ddw = _softmax_weight_jets(w, dl, second=True)
+        a1 = a2 = None
+        for s in range(ns):
+            ws, dws_, ddws_ = w[:, s:s + 1], dw[:, s:s + 1], ddw[:, s:s + 1]
+            t1 = ws * d1s[s][i] + dws_ * outs[s]
+            t2 = ws * d2s[s][i] + (2.0 * dws_) * d1s[s][i] + ddws_ * outs[s]
+            a1 = t1 if a1 is None else a1 + t1
+            a2 = t2 if a2 is None else a2 + t2
+        p1.append(a1)
+        p2.append(a2)
+        dws.append(dw)
+        ddws.append(ddw)
+    return p1, p2, dws, ddws
+
+
+def _mix_scales_jet2(module, outs, d1s, d2s, pos, dirs):
+    """``_mix_scales_jvp`` with second-order jets: ``outs[s]`` [n, C], ``d1s[s]`` / ``d2s[s]`` [nd, n, C] of every scale along ``dirs``
+    -> [value, D_v per direction ..., D_v^2 per direction ...], [n, C] each.  The value is ``_mix_scales``'s and, for an axis direction,
+    D_v is ``_mix_scales_jvp``'s plane, bit for bit.  Summed scales: the sum of each plane; one scale: the planes as they are.  With
+    softmax weights the scales of a row-list decoder see different lists, so neither sum_s w'_s o_s nor sum_s w''_s o_s vanishes
+    (``_mix_jet2_planes``); the logits are piecewise linear in the position (l'' = 0 away from the ReLU kinks of the weighting MLP).
+    Per-row fp32 operations only: a row's result does not depend on the chunk it is in."""
+    ns, nd = len(outs), len(dirs)
+    if ns == 1:
+        return [outs[0], *d1s[0].unbind(0), *d2s[0].unbind(0)]
+    if not module.use_scale_weights:
+        return ([_sum_scales(outs)] + [_sum_scales([j[d] for j in d1s]) for d in range(nd)]
+                + [_sum_scales([j[d] for j in d2s]) for d in range(nd)])
+    sw = module.scale_weighting
+    h = GF.linear(pos, sw[0].weight, sw[0].bias, act="relu", precision=0)
+    logits = GF.linear(h, sw[2].weight, sw[2].bias, precision=0)
+    value = GF.ScaleMixFn.apply(logits, *outs)
+    w = torch.softmax(logits, dim=1)                       # [n, scales]
+    active = (h > 0).to(h.dtype)                           # relu'(z): [n, 16]
+    dls = _logit_tangents(active, sw[0].weight, sw[2].weight, lambda x, wt: GF.linear(x, wt, None, precision=0))
+    p1, p2, _, _ = _mix_jet2_planes(w, dls, outs, d1s, d2s, dirs)
+    return [value, *p1, *p2]
 
 
 def _mix_scales_jvp(module, outs, jacs, pos):
@@ -529,21 +603,31 @@ class MAGNODecoder(nn.Module):
     HESSIAN_DIRS = ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0), (1.0, 1.0, 0.0), (0.0, 1.0, 1.0), (1.0, 0.0, 1.0))
     HESSIAN_PAIRS = ((0, 1), (1, 2), (0, 2))      # the axes of directions 3, 4, 5
 
-    def _jet2_stream(self, fn, rndata_flat, query_pos, lat, chunk_points):
-        """the argument rules and streaming conditions shared by ``sample_hessian`` and ``sample_laplacian`` -> (grid, chunk); raises
-        for every configuration they do not stream, naming the condition"""
+    def _jet2_stream(self, fn, rndata_flat, query_pos, lat, chunk_points, rows=False):
+        """the argument rules and streaming conditions shared by ``sample_hessian`` and ``sample_laplacian`` and, with ``rows``, by
+        ``sample_hessian_rows`` and ``sample_laplacian_rows`` on a 'radius' / 'bidirectional' decoder -> (grid, chunk); raises for
+        every configuration they do not stream, naming the condition"""
+        from ... import graph as device_graph
         from ... import ops
         if self.decoder_strategy == "reverse":
             raise ValueError(f"MAGNODecoder.{fn}: decoder strategy 'reverse' is the flip of the encoder's graph of the sample's own "
                              "points and is undefined for other query points")
         if chunk_points is not None and int(chunk_points) < 1:
             raise ValueError(f"chunk_points must be positive, got {chunk_points}")
-        no = lambda why: NotImplementedError(f"MAGNODecoder.{fn}: second derivatives stream on the regular k-neighbour lists only; {why}")
         k = int(self.k_neighbors)
-        if self.decoder_strategy != "knn":
-            raise no(f"decoder strategy {self.decoder_strategy!r} is not 'knn'")
-        if k not in ops.GNO_KNN_K:
-            raise no(f"k_neighbors = {k} is not in {ops.GNO_KNN_K}")
+        if rows:
+            no = lambda why: NotImplementedError(f"MAGNODecoder.{fn}: second derivatives on row lists stream for 'radius' and "
+                                                 f"'bidirectional' decoders; {why}")
+            if self.decoder_strategy not in ("radius", "bidirectional"):
+                raise no(f"decoder strategy {self.decoder_strategy!r} is neither")
+            if self.decoder_strategy == "bidirectional" and k > device_graph.QUERY_LIST_MAX_K:
+                raise no(f"k_neighbors = {k} is above {device_graph.QUERY_LIST_MAX_K}, the longest list graph.query_lists unites")
+        else:
+            no = lambda why: NotImplementedError(f"MAGNODecoder.{fn}: second derivatives stream on the regular k-neighbour lists only; {why}")
+            if self.decoder_strategy != "knn":
+                raise no(f"decoder strategy {self.decoder_strategy!r} is not 'knn'")
+            if k not in ops.GNO_KNN_K:
+                raise no(f"k_neighbors = {k} is not in {ops.GNO_KNN_K}")
         if getattr(self.gno, "use_attn", False):
             raise no("the attention-weighted transform (use_attn) is not supported")
         if self.use_geoembed:
@@ -637,6 +721,85 @@ class MAGNODecoder(nn.Module):
         for i in range(0, nq, chunk):
             _, d2 = self._jet2_chunk(rndata_flat, query_pos[i:i + chunk], latent_tokens_pos, grid, self.HESSIAN_DIRS[:3], pred[i:i + chunk])
             torch.add(d2[:, :, 0] + d2[:, :, 1], d2[:, :, 2], out=lap[i:i + chunk])
+        return pred, lap
+
+    def _jet2_rows_chunks(self, fn, rndata_flat, query_pos, lat, chunk_points, dirs, pred):
+        """the row-list route of ``sample_hessian_rows`` / ``sample_laplacian_rows``: yields (slice, d1, d2) per chunk of queries, d1 / d2
+        [n, out_channels, nd] the jets of the prediction along ``dirs``, the value written into ``pred``.  Per chunk and scale
+        ``graph.query_lists`` (led by as many padding edges as put the chunk's rows against the 32-edge tiles where the list of ALL
+        queries has them, as in ``sample_jacobian``), ``jet2_rows``, then ``_mix_scales_jet2`` and the projection's jets."""
+        from ... import graph as device_graph
+        grid, chunk = self._jet2_stream(fn, rndata_flat, query_pos, lat, chunk_points, rows=True)
+        strategy, k, nd = self.decoder_strategy, int(self.k_neighbors), len(dirs)
+        before = [0] * len(self.scales)           # edges of the earlier chunks, per scale
+        for i in range(0, int(query_pos.shape[0]), chunk):
+            q = query_pos[i:i + chunk]
+            outs, g1s, g2s = [], [], []
+            for si, scale in enumerate(self.scales):
+                lead = before[si] % 32
+                rows = device_graph.query_lists(strategy, q, grid, self.gno_radius * scale, k, lead=lead)
+                before[si] += rows.by_dst.num_edges - lead
+                o, g1, g2 = self.gno.jet2_rows(lat, q, rndata_flat, rows, dirs)
+                outs.append(o)
+                g1s.append(g1)
+                g2s.append(g2)
+            planes = _mix_scales_jet2(self, outs, g1s, g2s, q, dirs)
+            d1 = torch.empty(q.shape[0], self.out_channels, nd, dtype=pred.dtype, device=pred.device)
+            d2 = torch.empty_like(d1)
+            self.projection.jet2_rows(planes[0], planes[1:1 + nd], planes[1 + nd:1 + 2 * nd], out=(pred[i:i + chunk], d1, d2))
+            yield slice(i, i + chunk), d1, d2
+
+    @torch.no_grad()
+    def sample_hessian_rows(self, rndata_flat, query_pos, latent_tokens_pos, chunk_points: Optional[int] = None):
+        """``sample_hessian`` for 'radius' and 'bidirectional' decoders, on ROW lists: -> (pred [Nq, out_channels],
+        jac [Nq, out_channels, 3], hess [Nq, out_channels, 3, 3]), every query's list held fixed (valid almost everywhere: not across
+        the surfaces where a query's list changes, nor -- with softmax scale weights -- across the ReLU kinks of the weighting MLP, where
+        the second derivative of its piecewise linear logits is taken as 0).
+
+        Per chunk and scale ``graph.query_lists`` writes the by-query list and ``jet2_rows`` runs the jet kernel on its ragged rows
+        (two launches per 32-channel pass, the six directions ``HESSIAN_DIRS``); the scale mix carries the first AND second derivative
+        of its softmax weights, since the scales see different lists (``_mix_scales_jet2``); then the projection's jets and the
+        polarisation of ``sample_hessian``.  ``pred`` and ``jac`` are ``sample_jacobian(row_lists=True)``'s bit for bit; exact fp32 in
+        both precision modes; results independent of ``chunk_points`` (padding edges lead every chunk's list).  The lists are sized
+        by a host read: inside a stream capture the call raises GaotError before any launch.
+
+        Streams for 'radius', and for 'bidirectional' with k_neighbors <= ``graph.QUERY_LIST_MAX_K``, under ``sample``'s row-list
+        conditions plus a projection in the fused family (``sample_hessian``); on a 'knn' decoder the call IS ``sample_hessian``.
+        use_attn, a decoder GeoEmbed, neighbour sampling, tokens off the regular grid, 'bidirectional' with larger k and other
+        projections raise NotImplementedError naming the condition; 'reverse' and a non-positive ``chunk_points`` raise ValueError."""
+        if self.decoder_strategy == "knn":
+            return self.sample_hessian(rndata_flat, query_pos, latent_tokens_pos, chunk_points=chunk_points)
+        rndata_flat, query_pos = rndata_flat.detach(), query_pos.detach()
+        nq, oc = int(query_pos.shape[0]), self.out_channels
+        pred = torch.empty(nq, oc, dtype=rndata_flat.dtype, device=rndata_flat.device)
+        jac = torch.empty(nq, oc, 3, dtype=rndata_flat.dtype, device=rndata_flat.device)
+        hess = torch.empty(nq, oc, 3, 3, dtype=rndata_flat.dtype, device=rndata_flat.device)
+        for sl, d1, d2 in self._jet2_rows_chunks("sample_hessian_rows", rndata_flat, query_pos, latent_tokens_pos, chunk_points,
+                                                 self.HESSIAN_DIRS, pred):
+            jac[sl] = d1[:, :, :3]
+            hc = hess[sl]
+            for a in range(3):
+                hc[:, :, a, a] = d2[:, :, a]
+            for n, (a, b) in enumerate(self.HESSIAN_PAIRS):
+                off = 0.5 * (d2[:, :, 3 + n] - d2[:, :, a] - d2[:, :, b])
+                hc[:, :, a, b] = off
+                hc[:, :, b, a] = off
+        return pred, jac, hess
+
+    @torch.no_grad()
+    def sample_laplacian_rows(self, rndata_flat, query_pos, latent_tokens_pos, chunk_points: Optional[int] = None):
+        """``sample_hessian_rows``'s trace from the three axis directions: -> (pred [Nq, out_channels], lap [Nq, out_channels]), summed as
+        (d2_x + d2_y) + d2_z -- bit for bit hess[..., 0, 0] + hess[..., 1, 1] + hess[..., 2, 2] of ``sample_hessian_rows``.  Conditions
+        and errors as there; on a 'knn' decoder the call IS ``sample_laplacian``."""
+        if self.decoder_strategy == "knn":
+            return self.sample_laplacian(rndata_flat, query_pos, latent_tokens_pos, chunk_points=chunk_points)
+        rndata_flat, query_pos = rndata_flat.detach(), query_pos.detach()
+        nq, oc = int(query_pos.shape[0]), self.out_channels
+        pred = torch.empty(nq, oc, dtype=rndata_flat.dtype, device=rndata_flat.device)
+        lap = torch.empty(nq, oc, dtype=rndata_flat.dtype, device=rndata_flat.device)
+        for sl, _, d2 in self._jet2_rows_chunks("sample_laplacian_rows", rndata_flat, query_pos, latent_tokens_pos, chunk_points,
+                                                self.HESSIAN_DIRS[:3], pred):
+            torch.add(d2[:, :, 0] + d2[:, :, 1], d2[:, :, 2], out=lap[sl])
         return pred, lap
 
     def sample_jacobian(self, rndata_flat, query_pos, latent_tokens_pos, chunk_points: Optional[int] = None,

@@ -416,6 +416,32 @@ def gno_forward_jac(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Op
     return out, jac
 
 
+def gno_forward_jet2(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], src_table: Optional[Tensor],
+                     g: BipartiteGraph, dirs):
+    """``gno_forward_knn_jet2`` on RAGGED rows (gaot_gno_fwd_jet2): the value and the directional 2-jets of the fused transform on the
+    by-query list of any graph -> (out [n_query, 32], d1 [nd, n_query, 32], d2 [nd, n_query, 32]), every query's list held fixed, rows
+    of any length (an empty row gives exact zeros in all 1 + 2 nd planes).  Reads ``g.by_dst`` alone, as ``gno_forward_jac``.  Two
+    launches (the jet kernel and one fix-up over all planes), exact fp32 whatever the precision mode: ``out`` is ``gno_forward_jac``'s,
+    for an axis direction e_d plane d1 is its Jacobian plane d, and on a list of equal rows of k in ``GNO_KNN_K`` edges every plane is
+    ``gno_forward_knn_jet2``'s, bit for bit.  ``mode`` and the operands as in ``gno_forward_jac``, ``dirs`` as in
+    ``gno_forward_knn_jet2``.  Workspace: 256 (1 + 2 nd) bytes per 32-edge tile."""
+    lib = _lib.load()
+    md, m, keep, y_pos, x_pos, f_y, src_table = _gno_mode_args("gno_forward_jet2", mode, weights, biases, y_pos, x_pos, f_y, src_table)
+    if y_pos.shape[0] != g.num_src or x_pos.shape[0] != g.num_dst:
+        raise GaotError(f"y_pos / x_pos have {y_pos.shape[0]} / {x_pos.shape[0]} rows, the graph {g.num_src} / {g.num_dst}")
+    hd, nd = _host_dirs("gno_forward_jet2", dirs)
+    q, e = g.num_dst, g.by_dst.num_edges
+    out = torch.empty(q, m.channels, dtype=torch.float32, device=x_pos.device)
+    d1 = torch.empty(max(nd, 1), q, m.channels, dtype=torch.float32, device=x_pos.device)
+    d2 = torch.empty_like(d1)
+    ws = _ws(lib.gaot_gno_fwd_jet2_workspace_bytes(e, min(max(nd, 0), 6)), x_pos.device)
+    with _timed(f"gno_jet2_rows{f'_nl{md}' if md else ''}_nh{m.n_hidden}_d{nd}"):
+        check(lib.gaot_gno_fwd_jet2(C.byref(m), md, _ptr(y_pos), _ptr(x_pos), _ptr(f_y), _ptr(src_table), _ptr(g.by_dst.other),
+                                    _ptr(g.by_dst.key), _ptr(g.by_dst.rowptr), e, q, hd, nd, _ptr(out), _ptr(d1), _ptr(d2), _ptr(ws),
+                                    ws.numel(), _stream()), "gaot_gno_fwd_jet2")
+    return out, d1, d2
+
+
 def gno_nl_backward(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], src_table: Tensor, grad_out: Tensor,
                     g: BipartiteGraph, precision: Optional[int] = None, coords: bool = False):
     """-> (grad_f_y, grad_src_table, [grad_w...], [grad_b...]); with ``coords`` also (grad_y_pos, grad_x_pos) appended.

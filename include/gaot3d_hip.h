@@ -215,6 +215,25 @@ int gaot_gno_fwd_jac(const gaot_mlp_t* mlp /* host */, int mode, const float* y_
                      int64_t num_edges, int64_t num_queries, float* out /* [num_queries, channels] */,
                      float* jac /* [3, num_queries, channels] */, void* workspace, size_t workspace_bytes, gaot_stream_t stream);
 
+/* gaot_gno_fwd_knn_jet2's directional 2-jets on RAGGED rows (csrc/gno_jet2.hip): the value, D_v and D_v^2 planes of the by-query list
+ * of any graph, as gaot_gno_fwd_jac gives the value and the Jacobian -- the lists, the padding edges, the row reduction (every one
+ * of the 1 + 2 nd planes through its own two partial slots per tile) and the empty rows (exact zeros in every plane) are that entry
+ * point's, the per-edge arithmetic and the directions (`dirs`: HOST pointer, nd = 1..6, passed to the kernel by value) are
+ * gaot_gno_fwd_knn_jet2's.  Two launches: the jet kernel and one fix-up over all planes (num_edges == 0: the fix-up alone;
+ * num_queries == 0: none).  `out` is gaot_gno_fwd_jac's (hence gaot_gno_fwd's at precision 0), for an axis direction e_d plane d1 is
+ * plane d of gaot_gno_fwd_jac, and on a list whose rows all have k in {1, 2, 4, 8, 16, 32} edges every plane is gaot_gno_fwd_knn_jet2's,
+ * bit for bit; a direction's planes do not depend on the other directions or their order; a zero direction gives zero planes.  No
+ * atomics, exact fp32 in both precision modes.  workspace: gaot_gno_fwd_jet2_workspace_bytes(num_edges, nd) =
+ * ceil(num_edges / 32) * (1 + 2 nd) * 256 bytes (3.25 KiB per tile at six directions, about 104 bytes per edge; may be null when
+ * that is 0).  Argument errors before any launch (GAOT_ERR_ARG): those of gaot_gno_fwd_jac, nd outside 1..6, null dirs, a device
+ * pointer as dirs, a workspace that is too small. */
+size_t gaot_gno_fwd_jet2_workspace_bytes(int64_t num_edges, int nd);
+int gaot_gno_fwd_jet2(const gaot_mlp_t* mlp /* host */, int mode, const float* y_pos, const float* x_pos, const float* f_y,
+                      const float* src_table, const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr_dst,
+                      int64_t num_edges, int64_t num_queries, const float* dirs /* HOST, [nd][3] */, int nd,
+                      float* out /* [num_queries, channels] */, float* d1 /* [nd, num_queries, channels] */,
+                      float* d2 /* [nd, num_queries, channels] */, void* workspace, size_t workspace_bytes, gaot_stream_t stream);
+
 /* Dot-product attention scores of the attention-weighted transform (reference integral_transform.py:128-137, use_attn with
  * attention_type "dot_product") as a bilinear form of the homogeneous endpoint coordinates (csrc/gno_attn.hip):
  *   scores[e] = scale * [x_pos[dst[e]], 1]^T M [y_pos[src[e]], 1]        x_pos / y_pos: [*, 3] rows, m: DEVICE [4][4] fp32

@@ -646,13 +646,23 @@ elif what == "decoder_hessian":
     # is the median with max - min, the peak is the rise of allocated memory over the inputs.  Then the split of each -- neighbour
     # search, GNO jet kernel, scale mix + projection, every stage timed over all chunks on its own.  Kept in
     # profiles/decoder_hessian_microbench.txt.
+    # `--strategy radius|bidirectional`: the reference YAML's decoder instead (config/examples/drivaernet/pressure.yaml: r = 0.033,
+    # k_neighbors at its default 1, neighbor_strategy 'bidirectional'; 'radius' = the same decoder on the radius graph alone) on ROW
+    # lists: sample_jacobian(row_lists=True) (the yardstick), sample_laplacian_rows and sample_hessian_rows, alternated in the same
+    # way; the split is graph.query_lists, the GNO kernel + its fix-up, and scale mix + projection.  Kept in
+    # profiles/decoder_hessian_rows_microbench.txt.
     from gaot_3d_amd import graph as device_graph
     from gaot_3d_amd.data import latent_grid
-    from gaot_3d_amd.model.layers.magno import MAGNOConfig, MAGNODecoder
+    from gaot_3d_amd.model.layers.magno import MAGNOConfig, MAGNODecoder, _mix_scales_jet2, _mix_scales_jvp
     gaot_3d_amd.set_precision("fp32")
     latent = (64, 64, 32)
-    cfg = MAGNOConfig(gno_coord_dim=3, lifting_channels=32, mlp_type="linear", use_geoembed=[True, False], neighbor_strategy="knn",
-                      k_neighbors=8, out_gno_channel_mlp_hidden_layers=[64, 64], precompute_edges=False)
+    strategy = sys.argv[sys.argv.index("--strategy") + 1] if "--strategy" in sys.argv else "knn"
+    if strategy not in ("knn", "radius", "bidirectional"):
+        sys.exit(f"--strategy must be radius or bidirectional, got {strategy}")
+    rows = strategy != "knn"
+    cfg = MAGNOConfig(gno_coord_dim=3, lifting_channels=32, mlp_type="linear", use_geoembed=[True, False],
+                      neighbor_strategy=["knn", strategy] if rows else "knn", k_neighbors=1 if rows else 8, gno_radius=0.033,
+                      out_gno_channel_mlp_hidden_layers=[64, 64], precompute_edges=False)
     dec = MAGNODecoder(in_channels=32, out_channels=1, gno_config=cfg).to(dev).eval()
     dec.latent_dims = latent
     tokens = latent_grid(latent).to(dev)
@@ -677,9 +687,9 @@ elif what == "decoder_hessian":
 
     for nq in (500000, 8000000):
         q = torch.rand(nq, 3, device=dev) * 2 - 1
-        routes = {"sample_jacobian": lambda: dec.sample_jacobian(rn, q, tokens, chunk_points=chunk),
-                  "sample_laplacian": lambda: dec.sample_laplacian(rn, q, tokens, chunk_points=chunk),
-                  "sample_hessian": lambda: dec.sample_hessian(rn, q, tokens, chunk_points=chunk)}
+        routes = {"sample_jacobian": lambda: dec.sample_jacobian(rn, q, tokens, chunk_points=chunk, row_lists=rows),
+                  "sample_laplacian": lambda: (dec.sample_laplacian_rows if rows else dec.sample_laplacian)(rn, q, tokens, chunk_points=chunk),
+                  "sample_hessian": lambda: (dec.sample_hessian_rows if rows else dec.sample_hessian)(rn, q, tokens, chunk_points=chunk)}
         warm = {n: timed(f)[2] for n, f in routes.items()}            # warm-up, and the three agree where they must
         same = (torch.equal(warm["sample_hessian"][0], warm["sample_jacobian"][0]) and torch.equal(warm["sample_hessian"][1], warm["sample_jacobian"][1])
                 and torch.equal(warm["sample_laplacian"][0], warm["sample_jacobian"][0]))
@@ -693,12 +703,50 @@ elif what == "decoder_hessian":
         mj, lo_j, hi_j = median(ts["sample_jacobian"])
         for n in routes:
             m, lo, hi = median(ts[n])
-            print(f"Nq={nq} fp32: {n:16s} (chunk {step}) {m:9.3f} ms (max - min {hi - lo:.3f} ms = {100 * (hi - lo) / m:.1f} %), peak "
+            print(f"Nq={nq} fp32{' ' + strategy if rows else ''}: {n + ('_rows' if rows and n != 'sample_jacobian' else ''):21s} (chunk {step}) {m:9.3f} ms (max - min {hi - lo:.3f} ms = {100 * (hi - lo) / m:.1f} %), peak "
                   f"{pk[n] / 2**20:9.1f} MiB  = {m / mj:.2f} x sample_jacobian in time, {pk[n] / max(pk['sample_jacobian'], 1):.2f} x in peak memory")
         print(f"Nq={nq} fp32: pred / jac of sample_hessian and pred of sample_laplacian == sample_jacobian's bit for bit: {same}; "
               f"lap == ordered trace of hess bit for bit: {trace}", flush=True)
         # the split: every stage over all chunks on its own (the stages' inputs kept from the stage before)
         grid = dec._stream_grid(rn, q, tokens)
+        if rows:
+            with torch.no_grad():
+                chunks = [q[i:i + step] for i in range(0, nq, step)]
+                t_nbr, t_gno, t_prj = [], {"jac": [], "lap": [], "hess": []}, {"jac": [], "lap": [], "hess": []}
+                for _ in range(reps + 1):                                  # the first round warms up and is dropped
+                    t, _p, lists = timed(lambda: [device_graph.query_lists(strategy, c, grid, dec.gno_radius, 1) for c in chunks])
+                    t_nbr.append(t)
+                    edges = sum(g.by_dst.num_edges for g in lists)
+                    t, _p, outs = timed(lambda: [dec.gno.jacobian_rows(tokens, c, rn, g) for c, g in zip(chunks, lists)]); t_gno["jac"].append(t)
+                    def mix_jvp(c, o, j):
+                        p = _mix_scales_jvp(dec, [o], [j], c)
+                        return dec.projection.jvp_rows(p[0], p[1:])
+                    t, _p, prj = timed(lambda: [mix_jvp(c, o, j) for c, (o, j) in zip(chunks, outs)]); t_prj["jac"].append(t)
+                    del outs, prj
+                    for name, nd in (("lap", 3), ("hess", 6)):
+                        t, _p, outs = timed(lambda: [dec.gno.jet2_rows(tokens, c, rn, g, DIRS[:nd]) for c, g in zip(chunks, lists)])
+                        t_gno[name].append(t)
+                        def mix_jet(c, o, a, b, nd=nd):
+                            p = _mix_scales_jet2(dec, [o], [a], [b], c, DIRS[:nd])
+                            return dec.projection.jet2_rows(p[0], p[1:1 + nd], p[1 + nd:])
+                        t, _p, prj = timed(lambda: [mix_jet(c, *oab) for c, oab in zip(chunks, outs)])
+                        t_prj[name].append(t)
+                        del outs, prj
+                    del lists
+                mn = median(t_nbr[1:])[0]
+                gj = median(t_gno["jac"][1:])
+                for name, label, chains in (("jac", "sample_jacobian(row_lists=True)", 4), ("lap", "sample_laplacian_rows", 7),
+                                            ("hess", "sample_hessian_rows", 13)):
+                    mg, lo_g, hi_g = median(t_gno[name][1:])
+                    mp = median(t_prj[name][1:])[0]
+                    tot = mn + mg + mp
+                    print(f"Nq={nq} fp32 {strategy}: split of {label}: query_lists {mn:.3f} ms ({100 * mn / tot:.0f} %), GNO kernel + fix-up "
+                          f"{mg:.3f} ms ({100 * mg / tot:.0f} %; max - min {hi_g - lo_g:.3f}; {edges} edges), mix + projection {mp:.3f} ms "
+                          f"({100 * mp / tot:.0f} %); stages sum to {tot:.3f} ms; GNO kernel = {mg / gj[0]:.2f} x the Jacobian kernel's "
+                          f"({chains} plane-chains against 4 by count: {chains / 4:.2f} x; yardstick's max - min {gj[2] - gj[1]:.3f} ms)",
+                          flush=True)
+            del q, chunks
+            continue
         with torch.no_grad():
             chunks = [q[i:i + step] for i in range(0, nq, step)]
             t_nbr, t_gno, t_prj = [], {"jac": [], "lap": [], "hess": []}, {"jac": [], "lap": [], "hess": []}
