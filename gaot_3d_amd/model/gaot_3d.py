@@ -142,10 +142,7 @@ class GAOT3D(nn.Module):
         """Predictions [Nq, output_size] of ONE encoded sample (``latent`` [D*H*W, lifting_channels] from ``latent``) at any query
         coordinates, forward only (no autograd graph): ``MAGNODecoder.sample``.  ``tokens_pos``: the tokens ``latent`` was computed
         with (default: the model's grid); ``chunk_points``: queries per pass (None: one pass of at most 2^20 points)."""
-        if latent.dim() != 2 or latent.shape[0] != self.num_latent_tokens:
-            raise ValueError(f"sample: latent {tuple(latent.shape)} is not ONE sample's [{self.num_latent_tokens}, "
-                             f"{self.node_latent_size}] token rows (sample the graphs of a batch one by one)")
-        lat, _ = self._tokens(1, latent.device, tokens_pos, None)
+        lat = self._one_sample("sample", latent, tokens_pos)
         return self.decoder.sample(latent, query_pos.to(latent.device), lat, chunk_points=chunk_points)
 
     def sample_jacobian(self, latent: torch.Tensor, query_pos: torch.Tensor, tokens_pos: Optional[torch.Tensor] = None,
@@ -158,10 +155,7 @@ class GAOT3D(nn.Module):
         is exact fp32 in both precision modes, so in bf16 mode ``pred`` differs from ``sample``'s by bf16 rounding.
         ``row_lists=True`` streams 'radius' / 'bidirectional' decoders in the same way on row lists (``graph.query_lists`` and the
         tangent kernel on ragged rows) instead of the autograd route; it changes nothing for other decoders."""
-        if latent.dim() != 2 or latent.shape[0] != self.num_latent_tokens:
-            raise ValueError(f"sample_jacobian: latent {tuple(latent.shape)} is not ONE sample's [{self.num_latent_tokens}, "
-                             f"{self.node_latent_size}] token rows (sample the graphs of a batch one by one)")
-        lat, _ = self._tokens(1, latent.device, tokens_pos, None)
+        lat = self._one_sample("sample_jacobian", latent, tokens_pos)
         return self.decoder.sample_jacobian(latent, query_pos.to(latent.device), lat, chunk_points=chunk_points,
                                             row_lists=row_lists)
 

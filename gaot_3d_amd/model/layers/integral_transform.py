@@ -154,19 +154,11 @@ class IntegralTransform(nn.Module):
     def forward_knn(self, y_pos, x_pos, nbr, k: int, f_y: Optional[torch.Tensor] = None):
         """The transform's forward on a REGULAR neighbour list, without an edge list: ``nbr`` int32 [N_x * k] with nbr[q*k + j] = the
         j-th source of query q (``graph.knn_to_grid`` / ``ops.knn_grid`` output as it stands), k in ``ops.GNO_KNN_K``.  The operands
-        are prepared exactly as in ``_forward_fused`` (zero padding of coordinates / hidden widths / channel blocks, t = W_0f f_y of
-        the nonlinear types) and every 32-channel pass is one ``ops.gno_forward_knn`` launch: bit-identical to ``forward`` on the graph
-        of the same lists.  Forward only (nothing is recorded for autograd); runs exactly when ``_fused_plan`` is not None and raises
-        otherwise -- there is no general path on these lists."""
-        if self.transform_type not in ("linear", "nonlinear", "nonlinear_kernelonly"):
-            raise ValueError(f"Invalid transform_type: {self.transform_type}")
-        fcs = list(self.channel_mlp.fcs)
-        with torch.no_grad():
-            plan = self._fused_plan(fcs, f_y, y_pos, x_pos)
-            if plan is None or int(k) not in ops.GNO_KNN_K:
-                raise NotImplementedError("IntegralTransform.forward_knn: only the transforms the fused kernels evaluate (_fused_plan) "
-                                          f"on lists of k in {ops.GNO_KNN_K} neighbours per query; use forward() with an edge_index")
-            return self._forward_fused(fcs, y_pos, x_pos, f_y, None, *plan, knn=(nbr, int(k)))
+        are prepared exactly as in ``forward`` (``_fused_passes``: zero padding of coordinates / hidden widths / channel blocks,
+        t = W_0f f_y of the nonlinear types) and every 32-channel pass is one ``ops.gno_forward_knn`` launch: bit-identical to
+        ``forward`` on the graph of the same lists.  Forward only (nothing is recorded for autograd); runs exactly when ``_fused_plan``
+        is not None and raises otherwise -- there is no general path on these lists."""
+        return self._on_lists("forward_knn", y_pos, x_pos, f_y, (nbr, k), 0)[0]
 
     def jacobian_knn(self, y_pos, x_pos, nbr, k: int, f_y: Optional[torch.Tensor] = None):
         """``forward_knn`` with the spatial derivative of its result: -> (out [N_x, C], jac [3, N_x, C]) with
@@ -177,15 +169,7 @@ class IntegralTransform(nn.Module):
         is ``forward_knn``'s fp32-mode result bit for bit.  The operands are prepared exactly as in ``forward_knn``; the planes of the
         directions a coordinate dimension of 1 / 2 is padded with are exact zeros.  Runs exactly when ``_fused_plan`` is not None and
         k is in ``ops.GNO_KNN_K`` and raises NotImplementedError otherwise.  Nothing is recorded for autograd."""
-        if self.transform_type not in ("linear", "nonlinear", "nonlinear_kernelonly"):
-            raise ValueError(f"Invalid transform_type: {self.transform_type}")
-        fcs = list(self.channel_mlp.fcs)
-        with torch.no_grad():
-            plan = self._fused_plan(fcs, f_y, y_pos, x_pos)
-            if plan is None or int(k) not in ops.GNO_KNN_K:
-                raise NotImplementedError("IntegralTransform.jacobian_knn: only the transforms the fused kernels evaluate (_fused_plan) "
-                                          f"on lists of k in {ops.GNO_KNN_K} neighbours per query")
-            return self._forward_fused(fcs, y_pos, x_pos, f_y, None, *plan, knn=(nbr, int(k)), jac=True)
+        return self._on_lists("jacobian_knn", y_pos, x_pos, f_y, (nbr, k), 1)
 
     def jet2_knn(self, y_pos, x_pos, nbr, k: int, f_y: Optional[torch.Tensor] = None, dirs=((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0))):
         """``forward_knn`` with a directional 2-jet of its result: -> (out [N_x, C], d1 [nd, N_x, C], d2 [nd, N_x, C]), the first and
@@ -195,15 +179,7 @@ class IntegralTransform(nn.Module):
         ``forward_knn``'s fp32-mode result and, for an axis direction, d1 is ``jacobian_knn``'s plane, bit for bit.  The operands are
         prepared exactly as in ``jacobian_knn``.  Runs exactly when ``_fused_plan`` is not None and k is in ``ops.GNO_KNN_K`` and raises
         NotImplementedError otherwise.  Nothing is recorded for autograd."""
-        if self.transform_type not in ("linear", "nonlinear", "nonlinear_kernelonly"):
-            raise ValueError(f"Invalid transform_type: {self.transform_type}")
-        fcs = list(self.channel_mlp.fcs)
-        with torch.no_grad():
-            plan = self._fused_plan(fcs, f_y, y_pos, x_pos)
-            if plan is None or int(k) not in ops.GNO_KNN_K:
-                raise NotImplementedError("IntegralTransform.jet2_knn: only the transforms the fused kernels evaluate (_fused_plan) "
-                                          f"on lists of k in {ops.GNO_KNN_K} neighbours per query")
-            return self._forward_fused(fcs, y_pos, x_pos, f_y, None, *plan, knn=(nbr, int(k)), jet2=dirs)
+        return self._on_lists("jet2_knn", y_pos, x_pos, f_y, (nbr, k), 2, dirs)
 
     def jacobian_rows(self, y_pos, x_pos, f_y: Optional[torch.Tensor], graph):
         """``jacobian_knn`` on RAGGED rows: ``graph`` holds the by-query list of any graph (``graph.by_dst``; ``by_src`` may be None, as
@@ -212,14 +188,7 @@ class IntegralTransform(nn.Module):
         precision modes: ``out`` is ``forward``'s fp32-mode result on the same graph bit for bit.  The operands are prepared exactly
         as in ``forward``; the planes of the directions a coordinate dimension of 1 / 2 is padded with are exact zeros.  Runs exactly
         when ``_fused_plan`` is not None and raises NotImplementedError otherwise.  Nothing is recorded for autograd."""
-        if self.transform_type not in ("linear", "nonlinear", "nonlinear_kernelonly"):
-            raise ValueError(f"Invalid transform_type: {self.transform_type}")
-        fcs = list(self.channel_mlp.fcs)
-        with torch.no_grad():
-            plan = self._fused_plan(fcs, f_y, y_pos, x_pos)
-            if plan is None:
-                raise NotImplementedError("IntegralTransform.jacobian_rows: only the transforms the fused kernels evaluate (_fused_plan)")
-            return self._forward_fused(fcs, y_pos, x_pos, f_y, graph, *plan, jac=True)
+        return self._on_lists("jacobian_rows", y_pos, x_pos, f_y, graph, 1)
 
     def jet2_rows(self, y_pos, x_pos, f_y: Optional[torch.Tensor], graph, dirs):
         """``jet2_knn`` on RAGGED rows: ``graph`` holds the by-query list of any graph (``graph.by_dst``; ``by_src`` may be None, as
@@ -228,14 +197,37 @@ class IntegralTransform(nn.Module):
         jet kernel and its fix-up) per 32-channel pass, exact fp32 in both precision modes: ``out`` is ``jacobian_rows``'s and, for an
         axis direction, d1 is its Jacobian plane, bit for bit.  The operands are prepared exactly as in ``jacobian_rows``.  Runs
         exactly when ``_fused_plan`` is not None and raises NotImplementedError otherwise.  Nothing is recorded for autograd."""
+        return self._on_lists("jet2_rows", y_pos, x_pos, f_y, graph, 2, dirs)
+
+    def _on_lists(self, fn, y_pos, x_pos, f_y, lists, order: int, dirs=None):
+        """The five list methods: the forward-mode routes on the regular list ``lists`` = (nbr, k) or on the by-query list of the graph
+        ``lists``, at ``order`` 0 (value), 1 (and Jacobian) or 2 (and 2-jets along ``dirs``) -> the tuple of planes, channels last:
+        (out [N_x, c],), (out, jac [3, N_x, c]) or (out, d1 [nd, N_x, c], d2 [nd, N_x, c]).  Every pass of ``_fused_passes`` is one call
+        of the route's ``ops.gno_forward_*`` function; a pass is cut to its channels and the passes are concatenated.  Nothing is
+        recorded for autograd; ``fn`` names the public method in the refusal."""
         if self.transform_type not in ("linear", "nonlinear", "nonlinear_kernelonly"):
             raise ValueError(f"Invalid transform_type: {self.transform_type}")
         fcs = list(self.channel_mlp.fcs)
+        knn = isinstance(lists, tuple)
         with torch.no_grad():
             plan = self._fused_plan(fcs, f_y, y_pos, x_pos)
-            if plan is None:
-                raise NotImplementedError("IntegralTransform.jet2_rows: only the transforms the fused kernels evaluate (_fused_plan)")
-            return self._forward_fused(fcs, y_pos, x_pos, f_y, graph, *plan, jet2=dirs)
+            if plan is None or (knn and int(lists[1]) not in ops.GNO_KNN_K):
+                raise NotImplementedError(f"IntegralTransform.{fn}: only the transforms the fused kernels evaluate (_fused_plan)"
+                                          + (f" on lists of k in {ops.GNO_KNN_K} neighbours per query" if knn else "")
+                                          + ("; use forward() with an edge_index" if order == 0 else ""))
+            run = {(True, 0): ops.gno_forward_knn, (True, 1): ops.gno_forward_knn_jac, (True, 2): ops.gno_forward_knn_jet2,
+                   (False, 1): ops.gno_forward_jac, (False, 2): ops.gno_forward_jet2}[knn, order]
+            tail = ((lists[0], int(lists[1])) if knn else (lists,)) + ((dirs,) if order == 2 else ())
+            y3, x3, t, (w0, b0, *mid), blocks = self._fused_passes(fcs, y_pos, x_pos, f_y, *plan)
+            outs = []
+            for wb, bb, fb, n in blocks:
+                o = run(self.transform_type, [w0.contiguous(), *mid[0::2], wb.contiguous()], [b0, *mid[1::2], bb.contiguous()], y3, x3,
+                        None if fb is None else fb.contiguous(), t, *tail)
+                o = o if order else (o,)
+                outs.append(o if n == 32 else tuple(p[..., :n] for p in o))
+            if len(outs) > 1:
+                return tuple(torch.cat(ps, dim=-1) for ps in zip(*outs))
+            return tuple(p.contiguous() for p in outs[0]) if order else outs[0]
 
     @staticmethod
     def _pad3(pos):
@@ -247,7 +239,7 @@ class IntegralTransform(nn.Module):
         channels per pass) can evaluate this transform EXACTLY, possibly through zero padding; None -> general path.
         Kernel MLP coord-pair -> 64 (x 1..4; with gradients in fp32 mode: 1..3) -> C with GELU, mean reduction; 'linear' transform, or
         'nonlinear' / 'nonlinear_kernelonly' with the kernel MLP's input widened by f_y's channels (their term of the first layer is
-        the per-node product t = W_0f f_y, see ``_forward_fused``; 'nonlinear' needs as many input as output channels):
+        the per-node product t = W_0f f_y, see ``_fused_passes``; 'nonlinear' needs as many input as output channels):
           * coord_dim 1 / 2 (the reference's default is 2, magno.py:28): coordinates padded with zeros to 3-D and the first
             layer's weight given zero columns for them -- the products that are added are exactly 0;
           * C != 32 (the reference's default is 16, magno.py:25): the last layer / f_y / the output are cut into blocks of 32
@@ -307,32 +299,20 @@ class IntegralTransform(nn.Module):
         return (not self.use_attn and self.transform_type == "linear" and f_y is not None and dims[0] == (64, 6)
                 and dims[-1] == (32, 64) and f_y.shape[1] == 32)
 
-    def _forward_fused(self, fcs, y_pos, x_pos, f_y, graph, cd: int, c: int, edge_w=None, knn=None, jac=False, jet2=None):
-        """``edge_w`` [E] (dst-sorted order): the weighted transform of use_attn -- every pass runs ``GnoWFn`` with the same weights and
-        autograd adds the passes' gradients with respect to them (padded channels carry zero grad_out and zero f: exact zeros).
-        ``knn`` = (nbr, k) (``forward_knn``; ``graph`` is None, no autograd): the passes run ``ops.gno_forward_knn`` on the regular
-        list instead of the autograd Functions; with ``jac`` (``jacobian_knn``) they run ``ops.gno_forward_knn_jac`` and the result is
-        (out [N_x, c], jac [3, N_x, c]).  ``jac`` with a ``graph`` (``jacobian_rows``; no autograd either): the passes run
-        ``ops.gno_forward_jac`` on the graph's by-query list, with the same result shapes.  ``jet2`` = directions (``jet2_knn``; with
-        ``knn``): the passes run ``ops.gno_forward_knn_jet2`` and the result is (out [N_x, c], d1 [nd, N_x, c], d2 [nd, N_x, c]);
-        ``jet2`` with a ``graph`` (``jet2_rows``): ``ops.gno_forward_jet2`` on the graph's by-query list, the same result shapes."""
+    def _fused_passes(self, fcs, y_pos, x_pos, f_y, cd: int, c: int, straight: bool = True):
+        """The operands of the fused kernels for a transform ``_fused_plan`` accepts -> (y3, x3, t, [w0, b0, *mid], blocks): the 3-D
+        coordinates, the source table t = f_y W_0f^T of the nonlinear types (None for 'linear'), the parameters of every layer but the
+        last as the autograd Functions take them, and per 32-channel pass one (wb, bb, fb, n): the last layer's block, f_y's block
+        (None for 'nonlinear_kernelonly') and the channels that count -- a last block with n < 32 is zero-padded.  ``blocks`` is cut
+        pass by pass as it is iterated, so that autograd records every pass's slices right before its Function.  The shipped shape
+        (``straight``: 'linear', 3-D, C = 32, hidden widths 64) is the degenerate case: one pass of the operands as they stand."""
         w2 = lambda fc: fc.weight[:, :, 0] if fc.weight.dim() == 3 else fc.weight    # Conv1d(k=1) storage of mlp_type='channel'
-        pad_hidden = any(fc.weight.shape[0] != 64 for fc in fcs[:-1])
         tt = self.transform_type
-        if tt == "linear" and cd == 3 and c == 32 and not pad_hidden and edge_w is None:   # the shipped shape: straight through
-            if jet2 is not None and knn is None:
-                return ops.gno_forward_jet2(0, [w2(fc) for fc in fcs], [fc.bias for fc in fcs], y_pos, x_pos, f_y, None, graph, jet2)
-            if jet2 is not None:
-                return ops.gno_forward_knn_jet2(0, [w2(fc) for fc in fcs], [fc.bias for fc in fcs], y_pos, x_pos, f_y, None, *knn, jet2)
-            if knn is not None:
-                fwd = ops.gno_forward_knn_jac if jac else ops.gno_forward_knn
-                return fwd(0, [w2(fc) for fc in fcs], [fc.bias for fc in fcs], y_pos, x_pos, f_y, None, *knn)
-            if jac:
-                return ops.gno_forward_jac(0, [w2(fc) for fc in fcs], [fc.bias for fc in fcs], y_pos, x_pos, f_y, None, graph)
-            params = []
-            for fc in fcs:
-                params += [fc.weight, fc.bias]
-            return GF.GnoFn.apply(f_y, y_pos, x_pos, graph, *params)
+        if straight and self._straight_through(fcs, cd, c):
+            head = []
+            for fc in fcs[:-1]:
+                head += [w2(fc), fc.bias]
+            return y_pos, x_pos, None, head, [(w2(fcs[-1]), fcs[-1].bias, f_y, 32)]
         y3, x3, w0 = y_pos, x_pos, w2(fcs[0])
         t = None
         if tt != "linear":
@@ -354,35 +334,42 @@ class IntegralTransform(nn.Module):
         pad2 = lambda w, rows, cols: w if (w.shape[0] == rows and w.shape[1] == cols) else torch.nn.functional.pad(
             w, (0, cols - w.shape[1], 0, rows - w.shape[0]))
         pad1 = lambda v, n: v if v.shape[0] == n else torch.nn.functional.pad(v, (0, n - v.shape[0]))
-        w0, b0 = pad2(w0, 64, 6), pad1(fcs[0].bias, 64)
-        mid = []
+        head = [pad2(w0, 64, 6), pad1(fcs[0].bias, 64)]
         for fc in fcs[1:-1]:
-            mid += [pad2(w2(fc), 64, 64), pad1(fc.bias, 64)]
+            head += [pad2(w2(fc), 64, 64), pad1(fc.bias, 64)]
         wl, bl = w2(fcs[-1]), fcs[-1].bias
         wl = pad2(wl, wl.shape[0], 64)
+
+        def blocks():
+            for c0 in range(0, c, 32):
+                n = min(32, c - c0)
+                wb, bb = wl[c0:c0 + n], bl[c0:c0 + n]
+                fb = None if tt == "nonlinear_kernelonly" else f_y[:, c0:c0 + n]
+                if n < 32:
+                    wb = torch.nn.functional.pad(wb, (0, 0, 0, 32 - n))
+                    bb = torch.nn.functional.pad(bb, (0, 32 - n))
+                    fb = None if fb is None else torch.nn.functional.pad(fb, (0, 32 - n))
+                yield wb, bb, fb, n
+        return y3, x3, t, head, blocks()
+
+    def _straight_through(self, fcs, cd: int, c: int) -> bool:
+        """the shipped shape: the kernels take the operands as they stand, in one pass"""
+        return self.transform_type == "linear" and cd == 3 and c == 32 and all(fc.weight.shape[0] == 64 for fc in fcs[:-1])
+
+    def _forward_fused(self, fcs, y_pos, x_pos, f_y, graph, cd: int, c: int, edge_w=None):
+        """``forward`` on the fused kernels, through the autograd Functions: one per pass of ``_fused_passes``.  ``edge_w`` [E]
+        (dst-sorted order): the weighted transform of use_attn -- every pass runs ``GnoWFn`` with the same weights and autograd adds
+        the passes' gradients with respect to them (padded channels carry zero grad_out and zero f: exact zeros)."""
+        tt = self.transform_type
+        if edge_w is None and self._straight_through(fcs, cd, c):   # the shipped shape: the parameters themselves
+            params = []
+            for fc in fcs:
+                params += [fc.weight, fc.bias]
+            return GF.GnoFn.apply(f_y, y_pos, x_pos, graph, *params)
+        y3, x3, t, (w0, b0, *mid), blocks = self._fused_passes(fcs, y_pos, x_pos, f_y, cd, c, straight=False)
         outs = []
-        for c0 in range(0, c, 32):
-            n = min(32, c - c0)
-            wb, bb = wl[c0:c0 + n], bl[c0:c0 + n]
-            fb = None if tt == "nonlinear_kernelonly" else f_y[:, c0:c0 + n]
-            if n < 32:
-                wb = torch.nn.functional.pad(wb, (0, 0, 0, 32 - n))
-                bb = torch.nn.functional.pad(bb, (0, 32 - n))
-                fb = None if fb is None else torch.nn.functional.pad(fb, (0, 32 - n))
-            if jet2 is not None:
-                fwd = ops.gno_forward_jet2 if knn is None else ops.gno_forward_knn_jet2
-                o = fwd(tt, [w0.contiguous(), *mid[0::2], wb.contiguous()], [b0, *mid[1::2], bb.contiguous()], y3, x3,
-                        None if fb is None else fb.contiguous(), t, *(knn if knn is not None else (graph,)), jet2)
-                outs.append((o[0][:, :n], o[1][:, :, :n], o[2][:, :, :n]) if n < 32 else o)
-                continue
-            elif knn is not None or jac:
-                fwd = ops.gno_forward_jac if knn is None else ops.gno_forward_knn_jac if jac else ops.gno_forward_knn
-                o = fwd(tt, [w0.contiguous(), *mid[0::2], wb.contiguous()], [b0, *mid[1::2], bb.contiguous()], y3, x3,
-                        None if fb is None else fb.contiguous(), t, *(knn if knn is not None else (graph,)))
-                if jac:
-                    outs.append((o[0][:, :n], o[1][:, :, :n]) if n < 32 else o)
-                    continue
-            elif edge_w is not None:
+        for wb, bb, fb, n in blocks:
+            if edge_w is not None:
                 o = GF.GnoWFn.apply(tt, None if fb is None else fb.contiguous(), t, edge_w, y3, x3, graph, w0.contiguous(), b0, *mid,
                                     wb.contiguous(), bb.contiguous())
             elif tt == "linear":
@@ -391,15 +378,6 @@ class IntegralTransform(nn.Module):
                 o = GF.GnoNlFn.apply(tt, None if fb is None else fb.contiguous(), t, y3, x3, graph, w0.contiguous(), b0, *mid,
                                      wb.contiguous(), bb.contiguous())
             outs.append(o[:, :n] if n < 32 else o)
-        if jet2 is not None:
-            if len(outs) == 1:
-                return tuple(o.contiguous() for o in outs[0])
-            return (torch.cat([o[0] for o in outs], dim=1), torch.cat([o[1] for o in outs], dim=2),
-                    torch.cat([o[2] for o in outs], dim=2))
-        if jac:
-            if len(outs) == 1:
-                return outs[0][0].contiguous(), outs[0][1].contiguous()
-            return torch.cat([o[0] for o in outs], dim=1), torch.cat([o[1] for o in outs], dim=2)
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
 
     def _forward_general(self, fcs, y_pos, x_pos, f_y, g):

@@ -180,16 +180,20 @@ def _make_scale_weighting(coord_dim, num_scales):
     return nn.Sequential(nn.Linear(coord_dim, 16), nn.ReLU(), nn.Linear(16, num_scales))
 
 
+def _scale_logits(module, pos):
+    """the logits of the scale weights, l = W_2 relu(W_1 pos + b_1) + b_2 -> (l [n, scales], the hidden layer relu(..) [n, 16])"""
+    sw = module.scale_weighting
+    h = GF.linear(pos, sw[0].weight, sw[0].bias, act="relu", precision=0)
+    return GF.linear(h, sw[2].weight, sw[2].bias, precision=0), h
+
+
 def _mix_scales(module, outs, pos):
     """sum over scales, or softmax-weighted by an MLP of the query coordinates (reference magno.py:586-596)"""
     if len(outs) == 1:
         return outs[0]
     if not module.use_scale_weights:
         return _sum_scales(outs)
-    sw = module.scale_weighting
-    h = GF.linear(pos, sw[0].weight, sw[0].bias, act="relu", precision=0)
-    logits = GF.linear(h, sw[2].weight, sw[2].bias, precision=0)
-    return GF.ScaleMixFn.apply(logits, *outs)
+    return GF.ScaleMixFn.apply(_scale_logits(module, pos)[0], *outs)
 
 
 def _softmax_weight_tangents(w, active, w1, w2, rows_matmul):
@@ -226,13 +230,14 @@ def _softmax_weight_jets(w, dl, second=False):
     return dw, ddw
 
 
-def _mix_jet2_planes(w, dls, outs, d1s, d2s, dirs):
+def _mix_jet2_planes(w, dls, outs, d1s, d2s, dirs, second=True):
     """The softmax-weighted mix of the scales' 2-jets: ``w`` [n, scales], ``dls`` the logit tangents along the coordinate axes
     (``_logit_tangents``), ``outs[s]`` [n, C] and ``d1s[s]`` / ``d2s[s]`` [nd, n, C] the value, D_v and D_v^2 planes of scale s along
     ``dirs`` (host values [nd][3]) -> (D_v mix per direction, D_v^2 mix per direction, w' per direction, w'' per direction):
         D_v mix = sum_s (w_s D_v o_s + w'_s o_s),     D_v^2 mix = sum_s (w_s D_v^2 o_s + 2 w'_s D_v o_s + w''_s o_s)
     with l'_v = sum_c v_c d_c l formed from the axis tangents (an axis direction: that tangent itself; e_i + e_j: their sum).  Per-row
-    operations with the sums over the scales written term by term, in the dtype of the operands."""
+    operations with the sums over the scales written term by term, in the dtype of the operands.  Without ``second`` (first order:
+    ``d2s`` is not read) neither w'' nor a D_v^2 mix is formed: no second-order plane is returned and every w'' is None."""
     ns = len(outs)
     p1, p2, dws, ddws = [], [], [], []
     for i, v in enumerate(dirs):
@@ -244,71 +249,46 @@ def _mix_jet2_planes(w, dls, outs, d1s, d2s, dirs):
             dl = term if dl is None else dl + term
         if dl is None:
             dl = torch.zeros_like(w)
-        dw, ddw = _softmax_weight_jets(w, dl, second=True)
+        dw, ddw = _softmax_weight_jets(w, dl, second=second)
         a1 = a2 = None
         for s in range(ns):
-            ws, dws_, ddws_ = w[:, s:s + 1], dw[:, s:s + 1], ddw[:, s:s + 1]
+            ws, dws_ = w[:, s:s + 1], dw[:, s:s + 1]
             t1 = ws * d1s[s][i] + dws_ * outs[s]
-            t2 = ws * d2s[s][i] + (2.0 * dws_) * d1s[s][i] + ddws_ * outs[s]
             a1 = t1 if a1 is None else a1 + t1
-            a2 = t2 if a2 is None else a2 + t2
+            if second:
+                t2 = ws * d2s[s][i] + (2.0 * dws_) * d1s[s][i] + ddw[:, s:s + 1] * outs[s]
+                a2 = t2 if a2 is None else a2 + t2
         p1.append(a1)
-        p2.append(a2)
+        if second:
+            p2.append(a2)
         dws.append(dw)
         ddws.append(ddw)
     return p1, p2, dws, ddws
 
 
 def _mix_scales_jet2(module, outs, d1s, d2s, pos, dirs):
-    """``_mix_scales_jvp`` with second-order jets: ``outs[s]`` [n, C], ``d1s[s]`` / ``d2s[s]`` [nd, n, C] of every scale along ``dirs``
-    -> [value, D_v per direction ..., D_v^2 per direction ...], [n, C] each.  The value is ``_mix_scales``'s and, for an axis direction,
-    D_v is ``_mix_scales_jvp``'s plane, bit for bit.  Summed scales: the sum of each plane; one scale: the planes as they are.  With
-    softmax weights the scales of a row-list decoder see different lists, so neither sum_s w'_s o_s nor sum_s w''_s o_s vanishes
-    (``_mix_jet2_planes``); the logits are piecewise linear in the position (l'' = 0 away from the ReLU kinks of the weighting MLP).
-    Per-row fp32 operations only: a row's result does not depend on the chunk it is in."""
+    """``_mix_scales`` with its jets along ``dirs``: ``outs[s]`` [n, C], ``d1s[s]`` / ``d2s[s]`` [nd, n, C] of every scale
+    -> [value, D_v per direction ..., D_v^2 per direction ...], [n, C] each; FIRST ORDER with ``d2s`` None: [value, D_v per direction ...]
+    and nothing of second order is computed.  The value is ``_mix_scales``'s bit for bit, and a direction's D_v plane does not depend
+    on the order.  Summed scales: the sum of each plane; one scale: the planes as they are.  Softmax weights w = softmax(l),
+    l = W_2 relu(W_1 pos + b_1) + b_2, depend on the query position themselves, and the scales of a row-list decoder see different
+    lists, so neither sum_s w'_s o_s nor sum_s w''_s o_s vanishes (``_mix_jet2_planes``); the logits are piecewise linear in the
+    position (l'' = 0 away from the ReLU kinks of the weighting MLP).  Per-row fp32 operations only (the row kernels and elementwise
+    torch ops): a row's result does not depend on the chunk it is in."""
     ns, nd = len(outs), len(dirs)
+    jets = [d1s] if d2s is None else [d1s, d2s]
     if ns == 1:
-        return [outs[0], *d1s[0].unbind(0), *d2s[0].unbind(0)]
+        return [outs[0]] + [p for js in jets for p in js[0].unbind(0)]
     if not module.use_scale_weights:
-        return ([_sum_scales(outs)] + [_sum_scales([j[d] for j in d1s]) for d in range(nd)]
-                + [_sum_scales([j[d] for j in d2s]) for d in range(nd)])
+        return [_sum_scales(outs)] + [_sum_scales([j[d] for j in js]) for js in jets for d in range(nd)]
     sw = module.scale_weighting
-    h = GF.linear(pos, sw[0].weight, sw[0].bias, act="relu", precision=0)
-    logits = GF.linear(h, sw[2].weight, sw[2].bias, precision=0)
+    logits, h = _scale_logits(module, pos)
     value = GF.ScaleMixFn.apply(logits, *outs)
     w = torch.softmax(logits, dim=1)                       # [n, scales]
     active = (h > 0).to(h.dtype)                           # relu'(z): [n, 16]
     dls = _logit_tangents(active, sw[0].weight, sw[2].weight, lambda x, wt: GF.linear(x, wt, None, precision=0))
-    p1, p2, _, _ = _mix_jet2_planes(w, dls, outs, d1s, d2s, dirs)
+    p1, p2, _, _ = _mix_jet2_planes(w, dls, outs, d1s, d2s, dirs, second=d2s is not None)
     return [value, *p1, *p2]
-
-
-def _mix_scales_jvp(module, outs, jacs, pos):
-    """``_mix_scales`` with its tangent along the three query directions: ``outs[s]`` [n, C] and ``jacs[s]`` [3, n, C] of every scale
-    -> [value, d/dx, d/dy, d/dz], [n, C] each.  The value is ``_mix_scales``'s (bit for bit).  Summed scales: the sum of each plane.
-    Softmax weights w = softmax(l), l = W_2 relu(W_1 pos + b_1) + b_2, depend on the query position themselves:
-        d_d mix = sum_s w_s d_d out_s + sum_s (d_d w_s) out_s          (d_d w: ``_softmax_weight_tangents``)
-    -- with different lists per scale the second sum does not vanish.  Per-row fp32 operations only (the row kernels and
-    elementwise torch ops), so a row's result does not depend on the chunk it is in."""
-    ns = len(outs)
-    if ns == 1:
-        return [outs[0], *jacs[0].unbind(0)]
-    if not module.use_scale_weights:
-        return [_sum_scales(outs)] + [_sum_scales([j[d] for j in jacs]) for d in range(3)]
-    sw = module.scale_weighting
-    h = GF.linear(pos, sw[0].weight, sw[0].bias, act="relu", precision=0)
-    logits = GF.linear(h, sw[2].weight, sw[2].bias, precision=0)
-    planes = [GF.ScaleMixFn.apply(logits, *outs)]
-    w = torch.softmax(logits, dim=1)                       # [n, scales]
-    active = (h > 0).to(h.dtype)                           # relu'(z): [n, 16]
-    dws = _softmax_weight_tangents(w, active, sw[0].weight, sw[2].weight, lambda x, wt: GF.linear(x, wt, None, precision=0))
-    for d in range(3):
-        acc = None
-        for s in range(ns):
-            term = w[:, s:s + 1] * jacs[s][d] + dws[d][:, s:s + 1] * outs[s]
-            acc = term if acc is None else acc + term
-        planes.append(acc)
-    return planes
 
 
 class MAGNOEncoder(nn.Module):
@@ -534,6 +514,51 @@ class MAGNODecoder(nn.Module):
         for j in range(0, n, step):
             out[j:j + step] = self.projection.forward_rows(x[j:j + step])
 
+    def _sample_args(self, fn, chunk_points) -> int:
+        """the argument rules of every ``sample*`` method -> the queries per pass"""
+        if self.decoder_strategy == "reverse":
+            raise ValueError(f"MAGNODecoder.{fn}: decoder strategy 'reverse' is the flip of the encoder's graph of the sample's own "
+                             "points and is undefined for other query points")
+        if chunk_points is not None and int(chunk_points) < 1:
+            raise ValueError(f"chunk_points must be positive, got {chunk_points}")
+        return int(chunk_points) if chunk_points is not None else self.SAMPLE_CHUNK
+
+    def _stream_route(self):
+        """the lists the decoder's strategy streams on: 'knn' (the regular lists of ``knn_to_grid``, k_neighbors in ``ops.GNO_KNN_K``),
+        'rows' (``graph.query_lists``: 'radius', and 'bidirectional' up to ``graph.QUERY_LIST_MAX_K`` neighbours) or None"""
+        from ... import graph as device_graph
+        from ... import ops
+        strategy, k = self.decoder_strategy, int(self.k_neighbors)
+        if strategy == "knn":
+            return "knn" if k in ops.GNO_KNN_K else None
+        return "rows" if strategy == "radius" or (strategy == "bidirectional" and k <= device_graph.QUERY_LIST_MAX_K) else None
+
+    def _stream_chunks(self, grid, query_pos, chunk: int, route: str, lead: bool = True):
+        """The chunks of a streaming route: yields (slice, q, lists) per ``chunk`` queries.  Route 'knn': ``lists`` is the regular list
+        (nbr, k) of ``knn_to_grid``, the same for every scale.  Route 'rows': one ``graph.query_lists`` graph per scale, with the
+        radius of every scale as ``_decode`` derives it.  With ``lead`` a chunk's list is led by as many padding edges as put its rows
+        against the kernel's 32-edge tiles where the list of ALL queries has them, so that a row is summed in the same order whatever
+        the chunking (``sample`` streams without)."""
+        from ... import graph as device_graph
+        strategy, k = self.decoder_strategy, int(self.k_neighbors)
+        before = [0] * len(self.scales)           # edges of the earlier chunks, per scale
+        for i in range(0, int(query_pos.shape[0]), chunk):
+            q = query_pos[i:i + chunk]
+            if route == "knn":
+                lists = (device_graph.knn_to_grid(q, grid, k), k)
+            else:
+                lists = []
+                for si, scale in enumerate(self.scales):
+                    pad = {"lead": before[si] % 32} if lead else {}
+                    rows = device_graph.query_lists(strategy, q, grid, self.gno_radius * scale, k, **pad)
+                    before[si] += rows.by_dst.num_edges - pad.get("lead", 0)
+                    lists.append(rows)
+            yield slice(i, i + chunk), q, lists
+
+    def _new(self, like, nq, *tail):
+        """an uninitialised result [nq, out_channels, *tail] with the dtype and device of ``like``"""
+        return torch.empty(nq, self.out_channels, *tail, dtype=like.dtype, device=like.device)
+
     @torch.no_grad()
     def sample(self, rndata_flat, query_pos, latent_tokens_pos, chunk_points: Optional[int] = None) -> torch.Tensor:
         """Predictions [Nq, out_channels] of ONE sample's processed token features ``rndata_flat`` [M, C] at any query coordinates
@@ -557,38 +582,19 @@ class MAGNODecoder(nn.Module):
         decoder -- chunked in the same way.  The exception is a 'statistical' decoder GeoEmbed: its z-score runs over ALL query rows
         (geoembed.py:177-180), so it takes the queries in one piece whatever ``chunk_points`` says.
         'reverse' raises ValueError: it is the flip of a graph of the ENCODER's points and is undefined for other queries."""
-        from ... import graph as device_graph
-        from ... import ops
-        if self.decoder_strategy == "reverse":
-            raise ValueError("MAGNODecoder.sample: decoder strategy 'reverse' is the flip of the encoder's graph of the sample's own "
-                             "points and is undefined for other query points")
-        if chunk_points is not None and int(chunk_points) < 1:
-            raise ValueError(f"chunk_points must be positive, got {chunk_points}")
+        chunk = self._sample_args("sample", chunk_points)
         nq = int(query_pos.shape[0])
-        chunk = int(chunk_points) if chunk_points is not None else self.SAMPLE_CHUNK
         lat = latent_tokens_pos
-        k = int(self.k_neighbors)
-        grid = None
-        strategy = self.decoder_strategy
-        by_rows = strategy == "radius" or (strategy == "bidirectional" and k <= device_graph.QUERY_LIST_MAX_K)
-        if (strategy == "knn" and k in ops.GNO_KNN_K) or by_rows:
-            grid = self._stream_grid(rndata_flat, query_pos, lat)
-        out = torch.empty(nq, self.out_channels, dtype=rndata_flat.dtype, device=rndata_flat.device)
-        if grid is not None and by_rows:
-            for i in range(0, nq, chunk):
-                q = query_pos[i:i + chunk]
-                outs = []
-                for scale in self.scales:                     # the radius, hence the rows, of every scale as ``_decode`` derives it
-                    rows = device_graph.query_lists(strategy, q, grid, self.gno_radius * scale, k)
-                    outs.append(self.gno(y_pos=lat, x_pos=q, edge_index=None, f_y=rndata_flat, graph=rows))
-                self._project_into(_mix_scales(self, outs, q), out[i:i + chunk])
-            return out
+        route = self._stream_route()
+        grid = self._stream_grid(rndata_flat, query_pos, lat) if route else None
+        out = self._new(rndata_flat, nq)
         if grid is not None:
-            for i in range(0, nq, chunk):
-                q = query_pos[i:i + chunk]
-                nbr = device_graph.knn_to_grid(q, grid, k)
-                dec = self.gno.forward_knn(lat, q, nbr, k, rndata_flat)
-                self._project_into(_mix_scales(self, [dec] * len(self.scales), q), out[i:i + chunk])
+            for sl, q, lists in self._stream_chunks(grid, query_pos, chunk, route, lead=False):
+                if route == "knn":
+                    dec = self._mix_equal_scales([self.gno.forward_knn(lat, q, *lists, rndata_flat)], q)[0]
+                else:
+                    dec = _mix_scales(self, [self.gno(y_pos=lat, x_pos=q, edge_index=None, f_y=rndata_flat, graph=rows) for rows in lists], q)
+                self._project_into(dec, out[sl])
             return out
         if self.use_geoembed and self.geoembed.method == "statistical":
             chunk = max(nq, 1)
@@ -609,11 +615,7 @@ class MAGNODecoder(nn.Module):
         every configuration they do not stream, naming the condition"""
         from ... import graph as device_graph
         from ... import ops
-        if self.decoder_strategy == "reverse":
-            raise ValueError(f"MAGNODecoder.{fn}: decoder strategy 'reverse' is the flip of the encoder's graph of the sample's own "
-                             "points and is undefined for other query points")
-        if chunk_points is not None and int(chunk_points) < 1:
-            raise ValueError(f"chunk_points must be positive, got {chunk_points}")
+        chunk = self._sample_args(fn, chunk_points)
         k = int(self.k_neighbors)
         if rows:
             no = lambda why: NotImplementedError(f"MAGNODecoder.{fn}: second derivatives on row lists stream for 'radius' and "
@@ -643,33 +645,76 @@ class MAGNODecoder(nn.Module):
         if grid is None:
             raise no("the operands do not stream (fp32 3-D query coordinates on the device, ONE graph's tokens on the model's regular "
                      "grid and a transform the fused kernels evaluate are needed)")
-        return grid, int(chunk_points) if chunk_points is not None else self.SAMPLE_CHUNK
+        return grid, chunk
 
     def _mix_equal_scales(self, planes, q):
         """the scale mix of the knn route applied to every plane with the same weights: every scale sees the same list, so the mix is
         of equal operands and the derivatives of its softmax weights drop out (``sample_jacobian``); one scale: the planes as they are"""
         ns = len(self.scales)
         if ns > 1 and self.use_scale_weights:
-            sw = self.scale_weighting
-            h = GF.linear(q, sw[0].weight, sw[0].bias, act="relu", precision=0)
-            logits = GF.linear(h, sw[2].weight, sw[2].bias, precision=0)
+            logits = _scale_logits(self, q)[0]
             return [GF.ScaleMixFn.apply(logits, *([p] * ns)) for p in planes]
         if ns > 1:
             return [_sum_scales([p] * ns) for p in planes]
         return planes
 
-    def _jet2_chunk(self, rndata_flat, q, lat, grid, dirs, pred):
-        """one chunk of queries: -> (d1, d2) [n, out_channels, nd] of the prediction along ``dirs``, the value written into ``pred``"""
-        from ... import graph as device_graph
-        k = int(self.k_neighbors)
-        nbr = device_graph.knn_to_grid(q, grid, k)
-        dec, g1, g2 = self.gno.jet2_knn(lat, q, nbr, k, rndata_flat, dirs)
-        planes = self._mix_equal_scales([dec, *g1.unbind(0), *g2.unbind(0)], q)
+    def _jet_planes(self, rndata_flat, q, lat, lists, dirs=None):
+        """The mixed GNO planes of one chunk, [value, D_v per direction ..., D_v^2 per direction ...] along ``dirs``; first order with
+        ``dirs`` None: [value, d/dx, d/dy, d/dz].  On the regular list every scale sees the same rows and the mix is of equal operands
+        (``_mix_equal_scales``); on row lists every scale has its own and the mix carries the jets of its weights (``_mix_scales_jet2``)."""
+        if isinstance(lists, tuple):
+            jets = self.gno.jacobian_knn(lat, q, *lists, rndata_flat) if dirs is None else self.gno.jet2_knn(lat, q, *lists, rndata_flat, dirs)
+            return self._mix_equal_scales([jets[0]] + [p for js in jets[1:] for p in js.unbind(0)], q)
+        jets = [self.gno.jacobian_rows(lat, q, rndata_flat, rows) if dirs is None else self.gno.jet2_rows(lat, q, rndata_flat, rows, dirs)
+                for rows in lists]
+        outs, d1s = [j[0] for j in jets], [j[1] for j in jets]
+        d2s = None if dirs is None else [j[2] for j in jets]
+        return _mix_scales_jet2(self, outs, d1s, d2s, q, self.HESSIAN_DIRS[:3] if dirs is None else dirs)
+
+    def _jet2_chunk(self, rndata_flat, q, lat, lists, dirs, pred):
+        """one chunk of queries: -> (d1, d2) [n, out_channels, nd], the jets of the prediction along ``dirs`` (``_jet_planes``, then the
+        projection's jets), the value written into ``pred``.  A call of its own, so that a chunk's GNO planes are freed before the next
+        chunk's are allocated."""
         nd = len(dirs)
-        d1 = torch.empty(q.shape[0], self.out_channels, nd, dtype=pred.dtype, device=pred.device)
+        planes = self._jet_planes(rndata_flat, q, lat, lists, dirs)
+        d1 = self._new(pred, q.shape[0], nd)
         d2 = torch.empty_like(d1)
         self.projection.jet2_rows(planes[0], planes[1:1 + nd], planes[1 + nd:1 + 2 * nd], out=(pred, d1, d2))
         return d1, d2
+
+    def _polarise(self, d1, d2, jac, hess) -> None:
+        """``jac`` [n, out_channels, 3] and ``hess`` [n, out_channels, 3, 3] from the jets along ``HESSIAN_DIRS``: the D_v planes of the
+        three axes, H_ii = D^2_{e_i} and H_ij = H_ji = (D^2_{e_i + e_j} - D^2_{e_i} - D^2_{e_j}) / 2 written from one value"""
+        jac[:] = d1[:, :, :3]
+        for a in range(3):
+            hess[:, :, a, a] = d2[:, :, a]
+        for n, (a, b) in enumerate(self.HESSIAN_PAIRS):
+            off = 0.5 * (d2[:, :, 3 + n] - d2[:, :, a] - d2[:, :, b])
+            hess[:, :, a, b] = off
+            hess[:, :, b, a] = off
+
+    def _hessian(self, fn, rndata_flat, query_pos, lat, chunk_points, rows):
+        """``sample_hessian`` (``rows`` False) / ``sample_hessian_rows`` on a row-list decoder (True)"""
+        rndata_flat, query_pos = rndata_flat.detach(), query_pos.detach()
+        grid, chunk = self._jet2_stream(fn, rndata_flat, query_pos, lat, chunk_points, rows=rows)
+        nq = int(query_pos.shape[0])
+        pred, jac, hess = self._new(rndata_flat, nq), self._new(rndata_flat, nq, 3), self._new(rndata_flat, nq, 3, 3)
+        for sl, q, lists in self._stream_chunks(grid, query_pos, chunk, "rows" if rows else "knn"):
+            d1, d2 = self._jet2_chunk(rndata_flat, q, lat, lists, self.HESSIAN_DIRS, pred[sl])
+            self._polarise(d1, d2, jac[sl], hess[sl])
+        return pred, jac, hess
+
+    def _laplacian(self, fn, rndata_flat, query_pos, lat, chunk_points, rows):
+        """``sample_laplacian`` (``rows`` False) / ``sample_laplacian_rows`` on a row-list decoder (True): the ordered trace
+        (d2_x + d2_y) + d2_z from the three axis directions"""
+        rndata_flat, query_pos = rndata_flat.detach(), query_pos.detach()
+        grid, chunk = self._jet2_stream(fn, rndata_flat, query_pos, lat, chunk_points, rows=rows)
+        nq = int(query_pos.shape[0])
+        pred, lap = self._new(rndata_flat, nq), self._new(rndata_flat, nq)
+        for sl, q, lists in self._stream_chunks(grid, query_pos, chunk, "rows" if rows else "knn"):
+            _, d2 = self._jet2_chunk(rndata_flat, q, lat, lists, self.HESSIAN_DIRS[:3], pred[sl])
+            torch.add(d2[:, :, 0] + d2[:, :, 1], d2[:, :, 2], out=lap[sl])
+        return pred, lap
 
     @torch.no_grad()
     def sample_hessian(self, rndata_flat, query_pos, latent_tokens_pos, chunk_points: Optional[int] = None):
@@ -689,23 +734,7 @@ class MAGNODecoder(nn.Module):
         erf-GELU 32 -> {64, 128, 256} -> 1..4); every other configuration -- 'radius' / 'bidirectional' decoders, other k, use_attn, a
         decoder GeoEmbed, neighbour sampling, tokens off the regular grid, other projections -- raises NotImplementedError naming the
         condition.  'reverse' and a non-positive ``chunk_points`` raise ValueError."""
-        rndata_flat, query_pos = rndata_flat.detach(), query_pos.detach()
-        grid, chunk = self._jet2_stream("sample_hessian", rndata_flat, query_pos, latent_tokens_pos, chunk_points)
-        nq, oc = int(query_pos.shape[0]), self.out_channels
-        pred = torch.empty(nq, oc, dtype=rndata_flat.dtype, device=rndata_flat.device)
-        jac = torch.empty(nq, oc, 3, dtype=rndata_flat.dtype, device=rndata_flat.device)
-        hess = torch.empty(nq, oc, 3, 3, dtype=rndata_flat.dtype, device=rndata_flat.device)
-        for i in range(0, nq, chunk):
-            d1, d2 = self._jet2_chunk(rndata_flat, query_pos[i:i + chunk], latent_tokens_pos, grid, self.HESSIAN_DIRS, pred[i:i + chunk])
-            jac[i:i + chunk] = d1[:, :, :3]
-            hc = hess[i:i + chunk]
-            for a in range(3):
-                hc[:, :, a, a] = d2[:, :, a]
-            for n, (a, b) in enumerate(self.HESSIAN_PAIRS):
-                off = 0.5 * (d2[:, :, 3 + n] - d2[:, :, a] - d2[:, :, b])
-                hc[:, :, a, b] = off
-                hc[:, :, b, a] = off
-        return pred, jac, hess
+        return self._hessian("sample_hessian", rndata_flat, query_pos, latent_tokens_pos, chunk_points, False)
 
     @torch.no_grad()
     def sample_laplacian(self, rndata_flat, query_pos, latent_tokens_pos, chunk_points: Optional[int] = None):
@@ -713,41 +742,7 @@ class MAGNODecoder(nn.Module):
         lap = d^2 pred / dx^2 + d^2 pred / dy^2 + d^2 pred / dz^2, summed in that order from the D_v^2 planes of the three axis
         directions -- bit for bit hess[..., 0, 0] + hess[..., 1, 1] + hess[..., 2, 2] of ``sample_hessian``.  Conditions, errors,
         exactness and capture as there."""
-        rndata_flat, query_pos = rndata_flat.detach(), query_pos.detach()
-        grid, chunk = self._jet2_stream("sample_laplacian", rndata_flat, query_pos, latent_tokens_pos, chunk_points)
-        nq, oc = int(query_pos.shape[0]), self.out_channels
-        pred = torch.empty(nq, oc, dtype=rndata_flat.dtype, device=rndata_flat.device)
-        lap = torch.empty(nq, oc, dtype=rndata_flat.dtype, device=rndata_flat.device)
-        for i in range(0, nq, chunk):
-            _, d2 = self._jet2_chunk(rndata_flat, query_pos[i:i + chunk], latent_tokens_pos, grid, self.HESSIAN_DIRS[:3], pred[i:i + chunk])
-            torch.add(d2[:, :, 0] + d2[:, :, 1], d2[:, :, 2], out=lap[i:i + chunk])
-        return pred, lap
-
-    def _jet2_rows_chunks(self, fn, rndata_flat, query_pos, lat, chunk_points, dirs, pred):
-        """the row-list route of ``sample_hessian_rows`` / ``sample_laplacian_rows``: yields (slice, d1, d2) per chunk of queries, d1 / d2
-        [n, out_channels, nd] the jets of the prediction along ``dirs``, the value written into ``pred``.  Per chunk and scale
-        ``graph.query_lists`` (led by as many padding edges as put the chunk's rows against the 32-edge tiles where the list of ALL
-        queries has them, as in ``sample_jacobian``), ``jet2_rows``, then ``_mix_scales_jet2`` and the projection's jets."""
-        from ... import graph as device_graph
-        grid, chunk = self._jet2_stream(fn, rndata_flat, query_pos, lat, chunk_points, rows=True)
-        strategy, k, nd = self.decoder_strategy, int(self.k_neighbors), len(dirs)
-        before = [0] * len(self.scales)           # edges of the earlier chunks, per scale
-        for i in range(0, int(query_pos.shape[0]), chunk):
-            q = query_pos[i:i + chunk]
-            outs, g1s, g2s = [], [], []
-            for si, scale in enumerate(self.scales):
-                lead = before[si] % 32
-                rows = device_graph.query_lists(strategy, q, grid, self.gno_radius * scale, k, lead=lead)
-                before[si] += rows.by_dst.num_edges - lead
-                o, g1, g2 = self.gno.jet2_rows(lat, q, rndata_flat, rows, dirs)
-                outs.append(o)
-                g1s.append(g1)
-                g2s.append(g2)
-            planes = _mix_scales_jet2(self, outs, g1s, g2s, q, dirs)
-            d1 = torch.empty(q.shape[0], self.out_channels, nd, dtype=pred.dtype, device=pred.device)
-            d2 = torch.empty_like(d1)
-            self.projection.jet2_rows(planes[0], planes[1:1 + nd], planes[1 + nd:1 + 2 * nd], out=(pred[i:i + chunk], d1, d2))
-            yield slice(i, i + chunk), d1, d2
+        return self._laplacian("sample_laplacian", rndata_flat, query_pos, latent_tokens_pos, chunk_points, False)
 
     @torch.no_grad()
     def sample_hessian_rows(self, rndata_flat, query_pos, latent_tokens_pos, chunk_points: Optional[int] = None):
@@ -769,22 +764,7 @@ class MAGNODecoder(nn.Module):
         projections raise NotImplementedError naming the condition; 'reverse' and a non-positive ``chunk_points`` raise ValueError."""
         if self.decoder_strategy == "knn":
             return self.sample_hessian(rndata_flat, query_pos, latent_tokens_pos, chunk_points=chunk_points)
-        rndata_flat, query_pos = rndata_flat.detach(), query_pos.detach()
-        nq, oc = int(query_pos.shape[0]), self.out_channels
-        pred = torch.empty(nq, oc, dtype=rndata_flat.dtype, device=rndata_flat.device)
-        jac = torch.empty(nq, oc, 3, dtype=rndata_flat.dtype, device=rndata_flat.device)
-        hess = torch.empty(nq, oc, 3, 3, dtype=rndata_flat.dtype, device=rndata_flat.device)
-        for sl, d1, d2 in self._jet2_rows_chunks("sample_hessian_rows", rndata_flat, query_pos, latent_tokens_pos, chunk_points,
-                                                 self.HESSIAN_DIRS, pred):
-            jac[sl] = d1[:, :, :3]
-            hc = hess[sl]
-            for a in range(3):
-                hc[:, :, a, a] = d2[:, :, a]
-            for n, (a, b) in enumerate(self.HESSIAN_PAIRS):
-                off = 0.5 * (d2[:, :, 3 + n] - d2[:, :, a] - d2[:, :, b])
-                hc[:, :, a, b] = off
-                hc[:, :, b, a] = off
-        return pred, jac, hess
+        return self._hessian("sample_hessian_rows", rndata_flat, query_pos, latent_tokens_pos, chunk_points, True)
 
     @torch.no_grad()
     def sample_laplacian_rows(self, rndata_flat, query_pos, latent_tokens_pos, chunk_points: Optional[int] = None):
@@ -793,14 +773,7 @@ class MAGNODecoder(nn.Module):
         and errors as there; on a 'knn' decoder the call IS ``sample_laplacian``."""
         if self.decoder_strategy == "knn":
             return self.sample_laplacian(rndata_flat, query_pos, latent_tokens_pos, chunk_points=chunk_points)
-        rndata_flat, query_pos = rndata_flat.detach(), query_pos.detach()
-        nq, oc = int(query_pos.shape[0]), self.out_channels
-        pred = torch.empty(nq, oc, dtype=rndata_flat.dtype, device=rndata_flat.device)
-        lap = torch.empty(nq, oc, dtype=rndata_flat.dtype, device=rndata_flat.device)
-        for sl, _, d2 in self._jet2_rows_chunks("sample_laplacian_rows", rndata_flat, query_pos, latent_tokens_pos, chunk_points,
-                                                self.HESSIAN_DIRS[:3], pred):
-            torch.add(d2[:, :, 0] + d2[:, :, 1], d2[:, :, 2], out=lap[sl])
-        return pred, lap
+        return self._laplacian("sample_laplacian_rows", rndata_flat, query_pos, latent_tokens_pos, chunk_points, True)
 
     def sample_jacobian(self, rndata_flat, query_pos, latent_tokens_pos, chunk_points: Optional[int] = None,
                         row_lists: bool = False):
@@ -823,8 +796,8 @@ class MAGNODecoder(nn.Module):
         'radius' and 'bidirectional' decoders too, under exactly the conditions of ``sample``'s row-list route ('bidirectional':
         k_neighbors <= ``graph.QUERY_LIST_MAX_K``): per chunk and scale ``graph.query_lists`` writes the by-query list and
         ``jacobian_rows`` runs the tangent kernel on its ragged rows (two launches per 32-channel pass), then the scale mix WITH the
-        tangent of its weights -- the scales see different lists, so sum_s (dw_s) out_s does not vanish (``_mix_scales_jvp``) -- and
-        ``jvp_rows``.  Exact fp32 in both precision modes; ``pred`` is the fp32-mode result of ``sample`` with the queries
+        tangent of its weights -- the scales see different lists, so sum_s (dw_s) out_s does not vanish (``_mix_scales_jet2`` at first
+        order) -- and ``jvp_rows``.  Exact fp32 in both precision modes; ``pred`` is the fp32-mode result of ``sample`` with the queries
         in one piece, bit for bit.  The results do not depend on ``chunk_points``: a row that straddles two of the kernel's 32-edge
         tiles is summed from two partial sums, so every chunk's list is led by as many padding edges as put its rows against the
         tiles where the list of ALL queries would have them (``query_lists(..., lead=)``).  The lists are sized by a host read, so
@@ -834,70 +807,26 @@ class MAGNODecoder(nn.Module):
         decoder on a detached copy of the chunk that requires grad, then one backward pass per output channel.  use_attn raises the
         NotImplementedError ``IntegralTransform`` raises for coordinate gradients; a 'statistical' decoder GeoEmbed couples all
         queries through its z-score, so a per-query Jacobian is not what that route returns: NotImplementedError."""
-        from ... import graph as device_graph
-        from ... import ops
-        if self.decoder_strategy == "reverse":
-            raise ValueError("MAGNODecoder.sample_jacobian: decoder strategy 'reverse' is the flip of the encoder's graph of the "
-                             "sample's own points and is undefined for other query points")
-        if chunk_points is not None and int(chunk_points) < 1:
-            raise ValueError(f"chunk_points must be positive, got {chunk_points}")
+        chunk = self._sample_args("sample_jacobian", chunk_points)
         if self.use_geoembed and self.geoembed.method == "statistical":
             raise NotImplementedError("MAGNODecoder.sample_jacobian: a 'statistical' decoder GeoEmbed normalises over ALL query rows, "
                                       "which couples the queries; there is no per-query Jacobian")
-        nq = int(query_pos.shape[0])
-        chunk = int(chunk_points) if chunk_points is not None else self.SAMPLE_CHUNK
+        nq, cd = int(query_pos.shape[0]), int(query_pos.shape[1])
         lat = latent_tokens_pos
-        k = int(self.k_neighbors)
-        cd = int(query_pos.shape[1])
         rndata_flat = rndata_flat.detach()
         query_pos = query_pos.detach()
-        pred = torch.empty(nq, self.out_channels, dtype=rndata_flat.dtype, device=rndata_flat.device)
-        jac = torch.empty(nq, self.out_channels, cd, dtype=rndata_flat.dtype, device=rndata_flat.device)
-        grid = None
-        if self.decoder_strategy == "knn" and k in ops.GNO_KNN_K:
-            with torch.no_grad():           # the plan of the forward alone, as ``sample`` asks for it (four hidden layers stream in fp32 mode)
-                grid = self._stream_grid(rndata_flat, query_pos, lat)
-        strategy = self.decoder_strategy
-        by_rows = bool(row_lists) and (strategy == "radius" or (strategy == "bidirectional" and k <= device_graph.QUERY_LIST_MAX_K))
-        if by_rows:
-            with torch.no_grad():
-                grid = self._stream_grid(rndata_flat, query_pos, lat)
-        if grid is not None and by_rows:
-            with torch.no_grad():
-                before = [0] * len(self.scales)           # edges of the earlier chunks, per scale
-                for i in range(0, nq, chunk):
-                    q = query_pos[i:i + chunk]
-                    outs, jacs = [], []
-                    for si, scale in enumerate(self.scales):  # the radius, hence the rows, of every scale as ``_decode`` derives it
-                        # the chunk's rows lie against the kernel's 32-edge tiles as they would in the list of ALL queries (so many
-                        # padding edges lead the list): a row is summed in the same order whatever the chunking
-                        lead = before[si] % 32
-                        rows = device_graph.query_lists(strategy, q, grid, self.gno_radius * scale, k, lead=lead)
-                        before[si] += rows.by_dst.num_edges - lead
-                        o, j = self.gno.jacobian_rows(lat, q, rndata_flat, rows)
-                        outs.append(o)
-                        jacs.append(j)
-                    planes = _mix_scales_jvp(self, outs, jacs, q)
+        pred, jac = self._new(rndata_flat, nq), self._new(rndata_flat, nq, cd)
+        route = self._stream_route()
+        if route == "rows" and not row_lists:
+            route = None
+        with torch.no_grad():               # the plan of the forward alone, as ``sample`` asks for it (four hidden layers stream in fp32 mode)
+            grid = self._stream_grid(rndata_flat, query_pos, lat) if route else None
+            if grid is not None:
+                for sl, q, lists in self._stream_chunks(grid, query_pos, chunk, route):
+                    planes = self._jet_planes(rndata_flat, q, lat, lists)
                     # the planes of the real directions only (a padded direction's plane is zero and has no column in ``jac``)
-                    self.projection.jvp_rows(planes[0], planes[1:1 + cd], out=(pred[i:i + chunk], jac[i:i + chunk]))
-            return pred, jac
-        if grid is not None:
-            ns = len(self.scales)
-            with torch.no_grad():
-                for i in range(0, nq, chunk):
-                    q = query_pos[i:i + chunk]
-                    nbr = device_graph.knn_to_grid(q, grid, k)
-                    dec, dj = self.gno.jacobian_knn(lat, q, nbr, k, rndata_flat)
-                    planes = [dec, *dj.unbind(0)]
-                    if ns > 1 and self.use_scale_weights:
-                        sw = self.scale_weighting
-                        h = GF.linear(q, sw[0].weight, sw[0].bias, act="relu", precision=0)
-                        logits = GF.linear(h, sw[2].weight, sw[2].bias, precision=0)
-                        planes = [GF.ScaleMixFn.apply(logits, *([p] * ns)) for p in planes]
-                    elif ns > 1:
-                        planes = [_sum_scales([p] * ns) for p in planes]
-                    self.projection.jvp_rows(planes[0], planes[1:1 + cd], out=(pred[i:i + chunk], jac[i:i + chunk]))
-            return pred, jac
+                    self.projection.jvp_rows(planes[0], planes[1:1 + cd], out=(pred[sl], jac[sl]))
+                return pred, jac
         lat_bidx = torch.zeros(lat.shape[0], dtype=torch.long, device=lat.device)
         for i in range(0, nq, chunk):
             with torch.enable_grad():

@@ -284,9 +284,10 @@ def gno_nl_forward(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Opt
 GNO_KNN_K = (1, 2, 4, 8, 16, 32)      # the divisors of the kernels' 32-edge tile (gaot_gno_fwd_knn)
 
 
-def _gno_mode_args(fn, mode, weights, biases, y_pos, x_pos, f_y, src_table):
-    """the operand checks of the entry points that take the transform type as ``mode`` (0 / 'linear', 'nonlinear',
-    'nonlinear_kernelonly'): ``gno_forward_knn``, ``gno_forward_knn_jac``, ``gno_forward_jac``"""
+def _gno_mode_args(fn, mode, weights, biases, y_pos, x_pos, f_y, src_table, lists):
+    """the operand checks of the forward-mode entry points, which take the transform type as ``mode`` (0 / 'linear', 'nonlinear',
+    'nonlinear_kernelonly') and their neighbour lists as ``lists``: the regular list (nbr, k) of ``gno_forward_knn*`` or the graph whose
+    by-query list ``gno_forward_jac`` / ``gno_forward_jet2`` read -> (..., (nbr, k) or the graph, the number of queries)"""
     md = {"linear": 0, **GNO_MODES}.get(mode, mode)
     if md not in (0, 1, 2):
         raise GaotError(f"{fn}: mode must be 'linear' or one of {tuple(GNO_MODES)}, got {mode!r}")
@@ -308,18 +309,21 @@ def _gno_mode_args(fn, mode, weights, biases, y_pos, x_pos, f_y, src_table):
             raise GaotError(f"src_table must be [{n_src}, 64], got {tuple(src_table.shape)}")
     else:
         src_table = None
-    return md, m, keep, y_pos, x_pos, f_y, src_table
-
-
-def _gno_knn_args(fn, mode, weights, biases, y_pos, x_pos, f_y, src_table, nbr, k):
-    """the operand checks shared by ``gno_forward_knn`` and ``gno_forward_knn_jac``"""
-    md, m, keep, y_pos, x_pos, f_y, src_table = _gno_mode_args(fn, mode, weights, biases, y_pos, x_pos, f_y, src_table)
-    nbr = _req(nbr, torch.int32, "nbr")
-    k = int(k)
     q = int(x_pos.shape[0])
-    if nbr.numel() != q * k:
-        raise GaotError(f"nbr must hold {q} x {k} ids, got {nbr.numel()}")
-    return md, m, keep, y_pos, x_pos, f_y, src_table, nbr, k, q
+    if isinstance(lists, tuple):
+        nbr, k = _req(lists[0], torch.int32, "nbr"), int(lists[1])
+        if nbr.numel() != q * k:
+            raise GaotError(f"nbr must hold {q} x {k} ids, got {nbr.numel()}")
+        lists = (nbr, k)
+    elif n_src != lists.num_src or q != lists.num_dst:
+        raise GaotError(f"y_pos / x_pos have {n_src} / {q} rows, the graph {lists.num_src} / {lists.num_dst}")
+    return md, m, keep, y_pos, x_pos, f_y, src_table, lists, q
+
+
+def _gno_planes(x_pos, q, m, *counts):
+    """the results of a forward-mode entry point: out [q, channels] and one stack of derivative planes [max(n, 1), q, channels] per count"""
+    new = lambda *lead: torch.empty(*lead, q, m.channels, dtype=torch.float32, device=x_pos.device)
+    return (new(), *(new(max(n, 1)) for n in counts))
 
 
 def gno_forward_knn(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], src_table: Optional[Tensor],
@@ -331,9 +335,9 @@ def gno_forward_knn(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Op
     backward."""
     lib = _lib.load()
     prec = _PRECISION["mode"] if precision is None else precision
-    md, m, keep, y_pos, x_pos, f_y, src_table, nbr, k, q = _gno_knn_args("gno_forward_knn", mode, weights, biases, y_pos, x_pos, f_y,
-                                                                         src_table, nbr, k)
-    out = torch.empty(q, m.channels, dtype=torch.float32, device=x_pos.device)
+    md, m, keep, y_pos, x_pos, f_y, src_table, (nbr, k), q = _gno_mode_args("gno_forward_knn", mode, weights, biases, y_pos, x_pos, f_y,
+                                                                            src_table, (nbr, k))
+    (out,) = _gno_planes(x_pos, q, m)
     with _timed(f"gno_fwd_knn{f'_nl{md}' if md else ''}_nh{m.n_hidden}"):
         check(lib.gaot_gno_fwd_knn(C.byref(m), md, _ptr(y_pos), _ptr(x_pos), _ptr(f_y), _ptr(src_table), _ptr(nbr), k, q, _ptr(out),
                                    prec, _stream()), "gaot_gno_fwd_knn")
@@ -349,10 +353,9 @@ def gno_forward_knn_jac(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y
     nothing stored, no backward.  Exact fp32 whatever the precision mode: ``out`` is ``gno_forward_knn(..., precision=0)`` bit for
     bit.  Operands and their checks are those of ``gno_forward_knn``."""
     lib = _lib.load()
-    md, m, keep, y_pos, x_pos, f_y, src_table, nbr, k, q = _gno_knn_args("gno_forward_knn_jac", mode, weights, biases, y_pos, x_pos,
-                                                                         f_y, src_table, nbr, k)
-    out = torch.empty(q, m.channels, dtype=torch.float32, device=x_pos.device)
-    jac = torch.empty(3, q, m.channels, dtype=torch.float32, device=x_pos.device)
+    md, m, keep, y_pos, x_pos, f_y, src_table, (nbr, k), q = _gno_mode_args("gno_forward_knn_jac", mode, weights, biases, y_pos, x_pos,
+                                                                            f_y, src_table, (nbr, k))
+    out, jac = _gno_planes(x_pos, q, m, 3)
     with _timed(f"gno_fwd_knn_jac{f'_nl{md}' if md else ''}_nh{m.n_hidden}"):
         check(lib.gaot_gno_fwd_knn_jac(C.byref(m), md, _ptr(y_pos), _ptr(x_pos), _ptr(f_y), _ptr(src_table), _ptr(nbr), k, q,
                                        _ptr(out), _ptr(jac), _stream()), "gaot_gno_fwd_knn_jac")
@@ -381,12 +384,10 @@ def gno_forward_knn_jet2(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_
     plane d, bit for bit; a direction's planes do not depend on the other directions.  Six directions e_x, e_y, e_z, e_x+e_y, e_y+e_z,
     e_x+e_z give a Hessian by polarisation.  Operands and their checks are those of ``gno_forward_knn_jac``."""
     lib = _lib.load()
-    md, m, keep, y_pos, x_pos, f_y, src_table, nbr, k, q = _gno_knn_args("gno_forward_knn_jet2", mode, weights, biases, y_pos, x_pos,
-                                                                         f_y, src_table, nbr, k)
+    md, m, keep, y_pos, x_pos, f_y, src_table, (nbr, k), q = _gno_mode_args("gno_forward_knn_jet2", mode, weights, biases, y_pos, x_pos,
+                                                                            f_y, src_table, (nbr, k))
     hd, nd = _host_dirs("gno_forward_knn_jet2", dirs)
-    out = torch.empty(q, m.channels, dtype=torch.float32, device=x_pos.device)
-    d1 = torch.empty(max(nd, 1), q, m.channels, dtype=torch.float32, device=x_pos.device)
-    d2 = torch.empty_like(d1)
+    out, d1, d2 = _gno_planes(x_pos, q, m, nd, nd)
     with _timed(f"gno_jet2_knn{f'_nl{md}' if md else ''}_nh{m.n_hidden}_d{nd}"):
         check(lib.gaot_gno_fwd_knn_jet2(C.byref(m), md, _ptr(y_pos), _ptr(x_pos), _ptr(f_y), _ptr(src_table), _ptr(nbr), k, q, hd, nd,
                                         _ptr(out), _ptr(d1), _ptr(d2), _stream()), "gaot_gno_fwd_knn_jet2")
@@ -402,12 +403,10 @@ def gno_forward_jac(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Op
     ``gno_forward`` / ``gno_nl_forward(..., precision=0)`` on the same graph bit for bit, and on a list of equal rows of k in
     ``GNO_KNN_K`` edges both results are ``gno_forward_knn_jac``'s.  ``mode`` and the operands as in ``gno_forward_knn``."""
     lib = _lib.load()
-    md, m, keep, y_pos, x_pos, f_y, src_table = _gno_mode_args("gno_forward_jac", mode, weights, biases, y_pos, x_pos, f_y, src_table)
-    if y_pos.shape[0] != g.num_src or x_pos.shape[0] != g.num_dst:
-        raise GaotError(f"y_pos / x_pos have {y_pos.shape[0]} / {x_pos.shape[0]} rows, the graph {g.num_src} / {g.num_dst}")
-    q, e = g.num_dst, g.by_dst.num_edges
-    out = torch.empty(q, m.channels, dtype=torch.float32, device=x_pos.device)
-    jac = torch.empty(3, q, m.channels, dtype=torch.float32, device=x_pos.device)
+    md, m, keep, y_pos, x_pos, f_y, src_table, g, q = _gno_mode_args("gno_forward_jac", mode, weights, biases, y_pos, x_pos, f_y,
+                                                                     src_table, g)
+    e = g.by_dst.num_edges
+    out, jac = _gno_planes(x_pos, q, m, 3)
     ws = _ws(lib.gaot_gno_fwd_jac_workspace_bytes(e), x_pos.device)
     with _timed(f"gno_fwd_jac{f'_nl{md}' if md else ''}_nh{m.n_hidden}"):
         check(lib.gaot_gno_fwd_jac(C.byref(m), md, _ptr(y_pos), _ptr(x_pos), _ptr(f_y), _ptr(src_table), _ptr(g.by_dst.other),
@@ -426,14 +425,11 @@ def gno_forward_jet2(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: O
     ``gno_forward_knn_jet2``'s, bit for bit.  ``mode`` and the operands as in ``gno_forward_jac``, ``dirs`` as in
     ``gno_forward_knn_jet2``.  Workspace: 256 (1 + 2 nd) bytes per 32-edge tile."""
     lib = _lib.load()
-    md, m, keep, y_pos, x_pos, f_y, src_table = _gno_mode_args("gno_forward_jet2", mode, weights, biases, y_pos, x_pos, f_y, src_table)
-    if y_pos.shape[0] != g.num_src or x_pos.shape[0] != g.num_dst:
-        raise GaotError(f"y_pos / x_pos have {y_pos.shape[0]} / {x_pos.shape[0]} rows, the graph {g.num_src} / {g.num_dst}")
+    md, m, keep, y_pos, x_pos, f_y, src_table, g, q = _gno_mode_args("gno_forward_jet2", mode, weights, biases, y_pos, x_pos, f_y,
+                                                                     src_table, g)
     hd, nd = _host_dirs("gno_forward_jet2", dirs)
-    q, e = g.num_dst, g.by_dst.num_edges
-    out = torch.empty(q, m.channels, dtype=torch.float32, device=x_pos.device)
-    d1 = torch.empty(max(nd, 1), q, m.channels, dtype=torch.float32, device=x_pos.device)
-    d2 = torch.empty_like(d1)
+    e = g.by_dst.num_edges
+    out, d1, d2 = _gno_planes(x_pos, q, m, nd, nd)
     ws = _ws(lib.gaot_gno_fwd_jet2_workspace_bytes(e, min(max(nd, 0), 6)), x_pos.device)
     with _timed(f"gno_jet2_rows{f'_nl{md}' if md else ''}_nh{m.n_hidden}_d{nd}"):
         check(lib.gaot_gno_fwd_jet2(C.byref(m), md, _ptr(y_pos), _ptr(x_pos), _ptr(f_y), _ptr(src_table), _ptr(g.by_dst.other),

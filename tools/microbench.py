@@ -653,7 +653,7 @@ elif what == "decoder_hessian":
     # profiles/decoder_hessian_rows_microbench.txt.
     from gaot_3d_amd import graph as device_graph
     from gaot_3d_amd.data import latent_grid
-    from gaot_3d_amd.model.layers.magno import MAGNOConfig, MAGNODecoder, _mix_scales_jet2, _mix_scales_jvp
+    from gaot_3d_amd.model.layers.magno import MAGNOConfig, MAGNODecoder, _mix_scales_jet2
     gaot_3d_amd.set_precision("fp32")
     latent = (64, 64, 32)
     strategy = sys.argv[sys.argv.index("--strategy") + 1] if "--strategy" in sys.argv else "knn"
@@ -719,7 +719,7 @@ elif what == "decoder_hessian":
                     edges = sum(g.by_dst.num_edges for g in lists)
                     t, _p, outs = timed(lambda: [dec.gno.jacobian_rows(tokens, c, rn, g) for c, g in zip(chunks, lists)]); t_gno["jac"].append(t)
                     def mix_jvp(c, o, j):
-                        p = _mix_scales_jvp(dec, [o], [j], c)
+                        p = _mix_scales_jet2(dec, [o], [j], None, c, DIRS[:3])
                         return dec.projection.jvp_rows(p[0], p[1:])
                     t, _p, prj = timed(lambda: [mix_jvp(c, o, j) for c, (o, j) in zip(chunks, outs)]); t_prj["jac"].append(t)
                     del outs, prj
