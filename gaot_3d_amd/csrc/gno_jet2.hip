@@ -37,6 +37,9 @@
 // finished by segment_walk<32> -- complete rows stored as their mean, rows that straddle tiles left in the plane's partial buffer --
 // and by ONE fix-up launch over all planes (k_jet2_rows_fixup).  On a list whose rows all have k | 32 edges the two kernels perform
 // the same operations in the same order: bit-identical planes.
+//
+// PER-QUERY directions (gaot_gno_fwd_knn_jet2_qd / gaot_gno_fwd_jet2_qd): k_gno_qd_jet2_knn / k_gno_qd_jet2_rows, the same body once
+// more with QD = true -- see Jet2QDirs below.  All 24 instantiations are built without scratch (tests/test_field_directional_cpu.py).
 #include "gno_common.h"
 
 namespace {
@@ -72,6 +75,20 @@ __device__ __forceinline__ float dir_at(const Jet2Dirs& D, int d, int c) {
     for (int i = 1; i < MAXD; ++i) r = d == i ? D.v[i][c] : r;
     return r;
 }
+
+// PER-QUERY directions (gaot_gno_fwd_knn_jet2_qd / gaot_gno_fwd_jet2_qd): a DEVICE array [Nq][nd][3].  Edges sit on the lane axis and
+// every edge belongs to one query, so the direction of a pass is a per-lane value: at the top of the pass each lane loads the three
+// components of direction d of ITS edge's query and z'_0 is formed by the same fixed-order fma chain; nothing else in the kernel
+// body changes.  Kernels of their own (k_gno_qd_jet2_knn / k_gno_qd_jet2_rows): the host-direction kernels stay what they were.
+struct Jet2QDirs {
+    const float* v;         // [Nq][nd][3]
+    int nd;
+};
+
+// the overloads the kernel body's untaken `if constexpr` branch still has to compile against
+__device__ __forceinline__ float dir_at(const Jet2QDirs&, int, int) { return 0.f; }
+__device__ __forceinline__ const float* qdir_at(const Jet2Dirs&, int64_t) { return nullptr; }
+__device__ __forceinline__ const float* qdir_at(const Jet2QDirs& D, int64_t i) { return D.v + i; }
 
 // x, as a value the optimiser cannot trace: keeps the recomputation of gelu' / gelu'' from z_l INSIDE the direction loop (hoisted out
 // of it as loop-invariant, the derivatives of every layer are live across the loop again and the kernel spills)
@@ -116,7 +133,7 @@ __global__ __launch_bounds__(256, 1) void k_gno_fwd_knn_jet2(MlpPtrs mlp, const 
                                                              const float* __restrict__ ttab, const int* __restrict__ nbr, int lk,
                                                              int64_t E, const Jet2Dirs dirs, float* __restrict__ out,
                                                              float* __restrict__ d1, float* __restrict__ d2) {
-    constexpr bool R = false;
+    constexpr bool R = false, QD = false;
     [[maybe_unused]] const Jet2Rows rows{};
 #include "gno_jet2_body.inc"
 }
@@ -128,7 +145,29 @@ __global__ __launch_bounds__(256, 1) void k_gno_fwd_rows_jet2(MlpPtrs mlp, const
                                                               const float* __restrict__ ttab, const int* __restrict__ nbr, int64_t E,
                                                               const Jet2Dirs dirs, float* __restrict__ out, float* __restrict__ d1,
                                                               float* __restrict__ d2, const Jet2Rows rows) {
-    constexpr bool R = true;
+    constexpr bool R = true, QD = false;
+    [[maybe_unused]] constexpr int lk = 0;   // not read on row lists
+#include "gno_jet2_body.inc"
+}
+
+// the two kernels along PER-QUERY directions (names of their own: the host-direction kernels are counted by theirs)
+template <int NH, int MODE>
+__global__ __launch_bounds__(256, 1) void k_gno_qd_jet2_knn(MlpPtrs mlp, const float* __restrict__ y_pos, const float* __restrict__ x_pos,
+                                                            const float* __restrict__ f_y, const float* __restrict__ ttab,
+                                                            const int* __restrict__ nbr, int lk, int64_t E, const Jet2QDirs dirs,
+                                                            float* __restrict__ out, float* __restrict__ d1, float* __restrict__ d2) {
+    constexpr bool R = false, QD = true;
+    [[maybe_unused]] const Jet2Rows rows{};
+#include "gno_jet2_body.inc"
+}
+
+template <int NH, int MODE>
+__global__ __launch_bounds__(256, 1) void k_gno_qd_jet2_rows(MlpPtrs mlp, const float* __restrict__ y_pos, const float* __restrict__ x_pos,
+                                                             const float* __restrict__ f_y, const float* __restrict__ ttab,
+                                                             const int* __restrict__ nbr, int64_t E, const Jet2QDirs dirs,
+                                                             float* __restrict__ out, float* __restrict__ d1, float* __restrict__ d2,
+                                                             const Jet2Rows rows) {
+    constexpr bool R = true, QD = true;
     [[maybe_unused]] constexpr int lk = 0;   // not read on row lists
 #include "gno_jet2_body.inc"
 }
@@ -166,14 +205,19 @@ __global__ void k_jet2_rows_fixup(const int* __restrict__ rowptr, int64_t Q, con
     }
 }
 
-template <int NH, int MODE>
+// D: Jet2Dirs (host directions by value) or Jet2QDirs (per-query directions on the device) -- the kernel follows the type
+template <int NH, int MODE, class D>
 int launch_jet2_rows(const MlpPtrs& p, const float* y_pos, const float* x_pos, const float* f_y, const float* ttab, const int* src_s,
-                     const Jet2Rows& rows, int64_t E, const Jet2Dirs& dirs, float* out, float* d1, float* d2, hipStream_t st) {
+                     const Jet2Rows& rows, int64_t E, const D& dirs, float* out, float* d1, float* d2, hipStream_t st) {
     constexpr size_t lds = Jet2Lds<NH>::bytes_rows;
-    auto kern = k_gno_fwd_rows_jet2<NH, MODE>;
+    constexpr bool QD = std::is_same_v<D, Jet2QDirs>;
+    auto kern = [] {
+        if constexpr (QD) return k_gno_qd_jet2_rows<NH, MODE>;
+        else return k_gno_fwd_rows_jet2<NH, MODE>;
+    }();
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) {
-        gaot_set_error("gaot_gno_fwd_jet2: cannot set dynamic LDS %zu: %s", lds, hipGetErrorString(e));
+        gaot_set_error("gaot_gno_fwd_jet2%s: cannot set dynamic LDS %zu: %s", QD ? "_qd" : "", lds, hipGetErrorString(e));
         return GAOT_ERR_LAUNCH;
     }
     const int64_t n_tiles = ceil_div(E, 32);
@@ -182,14 +226,18 @@ int launch_jet2_rows(const MlpPtrs& p, const float* y_pos, const float* x_pos, c
     return GAOT_OK;
 }
 
-template <int NH, int MODE>
+template <int NH, int MODE, class D>
 int launch_jet2(const MlpPtrs& p, const float* y_pos, const float* x_pos, const float* f_y, const float* ttab, const int* nbr, int lk,
-                int64_t E, const Jet2Dirs& dirs, float* out, float* d1, float* d2, hipStream_t st) {
+                int64_t E, const D& dirs, float* out, float* d1, float* d2, hipStream_t st) {
     constexpr size_t lds = Jet2Lds<NH>::bytes;
-    auto kern = k_gno_fwd_knn_jet2<NH, MODE>;
+    constexpr bool QD = std::is_same_v<D, Jet2QDirs>;
+    auto kern = [] {
+        if constexpr (QD) return k_gno_qd_jet2_knn<NH, MODE>;
+        else return k_gno_fwd_knn_jet2<NH, MODE>;
+    }();
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) {
-        gaot_set_error("gaot_gno_fwd_knn_jet2: cannot set dynamic LDS %zu: %s", lds, hipGetErrorString(e));
+        gaot_set_error("gaot_gno_fwd_knn_jet2%s: cannot set dynamic LDS %zu: %s", QD ? "_qd" : "", lds, hipGetErrorString(e));
         return GAOT_ERR_LAUNCH;
     }
     const int64_t n_tiles = ceil_div(E, 32);
@@ -297,6 +345,110 @@ extern "C" int gaot_gno_fwd_jet2(const gaot_mlp_t* mlp, int mode, const float* y
     dv.nd = nd;
     for (int d = 0; d < MAXD; ++d)
         for (int c = 0; c < 3; ++c) dv.v[d][c] = d < nd ? dirs[d * 3 + c] : 0.f;
+    hipStream_t st = (hipStream_t)stream;
+    const Jet2Rows rows{dst_sorted, rowptr_dst, (float*)workspace, num_queries * C, ceil_div(num_edges, 32) * 2 * C};
+    if (num_edges > 0) {
+        int rc = GAOT_OK;
+#define GNO_JET2_CASE(NH_, MODE_)                                                                                               \
+    case NH_ * 3 + MODE_:                                                                                                       \
+        rc = launch_jet2_rows<NH_, MODE_>(p, y_pos, x_pos, f_y, src_table, src_sorted, rows, num_edges, dv, out, d1, d2, st);   \
+        break;
+#define GNO_JET2_CASES(NH_) GNO_JET2_CASE(NH_, MODE_LINEAR) GNO_JET2_CASE(NH_, MODE_NONLINEAR) GNO_JET2_CASE(NH_, MODE_KERNELONLY)
+        switch (mlp->n_hidden * 3 + mode) {
+            GNO_JET2_CASES(1) GNO_JET2_CASES(2) GNO_JET2_CASES(3) GNO_JET2_CASES(4)
+        }
+#undef GNO_JET2_CASES
+#undef GNO_JET2_CASE
+        if (rc != GAOT_OK) return rc;
+    }
+    // empty rows -> 0 and the rows that straddle tiles, all 1 + 2 nd planes (num_edges == 0: this launch alone)
+    GAOT_KLAUNCH(k_jet2_rows_fixup, dim3(segment_fixup_grid(num_queries * 8)), dim3(256), 0, st, rowptr_dst, num_queries, rows.part,
+                 rows.part_plane, nd, out, d1, d2);
+    GAOT_LAUNCH_CHECK();
+    return GAOT_OK;
+}
+
+// ---- per-query directions: `qdirs` is a DEVICE array [num_queries][nd][3] the kernel reads (no host read: capturable) ------------------
+extern "C" int gaot_gno_fwd_knn_jet2_qd(const gaot_mlp_t* mlp, int mode, const float* y_pos, const float* x_pos, const float* f_y,
+                                        const float* src_table, const int32_t* nbr, int k, int64_t num_queries, const float* qdirs,
+                                        int nd, float* out, float* d1, float* d2, gaot_stream_t stream) {
+    GAOT_ENTER();
+    GAOT_CHECK_ARG(mlp, "null mlp");
+    if (!(mlp->channels == C && mlp->hidden == H && mlp->n_hidden >= 1 && mlp->n_hidden <= 4)) {
+        gaot_set_error("gaot_gno_fwd_knn_jet2_qd: unsupported MLP shape (n_hidden=%d hidden=%d channels=%d)", mlp->n_hidden, mlp->hidden,
+                       mlp->channels);
+        return GAOT_ERR_UNSUPPORTED;
+    }
+    GAOT_CHECK_ARG(mode == MODE_LINEAR || mode == MODE_NONLINEAR || mode == MODE_KERNELONLY,
+                   "mode must be 0 (linear), 1 (nonlinear) or 2 (nonlinear_kernelonly)");
+    GAOT_CHECK_ARG(k == 1 || k == 2 || k == 4 || k == 8 || k == 16 || k == 32, "k must be 1, 2, 4, 8, 16 or 32 (a divisor of the 32-edge tile)");
+    GAOT_CHECK_ARG(nd >= 1 && nd <= MAXD, "nd must be 1..6 directions");
+    GAOT_CHECK_ARG(num_queries >= 0, "negative size");
+    GAOT_CHECK_ARG(num_queries <= (int64_t)INT32_MAX / k, "num_queries * k beyond int32 (sample the queries in chunks)");
+    if (num_queries > 0) {
+        GAOT_CHECK_ARG(qdirs, "null qdirs");
+        GAOT_CHECK_ARG(y_pos && x_pos && nbr && out && d1 && d2 && (f_y || mode == MODE_KERNELONLY), "null pointer");
+        GAOT_CHECK_ARG(mode == MODE_LINEAR || src_table, "null src_table");
+    }
+    MlpPtrs p;
+    for (int l = 0; l <= mlp->n_hidden; ++l) {
+        p.w[l] = mlp->weight[l];
+        p.b[l] = mlp->bias[l];
+        GAOT_CHECK_ARG(p.w[l] && p.b[l], "null MLP parameter");
+    }
+    if (num_queries == 0) return GAOT_OK;
+    const Jet2QDirs dv{qdirs, nd};
+    hipStream_t st = (hipStream_t)stream;
+    const int lk = __builtin_ctz((unsigned)k);
+    const int64_t num_edges = num_queries * k;
+    int rc = GAOT_OK;
+#define GNO_JET2_CASE(NH_, MODE_)                                                                                      \
+    case NH_ * 3 + MODE_:                                                                                              \
+        rc = launch_jet2<NH_, MODE_>(p, y_pos, x_pos, f_y, src_table, nbr, lk, num_edges, dv, out, d1, d2, st);        \
+        break;
+#define GNO_JET2_CASES(NH_) GNO_JET2_CASE(NH_, MODE_LINEAR) GNO_JET2_CASE(NH_, MODE_NONLINEAR) GNO_JET2_CASE(NH_, MODE_KERNELONLY)
+    switch (mlp->n_hidden * 3 + mode) {
+        GNO_JET2_CASES(1) GNO_JET2_CASES(2) GNO_JET2_CASES(3) GNO_JET2_CASES(4)
+    }
+#undef GNO_JET2_CASES
+#undef GNO_JET2_CASE
+    if (rc != GAOT_OK) return rc;
+    GAOT_LAUNCH_CHECK();
+    return GAOT_OK;
+}
+
+extern "C" int gaot_gno_fwd_jet2_qd(const gaot_mlp_t* mlp, int mode, const float* y_pos, const float* x_pos, const float* f_y,
+                                    const float* src_table, const int32_t* src_sorted, const int32_t* dst_sorted,
+                                    const int32_t* rowptr_dst, int64_t num_edges, int64_t num_queries, const float* qdirs, int nd,
+                                    float* out, float* d1, float* d2, void* workspace, size_t workspace_bytes, gaot_stream_t stream) {
+    GAOT_ENTER();
+    GAOT_CHECK_ARG(mlp, "null mlp");
+    if (!(mlp->channels == C && mlp->hidden == H && mlp->n_hidden >= 1 && mlp->n_hidden <= 4)) {
+        gaot_set_error("gaot_gno_fwd_jet2_qd: unsupported MLP shape (n_hidden=%d hidden=%d channels=%d)", mlp->n_hidden, mlp->hidden,
+                       mlp->channels);
+        return GAOT_ERR_UNSUPPORTED;
+    }
+    GAOT_CHECK_ARG(mode == MODE_LINEAR || mode == MODE_NONLINEAR || mode == MODE_KERNELONLY,
+                   "mode must be 0 (linear), 1 (nonlinear) or 2 (nonlinear_kernelonly)");
+    GAOT_CHECK_ARG(nd >= 1 && nd <= MAXD, "nd must be 1..6 directions");
+    GAOT_CHECK_ARG(num_edges >= 0 && num_queries >= 0, "negative size");
+    GAOT_CHECK_ARG(num_edges <= (int64_t)INT32_MAX, "num_edges beyond int32 (sample the queries in chunks)");
+    GAOT_CHECK_ARG(rowptr_dst && (num_queries == 0 || (out && d1 && d2)), "null pointer");
+    if (num_edges > 0) {
+        GAOT_CHECK_ARG(num_queries == 0 || qdirs, "null qdirs");
+        GAOT_CHECK_ARG(y_pos && x_pos && src_sorted && dst_sorted && (f_y || mode == MODE_KERNELONLY), "null pointer");
+        GAOT_CHECK_ARG(mode == MODE_LINEAR || src_table, "null src_table");
+        GAOT_CHECK_ARG(workspace, "null workspace");
+    }
+    GAOT_CHECK_ARG(workspace_bytes >= gaot_gno_fwd_jet2_workspace_bytes(num_edges, nd), "workspace too small");
+    MlpPtrs p;
+    for (int l = 0; l <= mlp->n_hidden; ++l) {
+        p.w[l] = mlp->weight[l];
+        p.b[l] = mlp->bias[l];
+        GAOT_CHECK_ARG(p.w[l] && p.b[l], "null MLP parameter");
+    }
+    if (num_queries == 0) return GAOT_OK;
+    const Jet2QDirs dv{qdirs, nd};
     hipStream_t st = (hipStream_t)stream;
     const Jet2Rows rows{dst_sorted, rowptr_dst, (float*)workspace, num_queries * C, ceil_div(num_edges, 32) * 2 * C};
     if (num_edges > 0) {

@@ -2,7 +2,9 @@
 // and k_gno_fwd_rows_jet2 (ragged rows, R = true).  Textual inclusion, not a shared __device__ function: inlined from a function the
 // regular-list kernels load their by-value arguments at other places and come out with other instruction streams; as statements of
 // the kernel itself they are the kernels they were.  In scope: NH, MODE, R, the kernel's arguments mlp, y_pos, x_pos, f_y, ttab, nbr,
-// lk, E, dirs, out, d1, d2 and a Jet2Rows `rows` (read only where R).
+// lk, E, dirs, out, d1, d2 and a Jet2Rows `rows` (read only where R), and QD: false with `dirs` a by-value Jet2Dirs, true in the two
+// per-query kernels k_gno_qd_jet2_knn / k_gno_qd_jet2_rows, where `dirs` is a Jet2QDirs and the direction of a lane is that of its
+// edge's query.
     using L = Jet2Lds<NH>;
     constexpr bool KEEP = NH <= 2;   // what the value path leaves for the direction passes (see the head of this file)
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -176,7 +178,26 @@
         // ---- one pass per direction: h' and h'' through the layers, two planes staged, one finished by each half ----
 #pragma unroll 1
         for (int d = 0; d < dirs.nd; ++d) {
-            const float vx = dir_at(dirs, d, 0), vy = dir_at(dirs, d, 1), vz = dir_at(dirs, d, 2);
+            float vx, vy, vz;
+            if constexpr (QD) {
+                // the lane's edge is base + l31 in both halves; its query is found again here (an LDS word / a shift), so that no
+                // register is held across the value path and the layer loops: query 0 for edges past E and padding edges
+                int q;
+                if constexpr (R) {
+                    q = qids[l31];
+                    q = q < 0 ? 0 : q;
+                } else {
+                    q = base + l31 < E ? (int)((base + l31) >> lk) : 0;
+                }
+                const float* v = qdir_at(dirs, ((int64_t)q * dirs.nd + d) * 3);
+                vx = v[0];
+                vy = v[1];
+                vz = v[2];
+            } else {
+                vx = dir_at(dirs, d, 0);
+                vy = dir_at(dirs, d, 1);
+                vz = dir_at(dirs, d, 2);
+            }
             f32x16 hd[KB], hdd[KB];
 #pragma unroll
             for (int ob = 0; ob < KB; ++ob)

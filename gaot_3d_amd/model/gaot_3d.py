@@ -201,6 +201,19 @@ class GAOT3D(nn.Module):
         lat = self._one_sample("sample_laplacian_rows", latent, tokens_pos)
         return self.decoder.sample_laplacian_rows(latent, query_pos.to(latent.device), lat, chunk_points=chunk_points)
 
+    def sample_directional(self, latent: torch.Tensor, query_pos: torch.Tensor, dirs: torch.Tensor,
+                           tokens_pos: Optional[torch.Tensor] = None, chunk_points: Optional[int] = None):
+        """Derivatives of the field along PER-QUERY directions: -> (pred [Nq, output_size], d1 [Nq, output_size, nd],
+        d2 [Nq, output_size, nd]) with d1[q, o, i] = v . grad pred[q, o] and d2[q, o, i] = v^T (Hessian of pred[q, o]) v for
+        v = dirs[q, i] -- the wall-normal derivative d p / d n and d^2 p / d n^2 of a surface field from the query points' normals, the
+        tangential gradient and the tangential part D^2_{t1} + D^2_{t2} of the Laplacian in a local frame (n, t1, t2).  ``dirs``:
+        float32 [Nq, nd, 3] on the queries' device, 1 <= nd <= 6 ([Nq, 3]: one direction), used as given (no normalisation).  Three
+        chains through the per-edge MLP for one direction where ``sample_hessian`` runs 13.  ``MAGNODecoder.sample_directional``:
+        'knn' decoders on the regular lists (capturable), 'radius' / 'bidirectional' on row lists; exact fp32 in both precision
+        modes, outside autograd; configurations that do not stream raise NotImplementedError, a bad ``dirs`` ValueError."""
+        lat = self._one_sample("sample_directional", latent, tokens_pos)
+        return self.decoder.sample_directional(latent, query_pos.to(latent.device), dirs, lat, chunk_points=chunk_points)
+
     def forward(self, batch, tokens_pos: Optional[torch.Tensor] = None, tokens_batch_idx: Optional[torch.Tensor] = None,
                 query_coord_pos: Optional[torch.Tensor] = None, query_coord_batch_idx: Optional[torch.Tensor] = None,
                 condition: Optional[float] = None) -> torch.Tensor:

@@ -24,7 +24,8 @@ per-edge MLP beside the value, exact fp32) -- what ``MAGNODecoder.sample_jacobia
 ragged by-query list of any graph (``gaot_gno_fwd_jac``: the tangent kernel finished by the forward's segmented walk and one fix-up
 launch) -- what ``sample_jacobian(row_lists=True)`` streams for 'radius' / 'bidirectional' decoders.  ``jet2_knn`` and ``jet2_rows``
 carry directional 2-jets (value, D_v, D_v^2) on the same two kinds of list (``gaot_gno_fwd_knn_jet2`` / ``gaot_gno_fwd_jet2``) -- what
-``sample_hessian`` / ``sample_laplacian`` and their ``_rows`` variants stream.
+``sample_hessian`` / ``sample_laplacian`` and their ``_rows`` variants stream; ``jet2_knn_qd`` and ``jet2_rows_qd`` carry them along a
+direction set of every query's own (``gaot_gno_fwd_knn_jet2_qd`` / ``gaot_gno_fwd_jet2_qd``) -- what ``sample_directional`` streams.
 HIP only, no CPU fallback."""
 from typing import Optional
 
@@ -199,9 +200,22 @@ class IntegralTransform(nn.Module):
         exactly when ``_fused_plan`` is not None and raises NotImplementedError otherwise.  Nothing is recorded for autograd."""
         return self._on_lists("jet2_rows", y_pos, x_pos, f_y, graph, 2, dirs)
 
-    def _on_lists(self, fn, y_pos, x_pos, f_y, lists, order: int, dirs=None):
-        """The five list methods: the forward-mode routes on the regular list ``lists`` = (nbr, k) or on the by-query list of the graph
-        ``lists``, at ``order`` 0 (value), 1 (and Jacobian) or 2 (and 2-jets along ``dirs``) -> the tuple of planes, channels last:
+    def jet2_knn_qd(self, y_pos, x_pos, nbr, k: int, f_y: Optional[torch.Tensor], qdirs: torch.Tensor):
+        """``jet2_knn`` along PER-QUERY directions: ``qdirs`` is a fp32 device tensor [N_x, nd, 3] (1..6 directions per query, used as
+        given) -> (out [N_x, C], d1 [nd, N_x, C], d2 [nd, N_x, C]) with d1[i, q] / d2[i, q] along qdirs[q, i].  One
+        ``ops.gno_forward_knn_jet2_qd`` launch per 32-channel pass, the operands prepared exactly as in ``jet2_knn``; the rows of
+        query q are ``jet2_knn``'s with q's directions, bit for bit."""
+        return self._on_lists("jet2_knn_qd", y_pos, x_pos, f_y, (nbr, k), 2, qdirs, qd=True)
+
+    def jet2_rows_qd(self, y_pos, x_pos, f_y: Optional[torch.Tensor], graph, qdirs: torch.Tensor):
+        """``jet2_rows`` along PER-QUERY directions ``qdirs`` [N_x, nd, 3] (``jet2_knn_qd``): one ``ops.gno_forward_jet2_qd`` call (the
+        jet kernel and its fix-up) per 32-channel pass, the operands prepared exactly as in ``jet2_rows``."""
+        return self._on_lists("jet2_rows_qd", y_pos, x_pos, f_y, graph, 2, qdirs, qd=True)
+
+    def _on_lists(self, fn, y_pos, x_pos, f_y, lists, order: int, dirs=None, qd: bool = False):
+        """The seven list methods: the forward-mode routes on the regular list ``lists`` = (nbr, k) or on the by-query list of the graph
+        ``lists``, at ``order`` 0 (value), 1 (and Jacobian) or 2 (and 2-jets along ``dirs``: host values [nd][3], or with ``qd`` a
+        device tensor [N_x, nd, 3] of per-query directions) -> the tuple of planes, channels last:
         (out [N_x, c],), (out, jac [3, N_x, c]) or (out, d1 [nd, N_x, c], d2 [nd, N_x, c]).  Every pass of ``_fused_passes`` is one call
         of the route's ``ops.gno_forward_*`` function; a pass is cut to its channels and the passes are concatenated.  Nothing is
         recorded for autograd; ``fn`` names the public method in the refusal."""
@@ -217,6 +231,8 @@ class IntegralTransform(nn.Module):
                                           + ("; use forward() with an edge_index" if order == 0 else ""))
             run = {(True, 0): ops.gno_forward_knn, (True, 1): ops.gno_forward_knn_jac, (True, 2): ops.gno_forward_knn_jet2,
                    (False, 1): ops.gno_forward_jac, (False, 2): ops.gno_forward_jet2}[knn, order]
+            if qd:                                 # order 2 along per-query directions: ``dirs`` is the device tensor [N_x, nd, 3]
+                run = ops.gno_forward_knn_jet2_qd if knn else ops.gno_forward_jet2_qd
             tail = ((lists[0], int(lists[1])) if knn else (lists,)) + ((dirs,) if order == 2 else ())
             y3, x3, t, (w0, b0, *mid), blocks = self._fused_passes(fcs, y_pos, x_pos, f_y, *plan)
             outs = []

@@ -230,25 +230,41 @@ def _softmax_weight_jets(w, dl, second=False):
     return dw, ddw
 
 
+def _logit_tangent_rows(dls, v):
+    """the logit tangent along a PER-ROW direction: l'_v = sum_c v[:, c] * d_c l from the axis tangents ``dls`` (``_logit_tangents``),
+    ``v`` [n, 3], summed in the order c = 0, 1, 2 -> [n, scales].  Per-row operations: a row's result does not depend on the other
+    rows; a row whose direction is an axis gets that axis tangent itself (products with 1 and sums with 0 are exact)."""
+    dl = v[:, 0:1] * dls[0]
+    for c in range(1, min(len(dls), v.shape[1])):
+        dl = dl + v[:, c:c + 1] * dls[c]
+    return dl
+
+
 def _mix_jet2_planes(w, dls, outs, d1s, d2s, dirs, second=True):
     """The softmax-weighted mix of the scales' 2-jets: ``w`` [n, scales], ``dls`` the logit tangents along the coordinate axes
     (``_logit_tangents``), ``outs[s]`` [n, C] and ``d1s[s]`` / ``d2s[s]`` [nd, n, C] the value, D_v and D_v^2 planes of scale s along
     ``dirs`` (host values [nd][3]) -> (D_v mix per direction, D_v^2 mix per direction, w' per direction, w'' per direction):
         D_v mix = sum_s (w_s D_v o_s + w'_s o_s),     D_v^2 mix = sum_s (w_s D_v^2 o_s + 2 w'_s D_v o_s + w''_s o_s)
     with l'_v = sum_c v_c d_c l formed from the axis tangents (an axis direction: that tangent itself; e_i + e_j: their sum).  Per-row
-    operations with the sums over the scales written term by term, in the dtype of the operands.  Without ``second`` (first order:
+    operations with the sums over the scales written term by term, in the dtype of the operands.  ``dirs`` may also be a TENSOR
+    [n, nd, 3] of per-row directions: then l'_v is the per-row expression of ``_logit_tangent_rows`` and everything after it is the
+    same code (rows whose directions are the axes get the axis results bit for bit).  Without ``second`` (first order:
     ``d2s`` is not read) neither w'' nor a D_v^2 mix is formed: no second-order plane is returned and every w'' is None."""
     ns = len(outs)
     p1, p2, dws, ddws = [], [], [], []
-    for i, v in enumerate(dirs):
-        dl = None
-        for c, vc in enumerate(v):
-            if vc == 0.0 or c >= len(dls):
-                continue
-            term = dls[c] if vc == 1.0 else vc * dls[c]
-            dl = term if dl is None else dl + term
-        if dl is None:
-            dl = torch.zeros_like(w)
+    per_row = isinstance(dirs, torch.Tensor)            # PER-ROW directions [n, nd, 3] (``sample_directional``)
+    for i in range(dirs.shape[1]) if per_row else range(len(dirs)):
+        if per_row:
+            dl = _logit_tangent_rows(dls, dirs[:, i])
+        else:
+            dl = None
+            for c, vc in enumerate(dirs[i]):
+                if vc == 0.0 or c >= len(dls):
+                    continue
+                term = dls[c] if vc == 1.0 else vc * dls[c]
+                dl = term if dl is None else dl + term
+            if dl is None:
+                dl = torch.zeros_like(w)
         dw, ddw = _softmax_weight_jets(w, dl, second=second)
         a1 = a2 = None
         for s in range(ns):
@@ -266,8 +282,13 @@ def _mix_jet2_planes(w, dls, outs, d1s, d2s, dirs, second=True):
     return p1, p2, dws, ddws
 
 
+def _num_dirs(dirs) -> int:
+    """the number of directions: host values [nd][3], or a tensor [n, nd, 3] of per-row directions"""
+    return int(dirs.shape[1]) if isinstance(dirs, torch.Tensor) else len(dirs)
+
+
 def _mix_scales_jet2(module, outs, d1s, d2s, pos, dirs):
-    """``_mix_scales`` with its jets along ``dirs``: ``outs[s]`` [n, C], ``d1s[s]`` / ``d2s[s]`` [nd, n, C] of every scale
+    """``_mix_scales`` with its jets along ``dirs`` (host values [nd][3] or per-row directions [n, nd, 3]):``outs[s]`` [n, C], ``d1s[s]`` / ``d2s[s]`` [nd, n, C] of every scale
     -> [value, D_v per direction ..., D_v^2 per direction ...], [n, C] each; FIRST ORDER with ``d2s`` None: [value, D_v per direction ...]
     and nothing of second order is computed.  The value is ``_mix_scales``'s bit for bit, and a direction's D_v plane does not depend
     on the order.  Summed scales: the sum of each plane; one scale: the planes as they are.  Softmax weights w = softmax(l),
@@ -275,7 +296,7 @@ def _mix_scales_jet2(module, outs, d1s, d2s, pos, dirs):
     lists, so neither sum_s w'_s o_s nor sum_s w''_s o_s vanishes (``_mix_jet2_planes``); the logits are piecewise linear in the
     position (l'' = 0 away from the ReLU kinks of the weighting MLP).  Per-row fp32 operations only (the row kernels and elementwise
     torch ops): a row's result does not depend on the chunk it is in."""
-    ns, nd = len(outs), len(dirs)
+    ns, nd = len(outs), _num_dirs(dirs)
     jets = [d1s] if d2s is None else [d1s, d2s]
     if ns == 1:
         return [outs[0]] + [p for js in jets for p in js[0].unbind(0)]
@@ -660,12 +681,15 @@ class MAGNODecoder(nn.Module):
 
     def _jet_planes(self, rndata_flat, q, lat, lists, dirs=None):
         """The mixed GNO planes of one chunk, [value, D_v per direction ..., D_v^2 per direction ...] along ``dirs``; first order with
-        ``dirs`` None: [value, d/dx, d/dy, d/dz].  On the regular list every scale sees the same rows and the mix is of equal operands
+        ``dirs`` None: [value, d/dx, d/dy, d/dz]; ``dirs`` a tensor [n, nd, 3]: every query's own directions.  On the regular list every scale sees the same rows and the mix is of equal operands
         (``_mix_equal_scales``); on row lists every scale has its own and the mix carries the jets of its weights (``_mix_scales_jet2``)."""
+        qd = isinstance(dirs, torch.Tensor)       # per-query directions [n, nd, 3] (``sample_directional``): the ..._qd kernels
         if isinstance(lists, tuple):
-            jets = self.gno.jacobian_knn(lat, q, *lists, rndata_flat) if dirs is None else self.gno.jet2_knn(lat, q, *lists, rndata_flat, dirs)
+            jet2 = self.gno.jet2_knn_qd if qd else self.gno.jet2_knn
+            jets = self.gno.jacobian_knn(lat, q, *lists, rndata_flat) if dirs is None else jet2(lat, q, *lists, rndata_flat, dirs)
             return self._mix_equal_scales([jets[0]] + [p for js in jets[1:] for p in js.unbind(0)], q)
-        jets = [self.gno.jacobian_rows(lat, q, rndata_flat, rows) if dirs is None else self.gno.jet2_rows(lat, q, rndata_flat, rows, dirs)
+        jet2 = self.gno.jet2_rows_qd if qd else self.gno.jet2_rows
+        jets = [self.gno.jacobian_rows(lat, q, rndata_flat, rows) if dirs is None else jet2(lat, q, rndata_flat, rows, dirs)
                 for rows in lists]
         outs, d1s = [j[0] for j in jets], [j[1] for j in jets]
         d2s = None if dirs is None else [j[2] for j in jets]
@@ -675,7 +699,7 @@ class MAGNODecoder(nn.Module):
         """one chunk of queries: -> (d1, d2) [n, out_channels, nd], the jets of the prediction along ``dirs`` (``_jet_planes``, then the
         projection's jets), the value written into ``pred``.  A call of its own, so that a chunk's GNO planes are freed before the next
         chunk's are allocated."""
-        nd = len(dirs)
+        nd = _num_dirs(dirs)
         planes = self._jet_planes(rndata_flat, q, lat, lists, dirs)
         d1 = self._new(pred, q.shape[0], nd)
         d2 = torch.empty_like(d1)
@@ -774,6 +798,59 @@ class MAGNODecoder(nn.Module):
         if self.decoder_strategy == "knn":
             return self.sample_laplacian(rndata_flat, query_pos, latent_tokens_pos, chunk_points=chunk_points)
         return self._laplacian("sample_laplacian_rows", rndata_flat, query_pos, latent_tokens_pos, chunk_points, True)
+
+    @staticmethod
+    def _query_dirs(fn, dirs, query_pos):
+        """``sample_directional``'s directions as a contiguous [Nq, nd, 3] tensor ([Nq, 3]: nd = 1); ValueError for everything else"""
+        nq = int(query_pos.shape[0])
+        if not isinstance(dirs, torch.Tensor):
+            raise ValueError(f"{fn}: dirs must be a float32 tensor [{nq}, nd, 3] or [{nq}, 3], got {type(dirs).__name__}")
+        if dirs.dtype != torch.float32 or dirs.device != query_pos.device:
+            raise ValueError(f"{fn}: dirs must be float32 on the queries' device ({query_pos.device}), got {dirs.dtype} on {dirs.device}")
+        if dirs.dim() == 2:
+            dirs = dirs[:, None, :]
+        if dirs.dim() != 3 or dirs.shape[0] != nq:
+            raise ValueError(f"{fn}: dirs must hold the directions of the {nq} queries, [{nq}, nd, 3] or [{nq}, 3], got {tuple(dirs.shape)}")
+        if dirs.shape[2] != 3:
+            raise ValueError(f"{fn}: a direction has 3 components, got dirs {tuple(dirs.shape)}")
+        if not 1 <= dirs.shape[1] <= 6:
+            raise ValueError(f"{fn}: 1..6 directions per query, got nd = {dirs.shape[1]}")
+        return dirs.detach().contiguous()
+
+    @torch.no_grad()
+    def sample_directional(self, rndata_flat, query_pos, dirs, latent_tokens_pos, chunk_points: Optional[int] = None):
+        """Derivatives of the field along PER-QUERY directions -- the wall-normal derivative d/dn and d^2/dn^2 of a surface field, the
+        derivatives in a local frame (n, t_1, t_2): -> (pred [Nq, out_channels], d1 [Nq, out_channels, nd], d2 [Nq, out_channels, nd])
+        with d1[q, o, i] = sum_d v[d] d pred[q, o] / d query_pos[q, d] and d2[q, o, i] = v^T (d^2 pred[q, o] / d query_pos[q]^2) v for
+        v = dirs[q, i], every query's neighbour list held fixed (valid almost everywhere, with the caveats of ``sample_hessian`` /
+        ``sample_hessian_rows``).  ``dirs``: float32 [Nq, nd, 3] on the queries' device, 1 <= nd <= 6 ([Nq, 3]: nd = 1), used AS GIVEN
+        -- no normalisation, d1 is linear and d2 quadratic in a direction's length.
+
+        One value chain and two per direction through the per-edge MLP (``sample_hessian`` runs 13 for v^T H v of any v): the jet
+        kernels with the direction of a pass loaded per lane from ``dirs`` (``jet2_knn_qd`` / ``jet2_rows_qd``), then the scale mix and
+        the projection's jets exactly as in ``sample_hessian`` / ``sample_hessian_rows``; on row lists with softmax scale weights the
+        logit tangent is formed along every row's own direction (``_logit_tangent_rows``).  The route follows the decoder strategy:
+        'knn' (k_neighbors in ``ops.GNO_KNN_K``) the regular lists -- no host synchronisation, capturable after one eager call, and
+        since ``dirs`` is read on the device a replay sees the directions then in the tensor; 'radius', and 'bidirectional' with
+        k_neighbors <= ``graph.QUERY_LIST_MAX_K``, row lists -- GaotError inside a stream capture, before any launch.  Exact fp32 in
+        both precision modes, outside autograd, results independent of ``chunk_points``.  With the three axes as every query's
+        directions ``pred`` / ``d1`` are ``sample_jacobian``'s (``row_lists=True``) and ``d2`` is the diagonal of ``sample_hessian``'s
+        (``_rows``) Hessian, bit for bit, softmax scale weights included.
+
+        Streams under exactly the conditions of ``sample_hessian`` resp. ``sample_hessian_rows`` and raises their NotImplementedError
+        otherwise; 'reverse' and a non-positive ``chunk_points`` raise ValueError, and so does a ``dirs`` that is not float32, is on
+        another device, or is not [Nq, 1..6, 3]."""
+        fn = "sample_directional"
+        self._sample_args(fn, chunk_points)
+        dirs = self._query_dirs(fn, dirs, query_pos)
+        rndata_flat, query_pos = rndata_flat.detach(), query_pos.detach()
+        rows = self.decoder_strategy != "knn"
+        grid, chunk = self._jet2_stream(fn, rndata_flat, query_pos, latent_tokens_pos, chunk_points, rows=rows)
+        nq, nd = int(query_pos.shape[0]), int(dirs.shape[1])
+        pred, d1, d2 = self._new(rndata_flat, nq), self._new(rndata_flat, nq, nd), self._new(rndata_flat, nq, nd)
+        for sl, q, lists in self._stream_chunks(grid, query_pos, chunk, "rows" if rows else "knn"):
+            d1[sl], d2[sl] = self._jet2_chunk(rndata_flat, q, latent_tokens_pos, lists, dirs[sl], pred[sl])
+        return pred, d1, d2
 
     def sample_jacobian(self, rndata_flat, query_pos, latent_tokens_pos, chunk_points: Optional[int] = None,
                         row_lists: bool = False):

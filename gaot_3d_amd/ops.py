@@ -438,6 +438,55 @@ def gno_forward_jet2(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: O
     return out, d1, d2
 
 
+def _query_dirs(fn, qdirs, x_pos: Tensor, q: int):
+    """per-query directions as a contiguous fp32 DEVICE tensor [q, nd, 3] on the queries' device -> (qdirs, nd); the range of nd is
+    the entry point's check"""
+    if not isinstance(qdirs, Tensor) or qdirs.dtype != torch.float32 or qdirs.device != x_pos.device:
+        raise GaotError(f"{fn}: qdirs must be a float32 tensor on {x_pos.device} (per-query directions are read by the kernel)")
+    if qdirs.dim() != 3 or qdirs.shape[0] != q or qdirs.shape[2] != 3:
+        raise GaotError(f"{fn}: qdirs must be [{q}, nd, 3], got {tuple(qdirs.shape)}")
+    return qdirs.contiguous(), int(qdirs.shape[1])
+
+
+def gno_forward_knn_jet2_qd(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], src_table: Optional[Tensor],
+                            nbr: Tensor, k: int, qdirs: Tensor):
+    """``gno_forward_knn_jet2`` along PER-QUERY directions (gaot_gno_fwd_knn_jet2_qd): ``qdirs`` is a DEVICE tensor [n_query, nd, 3]
+    (1..6 directions per query, used as given) -> (out [n_query, 32], d1 [nd, n_query, 32], d2 [nd, n_query, 32]) with
+    d1[i, q] = D_v out[q] and d2[i, q] = D_v^2 out[q] along v = qdirs[q, i].  One launch, exact fp32 whatever the precision mode, no
+    host read of the directions (capturable).  Per edge the operations of ``gno_forward_knn_jet2`` in its order: the rows of query q
+    are that call's with q's directions, bit for bit; a direction slot's planes do not depend on the other slots; a zero direction
+    gives zeros.  Operands and their checks are those of ``gno_forward_knn_jet2``."""
+    lib = _lib.load()
+    md, m, keep, y_pos, x_pos, f_y, src_table, (nbr, k), q = _gno_mode_args("gno_forward_knn_jet2_qd", mode, weights, biases, y_pos,
+                                                                            x_pos, f_y, src_table, (nbr, k))
+    qdirs, nd = _query_dirs("gno_forward_knn_jet2_qd", qdirs, x_pos, q)
+    out, d1, d2 = _gno_planes(x_pos, q, m, nd, nd)
+    with _timed(f"gno_jet2_knn_qd{f'_nl{md}' if md else ''}_nh{m.n_hidden}_d{nd}"):
+        check(lib.gaot_gno_fwd_knn_jet2_qd(C.byref(m), md, _ptr(y_pos), _ptr(x_pos), _ptr(f_y), _ptr(src_table), _ptr(nbr), k, q,
+                                           _ptr(qdirs), nd, _ptr(out), _ptr(d1), _ptr(d2), _stream()), "gaot_gno_fwd_knn_jet2_qd")
+    return out, d1, d2
+
+
+def gno_forward_jet2_qd(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], src_table: Optional[Tensor],
+                        g: BipartiteGraph, qdirs: Tensor):
+    """``gno_forward_jet2`` (RAGGED rows) along PER-QUERY directions (gaot_gno_fwd_jet2_qd): ``qdirs`` as in
+    ``gno_forward_knn_jet2_qd`` -> (out [n_query, 32], d1 [nd, n_query, 32], d2 [nd, n_query, 32]); an empty row gives exact zeros in
+    all 1 + 2 nd planes.  Two launches (the jet kernel and one fix-up over all planes), the workspace of ``gno_forward_jet2``; on a
+    list of equal rows of k in ``GNO_KNN_K`` edges every plane is ``gno_forward_knn_jet2_qd``'s, bit for bit."""
+    lib = _lib.load()
+    md, m, keep, y_pos, x_pos, f_y, src_table, g, q = _gno_mode_args("gno_forward_jet2_qd", mode, weights, biases, y_pos, x_pos, f_y,
+                                                                     src_table, g)
+    qdirs, nd = _query_dirs("gno_forward_jet2_qd", qdirs, x_pos, q)
+    e = g.by_dst.num_edges
+    out, d1, d2 = _gno_planes(x_pos, q, m, nd, nd)
+    ws = _ws(lib.gaot_gno_fwd_jet2_workspace_bytes(e, min(max(nd, 0), 6)), x_pos.device)
+    with _timed(f"gno_jet2_rows_qd{f'_nl{md}' if md else ''}_nh{m.n_hidden}_d{nd}"):
+        check(lib.gaot_gno_fwd_jet2_qd(C.byref(m), md, _ptr(y_pos), _ptr(x_pos), _ptr(f_y), _ptr(src_table), _ptr(g.by_dst.other),
+                                       _ptr(g.by_dst.key), _ptr(g.by_dst.rowptr), e, q, _ptr(qdirs), nd, _ptr(out), _ptr(d1), _ptr(d2),
+                                       _ptr(ws), ws.numel(), _stream()), "gaot_gno_fwd_jet2_qd")
+    return out, d1, d2
+
+
 def gno_nl_backward(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], src_table: Tensor, grad_out: Tensor,
                     g: BipartiteGraph, precision: Optional[int] = None, coords: bool = False):
     """-> (grad_f_y, grad_src_table, [grad_w...], [grad_b...]); with ``coords`` also (grad_y_pos, grad_x_pos) appended.

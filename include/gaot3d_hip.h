@@ -234,6 +234,28 @@ int gaot_gno_fwd_jet2(const gaot_mlp_t* mlp /* host */, int mode, const float* y
                       float* out /* [num_queries, channels] */, float* d1 /* [nd, num_queries, channels] */,
                       float* d2 /* [nd, num_queries, channels] */, void* workspace, size_t workspace_bytes, gaot_stream_t stream);
 
+/* The two jet entry points along PER-QUERY directions (csrc/gno_jet2.hip: k_gno_qd_jet2_knn / k_gno_qd_jet2_rows), for derivatives in a
+ * local frame of every query -- the wall-normal derivative d/dn and d^2/dn^2 of a surface field, a tangential gradient:
+ *   d1[i][q][c] = D_{v_qi} out[q][c],   d2[i][q][c] = D^2_{v_qi} out[q][c],   v_qi = qdirs[(q * nd + i) * 3 .. + 2]
+ * `qdirs` is a DEVICE pointer [num_queries][nd][3], nd = 1..6, read by the kernel (each lane loads the direction of its edge's query
+ * at the top of a direction pass; no host read, no synchronisation: the regular-list call is capturable and a replay sees the
+ * directions then in the buffer).  Directions are used as given (no normalisation).  Everything else -- operands, modes, lists,
+ * padding edges, launches (one; on rows two), workspace (gaot_gno_fwd_jet2_workspace_bytes), exact fp32 -- is gaot_gno_fwd_knn_jet2's
+ * resp. gaot_gno_fwd_jet2's, and so are the per-edge operations and their order: the rows of query q are, bit for bit, those of the
+ * host-direction entry point called with q's directions; `out` is the same value plane; a direction slot's planes do not depend on
+ * the other slots; a zero direction gives zeros.  GAOT_ERR_ARG before any launch: the argument errors of the originals, nd outside
+ * 1..6, null qdirs (with num_queries > 0). */
+int gaot_gno_fwd_knn_jet2_qd(const gaot_mlp_t* mlp /* host */, int mode, const float* y_pos, const float* x_pos, const float* f_y,
+                             const float* src_table, const int32_t* nbr /* [num_queries * k] */, int k, int64_t num_queries,
+                             const float* qdirs /* DEVICE, [num_queries][nd][3] */, int nd, float* out /* [num_queries, channels] */,
+                             float* d1 /* [nd, num_queries, channels] */, float* d2 /* [nd, num_queries, channels] */,
+                             gaot_stream_t stream);
+int gaot_gno_fwd_jet2_qd(const gaot_mlp_t* mlp /* host */, int mode, const float* y_pos, const float* x_pos, const float* f_y,
+                         const float* src_table, const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr_dst,
+                         int64_t num_edges, int64_t num_queries, const float* qdirs /* DEVICE, [num_queries][nd][3] */, int nd,
+                         float* out /* [num_queries, channels] */, float* d1 /* [nd, num_queries, channels] */,
+                         float* d2 /* [nd, num_queries, channels] */, void* workspace, size_t workspace_bytes, gaot_stream_t stream);
+
 /* Dot-product attention scores of the attention-weighted transform (reference integral_transform.py:128-137, use_attn with
  * attention_type "dot_product") as a bilinear form of the homogeneous endpoint coordinates (csrc/gno_attn.hip):
  *   scores[e] = scale * [x_pos[dst[e]], 1]^T M [y_pos[src[e]], 1]        x_pos / y_pos: [*, 3] rows, m: DEVICE [4][4] fp32

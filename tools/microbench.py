@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Kernel microbenchmarks at the configs[1] shapes (for rocprofv3 / quick A-B): attention fwd+bwd, GEMM shapes, GNO, PointNet GeoEmbed,
-the attention-weighted GNO, the forward-only decoder (decoder_sample), the sampled field's Jacobian (decoder_jacobian), the projection MLP's tangent alone (projection_jvp), the sampled field's Hessian and Laplacian (decoder_hessian)."""
+the attention-weighted GNO, the forward-only decoder (decoder_sample), the sampled field's Jacobian (decoder_jacobian), the projection MLP's tangent alone (projection_jvp), the sampled field's Hessian and Laplacian (decoder_hessian), its derivatives along per-query directions (decoder_directional)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 if os.environ.get("MB_TREE"):      # measure another checkout's package (gno_weighted: the parent commit's) with this script
@@ -779,6 +779,85 @@ elif what == "decoder_hessian":
                       f"{tot:.3f} ms; GNO kernel = {mg / gj[0]:.2f} x the Jacobian kernel's ({chains} plane-chains against 4 by count: "
                       f"{chains / 4:.2f} x; yardstick's max - min {gj[2] - gj[1]:.3f} ms)", flush=True)
         del q, chunks
+elif what == "decoder_directional":
+    # Derivatives of the sampled field along PER-QUERY directions (MAGNODecoder.sample_directional) on decoder_hessian's decoders --
+    # configs[1] (knn, k = 8), or with `--strategy radius|bidirectional` the reference YAML's decoder on row lists -- at 500 K and 8 M
+    # random query points with random unit directions, fp32 mode.  In this one process, alternated round by round after a warm-up of
+    # each: sample_jacobian (row_lists=True on rows; the yardstick), sample_directional at nd = 1 (d/dn and d^2/dn^2: 3 plane-chains
+    # through the per-edge MLP) and at nd = 3 (a local frame: 7), sample_laplacian(_rows) (7, host directions: the same work as
+    # nd = 3, so the difference is the cost of per-query directions) and sample_hessian(_rows) (13).  Device events around
+    # synchronised work; `reps` rounds (7 for the kept output); a row is the median with max - min, the peak is the rise of allocated
+    # memory over the inputs.  Kept in profiles/decoder_directional_microbench.txt / decoder_directional_rows_microbench.txt.
+    from gaot_3d_amd.data import latent_grid
+    from gaot_3d_amd.model.layers.magno import MAGNOConfig, MAGNODecoder
+    gaot_3d_amd.set_precision("fp32")
+    latent = (64, 64, 32)
+    strategy = sys.argv[sys.argv.index("--strategy") + 1] if "--strategy" in sys.argv else "knn"
+    if strategy not in ("knn", "radius", "bidirectional"):
+        sys.exit(f"--strategy must be knn, radius or bidirectional, got {strategy}")
+    rows = strategy != "knn"
+    cfg = MAGNOConfig(gno_coord_dim=3, lifting_channels=32, mlp_type="linear", use_geoembed=[True, False],
+                      neighbor_strategy=["knn", strategy] if rows else "knn", k_neighbors=1 if rows else 8, gno_radius=0.033,
+                      out_gno_channel_mlp_hidden_layers=[64, 64], precompute_edges=False)
+    dec = MAGNODecoder(in_channels=32, out_channels=1, gno_config=cfg).to(dev).eval()
+    dec.latent_dims = latent
+    tokens = latent_grid(latent).to(dev)
+    rn = torch.randn(tokens.shape[0], 32, device=dev)
+    chunk = int(os.environ["MB_CHUNK"]) if os.environ.get("MB_CHUNK") else None
+    step = chunk or dec.SAMPLE_CHUNK
+    sfx = "_rows" if rows else ""
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); out = fn(); e1.record()
+        torch.cuda.synchronize()
+        peak = torch.cuda.max_memory_allocated() - base
+        return e0.elapsed_time(e1), peak, out
+
+    def median(ts):
+        ts = sorted(ts)
+        return ts[len(ts) // 2], ts[0], ts[-1]
+
+    for nq in (500000, 8000000):
+        q = torch.rand(nq, 3, device=dev) * 2 - 1
+        n_ = torch.nn.functional.normalize(torch.randn(nq, 3, device=dev), dim=1)       # an orthonormal frame (n, t1, t2) per query
+        t1 = torch.randn(nq, 3, device=dev)
+        t1 = torch.nn.functional.normalize(t1 - (t1 * n_).sum(1, keepdim=True) * n_, dim=1)
+        frames = torch.stack([n_, t1, torch.linalg.cross(n_, t1)], dim=1).contiguous()
+        normal = frames[:, :1].contiguous()
+        del n_, t1
+        routes = {"sample_jacobian": lambda: dec.sample_jacobian(rn, q, tokens, chunk_points=chunk, row_lists=rows),
+                  "sample_directional nd=1": lambda: dec.sample_directional(rn, q, normal, tokens, chunk_points=chunk),
+                  "sample_directional nd=3": lambda: dec.sample_directional(rn, q, frames, tokens, chunk_points=chunk),
+                  "sample_laplacian" + sfx: lambda: (dec.sample_laplacian_rows if rows else dec.sample_laplacian)(rn, q, tokens, chunk_points=chunk),
+                  "sample_hessian" + sfx: lambda: (dec.sample_hessian_rows if rows else dec.sample_hessian)(rn, q, tokens, chunk_points=chunk)}
+        warm = {n: timed(f)[2] for n, f in routes.items()}            # warm-up, and the results agree where they must
+        d3, lap = warm["sample_directional nd=3"], warm["sample_laplacian" + sfx][1]
+        same = torch.equal(d3[0], warm["sample_jacobian"][0]) and torch.equal(warm["sample_directional nd=1"][1][..., 0], d3[1][..., 0])
+        err = ((d3[2].sum(-1) - lap).abs().max() / lap.abs().max()).item()
+        del warm, d3, lap
+        ts, pk = {n: [] for n in routes}, {n: 0 for n in routes}
+        for _ in range(reps):
+            for n, f in routes.items():
+                t, p, _o = timed(f); ts[n].append(t); pk[n] = max(pk[n], p); del _o
+        med = {n: median(ts[n]) for n in routes}
+        mj = med["sample_jacobian"][0]
+        for n in routes:
+            m, lo, hi = med[n]
+            print(f"Nq={nq} fp32{' ' + strategy if rows else ''}: {n:25s} (chunk {step}) {m:9.3f} ms (max - min {hi - lo:.3f} ms = {100 * (hi - lo) / m:.1f} %), "
+                  f"peak {pk[n] / 2**20:9.1f} MiB  = {m / mj:.2f} x sample_jacobian in time, {pk[n] / max(pk['sample_jacobian'], 1):.2f} x in peak memory")
+        m1, m3 = med["sample_directional nd=1"][0], med["sample_directional nd=3"][0]
+        ml, lo_l, hi_l = med["sample_laplacian" + sfx]
+        mh = med["sample_hessian" + sfx][0]
+        print(f"Nq={nq} fp32{' ' + strategy if rows else ''}: nd=1 : Jacobian = {m1 / mj:.2f} (3 plane-chains against 4 BY COUNT: 0.75), nd=1 : Hessian = {m1 / mh:.2f} "
+              f"(3 against 13 by count: 0.23); nd=3 - Laplacian = {m3 - ml:+.3f} ms = {100 * (m3 - ml) / ml:+.1f} % (both 7 plane-chains: the cost of "
+              f"per-query directions; the Laplacian's max - min is {hi_l - lo_l:.3f} ms = {100 * (hi_l - lo_l) / ml:.1f} %)")
+        print(f"Nq={nq} fp32: pred == sample_jacobian's and slot 0 of nd=3 == nd=1 bit for bit: {same}; max |sum of d2 over the frame - lap| / "
+              f"max |lap| = {err:.2e}", flush=True)
+        del q, frames, normal
 elif what == "projection_jvp":
     # The projection MLP's forward-mode tangent on its own (LinearChannelMLP 32 -> 256 -> out, out in {1, 4}, three tangent planes, fp32
     # mode, random rows), as MAGNODecoder.sample_jacobian calls it: SAMPLE_CHUNK rows at a time into preallocated pred [N, out] and
