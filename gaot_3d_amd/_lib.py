@@ -56,6 +56,8 @@ SIGNATURES = {
     "gaot_gno_bwd_w": (_i, [C.POINTER(MlpT), _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p,
                             C.POINTER(MlpGradT), _p, _i, _p, _sz, _p]),
     "gaot_gno_fwd_knn": (_i, [C.POINTER(MlpT), _i, _p, _p, _p, _p, _p, _i, _i64, _p, _i, _p]),
+    "gaot_gno_adj_workspace_bytes": (_sz, [_i64, _i]),
+    "gaot_gno_adj": (_i, [C.POINTER(MlpT), _p, _p, _p, _p, _i, _p, _p, _p, _i64, _i64, _i64, _p, _p, _sz, _p]),
     "gaot_gno_fwd_knn_jac": (_i, [C.POINTER(MlpT), _i, _p, _p, _p, _p, _p, _i, _i64, _p, _p, _p]),
     "gaot_gno_fwd_knn_jet2": (_i, [C.POINTER(MlpT), _i, _p, _p, _p, _p, _p, _i, _i64, _p, _i, _p, _p, _p, _p]),
     "gaot_gno_fwd_jac_workspace_bytes": (_sz, [_i64]),

@@ -19,6 +19,10 @@
 //     ds_read_b32 across lanes.
 //   * rows that straddle tiles are combined through a small partial buffer in tile order
 //     (deterministic; no float atomics anywhere).
+//   * the ADJOINT of the linear transform with respect to f_y (gaot_gno_adj: the sampled field's vector-Jacobian product with respect
+//     to the latent) is the forward kernel itself on the SOURCE-sorted list -- one forward evaluation of the per-edge MLP reduced by
+//     source, no MLP backward, no weight gradients -- as an instantiation of its own (an AdjFwd ends the pack).  Its rows are long
+//     (every query that selected a source), so most straddle tiles and the fix-up does real work; see the note at the entry point.
 #include <type_traits>
 
 #include "gno_common.h"
@@ -46,6 +50,9 @@ struct FwdLds {
 // and the rows are summed, not averaged
 // REGULAR LIST (a KnnFwd ends the pack, gno_common.h): sources from nbr, query = e >> lk, rows finished in the tile; src_s, dst_s, rowptr
 // and part are not read
+// ADJOINT (an AdjFwd ends the pack, gno_common.h; gaot_gno_adj): the lists are the SOURCE-sorted ones and rowptr their offsets; `f_y` is
+// the cotangent [num_queries][32], gathered by the edge's QUERY; the staged value is k_e g[q_e] / deg(q_e), applied like the weighted
+// variant's alpha, and the rows (one per source) are summed
 template <int NH, int H, int T, int MODE, class... Nl>
 __global__ __launch_bounds__(256, 2) void k_gno_fwd(MlpPtrs mlp, const float* __restrict__ y_pos,
                                                     const float* __restrict__ x_pos, const float* __restrict__ f_y,
@@ -57,7 +64,9 @@ __global__ __launch_bounds__(256, 2) void k_gno_fwd(MlpPtrs mlp, const float* __
     constexpr int KB = H / 32;
     constexpr bool W = pack_has<WFwd, Nl...>;
     constexpr bool K = pack_has<KnnFwd, Nl...>;
+    constexpr bool A = pack_has<AdjFwd, Nl...>;
     static_assert(!(W && K), "no weighted variant on regular lists");
+    static_assert(!A || (MODE == MODE_LINEAR && !W && !K), "the adjoint is the linear transform's, on the source-sorted list");
     using L = FwdLds<NH, H>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* stage_all = lds + L::weights_end;             // [4 waves][T][32][C]
@@ -117,9 +126,18 @@ __global__ __launch_bounds__(256, 2) void k_gno_fwd(MlpPtrs mlp, const float* __
             bin[t][2] = xq[1 + hf];
             if constexpr (MODE != MODE_LINEAR) sid[t] = s;
             if constexpr (W) aw[t] = valid ? last_arg(nl_...).alpha[e] : 0.f;
+            if constexpr (A) {   // 1 / deg(q) of this lane's edge (edges past E: 0)
+                const int* rd = last_arg(nl_...).rowptr_dst;
+                aw[t] = !valid ? 0.f : (rd ? 1.0f / (float)(rd[q + 1] - rd[q]) : last_arg(nl_...).inv_k);
+            }
             if (hf == 0) {
-                ids[(t * 2 + 0) * 32 + l31] = s;
-                if constexpr (!K) ids[(t * 2 + 1) * 32 + l31] = valid ? q : -1;
+                if constexpr (A) {   // the row gathered is the query's, the segment key the source
+                    ids[(t * 2 + 0) * 32 + l31] = q;
+                    ids[(t * 2 + 1) * 32 + l31] = valid ? s : -1;
+                } else {
+                    ids[(t * 2 + 0) * 32 + l31] = s;
+                    if constexpr (!K) ids[(t * 2 + 1) * 32 + l31] = valid ? q : -1;
+                }
             }
         }
         // ---- layer 0: 6 -> H ---------------------------------------------------------------------
@@ -207,7 +225,7 @@ __global__ __launch_bounds__(256, 2) void k_gno_fwd(MlpPtrs mlp, const float* __
             for (int r = 0; r < 16; ++r) {
                 const int el = mfma32_row(r, hf);
                 float kv = acc[r];
-                if constexpr (W) {   // lane el holds edge el of the tile: el = mfma32_row(r, 0) + 4 hf, two scalar reads and a select
+                if constexpr (W || A) {   // lane el holds edge el of the tile: el = mfma32_row(r, 0) + 4 hf, two scalar reads and a select
                     const int wa = __builtin_bit_cast(int, aw[t]);
                     const int a0 = __builtin_amdgcn_readlane(wa, mfma32_row(r, 0)), a1 = __builtin_amdgcn_readlane(wa, mfma32_row(r, 0) + 4);
                     kv *= __builtin_bit_cast(float, hf ? a1 : a0);
@@ -228,7 +246,7 @@ __global__ __launch_bounds__(256, 2) void k_gno_fwd(MlpPtrs mlp, const float* __
                 fixed_k_rows<C>(stage + hf * 32 * C, C, l31, base + 32 * hf, last_arg(nl_...).lk, E, out);
             else
                 segment_walk<C>(stage + hf * 32 * C, C, ids + (hf * 2 + 1) * 32, l31, base + 32 * hf, rowptr, out, part,
-                                !W);
+                                !W && !A);
         }
         wave_lds_fence();
     }
@@ -889,6 +907,24 @@ int launch_fwd_knn(const MlpPtrs& p, const float* y_pos, const float* x_pos, con
     return GAOT_OK;
 }
 
+// the adjoint instantiations (an AdjFwd ends the pack): the forward's launch on the source-sorted list
+template <int NH, int H>
+int launch_adj(const MlpPtrs& p, const float* y_pos, const float* x_pos, const float* grad_out, const int* src_s, const int* dst_s,
+               const int* rowptr_src, int64_t E, float* grad_f, float* part, const AdjFwd& adj, hipStream_t st) {
+    constexpr int T = 2;
+    const size_t lds = fwd_lds_bytes(NH, H, T);
+    auto kern = k_gno_fwd<NH, H, T, MODE_LINEAR, AdjFwd>;
+    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) {
+        gaot_set_error("gno_adj: cannot set dynamic LDS %zu: %s", lds, hipGetErrorString(e));
+        return GAOT_ERR_LAUNCH;
+    }
+    const int64_t n_macro = ceil_div(E, 32 * T);
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n_macro, 4), 256 * 2));
+    GAOT_KLAUNCH(kern, dim3(grid), dim3(256), lds, st, p, y_pos, x_pos, grad_out, src_s, dst_s, rowptr_src, E, grad_f, part, adj);
+    return GAOT_OK;
+}
+
 int bwd_grid(int64_t E) {
     const int64_t n_tiles = ceil_div(E, 32);
     return (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n_tiles, 4), 256));
@@ -1062,6 +1098,63 @@ extern "C" int gaot_gno_fwd_knn(const gaot_mlp_t* mlp, int mode, const float* y_
 #undef GNO_FWD_CASE
     }
     if (rc != GAOT_OK) return rc;
+    GAOT_LAUNCH_CHECK();
+    return GAOT_OK;
+}
+
+// The ADJOINT of the linear transform with respect to f_y (AdjFwd, gno_common.h):
+//     grad_f_y[t][c] = sum over row t of the SOURCE-sorted list of K_c(y_pos[t], x_pos[q_e]) * grad_out[q_e][c] / deg(q_e)
+// One forward evaluation of the per-edge MLP, no MLP backward, no weight gradients; exact fp32 (v_mfma_f32_32x32x2_f32) whatever the
+// precision mode.  The reduction is the forward's: 32-edge tiles, segment_walk (sum), two partial slots per tile and k_segment_fixup<32>
+// in tile order -- no atomics, a fixed summation order, bit-reproducible run to run; a source without edges gets exact zeros.
+// LONG ROWS: a source's row holds every query that selected it, tens to hundreds of edges at the shipped sizes and far more when
+// the queries cluster, so most rows straddle tiles and the fix-up does real work: ONE thread per (row, four channels) adds the row's
+// tile partials in order.  Queries that all sit on a few tokens make that thread sum thousands of partials: slow, but correct.
+extern "C" size_t gaot_gno_adj_workspace_bytes(int64_t num_edges, int channels) {
+    return gaot_gno_fwd_workspace_bytes(num_edges, channels);
+}
+
+extern "C" int gaot_gno_adj(const gaot_mlp_t* mlp, const float* y_pos, const float* x_pos, const float* grad_out,
+                            const int32_t* rowptr_dst, int k, const int32_t* src_sorted, const int32_t* dst_sorted,
+                            const int32_t* rowptr_src, int64_t num_edges, int64_t num_sources, int64_t num_queries, float* grad_f_y,
+                            void* workspace, size_t workspace_bytes, gaot_stream_t stream) {
+    GAOT_ENTER();
+    GAOT_CHECK_ARG(mlp, "null mlp");
+    if (!mlp_supported(mlp, false)) {
+        gaot_set_error("gaot_gno_adj: unsupported MLP shape (n_hidden=%d hidden=%d channels=%d)", mlp->n_hidden, mlp->hidden,
+                       mlp->channels);
+        return GAOT_ERR_UNSUPPORTED;
+    }
+    GAOT_CHECK_ARG(num_edges >= 0 && num_sources >= 0 && num_queries >= 0, "negative size");
+    GAOT_CHECK_ARG(num_edges <= (int64_t)INT32_MAX, "num_edges beyond int32 (take the queries in chunks)");
+    GAOT_CHECK_ARG(rowptr_dst || k > 0, "null rowptr_dst needs k > 0 (the degree of every query of a regular list)");
+    GAOT_CHECK_ARG(rowptr_dst || num_edges == num_queries * (int64_t)k, "a regular list holds num_queries * k edges");
+    GAOT_CHECK_ARG(rowptr_src && (num_sources == 0 || grad_f_y), "null pointer");
+    GAOT_CHECK_ARG(workspace_bytes >= gaot_gno_adj_workspace_bytes(num_edges, mlp->channels) && (workspace || num_edges == 0),
+                   "workspace too small");
+    MlpPtrs p;
+    for (int l = 0; l <= mlp->n_hidden; ++l) {
+        p.w[l] = mlp->weight[l];
+        p.b[l] = mlp->bias[l];
+        GAOT_CHECK_ARG(p.w[l] && p.b[l], "null MLP parameter");
+    }
+    if (num_sources == 0) return GAOT_OK;
+    hipStream_t st = (hipStream_t)stream;
+    float* part = (float*)workspace;
+    if (num_edges > 0) {
+        GAOT_CHECK_ARG(y_pos && x_pos && grad_out && src_sorted && dst_sorted, "null pointer");
+        const AdjFwd adj{rowptr_dst, rowptr_dst ? 0.f : 1.0f / (float)k};
+        int rc = GAOT_OK;
+        switch (mlp->n_hidden) {
+            case 1: rc = launch_adj<1, 64>(p, y_pos, x_pos, grad_out, src_sorted, dst_sorted, rowptr_src, num_edges, grad_f_y, part, adj, st); break;
+            case 2: rc = launch_adj<2, 64>(p, y_pos, x_pos, grad_out, src_sorted, dst_sorted, rowptr_src, num_edges, grad_f_y, part, adj, st); break;
+            case 3: rc = launch_adj<3, 64>(p, y_pos, x_pos, grad_out, src_sorted, dst_sorted, rowptr_src, num_edges, grad_f_y, part, adj, st); break;
+            case 4: rc = launch_adj<4, 64>(p, y_pos, x_pos, grad_out, src_sorted, dst_sorted, rowptr_src, num_edges, grad_f_y, part, adj, st); break;
+        }
+        if (rc != GAOT_OK) return rc;
+    }
+    GAOT_KLAUNCH((k_segment_fixup<32>), dim3(segment_fixup_grid(num_sources * 8)), dim3(256), 0, st, rowptr_src, num_sources, part,
+                 grad_f_y, 0);
     GAOT_LAUNCH_CHECK();
     return GAOT_OK;
 }

@@ -65,6 +65,16 @@ struct KnnFwd {
     const int* nbr;         // [num_queries * k]
     int lk;                 // log2(k), 0..5
 };
+// ADJOINT variant of the linear forward (gaot_gno_adj): the transform out_q = (1/deg q) sum_e k_e * f[s_e] is linear in f, and its
+// adjoint  df[t] = sum_{e: src_e = t} k_e * g[q_e] / deg(q_e)  is the same per-edge kernel MLP evaluated forward once, reduced by SOURCE
+// instead of by query: the kernel walks the SOURCE-sorted list (src_s = the segment key, dst_s = the query whose coordinates feed
+// the MLP and whose cotangent row is gathered through the f_y argument), scales the staged value by 1/deg(q_e) -- from the by-query
+// offsets, or the constant 1/k of a regular list when they are null -- and sums the rows (segment_walk, mean = false).  An AdjFwd
+// ENDS the forward's pack (linear mode only; never with a WFwd or a KnnFwd).
+struct AdjFwd {
+    const int* rowptr_dst;  // [num_queries + 1]; null: every query has k edges
+    float inv_k;            // 1 / k of a regular list (read when rowptr_dst is null)
+};
 template <class T, class... P>
 constexpr bool pack_has = (std::is_same_v<T, P> || ...);
 

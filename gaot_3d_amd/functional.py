@@ -1507,3 +1507,23 @@ class ScaleMixFn(Function):
         d = dout if dout.is_contiguous() else dout.contiguous()
         dxs, dlog = ops.scale_mix_bwd(xs, w, d)
         return (dlog, *dxs)
+
+
+class SampleLatentFn(Function):
+    """The sampled field as a differentiable function of the LATENT: forward = ``MAGNODecoder.sample`` at fp32 arithmetic in both
+    precision modes (``torch.equal`` to ``sample`` called in fp32 mode), backward = ``MAGNODecoder.sample_vjp`` (the streamed adjoint:
+    no edge list, no decoder autograd graph, no ``gno_bwd``).  Nothing is saved but the latent, the query coordinates and the token
+    tensor.  Gradients flow to ``latent`` ONLY: the decoder's parameters and the query coordinates are constants of this node."""
+
+    @staticmethod
+    def forward(ctx, latent: Tensor, decoder, query_pos: Tensor, tokens_pos: Tensor, chunk_points: Optional[int]):
+        ctx.decoder, ctx.chunk_points = decoder, chunk_points
+        ctx.save_for_backward(latent, query_pos, tokens_pos)
+        with ops.fp32_arithmetic():
+            return decoder.sample(latent.detach(), query_pos, tokens_pos, chunk_points=chunk_points)
+
+    @staticmethod
+    def backward(ctx, dout: Tensor):
+        latent, query_pos, tokens_pos = ctx.saved_tensors
+        g = ctx.decoder.sample_vjp(latent, query_pos, dout.to(torch.float32), tokens_pos, chunk_points=ctx.chunk_points)
+        return g.to(latent.dtype), None, None, None, None

@@ -354,6 +354,30 @@ def query_lists(strategy: str, query_pos: Tensor, grid: LatentGrid, radius: floa
     return ops.BipartiteGraph(ops.SortedEdges(offs, None, qi, tk, n), None, grid.num_tokens, n)
 
 
+def by_source(lists, num_src: int) -> ops.BipartiteGraph:
+    """The by-SOURCE list of a chunk of queries, which the adjoint (``ops.gno_adjoint``) reduces over: ``lists`` is the regular list
+    (nbr, k) of ``knn_to_grid`` (nbr int32, [n, k] or flat) or the forward-only graph of ``query_lists`` (built WITHOUT ``lead``
+    padding).  Forms the int32 [2, E] (source, query) pairs in by-query order and sorts them with the stable ``ops.csr_build(..., 0,
+    num_src)``, so a source's queries come in ascending order.  -> a graph with ``by_src`` set; ``by_dst`` is the list given (None for
+    a regular list, whose degree is the constant k)."""
+    if isinstance(lists, tuple):
+        nbr, k = lists[0], int(lists[1])
+        _need_cuda(nbr, "by_source")
+        if nbr.dtype != torch.int32 or k < 1 or nbr.numel() % k:
+            raise GaotError(f"by_source: nbr must hold int32 ids, k per query (k = {k}), got {nbr.dtype} {tuple(nbr.shape)}")
+        n = nbr.numel() // k
+        qi = torch.arange(n, dtype=torch.int32, device=nbr.device).repeat_interleave(k)
+        tk, by_dst = nbr.reshape(-1), None
+    else:
+        by_dst, n = lists.by_dst, lists.num_dst
+        if int(num_src) != lists.num_src:
+            raise GaotError(f"by_source: the lists were built for {lists.num_src} sources, got num_src = {num_src}")
+        if by_dst.num_edges and int(by_dst.rowptr[0]) != 0:
+            raise GaotError("by_source: the lists begin with padding edges (query_lists(..., lead=)); build them without")
+        qi, tk = by_dst.key, by_dst.other
+    return ops.BipartiteGraph(by_dst, ops.csr_build(torch.stack([tk, qi]), 0, int(num_src)), int(num_src), int(n))
+
+
 def get_neighbor_strategy(neighbor_strategy: str, phys_pos: Tensor, batch_idx_phys: Optional[Tensor], latent_tokens_pos: Tensor,
                           batch_idx_latent: Optional[Tensor], radius: float, k_neighbors: int = 1, is_decoder: bool = False,
                           latent_dims: Optional[Sequence[int]] = None) -> Tensor:

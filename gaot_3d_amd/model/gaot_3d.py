@@ -8,6 +8,7 @@ import torch
 import torch.nn as nn
 
 from .. import functional as GF
+from .. import ops
 from .layers.attn import Transformer, TransformerConfig
 from .layers.magno import MAGNOConfig, MAGNODecoder, MAGNOEncoder
 
@@ -213,6 +214,44 @@ class GAOT3D(nn.Module):
         modes, outside autograd; configurations that do not stream raise NotImplementedError, a bad ``dirs`` ValueError."""
         lat = self._one_sample("sample_directional", latent, tokens_pos)
         return self.decoder.sample_directional(latent, query_pos.to(latent.device), dirs, lat, chunk_points=chunk_points)
+
+    def sample_vjp(self, latent: torch.Tensor, query_pos: torch.Tensor, cotangent: torch.Tensor,
+                   tokens_pos: Optional[torch.Tensor] = None, chunk_points: Optional[int] = None) -> torch.Tensor:
+        """The ADJOINT of ``sample``: -> grad_latent [D*H*W, lifting_channels] (fp32) = sum_q cotangent[q] . d pred[q] / d latent for a
+        cotangent [Nq, output_size] (float32, on the queries' device) -- the gradient of a number computed from sampled values (an
+        integrated surface load, a misfit at sensor points) with respect to the latent, streamed in chunks of queries with no
+        edge_index, no decoder autograd graph and no weight gradients.  ``MAGNODecoder.sample_vjp``: exact fp32 in both precision
+        modes, outside autograd, bit-reproducible for a given ``chunk_points`` (not bit-identical across chunkings: a token's sum is
+        split at chunk boundaries).  The decoder's parameters and the query coordinates are constants.  Routes and refusals are
+        ``sample_hessian``'s / ``sample_hessian_rows``'s; a point-sharded model raises NotImplementedError."""
+        lat = self._one_sample("sample_vjp", latent, tokens_pos)
+        if getattr(self, "_shard_group", None) is not None:
+            raise NotImplementedError("GAOT3D.sample_vjp: a point-sharded model is not supported")
+        return self.decoder.sample_vjp(latent, query_pos.to(latent.device), cotangent, lat, chunk_points=chunk_points)
+
+    def sample_autograd(self, latent: torch.Tensor, query_pos: torch.Tensor, tokens_pos: Optional[torch.Tensor] = None,
+                        chunk_points: Optional[int] = None) -> torch.Tensor:
+        """``sample`` as a differentiable function of the latent: -> pred [Nq, output_size] whose backward is ``sample_vjp``
+        (``functional.SampleLatentFn``), so that a loss on sampled values reaches the encoder, the processor and ``batch.pos`` through
+        the ordinary autograd of ``latent`` -- at the memory of one chunk, without ``forward(query_coord_pos=...)``'s edge list and
+        decoder graph.  The forward is the streamed value at fp32 arithmetic in BOTH precision modes (``torch.equal`` to ``sample``
+        called in fp32 mode); only the latent, the queries and the token tensor are kept for the backward.  Gradients flow to
+        ``latent`` ONLY: the decoder's parameters are constants here (train them through ``forward``), and a ``query_pos`` that
+        requires grad raises ValueError -- the derivative with respect to the query is ``sample_jacobian``'s.  Configurations
+        ``sample_vjp`` refuses are refused here, before the forward runs."""
+        lat = self._one_sample("sample_autograd", latent, tokens_pos)
+        if query_pos.requires_grad:
+            raise ValueError("GAOT3D.sample_autograd: query_pos requires grad, but gradients flow to the latent only (the derivative "
+                             "with respect to the query coordinates is sample_jacobian's); detach it")
+        if getattr(self, "_shard_group", None) is not None:
+            raise NotImplementedError("GAOT3D.sample_autograd: a point-sharded model is not supported")
+        q = query_pos.to(latent.device)
+        dec = self.decoder
+        dec._sample_args("sample_autograd", chunk_points)
+        with torch.no_grad(), ops.fp32_arithmetic():      # sample_vjp's refusals, before anything runs
+            dec._jet2_stream("sample_autograd", latent.detach(), q, lat, chunk_points, rows=dec.decoder_strategy != "knn",
+                             what="the adjoint of the sampled field", jets=False)
+        return GF.SampleLatentFn.apply(latent, dec, q, lat, chunk_points)
 
     def forward(self, batch, tokens_pos: Optional[torch.Tensor] = None, tokens_batch_idx: Optional[torch.Tensor] = None,
                 query_coord_pos: Optional[torch.Tensor] = None, query_coord_batch_idx: Optional[torch.Tensor] = None,

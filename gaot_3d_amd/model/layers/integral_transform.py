@@ -26,6 +26,9 @@ launch) -- what ``sample_jacobian(row_lists=True)`` streams for 'radius' / 'bidi
 carry directional 2-jets (value, D_v, D_v^2) on the same two kinds of list (``gaot_gno_fwd_knn_jet2`` / ``gaot_gno_fwd_jet2``) -- what
 ``sample_hessian`` / ``sample_laplacian`` and their ``_rows`` variants stream; ``jet2_knn_qd`` and ``jet2_rows_qd`` carry them along a
 direction set of every query's own (``gaot_gno_fwd_knn_jet2_qd`` / ``gaot_gno_fwd_jet2_qd``) -- what ``sample_directional`` streams.
+``adjoint_knn`` / ``adjoint_rows`` are the ADJOINT of the 'linear' forward with respect to f_y on the by-source list of a chunk
+(``gaot_gno_adj``: the per-edge MLP evaluated forward once and reduced by source, exact fp32, no weight gradients) -- what
+``MAGNODecoder.sample_vjp`` streams.
 HIP only, no CPU fallback."""
 from typing import Optional
 
@@ -211,6 +214,42 @@ class IntegralTransform(nn.Module):
         """``jet2_rows`` along PER-QUERY directions ``qdirs`` [N_x, nd, 3] (``jet2_knn_qd``): one ``ops.gno_forward_jet2_qd`` call (the
         jet kernel and its fix-up) per 32-channel pass, the operands prepared exactly as in ``jet2_rows``."""
         return self._on_lists("jet2_rows_qd", y_pos, x_pos, f_y, graph, 2, qdirs, qd=True)
+
+    def adjoint_knn(self, y_pos, x_pos, nbr, k: int, grad_out, graph=None):
+        """The ADJOINT of ``forward_knn`` with respect to f_y: -> grad_f_y [N_y, C] = the vector-Jacobian product of the cotangent
+        ``grad_out`` [N_x, C] (fp32) with d forward_knn / d f_y, on the regular list ``nbr`` / ``k`` (1/deg = 1/k).  ``graph``: the
+        by-source list of these lists (``graph.by_source((nbr, k), N_y)``, built here when None).  The 'linear' transform is linear in
+        f_y, so this is one forward evaluation of the per-edge kernel MLP reduced by source (``ops.gno_adjoint``: two launches per
+        32-channel pass) -- no MLP backward, no weight gradients.  The operands are prepared exactly as in ``forward_knn``
+        (``_fused_passes``); exact fp32 in both precision modes; nothing is recorded for autograd.  Runs exactly when ``_fused_plan``
+        is not None, the transform is 'linear' and k is in ``ops.GNO_KNN_K``; raises NotImplementedError otherwise."""
+        if int(k) not in ops.GNO_KNN_K:
+            raise NotImplementedError(f"IntegralTransform.adjoint_knn: lists of k in {ops.GNO_KNN_K} neighbours per query, got k = {k}")
+        if graph is None:
+            from ... import graph as device_graph
+            graph = device_graph.by_source((nbr, int(k)), y_pos.shape[0])
+        return self._adjoint("adjoint_knn", y_pos, x_pos, grad_out, graph, int(k))
+
+    def adjoint_rows(self, y_pos, x_pos, grad_out, graph):
+        """``adjoint_knn`` on RAGGED rows: ``graph`` holds both lists of the chunk -- ``by_dst`` as ``graph.query_lists`` wrote it
+        (its offsets give 1/deg; a query without neighbours contributes nothing) and ``by_src`` from ``graph.by_source``."""
+        return self._adjoint("adjoint_rows", y_pos, x_pos, grad_out, graph, None)
+
+    def _adjoint(self, fn, y_pos, x_pos, grad_out, graph, k):
+        """the two adjoint methods: every pass of ``_fused_passes`` (its f_y block is the cotangent's) is one ``ops.gno_adjoint`` call"""
+        fcs = list(self.channel_mlp.fcs)
+        with torch.no_grad():
+            plan = self._fused_plan(fcs, grad_out, y_pos, x_pos) if self.transform_type == "linear" else None
+            if plan is None:
+                raise NotImplementedError(f"IntegralTransform.{fn}: only the 'linear' transforms the fused kernels evaluate (_fused_plan); "
+                                          f"transform_type = {self.transform_type!r}, use_attn = {bool(self.use_attn)}")
+            y3, x3, _, (w0, b0, *mid), blocks = self._fused_passes(fcs, y_pos, x_pos, grad_out, *plan)
+            outs = []
+            for wb, bb, gb, n in blocks:
+                o = ops.gno_adjoint([w0.contiguous(), *mid[0::2], wb.contiguous()], [b0, *mid[1::2], bb.contiguous()], y3, x3,
+                                    gb.contiguous(), graph, k)
+                outs.append(o if n == 32 else o[:, :n])
+            return outs[0].contiguous() if len(outs) == 1 else torch.cat(outs, dim=1)
 
     def _on_lists(self, fn, y_pos, x_pos, f_y, lists, order: int, dirs=None, qd: bool = False):
         """The seven list methods: the forward-mode routes on the regular list ``lists`` = (nbr, k) or on the by-query list of the graph

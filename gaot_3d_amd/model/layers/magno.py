@@ -630,23 +630,25 @@ class MAGNODecoder(nn.Module):
     HESSIAN_DIRS = ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0), (1.0, 1.0, 0.0), (0.0, 1.0, 1.0), (1.0, 0.0, 1.0))
     HESSIAN_PAIRS = ((0, 1), (1, 2), (0, 2))      # the axes of directions 3, 4, 5
 
-    def _jet2_stream(self, fn, rndata_flat, query_pos, lat, chunk_points, rows=False):
+    def _jet2_stream(self, fn, rndata_flat, query_pos, lat, chunk_points, rows=False, what="second derivatives", jets=True):
         """the argument rules and streaming conditions shared by ``sample_hessian`` and ``sample_laplacian`` and, with ``rows``, by
         ``sample_hessian_rows`` and ``sample_laplacian_rows`` on a 'radius' / 'bidirectional' decoder -> (grid, chunk); raises for
-        every configuration they do not stream, naming the condition"""
+        every configuration they do not stream, naming the condition.  ``sample_vjp`` (``what`` = its name in the refusals) shares
+        them without the projection's jet-kernel shape (``jets`` False): it needs the 'linear' transform and a projection of two
+        linear layers with a named activation instead."""
         from ... import graph as device_graph
         from ... import ops
         chunk = self._sample_args(fn, chunk_points)
         k = int(self.k_neighbors)
         if rows:
-            no = lambda why: NotImplementedError(f"MAGNODecoder.{fn}: second derivatives on row lists stream for 'radius' and "
+            no = lambda why: NotImplementedError(f"MAGNODecoder.{fn}: {what} on row lists stream for 'radius' and "
                                                  f"'bidirectional' decoders; {why}")
             if self.decoder_strategy not in ("radius", "bidirectional"):
                 raise no(f"decoder strategy {self.decoder_strategy!r} is neither")
             if self.decoder_strategy == "bidirectional" and k > device_graph.QUERY_LIST_MAX_K:
                 raise no(f"k_neighbors = {k} is above {device_graph.QUERY_LIST_MAX_K}, the longest list graph.query_lists unites")
         else:
-            no = lambda why: NotImplementedError(f"MAGNODecoder.{fn}: second derivatives stream on the regular k-neighbour lists only; {why}")
+            no = lambda why: NotImplementedError(f"MAGNODecoder.{fn}: {what} stream on the regular k-neighbour lists only; {why}")
             if self.decoder_strategy != "knn":
                 raise no(f"decoder strategy {self.decoder_strategy!r} is not 'knn'")
             if k not in ops.GNO_KNN_K:
@@ -658,7 +660,13 @@ class MAGNODecoder(nn.Module):
         if self.sampling_strategy is not None:
             raise no(f"neighbour sampling ({self.sampling_strategy!r}) is not supported")
         fcs = list(self.projection.fcs)
-        if not (len(fcs) == 2 and self.projection.non_linearity == "gelu" and fcs[0].bias is not None and ops.mlp2_jet2_supported(
+        if not jets:
+            if self.gno.transform_type != "linear":
+                raise no(f"transform type {self.gno.transform_type!r} is not 'linear' (the adjoint kernel is the linear transform's)")
+            if not (len(fcs) == 2 and self.projection.non_linearity in ops.ACT):
+                raise no("the projection is not two linear layers with a named activation between them (layers "
+                         f"{[tuple(fc.weight.shape[:2]) for fc in fcs]}, activation {self.projection.non_linearity!r})")
+        elif not (len(fcs) == 2 and self.projection.non_linearity == "gelu" and fcs[0].bias is not None and ops.mlp2_jet2_supported(
                 fcs[0].weight.shape[1], fcs[0].weight.shape[0], fcs[1].weight.shape[0], 3, ops.ACT["gelu"])):
             raise no("the projection is not a two-layer erf-GELU MLP 32 -> {64, 128, 256} -> 1..4 with a first bias (layers "
                      f"{[tuple(fc.weight.shape[:2]) for fc in fcs]})")
@@ -851,6 +859,107 @@ class MAGNODecoder(nn.Module):
         for sl, q, lists in self._stream_chunks(grid, query_pos, chunk, "rows" if rows else "knn"):
             d1[sl], d2[sl] = self._jet2_chunk(rndata_flat, q, latent_tokens_pos, lists, dirs[sl], pred[sl])
         return pred, d1, d2
+
+    def _project_vjp(self, x, g):
+        """the cotangent of the projection's input: dx [rows, C] = g (d projection(x) / d x) for x [rows, C] (the mixed GNO rows) and
+        the cotangent g [rows, out_channels], in exact fp32 on the GEMM / activation kernels: z = x W_1^T + b_1,
+        dh = (g W_2) * act'(z), dx = dh W_1.  Rows in blocks, so that the [rows, projection_channels] tensors stay no larger than x
+        itself (``_project_into``)."""
+        from ... import ops
+        fc1, fc2 = self.projection.fcs
+        w1, w2 = GF._w2d(fc1.weight).contiguous(), GF._w2d(fc2.weight).contiguous()
+        act = ops.ACT[self.projection.non_linearity]
+        n, c = x.shape
+        hid, oc = w1.shape[0], w2.shape[0]
+        dx = torch.empty_like(x)
+        step = n if hid <= c else max(1024, n * c // hid)
+        for j in range(0, n, step):
+            xb, gb = x[j:j + step], g[j:j + step]
+            m = xb.shape[0]
+            z = ops.gemm(xb, w1, m, hid, c, c, c, False, True, fc1.bias, 0, precision=0)
+            dh = ops.gemm(gb, w2, m, hid, oc, oc, hid, False, False, precision=0)
+            dz = ops.act_bwd(z, dh, act) if act else dh
+            ops.gemm(dz, w1, m, c, hid, hid, c, False, False, out=dx[j:j + step], ldc=c, precision=0)
+        return dx
+
+    def _vjp_chunk(self, rndata_flat, q, g, lat, lists):
+        """one chunk of ``sample_vjp``: -> its [M, C] part of the latent's gradient.  A call of its own, so that a chunk's rows and
+        lists are freed before the next chunk's are allocated."""
+        from ... import graph as device_graph
+        from ... import ops
+        m = lat.shape[0]
+        if isinstance(lists, tuple):                       # 'knn': every scale sees the same list, the mix is of equal operands
+            x = self._mix_equal_scales([self.gno.forward_knn(lat, q, *lists, rndata_flat)], q)[0]
+            dx = self._project_vjp(x, g)
+            del x
+            d = self._mix_equal_scales([dx], q)[0]      # (sum_s w_s) dx, formed as the forward forms sum_s w_s x
+            del dx
+            return self.gno.adjoint_knn(lat, q, *lists, d, graph=device_graph.by_source(lists, m))
+        outs = [self.gno(y_pos=lat, x_pos=q, edge_index=None, f_y=rndata_flat, graph=rows) for rows in lists]
+        if len(outs) == 1:
+            ds = [self._project_vjp(outs[0], g)]
+        elif not self.use_scale_weights:
+            ds = [self._project_vjp(_sum_scales(outs), g)] * len(outs)
+        else:                                              # the softmax weights depend on the query alone: d out_s = w_s dx
+            outs = [o.contiguous() for o in outs]
+            x, w = ops.scale_mix_fwd(outs, _scale_logits(self, q)[0].contiguous())
+            ds = ops.scale_mix_bwd(outs, w, self._project_vjp(x, g))[0]
+        part = None
+        for rows, d in zip(lists, ds):
+            p = self.gno.adjoint_rows(lat, q, d, device_graph.by_source(rows, m))
+            part = p if part is None else part.add_(p)
+        return part
+
+    @torch.no_grad()
+    def sample_vjp(self, rndata_flat, query_pos, cotangent, latent_tokens_pos, chunk_points: Optional[int] = None) -> torch.Tensor:
+        """The ADJOINT of ``sample``: -> grad_latent [M, C] (fp32) = sum_q cotangent[q] . d pred[q] / d rndata_flat, the vector-Jacobian
+        product of the sampled field with respect to the latent for a cotangent [Nq, out_channels] -- the gradient of any number
+        computed from sampled values (an integrated load sum_q a_q n_q p(x_q), a misfit at sensor points), which the autograd of
+        ``GAOT3D.latent`` carries on into the encoder, the processor and the sample's coordinates.  The decoder's parameters and the
+        query coordinates are CONSTANTS here (the derivative with respect to the query is ``sample_jacobian``'s).
+
+        Streamed as ``sample`` is, ``chunk_points`` queries at a time through the same chunk loop: per chunk the lists
+        (``knn_to_grid``, or ``graph.query_lists`` per scale), the GNO rows recomputed at fp32 arithmetic and mixed, the cotangent
+        of the mixed rows through the projection (``_project_vjp``: z = x W_1^T + b_1, dh = (g W_2) * act'(z), dx = dh W_1 in row
+        blocks), the scale mix's cotangent per scale (its softmax weights depend on the query only; on the 'knn' route the operands
+        are equal and it is the weights' sum times the cotangent, formed as the forward forms it), then ``graph.by_source`` and the
+        adjoint kernel (``IntegralTransform.adjoint_knn`` / ``adjoint_rows``: the per-edge kernel MLP evaluated forward once and
+        reduced by TOKEN -- no MLP backward, no weight gradients, no ``gno_bwd``), and the chunk's [M, C] part added into the result
+        in chunk order.  Nothing sized by Nq exists but the caller's own tensors.
+
+        Exact fp32 in both precision modes (bf16 and fp32 mode give the same bits); outside autograd; bit-reproducible run to run
+        for a given ``chunk_points``; NOT bit-identical across different ``chunk_points``, because a token's sum is split at the
+        chunk boundaries (the difference is fp32 rounding of a sum).  The 'rows' route sizes its lists by a host read and raises
+        GaotError inside a stream capture before any launch; capturing the 'knn' route is not promised.
+
+        Routes and refusals are ``sample_hessian``'s / ``sample_hessian_rows``'s: 'knn' with k_neighbors in ``ops.GNO_KNN_K`` on the
+        regular lists; 'radius', and 'bidirectional' with k_neighbors <= ``graph.QUERY_LIST_MAX_K``, on row lists.  use_attn, a decoder
+        GeoEmbed, neighbour sampling, tokens off the regular grid, other k, the 'nonlinear' / 'nonlinear_kernelonly' transforms, a
+        projection that is not two linear layers with a named activation, and a point-sharded model raise NotImplementedError naming
+        the condition; 'reverse', a non-positive ``chunk_points`` and a cotangent that is not float32 [Nq, out_channels] on the queries'
+        device raise ValueError."""
+        from ... import ops
+        fn = "sample_vjp"
+        self._sample_args(fn, chunk_points)
+        nq = int(query_pos.shape[0])
+        if not isinstance(cotangent, torch.Tensor) or cotangent.dtype != torch.float32 or cotangent.device != query_pos.device \
+                or tuple(cotangent.shape) != (nq, self.out_channels):
+            got = f"{cotangent.dtype} {tuple(cotangent.shape)} on {cotangent.device}" if isinstance(cotangent, torch.Tensor) \
+                else type(cotangent).__name__
+            raise ValueError(f"MAGNODecoder.{fn}: the cotangent must be float32 [{nq}, {self.out_channels}] on the queries' device "
+                             f"({query_pos.device}), got {got}")
+        if getattr(self, "_shard_group", None) is not None:
+            raise NotImplementedError(f"MAGNODecoder.{fn}: a point-sharded model is not supported (every rank would hold a partial sum)")
+        rndata_flat, query_pos, cotangent = rndata_flat.detach(), query_pos.detach(), cotangent.detach().contiguous()
+        rows = self.decoder_strategy != "knn"
+        with ops.fp32_arithmetic():
+            grid, chunk = self._jet2_stream(fn, rndata_flat, query_pos, latent_tokens_pos, chunk_points, rows=rows,
+                                            what="the adjoint of the sampled field", jets=False)
+            f = rndata_flat.to(torch.float32).contiguous()
+            grad = torch.zeros_like(f)
+            for sl, q, lists in self._stream_chunks(grid, query_pos, chunk, "rows" if rows else "knn", lead=False):
+                grad.add_(self._vjp_chunk(f, q.contiguous(), cotangent[sl], latent_tokens_pos, lists))
+        return grad
 
     def sample_jacobian(self, rndata_flat, query_pos, latent_tokens_pos, chunk_points: Optional[int] = None,
                         row_lists: bool = False):

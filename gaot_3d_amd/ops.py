@@ -2,6 +2,7 @@
 pass raw pointers to libgaot3d_hip.so.  Every function requires CUDA(HIP) tensors and raises otherwise."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import functools
 import os
@@ -344,6 +345,48 @@ def gno_forward_knn(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Op
     return out
 
 
+def gno_adjoint(weights, biases, y_pos: Tensor, x_pos: Tensor, grad_out: Tensor, g: BipartiteGraph, k: Optional[int] = None) -> Tensor:
+    """The ADJOINT of the linear transform with respect to f_y (gaot_gno_adj): -> grad_f_y [n_src, 32] with
+        grad_f_y[t] = sum over the edges e of source t of  K(y_pos[t], x_pos[q_e]) * grad_out[q_e] / deg(q_e)
+    -- what ``gno_backward`` returns as its first result, from ONE forward evaluation of the per-edge kernel MLP: no MLP backward, no
+    weight gradients, no f_y.  Reads the by-SOURCE list ``g.by_src`` (``graph.by_source`` builds it for a chunk of queries); deg(q)
+    comes from ``g.by_dst.rowptr``, or, with ``k`` given, is the constant k of a regular list and ``g.by_dst`` may be None.  Exact fp32
+    whatever the precision mode (the same bits in both), no atomics, bit-reproducible run to run; a source without edges gets exact
+    zeros.  Two launches (main + fix-up; the fix-up alone without edges).  Rows are long -- every query that selected a source -- so
+    most straddle the 32-edge tiles and one fix-up thread adds a row's tile partials in order: slow when the queries cluster on a
+    few sources, but correct."""
+    lib = _lib.load()
+    m, keep = _mlp_struct(weights, biases)
+    y_pos = _req(y_pos, torch.float32, "y_pos")
+    x_pos = _req(x_pos, torch.float32, "x_pos")
+    grad_out = _req(grad_out, torch.float32, "grad_out")
+    if y_pos.dim() != 2 or x_pos.dim() != 2 or y_pos.shape[1] != 3 or x_pos.shape[1] != 3:
+        raise GaotError(f"gno_adjoint: y_pos / x_pos must be [*, 3], got {tuple(y_pos.shape)} / {tuple(x_pos.shape)}")
+    if g.by_src is None:
+        raise GaotError("gno_adjoint: the graph has no by-source list (graph.by_source builds one)")
+    if y_pos.shape[0] != g.num_src or x_pos.shape[0] != g.num_dst:
+        raise GaotError(f"gno_adjoint: y_pos / x_pos have {y_pos.shape[0]} / {x_pos.shape[0]} rows, the graph {g.num_src} / {g.num_dst}")
+    if tuple(grad_out.shape) != (g.num_dst, m.channels):
+        raise GaotError(f"gno_adjoint: grad_out must be [{g.num_dst}, {m.channels}], got {tuple(grad_out.shape)}")
+    e = g.by_src.num_edges
+    if k is None:
+        if g.by_dst is None:
+            raise GaotError("gno_adjoint: the degrees need the by-query offsets (g.by_dst.rowptr) or the k of a regular list")
+        rowptr_dst, kk = g.by_dst.rowptr, 0
+    else:
+        rowptr_dst, kk = None, int(k)
+        if kk < 1 or e != g.num_dst * kk:
+            raise GaotError(f"gno_adjoint: a regular list of {g.num_dst} queries x k = {kk} holds {g.num_dst * max(kk, 0)} edges, got {e}")
+    dev = x_pos.device
+    grad_f = torch.empty(g.num_src, m.channels, dtype=torch.float32, device=dev)
+    ws = _ws(lib.gaot_gno_adj_workspace_bytes(e, m.channels), dev)
+    with _timed(f"gno_adj_nh{m.n_hidden}"):
+        check(lib.gaot_gno_adj(C.byref(m), _ptr(y_pos), _ptr(x_pos), _ptr(grad_out), _ptr(rowptr_dst), kk, _ptr(g.by_src.key),
+                               _ptr(g.by_src.other), _ptr(g.by_src.rowptr), e, g.num_src, g.num_dst, _ptr(grad_f), _ptr(ws), ws.numel(),
+                               _stream()), "gaot_gno_adj")
+    return grad_f
+
+
 def gno_forward_knn_jac(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], src_table: Optional[Tensor],
                         nbr: Tensor, k: int):
     """``gno_forward_knn`` with the spatial derivative of its result (gaot_gno_fwd_knn_jac): -> (out [n_query, 32],
@@ -663,6 +706,18 @@ def set_precision(mode: str):
 
 def get_precision() -> str:
     return "bf16" if _PRECISION["mode"] else "fp32"
+
+
+@contextlib.contextmanager
+def fp32_arithmetic():
+    """run the enclosed calls in fp32 mode whatever the mode set, and put the mode back (the sampled field's adjoint and the forward it
+    recomputes are exact fp32 in both precision modes)"""
+    was = _PRECISION["mode"]
+    _PRECISION["mode"] = 0
+    try:
+        yield
+    finally:
+        _PRECISION["mode"] = was
 
 
 # activation ids of the GEMM epilogues / gaot_act_bwd (csrc/common.h GAOT_ACT_*)

@@ -160,6 +160,27 @@ int gaot_gno_fwd_knn(const gaot_mlp_t* mlp /* host */, int mode, const float* y_
                      const float* src_table, const int32_t* nbr /* [num_queries * k] */, int k, int64_t num_queries,
                      float* out /* [num_queries, channels] */, int precision, gaot_stream_t stream);
 
+/* The ADJOINT of the linear transform (gaot_gno_fwd, mode 0) with respect to f_y, for the vector-Jacobian product of a sampled
+ * field with respect to the latent: the transform is linear in f_y, so
+ *   grad_f_y[t][c] = sum over row t of the SOURCE-sorted list of  K_c(y_pos[t], x_pos[q_e]) * grad_out[q_e][c] / deg(q_e)
+ * is the per-edge kernel MLP evaluated FORWARD once and reduced by source instead of by query: no MLP backward, no weight
+ * gradients (gaot_gno_bwd computes both, always).  The lists are SOURCE-sorted as in gaot_gno_bwd (gaot_csr_build with sort_row=0);
+ * deg(q) = rowptr_dst[q+1] - rowptr_dst[q] from the by-query offsets, or, with rowptr_dst NULL and k > 0, the constant k of a
+ * regular list (num_edges == num_queries * k).  grad_f_y [num_sources, channels] is overwritten; a source without edges gets exact
+ * zeros.  Exact fp32 (v_mfma_f32_32x32x2_f32) -- there is no precision argument, the two precision modes give the same bits.
+ * Linear mode only, 1 <= n_hidden <= 4, hidden 64, channels 32.  The reduction is the forward's: 32-edge tiles, a per-lane
+ * segmented walk, two partial slots per tile and one fix-up launch in tile order -- no atomics, a fixed summation order,
+ * bit-reproducible run to run.  LONG ROWS: a source's row holds every query that selected it (tens to hundreds of edges at the
+ * shipped sizes, far more when the queries cluster), so most rows straddle tiles and the fix-up does real work; queries that all
+ * sit on a few sources make ONE thread per (row, four channels) add thousands of partials in order -- slow, but correct.
+ * Two launches (none of the first with num_edges == 0); workspace: gaot_gno_adj_workspace_bytes. */
+size_t gaot_gno_adj_workspace_bytes(int64_t num_edges, int channels);
+int gaot_gno_adj(const gaot_mlp_t* mlp /* host */, const float* y_pos, const float* x_pos,
+                 const float* grad_out /* [num_queries, channels] */, const int32_t* rowptr_dst /* or null with k > 0 */, int k,
+                 const int32_t* src_sorted /* by source */, const int32_t* dst_sorted /* by source */, const int32_t* rowptr_src,
+                 int64_t num_edges, int64_t num_sources, int64_t num_queries, float* grad_f_y /* [num_sources, channels] */,
+                 void* workspace, size_t workspace_bytes, gaot_stream_t stream);
+
 /* gaot_gno_fwd_knn with the spatial derivative of its result, for the gradient / Jacobian of a sampled field at the query points:
  *   jac[d][q][c] = d out[q][c] / d x_pos[q][d],  d = 0..2        (direction-major: each direction is a plain [num_queries, channels]
  * row matrix), the neighbour list of every query held fixed -- the derivative autograd returns through gaot_gno_fwd / gaot_gno_bwd_coords

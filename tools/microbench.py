@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Kernel microbenchmarks at the configs[1] shapes (for rocprofv3 / quick A-B): attention fwd+bwd, GEMM shapes, GNO, PointNet GeoEmbed,
-the attention-weighted GNO, the forward-only decoder (decoder_sample), the sampled field's Jacobian (decoder_jacobian), the projection MLP's tangent alone (projection_jvp), the sampled field's Hessian and Laplacian (decoder_hessian), its derivatives along per-query directions (decoder_directional)."""
+the attention-weighted GNO, the forward-only decoder (decoder_sample), the sampled field's Jacobian (decoder_jacobian), the projection MLP's tangent alone (projection_jvp), the sampled field's Hessian and Laplacian (decoder_hessian), its derivatives along per-query directions (decoder_directional), its adjoint with respect to the latent (decoder_adjoint)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 if os.environ.get("MB_TREE"):      # measure another checkout's package (gno_weighted: the parent commit's) with this script
@@ -858,6 +858,170 @@ elif what == "decoder_directional":
         print(f"Nq={nq} fp32: pred == sample_jacobian's and slot 0 of nd=3 == nd=1 bit for bit: {same}; max |sum of d2 over the frame - lap| / "
               f"max |lap| = {err:.2e}", flush=True)
         del q, frames, normal
+elif what == "decoder_adjoint":
+    # The adjoint of the sampled field (MAGNODecoder.sample_vjp) on decoder_hessian's decoders -- configs[1] (knn, k = 8), or with
+    # `--strategy radius|bidirectional` the reference YAML's decoder on row lists -- at 500 K and 8 M random query points with a random
+    # cotangent, fp32 mode.  In this one process, alternated round by round after a warm-up of each:
+    #   (a) sample_vjp, streamed in chunks;
+    #   (b) the route it replaces: the general decoder on an edge list for ALL queries under autograd (what forward(query_coord_pos=..)
+    #       runs), then torch.autograd.grad of <cotangent, pred> with respect to the latent;
+    #   (c) kernels alone on one chunk's lists: gaot_gno_adj against gaot_gno_bwd (precision 0) on the same by-source list and against
+    #       the forward (gaot_gno_fwd_knn / gaot_gno_fwd, precision 0) on the same by-query list;
+    #   (d) the split of (a) into its stages, one chunk at a time with device events around every stage.
+    # Device events around synchronised work; `reps` rounds (7 for the kept output); a row is the median with max - min, the peak is
+    # the rise of allocated memory over the inputs.  (a) is also run at 2^20 queries (one chunk) for the peak's independence of Nq.
+    # Kept in profiles/decoder_adjoint_microbench.txt / decoder_adjoint_rows_microbench.txt.
+    from gaot_3d_amd import graph as device_graph
+    from gaot_3d_amd.data import latent_grid
+    from gaot_3d_amd.model.layers.magno import MAGNOConfig, MAGNODecoder
+    gaot_3d_amd.set_precision("fp32")
+    latent = (64, 64, 32)
+    strategy = sys.argv[sys.argv.index("--strategy") + 1] if "--strategy" in sys.argv else "knn"
+    if strategy not in ("knn", "radius", "bidirectional"):
+        sys.exit(f"--strategy must be knn, radius or bidirectional, got {strategy}")
+    rows = strategy != "knn"
+    cfg = MAGNOConfig(gno_coord_dim=3, lifting_channels=32, mlp_type="linear", use_geoembed=[True, False],
+                      neighbor_strategy=["knn", strategy] if rows else "knn", k_neighbors=1 if rows else 8, gno_radius=0.033,
+                      out_gno_channel_mlp_hidden_layers=[64, 64], precompute_edges=False)
+    dec = MAGNODecoder(in_channels=32, out_channels=1, gno_config=cfg).to(dev).eval()
+    dec.latent_dims = latent
+    for p_ in dec.parameters():
+        p_.requires_grad_(True)              # (b) computes every decoder gradient: gno_bwd has no entry that skips them
+    tokens = latent_grid(latent).to(dev)
+    m_tok = tokens.shape[0]
+    rn = torch.randn(m_tok, 32, device=dev)
+    chunk = int(os.environ["MB_CHUNK"]) if os.environ.get("MB_CHUNK") else None
+    step = chunk or dec.SAMPLE_CHUNK
+    tag = f"fp32{' ' + strategy if rows else ''}"
+    fcs = list(dec.gno.channel_mlp.fcs)
+    kw_, kb_ = [fc.weight.detach() for fc in fcs], [fc.bias.detach() for fc in fcs]
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); out = fn(); e1.record()
+        torch.cuda.synchronize()
+        peak = torch.cuda.max_memory_allocated() - base
+        return e0.elapsed_time(e1), peak, out
+
+    def median(ts):
+        ts = sorted(ts)
+        return ts[len(ts) // 2], ts[0], ts[-1]
+
+    def replaced(q, g):
+        leaf = rn.detach().clone().requires_grad_(True)
+        zq = torch.zeros(q.shape[0], dtype=torch.long, device=dev)
+        zl = torch.zeros(m_tok, dtype=torch.long, device=dev)
+        pred = dec._decode(leaf, q, zq, tokens, zl, None, False)
+        return torch.autograd.grad((pred * g).sum(), leaf)[0]
+
+    def staged(q, g):
+        """sample_vjp's chunk loop with device events between its stages (one scale) -> ({stage: ms}, grad)"""
+        ev = lambda: torch.cuda.Event(enable_timing=True)
+        marks, grad = [], torch.zeros_like(rn)
+        with torch.no_grad():
+            grid = dec._stream_grid(rn, q, tokens)
+            for i in range(0, q.shape[0], step):
+                qc, gc = q[i:i + step], g[i:i + step]
+                es = [ev() for _ in range(7)]
+                es[0].record()
+                lists = (device_graph.knn_to_grid(qc, grid, 8), 8) if not rows else \
+                    device_graph.query_lists(strategy, qc, grid, dec.gno_radius, int(dec.k_neighbors))
+                es[1].record()
+                x = dec.gno.forward_knn(tokens, qc, *lists, rn) if not rows else dec.gno(y_pos=tokens, x_pos=qc, edge_index=None, f_y=rn, graph=lists)
+                es[2].record()
+                dx = dec._project_vjp(x, gc)
+                es[3].record()
+                gs = device_graph.by_source(lists, m_tok)
+                es[4].record()
+                part = ops.gno_adjoint(kw_, kb_, tokens, qc, dx, gs, None if rows else 8)
+                es[5].record()
+                grad.add_(part)
+                es[6].record()
+                marks.append(es)
+                del lists, x, dx, gs, part
+        torch.cuda.synchronize()
+        names = ("neighbour search", "recomputed forward", "projection + mix cotangent", "by_source", "adjoint kernel + fix-up", "accumulation")
+        return {n: sum(es[j].elapsed_time(es[j + 1]) for es in marks) for j, n in enumerate(names)}, grad
+
+    for nq in (500000, 8000000):
+        q = torch.rand(nq, 3, device=dev) * 2 - 1
+        g = torch.randn(nq, 1, device=dev)
+        routes = {"(a) sample_vjp": lambda: dec.sample_vjp(rn, q, g, tokens, chunk_points=chunk),
+                  "(b) decoder on an edge list + autograd.grad": lambda: replaced(q, g)}
+        warm = {n: timed(f)[2] for n, f in routes.items()}
+        a_, b_ = warm["(a) sample_vjp"], warm["(b) decoder on an edge list + autograd.grad"]
+        err = ((a_ - b_).abs().max() / b_.abs().max()).item()
+        same = torch.equal(a_, staged(q, g)[1])
+        del warm, a_, b_
+        ts, pk = {n: [] for n in routes}, {n: 0 for n in routes}
+        split = []
+        for _ in range(reps):
+            for n, f in routes.items():
+                t, p, _o = timed(f); ts[n].append(t); pk[n] = max(pk[n], p); del _o
+            split.append(staged(q, g)[0])
+        med = {n: median(ts[n]) for n in routes}
+        ma, mb = med["(a) sample_vjp"][0], med["(b) decoder on an edge list + autograd.grad"][0]
+        for n in routes:
+            m, lo, hi = med[n]
+            print(f"Nq={nq} {tag}: {n:45s} (chunk {step if n.startswith('(a)') else nq}) {m:9.3f} ms (max - min {hi - lo:.3f} ms = "
+                  f"{100 * (hi - lo) / m:.1f} %), peak {pk[n] / 2**20:9.1f} MiB")
+        pa, pb = pk["(a) sample_vjp"], pk["(b) decoder on an edge list + autograd.grad"]
+        print(f"Nq={nq} {tag}: (a) : (b) = {ma / mb:.2f} in time, {pa / max(pb, 1):.3f} in peak memory; max |(a) - (b)| / max |(b)| = {err:.2e}; "
+              f"the staged loop of (d) returns (a)'s bits: {same}")
+        tot = sum(median([s[n] for s in split])[0] for n in split[0])
+        for n in split[0]:
+            m, lo, hi = median([s[n] for s in split])
+            print(f"Nq={nq} {tag}: (d) {n:28s} {m:9.3f} ms (max - min {hi - lo:.3f} ms) = {100 * m / tot:5.1f} % of the stages' sum {tot:.3f} ms")
+        # (c) the kernels alone, on the lists of the first chunk
+        with torch.no_grad():
+            qc = q[:step].contiguous()
+            gc = torch.randn(qc.shape[0], 32, device=dev)
+            grid = dec._stream_grid(rn, qc, tokens)
+            if rows:
+                lists = device_graph.query_lists(strategy, qc, grid, dec.gno_radius, int(dec.k_neighbors))
+                gboth = device_graph.by_source(lists, m_tok)
+                kk, ne = None, lists.by_dst.num_edges
+                fwd = ("gaot_gno_fwd", lambda: ops.gno_forward(kw_, kb_, tokens, qc, rn, lists, precision=0))
+            else:
+                nbr = device_graph.knn_to_grid(qc, grid, 8)
+                gsrc = device_graph.by_source((nbr, 8), m_tok)
+                ei = torch.stack([nbr.reshape(-1), torch.arange(qc.shape[0], dtype=torch.int32, device=dev).repeat_interleave(8)])
+                gboth = ops.BipartiteGraph(ops.csr_build(ei, 1, qc.shape[0]), gsrc.by_src, m_tok, qc.shape[0])
+                kk, ne = 8, nbr.numel()
+                fwd = ("gaot_gno_fwd_knn", lambda: ops.gno_forward_knn("linear", kw_, kb_, tokens, qc, rn, None, nbr, 8, precision=0))
+            kern = {"gaot_gno_adj": lambda: ops.gno_adjoint(kw_, kb_, tokens, qc, gc, gboth, kk),
+                    "gaot_gno_bwd (precision 0)": lambda: ops.gno_backward(kw_, kb_, tokens, qc, rn, gc, gboth, precision=0),
+                    fwd[0] + " (precision 0)": fwd[1]}
+            for f in kern.values():
+                f()
+            kt = {n: [] for n in kern}
+            for _ in range(reps):
+                for n, f in kern.items():
+                    t, _p, _o = timed(f); kt[n].append(t); del _o
+            deg = gboth.by_src.rowptr[1:] - gboth.by_src.rowptr[:-1]
+            print(f"Nq={nq} {tag}: (c) one chunk of {qc.shape[0]} queries, {ne} edges; token rows: mean {deg.float().mean().item():.1f}, "
+                  f"max {int(deg.max())} edges, {int((deg == 0).sum())} of {m_tok} empty")
+            ka = median(kt["gaot_gno_adj"])
+            for n in kern:
+                m, lo, hi = median(kt[n])
+                print(f"Nq={nq} {tag}: (c) {n:32s} {m:9.3f} ms (max - min {hi - lo:.3f} ms); gaot_gno_adj : this = {ka[0] / m:.2f}")
+            kbm, kblo, kbhi = median(kt["gaot_gno_bwd (precision 0)"])
+            print(f"Nq={nq} {tag}: (c) gaot_gno_bwd - gaot_gno_adj = {kbm - ka[0]:+.3f} ms against max - min {max(kbhi - kblo, ka[2] - ka[1]):.3f} ms of the rounds", flush=True)
+        del q, g, qc, gc, gboth
+    # (a)'s peak does not grow with the number of queries: 2^20 queries (one chunk) against 8 M
+    peaks = {}
+    for nq in (1 << 20, 8000000):
+        q = torch.rand(nq, 3, device=dev) * 2 - 1
+        g = torch.randn(nq, 1, device=dev)
+        timed(lambda: dec.sample_vjp(rn, q, g, tokens, chunk_points=chunk))
+        peaks[nq] = timed(lambda: dec.sample_vjp(rn, q, g, tokens, chunk_points=chunk))[1] + q.numel() * 4 + g.numel() * 4
+        del q, g
+    grow, allow = peaks[8000000] - peaks[1 << 20], 8000000 * 16
+    print(f"{tag}: (a) peak with its two inputs: 2^20 queries {peaks[1 << 20] / 2**20:.1f} MiB, 8 M queries {peaks[8000000] / 2**20:.1f} MiB: "
+          f"+{grow / 2**20:.1f} MiB against {allow / 2**20:.1f} MiB of query_pos and cotangent at 8 M: {'within' if grow <= allow else 'ABOVE'}")
 elif what == "projection_jvp":
     # The projection MLP's forward-mode tangent on its own (LinearChannelMLP 32 -> 256 -> out, out in {1, 4}, three tangent planes, fp32
     # mode, random rows), as MAGNODecoder.sample_jacobian calls it: SAMPLE_CHUNK rows at a time into preallocated pred [N, out] and
