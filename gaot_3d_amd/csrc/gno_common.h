@@ -84,6 +84,22 @@ __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_wave_barrier();
 }
 
+// gelu_fast's value (its own expression: bit-identical) and gelu_fast_pair's derivative; t, p, e are shared.  The activation of the
+// forward-mode kernels (gno_jac.hip, gno_jac_adj.hip)
+__device__ __forceinline__ void gelu_fast_tangent(float x, float& g, float& dg) {
+    const float u = fabsf(x) * 0.70710678118654752440f;
+    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, u, 1.0f));
+    const float e = __builtin_amdgcn_exp2f(-0.72134752044448170368f * x * x);
+    float p = fmaf(t, 0.5f * 1.061405429f, 0.5f * -1.453152027f);
+    p = fmaf(t, p, 0.5f * 1.421413741f);
+    p = fmaf(t, p, 0.5f * -0.284496736f);
+    p = fmaf(t, p, 0.5f * 0.254829592f);
+    const float h = t * p * e;                    // Phi(-|x|)
+    g = fmaf(-fabsf(x), h, fmaxf(x, 0.f));
+    const float cdf = x >= 0.f ? 1.0f - h : h;
+    dg = fmaf(x * e, 0.39894228040143267794f, cdf);
+}
+
 struct MlpPtrs {
     const float* w[GAOT_MAX_MLP_LAYERS];
     const float* b[GAOT_MAX_MLP_LAYERS];

@@ -62,21 +62,6 @@ struct JacRows {
     int64_t part_plane;     // n_tiles * 2 * 32: one plane of part
 };
 
-// gelu_fast's value (its own expression: bit-identical) and gelu_fast_pair's derivative; t, p, e are shared
-__device__ __forceinline__ void gelu_fast_tangent(float x, float& g, float& dg) {
-    const float u = fabsf(x) * 0.70710678118654752440f;
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, u, 1.0f));
-    const float e = __builtin_amdgcn_exp2f(-0.72134752044448170368f * x * x);
-    float p = fmaf(t, 0.5f * 1.061405429f, 0.5f * -1.453152027f);
-    p = fmaf(t, p, 0.5f * 1.421413741f);
-    p = fmaf(t, p, 0.5f * -0.284496736f);
-    p = fmaf(t, p, 0.5f * 0.254829592f);
-    const float h = t * p * e;                    // Phi(-|x|)
-    g = fmaf(-fabsf(x), h, fmaxf(x, 0.f));
-    const float cdf = x >= 0.f ? 1.0f - h : h;
-    dg = fmaf(x * e, 0.39894228040143267794f, cdf);
-}
-
 template <int NH, int MODE, class... Rows>
 __global__ __launch_bounds__(256, 1) void k_gno_fwd_knn_jac(MlpPtrs mlp, const float* __restrict__ y_pos,
                                                             const float* __restrict__ x_pos, const float* __restrict__ f_y,

@@ -97,7 +97,7 @@ __device__ __forceinline__ float opaque(float x) {
     return x;
 }
 
-// gelu_fast's value (its own expression: bit-identical), gelu_fast_pair's derivative (gelu_fast_tangent of gno_jac.hip) and the
+// gelu_fast's value (its own expression: bit-identical), gelu_fast_pair's derivative (gelu_fast_tangent of gno_common.h) and the
 // second derivative phi(x) (2 - x^2); t, p, e are shared
 __device__ __forceinline__ void gelu_fast_jet2(float x, float& g, float& dg, float& ddg) {
     const float u = fabsf(x) * 0.70710678118654752440f;

@@ -1527,3 +1527,30 @@ class SampleLatentFn(Function):
         latent, query_pos, tokens_pos = ctx.saved_tensors
         g = ctx.decoder.sample_vjp(latent, query_pos, dout.to(torch.float32), tokens_pos, chunk_points=ctx.chunk_points)
         return g.to(latent.dtype), None, None, None, None
+
+
+class SampleJacobianLatentFn(Function):
+    """The sampled field AND its spatial derivative as a differentiable function of the LATENT: forward =
+    ``MAGNODecoder.sample_jacobian(..., row_lists=True)`` bit for bit -> (pred, jac), backward = ``MAGNODecoder.sample_jacobian_vjp``
+    (the streamed adjoint of the tangent kernel).  An output that received no gradient contributes no cotangent (``pred``: None,
+    ``jac``: zeros).  Nothing is saved but the latent, the query coordinates and the token tensor.  Gradients flow to ``latent``
+    ONLY."""
+
+    @staticmethod
+    def forward(ctx, latent: Tensor, decoder, query_pos: Tensor, tokens_pos: Tensor, chunk_points: Optional[int]):
+        ctx.decoder, ctx.chunk_points = decoder, chunk_points
+        ctx.save_for_backward(latent, query_pos, tokens_pos)
+        ctx.set_materialize_grads(False)
+        return decoder.sample_jacobian(latent.detach(), query_pos, tokens_pos, chunk_points=chunk_points, row_lists=True)
+
+    @staticmethod
+    def backward(ctx, dpred: Optional[Tensor], djac: Optional[Tensor]):
+        latent, query_pos, tokens_pos = ctx.saved_tensors
+        if dpred is None and djac is None:
+            return None, None, None, None, None
+        nq = query_pos.shape[0]
+        cot_pred = None if dpred is None else dpred.to(torch.float32).contiguous()
+        cot_jac = torch.zeros(nq, ctx.decoder.out_channels, 3, dtype=torch.float32, device=query_pos.device) if djac is None \
+            else djac.to(torch.float32).contiguous()
+        g = ctx.decoder.sample_jacobian_vjp(latent, query_pos, cot_pred, cot_jac, tokens_pos, chunk_points=ctx.chunk_points)
+        return g.to(latent.dtype), None, None, None, None

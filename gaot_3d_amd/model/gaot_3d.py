@@ -253,6 +253,50 @@ class GAOT3D(nn.Module):
                              what="the adjoint of the sampled field", jets=False)
         return GF.SampleLatentFn.apply(latent, dec, q, lat, chunk_points)
 
+    def sample_jacobian_vjp(self, latent: torch.Tensor, query_pos: torch.Tensor, cot_pred: Optional[torch.Tensor],
+                            cot_jac: torch.Tensor, tokens_pos: Optional[torch.Tensor] = None,
+                            chunk_points: Optional[int] = None) -> torch.Tensor:
+        """The ADJOINT of ``sample_jacobian``: -> grad_latent [D*H*W, lifting_channels] (fp32)
+        = sum_q cot_pred[q] . d pred[q] / d latent + sum_q cot_jac[q] . d jac[q] / d latent for cotangents ``cot_pred``
+        [Nq, output_size] (float32, or None for a loss on the derivative alone) and ``cot_jac`` [Nq, output_size, 3] -- the gradient
+        of a loss on the field's SPATIAL DERIVATIVE (a wall-normal gradient misfit, a Sobolev term, a first-order PDE or boundary
+        residual) with respect to the latent, streamed in chunks of queries with no edge_index, no decoder autograd graph and no
+        weight gradients.  ``MAGNODecoder.sample_jacobian_vjp``: exact fp32 in both precision modes, outside autograd,
+        bit-reproducible for a given ``chunk_points``.  The decoder's parameters and the query coordinates are constants.  Routes and
+        refusals are ``sample_vjp``'s."""
+        lat = self._one_sample("sample_jacobian_vjp", latent, tokens_pos)
+        if getattr(self, "_shard_group", None) is not None:
+            raise NotImplementedError("GAOT3D.sample_jacobian_vjp: a point-sharded model is not supported")
+        return self.decoder.sample_jacobian_vjp(latent, query_pos.to(latent.device), cot_pred, cot_jac, lat, chunk_points=chunk_points)
+
+    def sample_jacobian_autograd(self, latent: torch.Tensor, query_pos: torch.Tensor, tokens_pos: Optional[torch.Tensor] = None,
+                                 chunk_points: Optional[int] = None):
+        """``sample_jacobian`` as a differentiable function of the latent: -> (pred [Nq, output_size], jac [Nq, output_size, 3]) whose
+        backward is ``sample_jacobian_vjp`` (``functional.SampleJacobianLatentFn``), so that a loss on the field's derivative reaches
+        the encoder, the processor and ``batch.pos`` through the ordinary autograd of ``latent``.  The forward is
+        ``sample_jacobian(..., row_lists=True)``'s result bit for bit (the flag changes nothing on a 'knn' decoder); an output that
+        received no gradient contributes a zero cotangent.  A normal derivative needs no API of its own:
+        ``(jac * n[:, None, :]).sum(-1)`` in ordinary autograd hands the backward cot_jac = g (x) n.  Gradients flow to ``latent``
+        ONLY: the decoder's parameters are constants here, and a ``query_pos`` that requires grad raises ValueError (no second
+        derivative in the query is formed).  Configurations ``sample_jacobian_vjp`` refuses are refused here, before the forward
+        runs."""
+        fn = "sample_jacobian_autograd"
+        lat = self._one_sample(fn, latent, tokens_pos)
+        if query_pos.requires_grad:
+            raise ValueError(f"GAOT3D.{fn}: query_pos requires grad, but gradients flow to the latent only; detach it")
+        if getattr(self, "_shard_group", None) is not None:
+            raise NotImplementedError(f"GAOT3D.{fn}: a point-sharded model is not supported")
+        q = query_pos.to(latent.device)
+        dec = self.decoder
+        dec._sample_args(fn, chunk_points)
+        with torch.no_grad(), ops.fp32_arithmetic():      # sample_jacobian_vjp's refusals, before anything runs
+            dec._jet2_stream(fn, latent.detach(), q, lat, chunk_points, rows=dec.decoder_strategy != "knn",
+                             what="the adjoint of the field's Jacobian", jets=False)
+            if dec.projection.non_linearity not in dec.JAC_VJP_ACTS:
+                raise NotImplementedError(f"GAOT3D.{fn}: the second derivative of the projection's activation "
+                                          f"{dec.projection.non_linearity!r} is not written (covered: {dec.JAC_VJP_ACTS})")
+        return GF.SampleJacobianLatentFn.apply(latent, dec, q, lat, chunk_points)
+
     def forward(self, batch, tokens_pos: Optional[torch.Tensor] = None, tokens_batch_idx: Optional[torch.Tensor] = None,
                 query_coord_pos: Optional[torch.Tensor] = None, query_coord_batch_idx: Optional[torch.Tensor] = None,
                 condition: Optional[float] = None) -> torch.Tensor:

@@ -235,19 +235,45 @@ class IntegralTransform(nn.Module):
         (its offsets give 1/deg; a query without neighbours contributes nothing) and ``by_src`` from ``graph.by_source``."""
         return self._adjoint("adjoint_rows", y_pos, x_pos, grad_out, graph, None)
 
-    def _adjoint(self, fn, y_pos, x_pos, grad_out, graph, k):
-        """the two adjoint methods: every pass of ``_fused_passes`` (its f_y block is the cotangent's) is one ``ops.gno_adjoint`` call"""
+    def adjoint_jac_knn(self, y_pos, x_pos, nbr, k: int, grad_out, grad_jac, graph=None):
+        """The ADJOINT of ``jacobian_knn`` with respect to f_y: -> grad_f_y [N_y, C] for the cotangents ``grad_out`` [N_x, C] on the
+        value and ``grad_jac`` [3, N_x, C] on the Jacobian planes (fp32, ``jacobian_knn``'s layout), on the regular list ``nbr`` /
+        ``k``.  Value and tangent planes of the 'linear' transform are linear in f_y, so this is the tangent kernel's per-edge work
+        contracted with the cotangents and reduced by source (``ops.gno_adjoint_jac``: two launches per 32-channel pass).  ``graph``,
+        the preparation of the operands (the cotangent planes ride where ``grad_out`` does), exactness and refusals are
+        ``adjoint_knn``'s."""
+        if int(k) not in ops.GNO_KNN_K:
+            raise NotImplementedError(f"IntegralTransform.adjoint_jac_knn: lists of k in {ops.GNO_KNN_K} neighbours per query, got k = {k}")
+        if graph is None:
+            from ... import graph as device_graph
+            graph = device_graph.by_source((nbr, int(k)), y_pos.shape[0])
+        return self._adjoint("adjoint_jac_knn", y_pos, x_pos, grad_out, graph, int(k), grad_jac)
+
+    def adjoint_jac_rows(self, y_pos, x_pos, grad_out, grad_jac, graph):
+        """``adjoint_jac_knn`` on RAGGED rows: ``graph`` holds both lists of the chunk, as for ``adjoint_rows``."""
+        return self._adjoint("adjoint_jac_rows", y_pos, x_pos, grad_out, graph, None, grad_jac)
+
+    def _adjoint(self, fn, y_pos, x_pos, grad_out, graph, k, grad_jac=None):
+        """the four adjoint methods: every pass of ``_fused_passes`` (its f_y block is the cotangent's) is one ``ops.gno_adjoint`` call,
+        or with ``grad_jac`` [3, N_x, C] one ``ops.gno_adjoint_jac`` call on the same channels of every plane"""
         fcs = list(self.channel_mlp.fcs)
         with torch.no_grad():
             plan = self._fused_plan(fcs, grad_out, y_pos, x_pos) if self.transform_type == "linear" else None
             if plan is None:
                 raise NotImplementedError(f"IntegralTransform.{fn}: only the 'linear' transforms the fused kernels evaluate (_fused_plan); "
                                           f"transform_type = {self.transform_type!r}, use_attn = {bool(self.use_attn)}")
+            if grad_jac is not None and (grad_jac.dim() != 3 or grad_jac.shape[0] != 3 or grad_jac.shape[1:] != grad_out.shape):
+                raise ValueError(f"IntegralTransform.{fn}: grad_jac must be [3, {grad_out.shape[0]}, {grad_out.shape[1]}], "
+                                 f"got {tuple(grad_jac.shape)}")
             y3, x3, _, (w0, b0, *mid), blocks = self._fused_passes(fcs, y_pos, x_pos, grad_out, *plan)
             outs = []
-            for wb, bb, gb, n in blocks:
-                o = ops.gno_adjoint([w0.contiguous(), *mid[0::2], wb.contiguous()], [b0, *mid[1::2], bb.contiguous()], y3, x3,
-                                    gb.contiguous(), graph, k)
+            for i, (wb, bb, gb, n) in enumerate(blocks):
+                ws, bs = [w0.contiguous(), *mid[0::2], wb.contiguous()], [b0, *mid[1::2], bb.contiguous()]
+                if grad_jac is None:
+                    o = ops.gno_adjoint(ws, bs, y3, x3, gb.contiguous(), graph, k)
+                else:
+                    jb = grad_jac if grad_jac.shape[2] == 32 else torch.nn.functional.pad(grad_jac[:, :, 32 * i:32 * i + n], (0, 32 - n))
+                    o = ops.gno_adjoint_jac(ws, bs, y3, x3, gb.contiguous(), jb.contiguous(), graph, k)
                 outs.append(o if n == 32 else o[:, :n])
             return outs[0].contiguous() if len(outs) == 1 else torch.cat(outs, dim=1)
 

@@ -961,6 +961,155 @@ class MAGNODecoder(nn.Module):
                 grad.add_(self._vjp_chunk(f, q.contiguous(), cotangent[sl], latent_tokens_pos, lists))
         return grad
 
+    # the projection activations ``sample_jacobian_vjp`` differentiates twice: act' and act'' as plain fp32 tensor operations
+    JAC_VJP_ACTS = (None, "none", "gelu", "relu")
+
+    @staticmethod
+    def _act_jets(z, act):
+        """(act'(z), act''(z)) for the names in ``JAC_VJP_ACTS``; None stands for a factor that is identically 1 (first) or 0 (second):
+        gelu' = Phi(z) + z phi(z), gelu'' = phi(z) (2 - z^2); relu' = 1[z > 0], relu'' = 0"""
+        if act in (None, "none"):
+            return None, None
+        if act == "relu":
+            return (z > 0).to(z.dtype), None
+        phi = torch.exp(-0.5 * z * z) * 0.3989422804014327
+        return 0.5 * (1.0 + torch.erf(z * 0.7071067811865476)) + z * phi, phi * (2.0 - z * z)
+
+    def _project_jac_vjp(self, planes, gy, gj):
+        """The cotangent of the projection's input JET: for the mixed GNO planes ``planes`` = [x, x'_0, x'_1, x'_2] ([rows, C] each) and
+        the cotangents ``gy`` [rows, out_channels] (or None) on y = W_2 act(z) + b_2 and ``gj`` [rows, out_channels, 3] on
+        y'_d = W_2 (act'(z) * W_1 x'_d), z = W_1 x + b_1 -> [dx, dx'_0, dx'_1, dx'_2]:
+            a = g_y W_2,  a_d = g_y'd W_2,  u_d = x'_d W_1^T
+            dz = act'(z) * a + act''(z) * sum_d u_d * a_d,   dx = dz W_1;      du_d = act'(z) * a_d,   dx'_d = du_d W_1
+        Exact fp32: three GEMMs per row block on the four planes STACKED ([4 rows, .]: one launch per product, precision 0) and the
+        elementwise middle as plain fp32 tensor operations (``_act_jets``).  Rows in blocks sized as in ``_project_vjp``."""
+        from ... import ops
+        fc1, fc2 = self.projection.fcs
+        w1, w2 = GF._w2d(fc1.weight).contiguous(), GF._w2d(fc2.weight).contiguous()
+        act = self.projection.non_linearity
+        n, c = planes[0].shape
+        hid, oc = w1.shape[0], w2.shape[0]
+        outs = [torch.empty_like(planes[0]) for _ in range(4)]
+        step = n if hid <= c else max(1024, n * c // hid)
+        for j in range(0, n, step):
+            m = planes[0][j:j + step].shape[0]
+            x4 = torch.cat([p[j:j + step] for p in planes])
+            g0 = gy[j:j + step] if gy is not None else gj.new_zeros(m, oc)
+            g4 = torch.cat([g0] + [gj[j:j + step, :, d] for d in range(3)])
+            zu = ops.gemm(x4, w1, 4 * m, hid, c, c, c, False, True, precision=0)          # [z - b_1; u_0; u_1; u_2]
+            a4 = ops.gemm(g4, w2, 4 * m, hid, oc, oc, hid, False, False, precision=0)     # [a; a_0; a_1; a_2]
+            del x4, g4
+            z = zu[:m]
+            if fc1.bias is not None:
+                z += fc1.bias
+            d1, d2 = self._act_jets(z, act)
+            if d2 is not None:
+                s = zu[m:2 * m] * a4[m:2 * m]
+                for d in (1, 2):
+                    s += zu[(1 + d) * m:(2 + d) * m] * a4[(1 + d) * m:(2 + d) * m]
+                s *= d2
+            del zu, z
+            if d1 is not None:                       # a4 becomes [dz; du_0; du_1; du_2] in place
+                a4.view(4, m, hid).mul_(d1)
+            if d2 is not None:
+                a4[:m] += s
+                del s
+            dx4 = ops.gemm(a4, w1, 4 * m, c, hid, hid, c, False, False, precision=0)
+            for p in range(4):
+                outs[p][j:j + step] = dx4[p * m:(p + 1) * m]
+        return outs
+
+    def _jac_vjp_chunk(self, rndata_flat, q, gy, gj, lat, lists):
+        """one chunk of ``sample_jacobian_vjp``: -> its [M, C] part of the latent's gradient.  A call of its own, so that a chunk's
+        planes and lists are freed before the next chunk's are allocated."""
+        from ... import graph as device_graph
+        m = lat.shape[0]
+        planes = self._jet_planes(rndata_flat, q, lat, lists)      # the mixed [x, x'_0, x'_1, x'_2], recomputed at fp32
+        d = self._project_jac_vjp(planes, gy, gj)
+        del planes
+        if isinstance(lists, tuple):                       # 'knn': equal operands, the weights' tangents drop out (``sample_jacobian``)
+            d = self._mix_equal_scales(d, q)
+            return self.gno.adjoint_jac_knn(lat, q, *lists, d[0], torch.stack(d[1:]), graph=device_graph.by_source(lists, m))
+        ns = len(lists)
+        if ns == 1 or not self.use_scale_weights:          # one scale, or summed scales: every scale gets the planes as they are
+            per = [(d[0], torch.stack(d[1:]))] * ns
+        else:
+            # x = sum_s w_s o_s and x'_d = sum_s (w_s o'_s,d + w'_s,d o_s) with w = softmax(l(q)), a function of the query alone:
+            # G_s = w_s dx + sum_d w'_s,d dx'_d on o_s,  J_s,d = w_s dx'_d on o'_s,d
+            sw = self.scale_weighting
+            logits, hdn = _scale_logits(self, q)
+            w = torch.softmax(logits, dim=1)
+            dls = _logit_tangents((hdn > 0).to(hdn.dtype), sw[0].weight, sw[2].weight, lambda x, wt: GF.linear(x, wt, None, precision=0))
+            dws = [_softmax_weight_jets(w, dl)[0] for dl in dls]
+            per = []
+            for s in range(ns):
+                ws = w[:, s:s + 1]
+                g = ws * d[0]
+                for di, dw in enumerate(dws):
+                    g += dw[:, s:s + 1] * d[1 + di]
+                per.append((g, torch.stack([ws * d[1 + di] for di in range(3)])))
+        del d
+        part = None
+        for rows, (g, jc) in zip(lists, per):
+            p = self.gno.adjoint_jac_rows(lat, q, g, jc, device_graph.by_source(rows, m))
+            part = p if part is None else part.add_(p)
+        return part
+
+    @torch.no_grad()
+    def sample_jacobian_vjp(self, rndata_flat, query_pos, cot_pred, cot_jac, latent_tokens_pos,
+                            chunk_points: Optional[int] = None) -> torch.Tensor:
+        """The ADJOINT of ``sample_jacobian(row_lists=True)``: -> grad_latent [M, C] (fp32)
+            = sum_q cot_pred[q] . d pred[q] / d rndata_flat + sum_q cot_jac[q] . d jac[q] / d rndata_flat,
+        the vector-Jacobian product of the sampled field AND its spatial derivative with respect to the latent -- the gradient of a
+        loss on the field's derivative (a misfit of d p / d n against measured wall-normal gradients, a Sobolev term, a first-order
+        PDE or boundary residual at collocation points), which the autograd of ``GAOT3D.latent`` carries on into the encoder, the
+        processor and the sample's coordinates.  ``cot_pred``: float32 [Nq, out_channels], or None for a loss on the derivative
+        alone; ``cot_jac``: float32 [Nq, out_channels, 3].  The decoder's parameters and the query coordinates are CONSTANTS here.
+
+        Streamed as ``sample_vjp`` is, through the same chunk loop.  Per chunk: the lists; the mixed value and three tangent planes
+        recomputed at fp32 (``_jet_planes``, as ``sample_jacobian`` forms them; on row lists with the tangents of the scale weights);
+        the cotangent of that jet through the projection (``_project_jac_vjp``: it needs act'' -- gelu'' = phi(z)(2 - z^2),
+        relu'' = 0); the scale mix's cotangent (``knn``: equal operands, ``_mix_equal_scales`` on the four planes; row lists with
+        softmax weights: G_s = w_s dx + sum_d w'_s,d dx'_d and J_s,d = w_s dx'_d, the weights being functions of the query alone);
+        then per scale ``graph.by_source`` and the adjoint of the tangent kernel (``IntegralTransform.adjoint_jac_knn`` /
+        ``adjoint_jac_rows``: value and three tangent chains through the per-edge MLP, contracted with the four cotangent planes and
+        reduced by TOKEN -- no MLP backward, no weight gradients, no ``gno_bwd``), and the chunk's [M, C] part added in chunk order.
+        Nothing sized by Nq exists but the caller's own tensors.
+
+        Exact fp32 in both precision modes (the same bits), outside autograd, bit-reproducible run to run for a given
+        ``chunk_points``; not bit-identical across chunkings (a token's sum is split at the chunk boundaries).  Routes and refusals
+        are ``sample_vjp``'s; in addition a projection activation outside ``JAC_VJP_ACTS`` raises NotImplementedError naming it, and
+        cotangents of the wrong dtype, shape or device raise ValueError."""
+        from ... import ops
+        fn = "sample_jacobian_vjp"
+        self._sample_args(fn, chunk_points)
+        nq, oc = int(query_pos.shape[0]), self.out_channels
+        for name, cot, shape, optional in (("cot_pred", cot_pred, (nq, oc), True), ("cot_jac", cot_jac, (nq, oc, 3), False)):
+            if cot is None and optional:
+                continue
+            if not isinstance(cot, torch.Tensor) or cot.dtype != torch.float32 or cot.device != query_pos.device \
+                    or tuple(cot.shape) != shape:
+                got = f"{cot.dtype} {tuple(cot.shape)} on {cot.device}" if isinstance(cot, torch.Tensor) else type(cot).__name__
+                raise ValueError(f"MAGNODecoder.{fn}: {name} must be float32 {list(shape)} on the queries' device "
+                                 f"({query_pos.device}){' or None' if optional else ''}, got {got}")
+        if getattr(self, "_shard_group", None) is not None:
+            raise NotImplementedError(f"MAGNODecoder.{fn}: a point-sharded model is not supported (every rank would hold a partial sum)")
+        rndata_flat, query_pos, cot_jac = rndata_flat.detach(), query_pos.detach(), cot_jac.detach()
+        cot_pred = None if cot_pred is None else cot_pred.detach()
+        rows = self.decoder_strategy != "knn"
+        with ops.fp32_arithmetic():
+            grid, chunk = self._jet2_stream(fn, rndata_flat, query_pos, latent_tokens_pos, chunk_points, rows=rows,
+                                            what="the adjoint of the field's Jacobian", jets=False)
+            if self.projection.non_linearity not in self.JAC_VJP_ACTS:
+                raise NotImplementedError(f"MAGNODecoder.{fn}: the second derivative of the projection's activation "
+                                          f"{self.projection.non_linearity!r} is not written (covered: {self.JAC_VJP_ACTS})")
+            f = rndata_flat.to(torch.float32).contiguous()
+            grad = torch.zeros_like(f)
+            for sl, q, lists in self._stream_chunks(grid, query_pos, chunk, "rows" if rows else "knn", lead=False):
+                grad.add_(self._jac_vjp_chunk(f, q.contiguous(), None if cot_pred is None else cot_pred[sl], cot_jac[sl],
+                                              latent_tokens_pos, lists))
+        return grad
+
     def sample_jacobian(self, rndata_flat, query_pos, latent_tokens_pos, chunk_points: Optional[int] = None,
                         row_lists: bool = False):
         """``sample`` with the spatial derivative of the field: -> (pred [Nq, out_channels], jac [Nq, out_channels, coord_dim]) with

@@ -356,27 +356,7 @@ def gno_adjoint(weights, biases, y_pos: Tensor, x_pos: Tensor, grad_out: Tensor,
     most straddle the 32-edge tiles and one fix-up thread adds a row's tile partials in order: slow when the queries cluster on a
     few sources, but correct."""
     lib = _lib.load()
-    m, keep = _mlp_struct(weights, biases)
-    y_pos = _req(y_pos, torch.float32, "y_pos")
-    x_pos = _req(x_pos, torch.float32, "x_pos")
-    grad_out = _req(grad_out, torch.float32, "grad_out")
-    if y_pos.dim() != 2 or x_pos.dim() != 2 or y_pos.shape[1] != 3 or x_pos.shape[1] != 3:
-        raise GaotError(f"gno_adjoint: y_pos / x_pos must be [*, 3], got {tuple(y_pos.shape)} / {tuple(x_pos.shape)}")
-    if g.by_src is None:
-        raise GaotError("gno_adjoint: the graph has no by-source list (graph.by_source builds one)")
-    if y_pos.shape[0] != g.num_src or x_pos.shape[0] != g.num_dst:
-        raise GaotError(f"gno_adjoint: y_pos / x_pos have {y_pos.shape[0]} / {x_pos.shape[0]} rows, the graph {g.num_src} / {g.num_dst}")
-    if tuple(grad_out.shape) != (g.num_dst, m.channels):
-        raise GaotError(f"gno_adjoint: grad_out must be [{g.num_dst}, {m.channels}], got {tuple(grad_out.shape)}")
-    e = g.by_src.num_edges
-    if k is None:
-        if g.by_dst is None:
-            raise GaotError("gno_adjoint: the degrees need the by-query offsets (g.by_dst.rowptr) or the k of a regular list")
-        rowptr_dst, kk = g.by_dst.rowptr, 0
-    else:
-        rowptr_dst, kk = None, int(k)
-        if kk < 1 or e != g.num_dst * kk:
-            raise GaotError(f"gno_adjoint: a regular list of {g.num_dst} queries x k = {kk} holds {g.num_dst * max(kk, 0)} edges, got {e}")
+    m, keep, y_pos, x_pos, grad_out, rowptr_dst, kk, e = _gno_adjoint_args("gno_adjoint", weights, biases, y_pos, x_pos, grad_out, g, k)
     dev = x_pos.device
     grad_f = torch.empty(g.num_src, m.channels, dtype=torch.float32, device=dev)
     ws = _ws(lib.gaot_gno_adj_workspace_bytes(e, m.channels), dev)
@@ -384,6 +364,61 @@ def gno_adjoint(weights, biases, y_pos: Tensor, x_pos: Tensor, grad_out: Tensor,
         check(lib.gaot_gno_adj(C.byref(m), _ptr(y_pos), _ptr(x_pos), _ptr(grad_out), _ptr(rowptr_dst), kk, _ptr(g.by_src.key),
                                _ptr(g.by_src.other), _ptr(g.by_src.rowptr), e, g.num_src, g.num_dst, _ptr(grad_f), _ptr(ws), ws.numel(),
                                _stream()), "gaot_gno_adj")
+    return grad_f
+
+
+def _gno_adjoint_args(fn, weights, biases, y_pos, x_pos, grad_out, g, k):
+    """the operand rules of ``gno_adjoint`` and ``gno_adjoint_jac`` -> (the MLP struct, what keeps its arrays alive, y_pos, x_pos,
+    grad_out, rowptr_dst or None, the k passed to the ABI, the number of edges)"""
+    m, keep = _mlp_struct(weights, biases)
+    y_pos = _req(y_pos, torch.float32, "y_pos")
+    x_pos = _req(x_pos, torch.float32, "x_pos")
+    grad_out = _req(grad_out, torch.float32, "grad_out")
+    if y_pos.dim() != 2 or x_pos.dim() != 2 or y_pos.shape[1] != 3 or x_pos.shape[1] != 3:
+        raise GaotError(f"{fn}: y_pos / x_pos must be [*, 3], got {tuple(y_pos.shape)} / {tuple(x_pos.shape)}")
+    if g.by_src is None:
+        raise GaotError(f"{fn}: the graph has no by-source list (graph.by_source builds one)")
+    if y_pos.shape[0] != g.num_src or x_pos.shape[0] != g.num_dst:
+        raise GaotError(f"{fn}: y_pos / x_pos have {y_pos.shape[0]} / {x_pos.shape[0]} rows, the graph {g.num_src} / {g.num_dst}")
+    if tuple(grad_out.shape) != (g.num_dst, m.channels):
+        raise GaotError(f"{fn}: grad_out must be [{g.num_dst}, {m.channels}], got {tuple(grad_out.shape)}")
+    e = g.by_src.num_edges
+    if k is None:
+        if g.by_dst is None:
+            raise GaotError(f"{fn}: the degrees need the by-query offsets (g.by_dst.rowptr) or the k of a regular list")
+        rowptr_dst, kk = g.by_dst.rowptr, 0
+    else:
+        rowptr_dst, kk = None, int(k)
+        if kk < 1 or e != g.num_dst * kk:
+            raise GaotError(f"{fn}: a regular list of {g.num_dst} queries x k = {kk} holds {g.num_dst * max(kk, 0)} edges, got {e}")
+    return m, keep, y_pos, x_pos, grad_out, rowptr_dst, kk, e
+
+
+def gno_adjoint_jac(weights, biases, y_pos: Tensor, x_pos: Tensor, grad_out: Tensor, grad_jac: Tensor, g: BipartiteGraph,
+                    k: Optional[int] = None) -> Tensor:
+    """The ADJOINT of ``gno_forward_knn_jac`` / ``gno_forward_jac`` ('linear') with respect to f_y (gaot_gno_adj_jac): for cotangents
+    ``grad_out`` [n_query, 32] on the value and ``grad_jac`` [3, n_query, 32] on the three tangent planes (the layout those two
+    write) -> grad_f_y [n_src, 32] with
+        grad_f_y[t] = sum over the edges e of source t of  (K_e * grad_out[q_e] + sum_d d_d K_e * grad_jac[d, q_e]) / deg(q_e)
+    where d_d K is the derivative of the kernel MLP in coordinate d of the query.  The tangent kernel's per-edge work (value and
+    three tangent chains, forward mode) contracted with four gathered cotangent rows into one plane and reduced by source: no MLP
+    backward, no weight gradients, no f_y.  Operand rules are ``gno_adjoint``'s, with ``grad_jac`` float32, contiguous, on the
+    device; exact fp32 whatever the precision mode (the same bits in both), no atomics, bit-reproducible run to run; a source
+    without edges gets exact zeros.  Two launches (main + fix-up; the fix-up alone without edges)."""
+    lib = _lib.load()
+    m, keep, y_pos, x_pos, grad_out, rowptr_dst, kk, e = _gno_adjoint_args("gno_adjoint_jac", weights, biases, y_pos, x_pos, grad_out, g, k)
+    if not isinstance(grad_jac, Tensor) or not grad_jac.is_cuda or grad_jac.dtype != torch.float32 or not grad_jac.is_contiguous() \
+            or tuple(grad_jac.shape) != (3, g.num_dst, m.channels) or grad_jac.device != grad_out.device:
+        got = f"{grad_jac.dtype} {tuple(grad_jac.shape)} on {grad_jac.device}, strides {tuple(grad_jac.stride())}" \
+            if isinstance(grad_jac, Tensor) else type(grad_jac).__name__
+        raise GaotError(f"gno_adjoint_jac: grad_jac must be contiguous float32 [3, {g.num_dst}, {m.channels}] on {grad_out.device}, got {got}")
+    dev = x_pos.device
+    grad_f = torch.empty(g.num_src, m.channels, dtype=torch.float32, device=dev)
+    ws = _ws(lib.gaot_gno_adj_jac_workspace_bytes(e), dev)
+    with _timed(f"gno_adj_jac_nh{m.n_hidden}"):
+        check(lib.gaot_gno_adj_jac(C.byref(m), _ptr(y_pos), _ptr(x_pos), _ptr(grad_out), _ptr(grad_jac), _ptr(rowptr_dst), kk,
+                                   _ptr(g.by_src.key), _ptr(g.by_src.other), _ptr(g.by_src.rowptr), e, g.num_src, g.num_dst,
+                                   _ptr(grad_f), _ptr(ws), ws.numel(), _stream()), "gaot_gno_adj_jac")
     return grad_f
 
 

@@ -236,6 +236,25 @@ int gaot_gno_fwd_jac(const gaot_mlp_t* mlp /* host */, int mode, const float* y_
                      int64_t num_edges, int64_t num_queries, float* out /* [num_queries, channels] */,
                      float* jac /* [3, num_queries, channels] */, void* workspace, size_t workspace_bytes, gaot_stream_t stream);
 
+/* The ADJOINT of gaot_gno_fwd_knn_jac / gaot_gno_fwd_jac (mode 0) with respect to f_y (csrc/gno_jac_adj.hip), for the vector-Jacobian
+ * product of a sampled field's value AND spatial derivative with respect to the latent.  Value and tangent planes are linear in f_y:
+ *   grad_f_y[t][c] = sum over row t of the SOURCE-sorted list of
+ *                    ( K_c(y_pos[t], x_pos[q_e]) grad_out[q_e][c] + sum_d d_d K_c(y_pos[t], x_pos[q_e]) grad_jac[d][q_e][c] ) / deg(q_e)
+ * with d_d K the derivative of the kernel MLP in the query coordinate d: the tangent kernel's per-edge work (the value and three
+ * tangent chains, forward mode), the four planes contracted with four gathered cotangent rows into ONE plane (the value term, then
+ * one fma per direction d = 0, 1, 2, then 1/deg) and reduced by source as gaot_gno_adj reduces it.  No MLP backward, no weight
+ * gradients, no atomics; a fixed summation order, bit-reproducible run to run; a source without edges gets exact zeros.  grad_jac is
+ * [3, num_queries, channels], the layout gaot_gno_fwd_knn_jac writes.  Lists, degrees (rowptr_dst, or NULL with the k of a regular
+ * list), sizes and workspace rules are gaot_gno_adj's.  Exact fp32, no precision argument.  Linear mode only, 1 <= n_hidden <= 4,
+ * hidden 64, channels 32.  Two launches (the fix-up alone with num_edges == 0). */
+size_t gaot_gno_adj_jac_workspace_bytes(int64_t num_edges);
+int gaot_gno_adj_jac(const gaot_mlp_t* mlp /* host */, const float* y_pos, const float* x_pos,
+                     const float* grad_out /* [num_queries, channels] */, const float* grad_jac /* [3, num_queries, channels] */,
+                     const int32_t* rowptr_dst /* or null with k > 0 */, int k, const int32_t* src_sorted /* by source */,
+                     const int32_t* dst_sorted /* by source */, const int32_t* rowptr_src, int64_t num_edges, int64_t num_sources,
+                     int64_t num_queries, float* grad_f_y /* [num_sources, channels] */, void* workspace, size_t workspace_bytes,
+                     gaot_stream_t stream);
+
 /* gaot_gno_fwd_knn_jet2's directional 2-jets on RAGGED rows (csrc/gno_jet2.hip): the value, D_v and D_v^2 planes of the by-query list
  * of any graph, as gaot_gno_fwd_jac gives the value and the Jacobian -- the lists, the padding edges, the row reduction (every one
  * of the 1 + 2 nd planes through its own two partial slots per tile) and the empty rows (exact zeros in every plane) are that entry
