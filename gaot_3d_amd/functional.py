@@ -1554,3 +1554,32 @@ class SampleJacobianLatentFn(Function):
             else djac.to(torch.float32).contiguous()
         g = ctx.decoder.sample_jacobian_vjp(latent, query_pos, cot_pred, cot_jac, tokens_pos, chunk_points=ctx.chunk_points)
         return g.to(latent.dtype), None, None, None, None
+
+
+class SampleLaplacianLatentFn(Function):
+    """The sampled field, its spatial derivative AND its Laplacian as a differentiable function of the LATENT: forward = one jet pass
+    along the three axes (``MAGNODecoder._laplacian_jets``: pred and lap are ``sample_laplacian``'s / ``sample_laplacian_rows``'s, jac
+    is ``sample_hessian``'s / ``sample_hessian_rows``'s, bit for bit) -> (pred, jac, lap), backward =
+    ``MAGNODecoder.sample_laplacian_vjp`` (the streamed adjoint of the jet kernel).  An output that received no gradient contributes
+    no cotangent (``pred`` / ``jac``: None, ``lap``: zeros).  Nothing is saved but the latent, the query coordinates and the token
+    tensor.  Gradients flow to ``latent`` ONLY."""
+
+    @staticmethod
+    def forward(ctx, latent: Tensor, decoder, query_pos: Tensor, tokens_pos: Tensor, chunk_points: Optional[int]):
+        ctx.decoder, ctx.chunk_points = decoder, chunk_points
+        ctx.save_for_backward(latent, query_pos, tokens_pos)
+        ctx.set_materialize_grads(False)
+        return decoder._laplacian_jets("sample_laplacian_autograd", latent.detach(), query_pos, tokens_pos, chunk_points)
+
+    @staticmethod
+    def backward(ctx, dpred: Optional[Tensor], djac: Optional[Tensor], dlap: Optional[Tensor]):
+        latent, query_pos, tokens_pos = ctx.saved_tensors
+        if dpred is None and djac is None and dlap is None:
+            return None, None, None, None, None
+        nq = query_pos.shape[0]
+        cot_pred = None if dpred is None else dpred.to(torch.float32).contiguous()
+        cot_jac = None if djac is None else djac.to(torch.float32).contiguous()
+        cot_lap = torch.zeros(nq, ctx.decoder.out_channels, dtype=torch.float32, device=query_pos.device) if dlap is None \
+            else dlap.to(torch.float32).contiguous()
+        g = ctx.decoder.sample_laplacian_vjp(latent, query_pos, cot_pred, cot_jac, cot_lap, tokens_pos, chunk_points=ctx.chunk_points)
+        return g.to(latent.dtype), None, None, None, None

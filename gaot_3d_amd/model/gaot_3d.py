@@ -297,6 +297,47 @@ class GAOT3D(nn.Module):
                                           f"{dec.projection.non_linearity!r} is not written (covered: {dec.JAC_VJP_ACTS})")
         return GF.SampleJacobianLatentFn.apply(latent, dec, q, lat, chunk_points)
 
+    def sample_laplacian_vjp(self, latent: torch.Tensor, query_pos: torch.Tensor, cot_pred: Optional[torch.Tensor],
+                             cot_jac: Optional[torch.Tensor], cot_lap: torch.Tensor, tokens_pos: Optional[torch.Tensor] = None,
+                             chunk_points: Optional[int] = None) -> torch.Tensor:
+        """The ADJOINT of ``sample_laplacian`` (and of the derivative ``sample_hessian`` returns beside it): -> grad_latent
+        [D*H*W, lifting_channels] (fp32) = sum_q cot_pred[q] . d pred[q] / d latent + sum_q cot_jac[q] . d jac[q] / d latent
+        + sum_q cot_lap[q] . d lap[q] / d latent for cotangents ``cot_pred`` [Nq, output_size] and ``cot_jac`` [Nq, output_size, 3]
+        (float32, each may be None) and ``cot_lap`` [Nq, output_size] -- the gradient of a loss on a PDE RESIDUAL (a Poisson residual
+        Lap p - s, a diffusion term nu Lap u, a convection-diffusion residual at collocation points) with respect to the latent,
+        streamed in chunks of queries with no edge_index, no decoder autograd graph and no weight gradients.
+        ``MAGNODecoder.sample_laplacian_vjp``: exact fp32 in both precision modes, outside autograd, bit-reproducible for a given
+        ``chunk_points``.  The decoder's parameters and the query coordinates are constants.  Routes and refusals are
+        ``sample_laplacian``'s on a 'knn' decoder and ``sample_laplacian_rows``'s on 'radius' / 'bidirectional'; a transform that is
+        not 'linear' and a point-sharded model raise NotImplementedError."""
+        lat = self._one_sample("sample_laplacian_vjp", latent, tokens_pos)
+        if getattr(self, "_shard_group", None) is not None:
+            raise NotImplementedError("GAOT3D.sample_laplacian_vjp: a point-sharded model is not supported")
+        return self.decoder.sample_laplacian_vjp(latent, query_pos.to(latent.device), cot_pred, cot_jac, cot_lap, lat,
+                                                 chunk_points=chunk_points)
+
+    def sample_laplacian_autograd(self, latent: torch.Tensor, query_pos: torch.Tensor, tokens_pos: Optional[torch.Tensor] = None,
+                                  chunk_points: Optional[int] = None):
+        """``sample_laplacian`` as a differentiable function of the latent: -> (pred [Nq, output_size], jac [Nq, output_size, 3],
+        lap [Nq, output_size]) whose backward is ``sample_laplacian_vjp`` (``functional.SampleLaplacianLatentFn``), so that a loss on
+        a PDE residual reaches the encoder, the processor and ``batch.pos`` through the ordinary autograd of ``latent``.  The forward
+        is ONE jet pass along the three axes: on a 'knn' decoder ``pred`` and ``lap`` are ``sample_laplacian``'s and ``jac`` is
+        ``sample_hessian``'s, on 'radius' / 'bidirectional' they are ``sample_laplacian_rows``'s and ``sample_hessian_rows``'s, bit for
+        bit.  An output that received no gradient contributes no cotangent.  Gradients flow to ``latent`` ONLY: the decoder's
+        parameters are constants here, and a ``query_pos`` that requires grad raises ValueError (no third derivative in the query is
+        formed).  Configurations ``sample_laplacian_vjp`` refuses are refused here, before the forward runs."""
+        fn = "sample_laplacian_autograd"
+        lat = self._one_sample(fn, latent, tokens_pos)
+        if query_pos.requires_grad:
+            raise ValueError(f"GAOT3D.{fn}: query_pos requires grad, but gradients flow to the latent only; detach it")
+        if getattr(self, "_shard_group", None) is not None:
+            raise NotImplementedError(f"GAOT3D.{fn}: a point-sharded model is not supported")
+        q = query_pos.to(latent.device)
+        dec = self.decoder
+        with torch.no_grad(), ops.fp32_arithmetic():      # sample_laplacian_vjp's refusals, before anything runs
+            dec._lap_vjp_stream(fn, latent.detach(), q, lat, chunk_points)
+        return GF.SampleLaplacianLatentFn.apply(latent, dec, q, lat, chunk_points)
+
     def forward(self, batch, tokens_pos: Optional[torch.Tensor] = None, tokens_batch_idx: Optional[torch.Tensor] = None,
                 query_coord_pos: Optional[torch.Tensor] = None, query_coord_batch_idx: Optional[torch.Tensor] = None,
                 condition: Optional[float] = None) -> torch.Tensor:

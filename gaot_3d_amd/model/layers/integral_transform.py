@@ -253,9 +253,29 @@ class IntegralTransform(nn.Module):
         """``adjoint_jac_knn`` on RAGGED rows: ``graph`` holds both lists of the chunk, as for ``adjoint_rows``."""
         return self._adjoint("adjoint_jac_rows", y_pos, x_pos, grad_out, graph, None, grad_jac)
 
-    def _adjoint(self, fn, y_pos, x_pos, grad_out, graph, k, grad_jac=None):
-        """the four adjoint methods: every pass of ``_fused_passes`` (its f_y block is the cotangent's) is one ``ops.gno_adjoint`` call,
-        or with ``grad_jac`` [3, N_x, C] one ``ops.gno_adjoint_jac`` call on the same channels of every plane"""
+    def adjoint_jet2_knn(self, y_pos, x_pos, nbr, k: int, dirs, grad_out, grad_d1, grad_d2, graph=None):
+        """The ADJOINT of ``jet2_knn`` with respect to f_y: -> grad_f_y [N_y, C] for the directions ``dirs`` (host values [nd][3],
+        1..6) and the cotangents ``grad_out`` [N_x, C] on the value, ``grad_d1`` [nd, N_x, C] on the first and ``grad_d2``
+        [nd, N_x, C] on the second directional derivatives (fp32, ``jet2_knn``'s layout), on the regular list ``nbr`` / ``k``.
+        ``grad_d2`` may be [1, N_x, C]: ONE plane every direction contracts with (the Laplacian's cotangent along the three axes).
+        All 1 + 2 nd planes of the 'linear' transform are linear in f_y, so this is the jet kernel's per-edge work contracted with the
+        cotangents and reduced by source (``ops.gno_adjoint_jet2``: two launches per 32-channel pass).  ``graph``, the preparation of
+        the operands, exactness and refusals are ``adjoint_knn``'s."""
+        if int(k) not in ops.GNO_KNN_K:
+            raise NotImplementedError(f"IntegralTransform.adjoint_jet2_knn: lists of k in {ops.GNO_KNN_K} neighbours per query, got k = {k}")
+        if graph is None:
+            from ... import graph as device_graph
+            graph = device_graph.by_source((nbr, int(k)), y_pos.shape[0])
+        return self._adjoint("adjoint_jet2_knn", y_pos, x_pos, grad_out, graph, int(k), jet2=(dirs, grad_d1, grad_d2))
+
+    def adjoint_jet2_rows(self, y_pos, x_pos, dirs, grad_out, grad_d1, grad_d2, graph):
+        """``adjoint_jet2_knn`` on RAGGED rows: ``graph`` holds both lists of the chunk, as for ``adjoint_rows``."""
+        return self._adjoint("adjoint_jet2_rows", y_pos, x_pos, grad_out, graph, None, jet2=(dirs, grad_d1, grad_d2))
+
+    def _adjoint(self, fn, y_pos, x_pos, grad_out, graph, k, grad_jac=None, jet2=None):
+        """the six adjoint methods: every pass of ``_fused_passes`` (its f_y block is the cotangent's) is one ``ops.gno_adjoint`` call,
+        with ``grad_jac`` [3, N_x, C] one ``ops.gno_adjoint_jac`` call on the same channels of every plane, or with ``jet2`` = (dirs,
+        grad_d1 [nd, N_x, C], grad_d2 [nd or 1, N_x, C]) one ``ops.gno_adjoint_jet2`` call"""
         fcs = list(self.channel_mlp.fcs)
         with torch.no_grad():
             plan = self._fused_plan(fcs, grad_out, y_pos, x_pos) if self.transform_type == "linear" else None
@@ -265,11 +285,23 @@ class IntegralTransform(nn.Module):
             if grad_jac is not None and (grad_jac.dim() != 3 or grad_jac.shape[0] != 3 or grad_jac.shape[1:] != grad_out.shape):
                 raise ValueError(f"IntegralTransform.{fn}: grad_jac must be [3, {grad_out.shape[0]}, {grad_out.shape[1]}], "
                                  f"got {tuple(grad_jac.shape)}")
+            if jet2 is not None:
+                dirs, grad_d1, grad_d2 = jet2
+                nd = len(dirs)
+                for name, t, lead in (("grad_d1", grad_d1, (nd,)), ("grad_d2", grad_d2, (nd, 1))):
+                    if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.shape[0] not in lead or t.shape[1:] != grad_out.shape:
+                        raise ValueError(f"IntegralTransform.{fn}: {name} must be [{' or '.join(str(n) for n in lead)}, "
+                                         f"{grad_out.shape[0]}, {grad_out.shape[1]}], got "
+                                         f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
             y3, x3, _, (w0, b0, *mid), blocks = self._fused_passes(fcs, y_pos, x_pos, grad_out, *plan)
             outs = []
             for i, (wb, bb, gb, n) in enumerate(blocks):
                 ws, bs = [w0.contiguous(), *mid[0::2], wb.contiguous()], [b0, *mid[1::2], bb.contiguous()]
-                if grad_jac is None:
+                if jet2 is not None:
+                    p1, p2 = (t if t.shape[2] == 32 else torch.nn.functional.pad(t[:, :, 32 * i:32 * i + n], (0, 32 - n))
+                              for t in (grad_d1, grad_d2))
+                    o = ops.gno_adjoint_jet2(ws, bs, y3, x3, dirs, gb.contiguous(), p1.contiguous(), p2.contiguous(), graph, k)
+                elif grad_jac is None:
                     o = ops.gno_adjoint(ws, bs, y3, x3, gb.contiguous(), graph, k)
                 else:
                     jb = grad_jac if grad_jac.shape[2] == 32 else torch.nn.functional.pad(grad_jac[:, :, 32 * i:32 * i + n], (0, 32 - n))

@@ -1110,6 +1110,175 @@ class MAGNODecoder(nn.Module):
                                               latent_tokens_pos, lists))
         return grad
 
+    def _project_lap_vjp(self, planes, gy, gj, gl):
+        """The cotangent of the projection's input LAPLACIAN jet: for the mixed GNO planes ``planes`` = [x, x'_0, x'_1, x'_2, x''_0,
+        x''_1, x''_2] ([rows, C] each; only the SUM of the three second-order planes enters) and the cotangents ``gy``
+        [rows, out_channels] (or None) on y = W_2 a(z) + b_2, ``gj`` [rows, out_channels, 3] on y'_d = W_2 (a'(z) * u_d) and ``gl``
+        [rows, out_channels] on Lap y = W_2 (a''(z) * sum_d u_d^2 + a'(z) * s), z = W_1 x + b_1, u_d = W_1 x'_d, s = W_1 sum_d x''_d
+        -> [dx, dx'_0, dx'_1, dx'_2, dx''] (dx'' is the cotangent of EVERY x''_d):
+            A = g_y W_2,  A_d = g_y'd W_2,  A_L = g_Lap W_2
+            dz = a' A + a'' sum_d u_d A_d + (a''' sum_d u_d^2 + a'' s) A_L,   du_d = a' A_d + 2 a'' u_d A_L,   ds = a' A_L
+            dx = dz W_1,  dx'_d = du_d W_1,  dx'' = ds W_1
+        Exact fp32: three GEMMs per row block on the planes STACKED (one launch per product, precision 0) and the elementwise middle
+        as ONE kernel (``ops.mlp2_lap_cot_mid``, erf-GELU: the only projection ``_jet2_stream`` admits), written over the cotangent
+        stack.  Rows in blocks sized as in ``_project_jac_vjp``."""
+        from ... import ops
+        fc1, fc2 = self.projection.fcs
+        w1, w2 = GF._w2d(fc1.weight).contiguous(), GF._w2d(fc2.weight).contiguous()
+        b1 = fc1.bias.detach().to(torch.float32).contiguous()
+        n, c = planes[0].shape
+        hid, oc = w1.shape[0], w2.shape[0]
+        outs = [torch.empty_like(planes[0]) for _ in range(5)]
+        step = n if hid <= c else max(1024, n * c // hid)
+        for j in range(0, n, step):
+            m = planes[0][j:j + step].shape[0]
+            xs = torch.add(planes[4][j:j + step] + planes[5][j:j + step], planes[6][j:j + step])   # (x''_0 + x''_1) + x''_2
+            x5 = torch.cat([p[j:j + step] for p in planes[:4]] + [xs])
+            del xs
+            g = ([] if gy is None else [gy[j:j + step]]) + [gj[j:j + step, :, d] for d in range(3)] + [gl[j:j + step]]
+            ng = len(g)
+            g = torch.cat(g)
+            zus = ops.gemm(x5, w1, 5 * m, hid, c, c, c, False, True, precision=0)            # [z - b_1; u_0; u_1; u_2; s]
+            a = ops.gemm(g, w2, ng * m, hid, oc, oc, hid, False, False, precision=0)         # [A;] A_0; A_1; A_2; A_L
+            del x5, g
+            zus, a = zus.view(5, m, hid), a.view(ng, m, hid)
+            if gy is None:                           # no A plane: the result goes over the z stack
+                mid = ops.mlp2_lap_cot_mid(zus, None, a[:3], a[3], b1, out=zus)
+            else:                                    # [A; A_d; A_L] becomes [dz; du_d; ds] in place
+                mid = ops.mlp2_lap_cot_mid(zus, a[0], a[1:4], a[4], b1, out=a)
+            dx5 = ops.gemm(mid.view(5 * m, hid), w1, 5 * m, c, hid, hid, c, False, False, precision=0)
+            del zus, a, mid
+            for p in range(5):
+                outs[p][j:j + step] = dx5[p * m:(p + 1) * m]
+        return outs
+
+    LAP_VJP_DIRS = HESSIAN_DIRS[:3]       # the three axes: D_v^2 along them sums to the Laplacian
+
+    def _lap_vjp_chunk(self, rndata_flat, q, gy, gj, gl, lat, lists):
+        """one chunk of ``sample_laplacian_vjp``: -> its [M, C] part of the latent's gradient.  A call of its own, so that a chunk's
+        planes and lists are freed before the next chunk's are allocated."""
+        from ... import graph as device_graph
+        m = lat.shape[0]
+        dirs = self.LAP_VJP_DIRS
+        planes = self._jet_planes(rndata_flat, q, lat, lists, dirs)     # [x, x'_d, x''_d] mixed, recomputed at fp32
+        d = self._project_lap_vjp(planes, gy, gj, gl)                   # [dx, dx'_0, dx'_1, dx'_2, dx'']
+        del planes
+        if isinstance(lists, tuple):                       # 'knn': equal operands, the weights' jets drop out (``sample_laplacian``)
+            d = self._mix_equal_scales(d, q)
+            return self.gno.adjoint_jet2_knn(lat, q, *lists, dirs, d[0], torch.stack(d[1:4]), d[4].unsqueeze(0),
+                                             graph=device_graph.by_source(lists, m))
+        ns = len(lists)
+        if ns == 1 or not self.use_scale_weights:          # one scale, or summed scales: every scale gets the planes as they are
+            per = [(d[0], torch.stack(d[1:4]), d[4].unsqueeze(0))] * ns
+        else:
+            # x = sum_s w_s o_s,  x'_d = sum_s (w_s o'_s,d + w'_s,d o_s),  x''_d = sum_s (w_s o''_s,d + 2 w'_s,d o'_s,d + w''_s,d o_s) with
+            # w = softmax(l(q)), a function of the query alone; with G = dx, G'_d = dx'_d and L = dx'' on every x''_d:
+            #   G_s = w_s G + sum_d w'_s,d G'_d + (sum_d w''_s,d) L,   G'_s,d = w_s G'_d + 2 w'_s,d L,   L_s = w_s L
+            sw = self.scale_weighting
+            logits, hdn = _scale_logits(self, q)
+            w = torch.softmax(logits, dim=1)
+            dls = _logit_tangents((hdn > 0).to(hdn.dtype), sw[0].weight, sw[2].weight, lambda x, wt: GF.linear(x, wt, None, precision=0))
+            jets = [_softmax_weight_jets(w, dl, second=True) for dl in dls]
+            dws = [j[0] for j in jets]
+            lw = torch.add(jets[0][1] + jets[1][1], jets[2][1])          # the Laplacian of the weights
+            per = []
+            for s in range(ns):
+                ws = w[:, s:s + 1]
+                g = ws * d[0]
+                for di, dw in enumerate(dws):
+                    g += dw[:, s:s + 1] * d[1 + di]
+                g += lw[:, s:s + 1] * d[4]
+                p1 = torch.stack([ws * d[1 + di] + (2.0 * dws[di][:, s:s + 1]) * d[4] for di in range(3)])
+                per.append((g, p1, (ws * d[4]).unsqueeze(0)))
+        del d
+        part = None
+        for rows, (g, p1, p2) in zip(lists, per):
+            p = self.gno.adjoint_jet2_rows(lat, q, dirs, g, p1, p2, device_graph.by_source(rows, m))
+            part = p if part is None else part.add_(p)
+        return part
+
+    def _lap_vjp_stream(self, fn, rndata_flat, query_pos, lat, chunk_points):
+        """the refusals of ``sample_laplacian_vjp``, before anything runs: ``sample_laplacian``'s / ``sample_laplacian_rows``'s
+        (``_jet2_stream``), a point-sharded model and a transform that is not 'linear' -> (grid, chunk, rows)"""
+        self._sample_args(fn, chunk_points)
+        if getattr(self, "_shard_group", None) is not None:
+            raise NotImplementedError(f"MAGNODecoder.{fn}: a point-sharded model is not supported (every rank would hold a partial sum)")
+        rows = self.decoder_strategy != "knn"
+        what = "the adjoint of the field's Laplacian"
+        if self.gno.transform_type != "linear":          # the forward's jets cover the other transforms: named before its conditions
+            raise NotImplementedError(f"MAGNODecoder.{fn}: {what} needs the 'linear' transform (the adjoint kernel is the linear "
+                                      f"transform's); transform type {self.gno.transform_type!r} is not")
+        grid, chunk = self._jet2_stream(fn, rndata_flat, query_pos, lat, chunk_points, rows=rows, what=what)
+        return grid, chunk, rows
+
+    @torch.no_grad()
+    def sample_laplacian_vjp(self, rndata_flat, query_pos, cot_pred, cot_jac, cot_lap, latent_tokens_pos,
+                             chunk_points: Optional[int] = None) -> torch.Tensor:
+        """The ADJOINT of the field's value, spatial derivative AND Laplacian: -> grad_latent [M, C] (fp32)
+            = sum_q cot_pred[q] . d pred[q] / d rndata_flat + sum_q cot_jac[q] . d jac[q] / d rndata_flat
+              + sum_q cot_lap[q] . d lap[q] / d rndata_flat,
+        the vector-Jacobian product of ``sample_laplacian`` / ``sample_laplacian_rows`` (and of the derivative planes of
+        ``sample_hessian`` / ``sample_hessian_rows``) with respect to the latent -- the gradient of a loss on a PDE residual at
+        collocation points (a Poisson residual Lap p - s, a diffusion term nu Lap u, a convection-diffusion residual), which the
+        autograd of ``GAOT3D.latent`` carries on into the encoder, the processor and the sample's coordinates.  ``cot_pred``: float32
+        [Nq, out_channels] or None; ``cot_jac``: float32 [Nq, out_channels, 3] or None; ``cot_lap``: float32 [Nq, out_channels].  The
+        decoder's parameters and the query coordinates are CONSTANTS here.
+
+        Streamed as ``sample_jacobian_vjp`` is, through the same chunk loop.  Per chunk: the lists; the mixed value, first- and
+        second-order planes along the three axes recomputed at fp32 (``_jet_planes``, as ``sample_laplacian`` forms them; on row
+        lists with the jets of the scale weights); the cotangent of that jet through the projection (``_project_lap_vjp``: a''' of the
+        erf-GELU, the elementwise middle one kernel); the scale mix's cotangent (``knn``: equal operands, ``_mix_equal_scales`` on the
+        five planes; row lists with softmax weights: G_s = w_s G + sum_d w'_s,d G'_d + Lap w_s L, G'_s,d = w_s G'_d + 2 w'_s,d L and
+        L_s = w_s L, the weights being functions of the query alone); then per scale ``graph.by_source`` and the adjoint of the jet
+        kernel (``IntegralTransform.adjoint_jet2_knn`` / ``adjoint_jet2_rows`` along the three axes, ONE second-order cotangent plane
+        shared by the three directions), and the chunk's [M, C] part added in chunk order.
+
+        Exact fp32 in both precision modes (the same bits), outside autograd, bit-reproducible run to run for a given
+        ``chunk_points``; not bit-identical across chunkings (a token's sum is split at the chunk boundaries).  Refusals are
+        ``sample_laplacian``'s ('knn') / ``sample_laplacian_rows``'s ('radius', 'bidirectional'); in addition a transform that is not
+        'linear' and a point-sharded model raise NotImplementedError naming it, cotangents of the wrong dtype, shape or device raise
+        ValueError, and on row lists (sized by a host read) the call raises GaotError inside a stream capture before any launch."""
+        from ... import ops
+        fn = "sample_laplacian_vjp"
+        self._sample_args(fn, chunk_points)
+        nq, oc = int(query_pos.shape[0]), self.out_channels
+        for name, cot, shape, optional in (("cot_pred", cot_pred, (nq, oc), True), ("cot_jac", cot_jac, (nq, oc, 3), True),
+                                           ("cot_lap", cot_lap, (nq, oc), False)):
+            if cot is None and optional:
+                continue
+            if not isinstance(cot, torch.Tensor) or cot.dtype != torch.float32 or cot.device != query_pos.device \
+                    or tuple(cot.shape) != shape:
+                got = f"{cot.dtype} {tuple(cot.shape)} on {cot.device}" if isinstance(cot, torch.Tensor) else type(cot).__name__
+                raise ValueError(f"MAGNODecoder.{fn}: {name} must be float32 {list(shape)} on the queries' device "
+                                 f"({query_pos.device}){' or None' if optional else ''}, got {got}")
+        rndata_flat, query_pos, cot_lap = rndata_flat.detach(), query_pos.detach(), cot_lap.detach()
+        cot_pred = None if cot_pred is None else cot_pred.detach()
+        cot_jac = torch.zeros(nq, oc, 3, dtype=torch.float32, device=query_pos.device) if cot_jac is None else cot_jac.detach()
+        with ops.fp32_arithmetic():
+            grid, chunk, rows = self._lap_vjp_stream(fn, rndata_flat, query_pos, latent_tokens_pos, chunk_points)
+            f = rndata_flat.to(torch.float32).contiguous()
+            grad = torch.zeros_like(f)
+            for sl, q, lists in self._stream_chunks(grid, query_pos, chunk, "rows" if rows else "knn", lead=False):
+                grad.add_(self._lap_vjp_chunk(f, q.contiguous(), None if cot_pred is None else cot_pred[sl], cot_jac[sl], cot_lap[sl],
+                                              latent_tokens_pos, lists))
+        return grad
+
+    @torch.no_grad()
+    def _laplacian_jets(self, fn, rndata_flat, query_pos, lat, chunk_points):
+        """the forward of ``functional.SampleLaplacianLatentFn``: ONE jet pass along the three axes -> (pred [Nq, out_channels],
+        jac [Nq, out_channels, 3], lap [Nq, out_channels]); pred and lap are ``sample_laplacian``'s / ``sample_laplacian_rows``'s and
+        jac is ``sample_hessian``'s / ``sample_hessian_rows``'s bit for bit (a direction's planes depend on that direction alone)"""
+        rows = self.decoder_strategy != "knn"
+        rndata_flat, query_pos = rndata_flat.detach(), query_pos.detach()
+        grid, chunk = self._jet2_stream(fn, rndata_flat, query_pos, lat, chunk_points, rows=rows)
+        nq = int(query_pos.shape[0])
+        pred, jac, lap = self._new(rndata_flat, nq), self._new(rndata_flat, nq, 3), self._new(rndata_flat, nq)
+        for sl, q, lists in self._stream_chunks(grid, query_pos, chunk, "rows" if rows else "knn"):
+            d1, d2 = self._jet2_chunk(rndata_flat, q, lat, lists, self.LAP_VJP_DIRS, pred[sl])
+            jac[sl] = d1
+            torch.add(d2[:, :, 0] + d2[:, :, 1], d2[:, :, 2], out=lap[sl])
+        return pred, jac, lap
+
     def sample_jacobian(self, rndata_flat, query_pos, latent_tokens_pos, chunk_points: Optional[int] = None,
                         row_lists: bool = False):
         """``sample`` with the spatial derivative of the field: -> (pred [Nq, out_channels], jac [Nq, out_channels, coord_dim]) with

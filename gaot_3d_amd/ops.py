@@ -422,6 +422,42 @@ def gno_adjoint_jac(weights, biases, y_pos: Tensor, x_pos: Tensor, grad_out: Ten
     return grad_f
 
 
+def gno_adjoint_jet2(weights, biases, y_pos: Tensor, x_pos: Tensor, dirs, grad_out: Tensor, grad_d1: Tensor, grad_d2: Tensor,
+                     g: BipartiteGraph, k: Optional[int] = None) -> Tensor:
+    """The ADJOINT of ``gno_forward_knn_jet2`` / ``gno_forward_jet2`` ('linear') with respect to f_y (gaot_gno_adj_jet2): for the
+    directions ``dirs`` (1..6, host values [nd][3]) and cotangents ``grad_out`` [n_query, 32] on the value, ``grad_d1``
+    [nd, n_query, 32] on the first and ``grad_d2`` on the second directional derivatives -> grad_f_y [n_src, 32] with
+        grad_f_y[t] = sum over the edges e of source t of
+                      (K_e * grad_out[q_e] + sum_i D_vi K_e * grad_d1[i, q_e] + sum_i D_vi^2 K_e * grad_d2[i, q_e]) / deg(q_e)
+    ``grad_d2`` is [nd, n_query, 32] (one plane per direction) or [1, n_query, 32]: ONE plane every direction contracts with -- the
+    cotangent of a Laplacian along the three axes, without copies.  The jet kernel's per-edge work (the value path once, h' and h''
+    per direction) contracted with the gathered cotangent rows into one plane and reduced by source: no MLP backward, no weight
+    gradients, no f_y.  Operand rules are ``gno_adjoint``'s, with the cotangent planes float32, contiguous, on the device; exact
+    fp32 whatever the precision mode (the same bits in both), no atomics, bit-reproducible run to run; a source without edges gets
+    exact zeros.  Two launches (main + fix-up; the fix-up alone without edges)."""
+    lib = _lib.load()
+    fn = "gno_adjoint_jet2"
+    m, keep, y_pos, x_pos, grad_out, rowptr_dst, kk, e = _gno_adjoint_args(fn, weights, biases, y_pos, x_pos, grad_out, g, k)
+    hd, nd = _host_dirs(fn, dirs)
+    if not 1 <= nd <= 6:
+        raise GaotError(f"{fn}: 1..6 directions, got {nd}")
+    for name, t, lead in (("grad_d1", grad_d1, (nd,)), ("grad_d2", grad_d2, (nd, 1))):
+        if not isinstance(t, Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 3 \
+                or t.shape[0] not in lead or tuple(t.shape[1:]) != (g.num_dst, m.channels) or t.device != grad_out.device:
+            got = f"{t.dtype} {tuple(t.shape)} on {t.device}, strides {tuple(t.stride())}" if isinstance(t, Tensor) else type(t).__name__
+            raise GaotError(f"{fn}: {name} must be contiguous float32 [{' or '.join(str(n) for n in lead)}, {g.num_dst}, {m.channels}] "
+                            f"on {grad_out.device}, got {got}")
+    stride2 = 0 if grad_d2.shape[0] == 1 and nd > 1 else g.num_dst * m.channels    # one direction: both forms name the same plane
+    dev = x_pos.device
+    grad_f = torch.empty(g.num_src, m.channels, dtype=torch.float32, device=dev)
+    ws = _ws(lib.gaot_gno_adj_jet2_workspace_bytes(e), dev)
+    with _timed(f"gno_adj_jet2_nh{m.n_hidden}"):
+        check(lib.gaot_gno_adj_jet2(C.byref(m), _ptr(y_pos), _ptr(x_pos), hd, nd, _ptr(grad_out), _ptr(grad_d1), _ptr(grad_d2), stride2,
+                                    _ptr(rowptr_dst), kk, _ptr(g.by_src.key), _ptr(g.by_src.other), _ptr(g.by_src.rowptr), e, g.num_src,
+                                    g.num_dst, _ptr(grad_f), _ptr(ws), ws.numel(), _stream()), "gaot_gno_adj_jet2")
+    return grad_f
+
+
 def gno_forward_knn_jac(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], src_table: Optional[Tensor],
                         nbr: Tensor, k: int):
     """``gno_forward_knn`` with the spatial derivative of its result (gaot_gno_fwd_knn_jac): -> (out [n_query, 32],
@@ -1979,6 +2015,38 @@ def mlp2_jet2(x: Tensor, dxs: Sequence[Tensor], ddxs: Sequence[Tensor], w1: Tens
                                  _ptr(b2), _ptr(y) if y is not None else None, ldy, _ptr(d1), _ptr(d2), js[0], js[1], js[2], _stream()),
               "gaot_mlp2_jet2")
     return y, d1, d2
+
+
+def mlp2_lap_cot_mid(zus: Tensor, a: Optional[Tensor], ad: Tensor, al: Tensor, b1: Optional[Tensor] = None,
+                     out: Optional[Tensor] = None) -> Tensor:
+    """The elementwise middle of the cotangent of the two-layer MLP's LAPLACIAN jet in one launch (include/gaot3d_hip.h:
+    gaot_mlp2_lap_cot_mid).  ``zus`` [5, rows, hidden]: the stack [z - b1; u_0; u_1; u_2; s] one product with W1 gives (``b1``
+    [hidden] or None is added to z here); ``a`` [rows, hidden] or None (no cotangent on the value), ``ad`` [3, rows, hidden], ``al``
+    [rows, hidden]: the cotangents of y, y'_d and Lap y pulled to hidden width -> ``out`` [5, rows, hidden] = [dz; du_0; du_1; du_2; ds]
+    (erf-GELU: a', a'', a''' from one phi and one Phi per element).  ``out`` may be the storage of the stack [a; ad; al] or ``zus`` itself.
+    Everything float32, contiguous, on one device; hidden a multiple of 4.  Bad operands raise GaotError before the launch."""
+    lib = _lib.load()
+    fn = "mlp2_lap_cot_mid"
+    if not isinstance(zus, Tensor) or zus.dim() != 3 or zus.shape[0] != 5:
+        raise GaotError(f"{fn}: zus must be [5, rows, hidden], got {tuple(zus.shape) if isinstance(zus, Tensor) else type(zus).__name__}")
+    rows, hid = int(zus.shape[1]), int(zus.shape[2])
+    if hid < 4 or hid % 4:
+        raise GaotError(f"{fn}: hidden must be a positive multiple of 4, got {hid}")
+    if out is None:
+        out = torch.empty_like(zus)
+    for name, t, shape, optional in (("zus", zus, (5, rows, hid), False), ("a", a, (rows, hid), True), ("ad", ad, (3, rows, hid), False),
+                                     ("al", al, (rows, hid), False), ("b1", b1, (hid,), True), ("out", out, (5, rows, hid), False)):
+        if t is None and optional:
+            continue
+        if not isinstance(t, Tensor) or not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() \
+                or t.device != zus.device or t.data_ptr() % 16:
+            got = f"{t.dtype} {tuple(t.shape)} on {t.device}, strides {tuple(t.stride())}" if isinstance(t, Tensor) else type(t).__name__
+            raise GaotError(f"{fn}: {name} must be contiguous, 16-byte aligned float32 {list(shape)} on {zus.device}, got {got}")
+    n = rows * hid
+    with _timed(f"mlp2_lap_cot_mid_h{hid}"):
+        check(lib.gaot_mlp2_lap_cot_mid(_ptr(zus[0]), _ptr(zus[1]), n, _ptr(zus[4]), _ptr(b1), _ptr(a), _ptr(ad), n, _ptr(al), rows, hid,
+                                        _ptr(out), n, _stream()), "gaot_mlp2_lap_cot_mid")
+    return out
 
 
 def _finish_tables(ws: Tensor, outs, parts, lanes, defer: bool) -> None:

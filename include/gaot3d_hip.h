@@ -255,6 +255,31 @@ int gaot_gno_adj_jac(const gaot_mlp_t* mlp /* host */, const float* y_pos, const
                      int64_t num_queries, float* grad_f_y /* [num_sources, channels] */, void* workspace, size_t workspace_bytes,
                      gaot_stream_t stream);
 
+/* The ADJOINT of gaot_gno_fwd_knn_jet2 / gaot_gno_fwd_jet2 (mode 0) with respect to f_y (csrc/gno_jet2_adj.hip), for the
+ * vector-Jacobian product of a sampled field's value, first AND second directional derivatives with respect to the latent -- the
+ * pull-back of a loss on a Laplacian, a Hessian or a directional second derivative.  All 1 + 2 nd planes are linear in f_y:
+ *   grad_f_y[t][c] = sum over row t of the SOURCE-sorted list of
+ *       ( K_c grad_out[q_e][c] + sum_i D_vi K_c grad_d1[i][q_e][c] + sum_i D_vi^2 K_c grad_d2[i][q_e][c] ) / deg(q_e)
+ * with K = K(y_pos[t], x_pos[q_e]) and D_v the derivative of the kernel MLP along v in the query coordinate: gaot_gno_fwd_knn_jet2's
+ * per-edge work (the value path once, a pass with h' and h'' per direction), the planes contracted with the gathered cotangent rows
+ * into ONE register tile in a fixed order (the value, then grad_d1[i] and grad_d2[i] for i ascending, then 1/deg) and reduced by source
+ * as gaot_gno_adj reduces it.  `dirs`: HOST pointer [nd][3], nd = 1..6, passed to the kernel by value.  grad_d1 is
+ * [nd, num_queries, channels]; plane i of grad_d2 starts at grad_d2 + i * grad_d2_stride floats, grad_d2_stride either
+ * num_queries * channels (one plane per direction) or 0 (every direction contracts with the SAME plane: the Laplacian's cotangent,
+ * without copies).  No MLP backward, no weight gradients, no atomics; a fixed summation order, bit-reproducible run to run; a source
+ * without edges gets exact zeros.  Lists, degrees (rowptr_dst, or NULL with the k of a regular list), sizes and workspace rules are
+ * gaot_gno_adj's.  Exact fp32, no precision argument.  Linear mode only, 1 <= n_hidden <= 4, hidden 64, channels 32.  Two launches
+ * (the fix-up alone with num_edges == 0).  Argument errors before any launch (GAOT_ERR_ARG): those of gaot_gno_adj_jac, nd outside
+ * 1..6, null dirs, a device pointer as dirs, null grad_d1 / grad_d2 with edges, a grad_d2_stride that is neither of the two values. */
+size_t gaot_gno_adj_jet2_workspace_bytes(int64_t num_edges);
+int gaot_gno_adj_jet2(const gaot_mlp_t* mlp /* host */, const float* y_pos, const float* x_pos, const float* dirs /* HOST, [nd][3] */,
+                      int nd, const float* grad_out /* [num_queries, channels] */, const float* grad_d1 /* [nd, num_queries, channels] */,
+                      const float* grad_d2 /* [nd or 1, num_queries, channels] */, int64_t grad_d2_stride,
+                      const int32_t* rowptr_dst /* or null with k > 0 */, int k, const int32_t* src_sorted /* by source */,
+                      const int32_t* dst_sorted /* by source */, const int32_t* rowptr_src, int64_t num_edges, int64_t num_sources,
+                      int64_t num_queries, float* grad_f_y /* [num_sources, channels] */, void* workspace, size_t workspace_bytes,
+                      gaot_stream_t stream);
+
 /* gaot_gno_fwd_knn_jet2's directional 2-jets on RAGGED rows (csrc/gno_jet2.hip): the value, D_v and D_v^2 planes of the by-query list
  * of any graph, as gaot_gno_fwd_jac gives the value and the Jacobian -- the lists, the padding edges, the row reduction (every one
  * of the 1 + 2 nd planes through its own two partial slots per tile) and the empty rows (exact zeros in every plane) are that entry
@@ -810,6 +835,21 @@ int gaot_mlp2_jet2(const float* x, const float* dx0, const float* dx1, const flo
                    const float* ddx2, int nd, int64_t num_rows, int in_dim, int hidden, int out_dim, const float* w1, const float* b1,
                    const float* w2, const float* b2, float* y, int64_t ldy, float* d1, float* d2, int64_t row_stride,
                    int64_t chan_stride, int64_t dir_stride, gaot_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The elementwise middle of the COTANGENT of that MLP's Laplacian jet (csrc/mlp2_lap_cot.hip; the projection under
+ * sample_laplacian_vjp), one launch, fp32.  With z = W1 x + b1, u_d = W1 x'_d (d = 0, 1, 2), s = W1 sum_d x''_d, erf-GELU a and the
+ * cotangents at hidden width A = g_y W2, A_d = g_y'd W2, A_L = g_Lap W2:
+ *   dz = a' A + a'' sum_d u_d A_d + (a''' sum_d u_d^2 + a'' s) A_L,   du_d = a' A_d + 2 a'' u_d A_L,   ds = a' A_L
+ * (a' = Phi + z phi, a'' = phi (2 - z^2), a''' = phi z (z^2 - 4)).  Every plane is dense [num_rows, hidden], 16-byte aligned, hidden a
+ * multiple of 4.  z is given WITHOUT its bias, b1 [hidden] (or NULL) is added here; plane d of u / a_d starts at u + d * u_stride /
+ * a_d + d * ad_stride floats; a may be NULL (A = 0: no cotangent on the value).  out: the five planes dz, du_0, du_1, du_2, ds at
+ * out + p * out_stride, ready for ONE product with W1.  out may alias the A stack or the z stack plane for plane (an element of the result depends
+ * on that element of each input alone).  No workspace, no atomics; num_rows == 0 is a no-op.
+ * ------------------------------------------------------------------------------------------- */
+int gaot_mlp2_lap_cot_mid(const float* z, const float* u, int64_t u_stride, const float* s, const float* b1, const float* a,
+                          const float* a_d, int64_t ad_stride, const float* a_l, int64_t num_rows, int hidden, float* out,
+                          int64_t out_stride, gaot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Thin fp32 linears over many rows in one pass (csrc/rowlinear.hip):  y = act([x_0 | x_1 | ...] W^T + b),

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Kernel microbenchmarks at the configs[1] shapes (for rocprofv3 / quick A-B): attention fwd+bwd, GEMM shapes, GNO, PointNet GeoEmbed,
-the attention-weighted GNO, the forward-only decoder (decoder_sample), the sampled field's Jacobian (decoder_jacobian), the projection MLP's tangent alone (projection_jvp), the sampled field's Hessian and Laplacian (decoder_hessian), its derivatives along per-query directions (decoder_directional), its adjoint with respect to the latent (decoder_adjoint), the adjoint of its Jacobian (decoder_jacobian_adjoint)."""
+the attention-weighted GNO, the forward-only decoder (decoder_sample), the sampled field's Jacobian (decoder_jacobian), the projection MLP's tangent alone (projection_jvp), the sampled field's Hessian and Laplacian (decoder_hessian), its derivatives along per-query directions (decoder_directional), its adjoint with respect to the latent (decoder_adjoint), the adjoint of its Jacobian (decoder_jacobian_adjoint), the adjoint of its Laplacian (decoder_laplacian_adjoint)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 if os.environ.get("MB_TREE"):      # measure another checkout's package (gno_weighted: the parent commit's) with this script
@@ -1158,6 +1158,179 @@ elif what == "decoder_jacobian_adjoint":
                 m, lo, hi = median(kt[n])
                 print(f"Nq={nq} {tag}: (e) {n:24s} {m:9.3f} ms (max - min {hi - lo:.3f} ms); gaot_gno_adj_jac : this = {ka[0] / m:.2f}", flush=True)
         del q, gy, gj, qc, gc, gjc, gboth
+elif what == "decoder_laplacian_adjoint":
+    # The adjoint of the field's Laplacian (MAGNODecoder.sample_laplacian_vjp) on decoder_jacobian_adjoint's decoders -- configs[1] (knn,
+    # k = 8), or with `--strategy radius|bidirectional` the reference YAML's decoder on row lists -- at 500 K and 8 M random query points
+    # with random cotangents, fp32 mode.  There is no older route to beat; the yardsticks are the existing calls, alternated with the new
+    # one round by round in this one process after a warm-up of each:
+    #   (a) sample_laplacian_vjp;   (b) sample_laplacian / sample_laplacian_rows;   (c) sample_jacobian_vjp;
+    #   (d) the split of (a) into its stages, one chunk at a time with device events around every stage (one scale);
+    #   (e) the kernel alone on one chunk's lists: gaot_gno_adj_jet2 (three axes, one second-order plane) against gaot_gno_adj_jac on
+    #       the same by-source list and against gaot_gno_fwd_knn_jet2 / gaot_gno_fwd_jet2 (three axes) on the same by-query list;
+    #   (f) the projection cotangent's elementwise middle on one chunk's rows: gaot_mlp2_lap_cot_mid against the same expression as
+    #       fp32 tensor operations.
+    # Device events around synchronised work; `reps` rounds (7 for the kept output); a row is the median with max - min, the peak is
+    # the rise of allocated memory over the inputs.  Kept in profiles/decoder_laplacian_adjoint_microbench.txt / ..._rows_microbench.txt.
+    from gaot_3d_amd import graph as device_graph
+    from gaot_3d_amd.data import latent_grid
+    from gaot_3d_amd.model.layers.magno import MAGNOConfig, MAGNODecoder
+    gaot_3d_amd.set_precision("fp32")
+    latent = (64, 64, 32)
+    strategy = sys.argv[sys.argv.index("--strategy") + 1] if "--strategy" in sys.argv else "knn"
+    if strategy not in ("knn", "radius", "bidirectional"):
+        sys.exit(f"--strategy must be knn, radius or bidirectional, got {strategy}")
+    rows = strategy != "knn"
+    cfg = MAGNOConfig(gno_coord_dim=3, lifting_channels=32, mlp_type="linear", use_geoembed=[True, False],
+                      neighbor_strategy=["knn", strategy] if rows else "knn", k_neighbors=1 if rows else 8, gno_radius=0.033,
+                      out_gno_channel_mlp_hidden_layers=[64, 64], precompute_edges=False)
+    dec = MAGNODecoder(in_channels=32, out_channels=1, gno_config=cfg).to(dev).eval()
+    dec.latent_dims = latent
+    tokens = latent_grid(latent).to(dev)
+    m_tok = tokens.shape[0]
+    rn = torch.randn(m_tok, 32, device=dev)
+    chunk = int(os.environ["MB_CHUNK"]) if os.environ.get("MB_CHUNK") else None
+    step = chunk or dec.SAMPLE_CHUNK
+    tag = f"fp32{' ' + strategy if rows else ''}"
+    fcs = list(dec.gno.channel_mlp.fcs)
+    kw_, kb_ = [fc.weight.detach() for fc in fcs], [fc.bias.detach() for fc in fcs]
+    axes = dec.LAP_VJP_DIRS
+    hid = dec.projection.fcs[0].weight.shape[0]
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); out = fn(); e1.record()
+        torch.cuda.synchronize()
+        peak = torch.cuda.max_memory_allocated() - base
+        return e0.elapsed_time(e1), peak, out
+
+    def median(ts):
+        ts = sorted(ts)
+        return ts[len(ts) // 2], ts[0], ts[-1]
+
+    def staged(q, gy, gj, gl):
+        """sample_laplacian_vjp's chunk loop with device events between its stages (one scale) -> ({stage: ms}, grad)"""
+        ev = lambda: torch.cuda.Event(enable_timing=True)
+        marks, grad = [], torch.zeros_like(rn)
+        with torch.no_grad():
+            grid = dec._stream_grid(rn, q, tokens)
+            for i in range(0, q.shape[0], step):
+                qc = q[i:i + step]
+                es = [ev() for _ in range(7)]
+                es[0].record()
+                lists = (device_graph.knn_to_grid(qc, grid, 8), 8) if not rows else \
+                    [device_graph.query_lists(strategy, qc, grid, dec.gno_radius, int(dec.k_neighbors))]
+                es[1].record()
+                planes = dec._jet_planes(rn, qc, tokens, lists, axes)
+                es[2].record()
+                d = dec._project_lap_vjp(planes, gy[i:i + step], gj[i:i + step], gl[i:i + step])
+                d1, d2 = torch.stack(d[1:4]), d[4].unsqueeze(0)
+                es[3].record()
+                gs = device_graph.by_source(lists if not rows else lists[0], m_tok)
+                es[4].record()
+                part = ops.gno_adjoint_jet2(kw_, kb_, tokens, qc, axes, d[0], d1, d2, gs, None if rows else 8)
+                es[5].record()
+                grad.add_(part)
+                es[6].record()
+                marks.append(es)
+                del lists, planes, d, d1, d2, gs, part
+        torch.cuda.synchronize()
+        names = ("neighbour search", "recomputed planes (value + 3 x 2 jets)", "projection cotangent", "by_source",
+                 "adjoint kernel + fix-up", "accumulation")
+        return {n: sum(es[j].elapsed_time(es[j + 1]) for es in marks) for j, n in enumerate(names)}, grad
+
+    def mid_as_tensor_ops(zus, a, ad, al, b1):
+        """gaot_mlp2_lap_cot_mid's expression as fp32 tensor operations -> [5, rows, hidden]"""
+        z = zus[0] + b1
+        phi = torch.exp(-0.5 * z * z) * 0.3989422804014327
+        a1 = 0.5 * (1.0 + torch.erf(z * 0.7071067811865476)) + z * phi
+        a2, a3 = phi * (2.0 - z * z), phi * z * (z * z - 4.0)
+        u = zus[1:4]
+        dz = a1 * a + a2 * (u * ad).sum(0) + (a3 * (u * u).sum(0) + a2 * zus[4]) * al
+        return torch.cat([dz[None], a1 * ad + (2.0 * a2 * al) * u, (a1 * al)[None]])
+
+    lap_fwd = dec.sample_laplacian_rows if rows else dec.sample_laplacian
+    for nq in (500000, 8000000):
+        q = torch.rand(nq, 3, device=dev) * 2 - 1
+        gy, gj, gl = torch.randn(nq, 1, device=dev), torch.randn(nq, 1, 3, device=dev), torch.randn(nq, 1, device=dev)
+        routes = {"(a) sample_laplacian_vjp": lambda: dec.sample_laplacian_vjp(rn, q, gy, gj, gl, tokens, chunk_points=chunk),
+                  "(b) sample_laplacian": lambda: lap_fwd(rn, q, tokens, chunk_points=chunk),
+                  "(c) sample_jacobian_vjp": lambda: dec.sample_jacobian_vjp(rn, q, gy, gj, tokens, chunk_points=chunk)}
+        warm = {n: timed(f)[2] for n, f in routes.items()}
+        same = torch.equal(warm["(a) sample_laplacian_vjp"], staged(q, gy, gj, gl)[1])
+        del warm
+        ts, pk = {n: [] for n in routes}, {n: 0 for n in routes}
+        split = []
+        for _ in range(reps):
+            for n, f in routes.items():
+                t, p, _o = timed(f); ts[n].append(t); pk[n] = max(pk[n], p); del _o
+            split.append(staged(q, gy, gj, gl)[0])
+        med = {n: median(ts[n]) for n in routes}
+        for n in routes:
+            m, lo, hi = med[n]
+            print(f"Nq={nq} {tag}: {n:26s} (chunk {step}) {m:9.3f} ms (max - min {hi - lo:.3f} ms = {100 * (hi - lo) / m:.1f} %), "
+                  f"peak {pk[n] / 2**20:9.1f} MiB")
+        ma, mb, mc = (med[n][0] for n in routes)
+        print(f"Nq={nq} {tag}: (a) : (b) = {ma / mb:.2f}, (a) : (c) = {ma / mc:.2f} in time (by count of plane-chains (7 + 7) : 7 = 2 "
+              f"against (b), (7 + 7) : (4 + 4) = 1.75 against (c)); the staged loop of (d) returns (a)'s bits: {same}")
+        tot = sum(median([s[n] for s in split])[0] for n in split[0])
+        for n in split[0]:
+            m, lo, hi = median([s[n] for s in split])
+            print(f"Nq={nq} {tag}: (d) {n:38s} {m:9.3f} ms (max - min {hi - lo:.3f} ms) = {100 * m / tot:5.1f} % of the stages' sum {tot:.3f} ms")
+        # (e) the kernels alone, on the lists of the first chunk
+        with torch.no_grad():
+            qc = q[:step].contiguous()
+            nc = qc.shape[0]
+            gc, gjc = torch.randn(nc, 32, device=dev), torch.randn(3, nc, 32, device=dev)
+            glc = torch.randn(1, nc, 32, device=dev)
+            grid = dec._stream_grid(rn, qc, tokens)
+            if rows:
+                lists = device_graph.query_lists(strategy, qc, grid, dec.gno_radius, int(dec.k_neighbors))
+                gboth = device_graph.by_source(lists, m_tok)
+                kk, ne = None, lists.by_dst.num_edges
+                fwd = ("gaot_gno_fwd_jet2", lambda: ops.gno_forward_jet2("linear", kw_, kb_, tokens, qc, rn, None, lists, axes))
+            else:
+                nbr = device_graph.knn_to_grid(qc, grid, 8)
+                gboth = device_graph.by_source((nbr, 8), m_tok)
+                kk, ne = 8, nbr.numel()
+                fwd = ("gaot_gno_fwd_knn_jet2", lambda: ops.gno_forward_knn_jet2("linear", kw_, kb_, tokens, qc, rn, None, nbr, 8, axes))
+            kern = {"gaot_gno_adj_jet2": lambda: ops.gno_adjoint_jet2(kw_, kb_, tokens, qc, axes, gc, gjc, glc, gboth, kk),
+                    "gaot_gno_adj_jac": lambda: ops.gno_adjoint_jac(kw_, kb_, tokens, qc, gc, gjc, gboth, kk),
+                    fwd[0]: fwd[1]}
+            for f in kern.values():
+                f()
+            kt = {n: [] for n in kern}
+            for _ in range(reps):
+                for n, f in kern.items():
+                    t, _p, _o = timed(f); kt[n].append(t); del _o
+            print(f"Nq={nq} {tag}: (e) one chunk of {nc} queries, {ne} edges, {len(fcs) - 1} hidden layers")
+            ka = median(kt["gaot_gno_adj_jet2"])
+            for n in kern:
+                m, lo, hi = median(kt[n])
+                print(f"Nq={nq} {tag}: (e) {n:24s} {m:9.3f} ms (max - min {hi - lo:.3f} ms); gaot_gno_adj_jet2 : this = {ka[0] / m:.2f}", flush=True)
+            del gc, gjc, glc, gboth
+            # (f) the projection cotangent's middle alone, on the rows of one of _project_lap_vjp's blocks
+            mr = nc if hid <= 32 else max(1024, nc * 32 // hid)
+            zus, a5 = torch.randn(5, mr, hid, device=dev), torch.randn(5, mr, hid, device=dev)
+            b1 = dec.projection.fcs[0].bias.detach()
+            mids = {"gaot_mlp2_lap_cot_mid": lambda: ops.mlp2_lap_cot_mid(zus, a5[0], a5[1:4], a5[4], b1),
+                    "tensor operations": lambda: mid_as_tensor_ops(zus, a5[0], a5[1:4], a5[4], b1)}
+            close = (mids["gaot_mlp2_lap_cot_mid"]() - mids["tensor operations"]()).abs().max().item()
+            mt, mp = {n: [] for n in mids}, {n: 0 for n in mids}
+            for _ in range(reps):
+                for n, f in mids.items():
+                    t, p, _o = timed(f); mt[n].append(t); mp[n] = max(mp[n], p); del _o
+            km = median(mt["gaot_mlp2_lap_cot_mid"])
+            print(f"Nq={nq} {tag}: (f) the middle on [{mr}, {hid}] planes ({15 * mr * hid * 4 / 2**20:.0f} MiB read and written); "
+                  f"max |kernel - tensor operations| = {close:.2e}")
+            for n in mids:
+                m, lo, hi = median(mt[n])
+                print(f"Nq={nq} {tag}: (f) {n:24s} {m:9.3f} ms (max - min {hi - lo:.3f} ms), peak {mp[n] / 2**20:8.1f} MiB; "
+                      f"this : gaot_mlp2_lap_cot_mid = {m / km[0]:.2f}", flush=True)
+            del zus, a5
+        del q, gy, gj, gl, qc
 elif what == "projection_jvp":
     # The projection MLP's forward-mode tangent on its own (LinearChannelMLP 32 -> 256 -> out, out in {1, 4}, three tangent planes, fp32
     # mode, random rows), as MAGNODecoder.sample_jacobian calls it: SAMPLE_CHUNK rows at a time into preallocated pred [N, out] and
