@@ -90,29 +90,7 @@ __device__ __forceinline__ float dir_at(const Jet2QDirs&, int, int) { return 0.f
 __device__ __forceinline__ const float* qdir_at(const Jet2Dirs&, int64_t) { return nullptr; }
 __device__ __forceinline__ const float* qdir_at(const Jet2QDirs& D, int64_t i) { return D.v + i; }
 
-// x, as a value the optimiser cannot trace: keeps the recomputation of gelu' / gelu'' from z_l INSIDE the direction loop (hoisted out
-// of it as loop-invariant, the derivatives of every layer are live across the loop again and the kernel spills)
-__device__ __forceinline__ float opaque(float x) {
-    asm volatile("" : "+v"(x));
-    return x;
-}
-
-// gelu_fast's value (its own expression: bit-identical), gelu_fast_pair's derivative (gelu_fast_tangent of gno_common.h) and the
-// second derivative phi(x) (2 - x^2); t, p, e are shared
-__device__ __forceinline__ void gelu_fast_jet2(float x, float& g, float& dg, float& ddg) {
-    const float u = fabsf(x) * 0.70710678118654752440f;
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, u, 1.0f));
-    const float e = __builtin_amdgcn_exp2f(-0.72134752044448170368f * x * x);
-    float p = fmaf(t, 0.5f * 1.061405429f, 0.5f * -1.453152027f);
-    p = fmaf(t, p, 0.5f * 1.421413741f);
-    p = fmaf(t, p, 0.5f * -0.284496736f);
-    p = fmaf(t, p, 0.5f * 0.254829592f);
-    const float h = t * p * e;                    // Phi(-|x|)
-    g = fmaf(-fabsf(x), h, fmaxf(x, 0.f));
-    const float cdf = x >= 0.f ? 1.0f - h : h;
-    dg = fmaf(x * e, 0.39894228040143267794f, cdf);
-    ddg = 0.39894228040143267794f * e * fmaf(-x, x, 2.0f);
-}
+// opaque() and the activation jet gelu_fast_jet2(): gno_common.h
 
 // ROW-LIST variant (gaot_gno_fwd_jet2, k_gno_fwd_rows_jet2): the kernel body (gno_jet2_body.inc) with R = true and a Jet2Rows as the
 // kernel's last argument.  As JacRows of gno_jac.hip: `nbr` is the by-query list's source ids (src_sorted), the

@@ -12,8 +12,8 @@
 // Per-edge work: gno_jet2_body.inc's, statement by statement (see the head of gno_jet2.hip) -- the value path runs once per tile and
 // is kept; what it leaves behind is gelu'(z_l) and gelu''(z_l) with one hidden layer and the pre-activations z_l with two to four
 // (the forward keeps the derivatives at two as well: see KEEP below), from which a pass recomputes the two derivatives; a direction
-// pass carries h' and h'' and two sets of accumulators; z'_0 is the fixed-order chain fma(v_z, w_5, fma(v_y, w_4, v_x w_3)).  The body is COPIED here with its small helpers (Jet2Dirs, dir_at,
-// opaque, gelu_fast_jet2), not included with a flag: the forward's f_y gather, its staging of two planes and its row reductions are
+// pass carries h' and h'' and two sets of accumulators; z'_0 is the fixed-order chain fma(v_z, w_5, fma(v_y, w_4, v_x w_3)).  The body is COPIED here with its small helpers (Jet2Dirs, dir_at;
+// opaque and gelu_fast_jet2 are gno_common.h's), not included with a flag: the forward's f_y gather, its staging of two planes and its row reductions are
 // all replaced, and the 24 forward kernels of gno_jet2.hip are not rebuilt from changed text.
 //
 // Lists and reduction: k_gno_adj_jac's (gno_jac_adj.hip).  The lists are SOURCE-sorted: src_s = the token (the row of y_pos and the
@@ -59,27 +59,7 @@ __device__ __forceinline__ float dir_at(const Jet2Dirs& D, int d, int c) {
     return r;
 }
 
-// x, as a value the optimiser cannot trace: keeps the recomputation of gelu' / gelu'' from z_l INSIDE the direction loop
-__device__ __forceinline__ float opaque(float x) {
-    asm volatile("" : "+v"(x));
-    return x;
-}
-
-// gno_jet2.hip's activation jet: gelu_fast's value, gelu_fast_tangent's derivative and the second derivative phi(x) (2 - x^2)
-__device__ __forceinline__ void gelu_fast_jet2(float x, float& g, float& dg, float& ddg) {
-    const float u = fabsf(x) * 0.70710678118654752440f;
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, u, 1.0f));
-    const float e = __builtin_amdgcn_exp2f(-0.72134752044448170368f * x * x);
-    float p = fmaf(t, 0.5f * 1.061405429f, 0.5f * -1.453152027f);
-    p = fmaf(t, p, 0.5f * 1.421413741f);
-    p = fmaf(t, p, 0.5f * -0.284496736f);
-    p = fmaf(t, p, 0.5f * 0.254829592f);
-    const float h = t * p * e;                    // Phi(-|x|)
-    g = fmaf(-fabsf(x), h, fmaxf(x, 0.f));
-    const float cdf = x >= 0.f ? 1.0f - h : h;
-    dg = fmaf(x * e, 0.39894228040143267794f, cdf);
-    ddg = 0.39894228040143267794f * e * fmaf(-x, x, 2.0f);
-}
+// opaque() and the activation jet gelu_fast_jet2(): gno_common.h
 
 constexpr int WG_PER_CU = 1;
 

@@ -1509,6 +1509,29 @@ class ScaleMixFn(Function):
         return (dlog, *dxs)
 
 
+def _sample_latent_setup(ctx, latent: Tensor, decoder, query_pos: Tensor, tokens_pos: Tensor, chunk_points: Optional[int]) -> Tensor:
+    """what the forwards of the three Functions below share: nothing is saved but the latent, the query coordinates and the token
+    tensor, and an output that received no gradient reaches the backward as None -> the detached latent"""
+    ctx.decoder, ctx.chunk_points = decoder, chunk_points
+    ctx.save_for_backward(latent, query_pos, tokens_pos)
+    ctx.set_materialize_grads(False)
+    return latent.detach()
+
+
+def _sample_latent_backward(ctx, vjp, grads, required: int, tail=()):
+    """what their backwards share: ``grads`` (one per output, None: the output received no gradient) as the cotangents of the decoder's
+    ``vjp`` -- float32, contiguous, None kept as None except the ``required``-th, which is zeros [Nq, out_channels, *tail] then -- ->
+    the gradients of forward's five arguments: the latent's, in its dtype, and four None.  No output used: five None, nothing runs."""
+    latent, query_pos, tokens_pos = ctx.saved_tensors
+    if all(g is None for g in grads):
+        return None, None, None, None, None
+    cots = [None if g is None else g.to(torch.float32).contiguous() for g in grads]
+    if cots[required] is None:
+        cots[required] = torch.zeros(query_pos.shape[0], ctx.decoder.out_channels, *tail, dtype=torch.float32, device=query_pos.device)
+    g = vjp(latent, query_pos, *cots, tokens_pos, chunk_points=ctx.chunk_points)
+    return g.to(latent.dtype), None, None, None, None
+
+
 class SampleLatentFn(Function):
     """The sampled field as a differentiable function of the LATENT: forward = ``MAGNODecoder.sample`` at fp32 arithmetic in both
     precision modes (``torch.equal`` to ``sample`` called in fp32 mode), backward = ``MAGNODecoder.sample_vjp`` (the streamed adjoint:
@@ -1517,16 +1540,13 @@ class SampleLatentFn(Function):
 
     @staticmethod
     def forward(ctx, latent: Tensor, decoder, query_pos: Tensor, tokens_pos: Tensor, chunk_points: Optional[int]):
-        ctx.decoder, ctx.chunk_points = decoder, chunk_points
-        ctx.save_for_backward(latent, query_pos, tokens_pos)
+        latent = _sample_latent_setup(ctx, latent, decoder, query_pos, tokens_pos, chunk_points)
         with ops.fp32_arithmetic():
-            return decoder.sample(latent.detach(), query_pos, tokens_pos, chunk_points=chunk_points)
+            return decoder.sample(latent, query_pos, tokens_pos, chunk_points=chunk_points)
 
     @staticmethod
-    def backward(ctx, dout: Tensor):
-        latent, query_pos, tokens_pos = ctx.saved_tensors
-        g = ctx.decoder.sample_vjp(latent, query_pos, dout.to(torch.float32), tokens_pos, chunk_points=ctx.chunk_points)
-        return g.to(latent.dtype), None, None, None, None
+    def backward(ctx, dout: Optional[Tensor]):
+        return _sample_latent_backward(ctx, ctx.decoder.sample_vjp, (dout,), 0)
 
 
 class SampleJacobianLatentFn(Function):
@@ -1538,22 +1558,12 @@ class SampleJacobianLatentFn(Function):
 
     @staticmethod
     def forward(ctx, latent: Tensor, decoder, query_pos: Tensor, tokens_pos: Tensor, chunk_points: Optional[int]):
-        ctx.decoder, ctx.chunk_points = decoder, chunk_points
-        ctx.save_for_backward(latent, query_pos, tokens_pos)
-        ctx.set_materialize_grads(False)
-        return decoder.sample_jacobian(latent.detach(), query_pos, tokens_pos, chunk_points=chunk_points, row_lists=True)
+        latent = _sample_latent_setup(ctx, latent, decoder, query_pos, tokens_pos, chunk_points)
+        return decoder.sample_jacobian(latent, query_pos, tokens_pos, chunk_points=chunk_points, row_lists=True)
 
     @staticmethod
     def backward(ctx, dpred: Optional[Tensor], djac: Optional[Tensor]):
-        latent, query_pos, tokens_pos = ctx.saved_tensors
-        if dpred is None and djac is None:
-            return None, None, None, None, None
-        nq = query_pos.shape[0]
-        cot_pred = None if dpred is None else dpred.to(torch.float32).contiguous()
-        cot_jac = torch.zeros(nq, ctx.decoder.out_channels, 3, dtype=torch.float32, device=query_pos.device) if djac is None \
-            else djac.to(torch.float32).contiguous()
-        g = ctx.decoder.sample_jacobian_vjp(latent, query_pos, cot_pred, cot_jac, tokens_pos, chunk_points=ctx.chunk_points)
-        return g.to(latent.dtype), None, None, None, None
+        return _sample_latent_backward(ctx, ctx.decoder.sample_jacobian_vjp, (dpred, djac), 1, (3,))
 
 
 class SampleLaplacianLatentFn(Function):
@@ -1566,20 +1576,9 @@ class SampleLaplacianLatentFn(Function):
 
     @staticmethod
     def forward(ctx, latent: Tensor, decoder, query_pos: Tensor, tokens_pos: Tensor, chunk_points: Optional[int]):
-        ctx.decoder, ctx.chunk_points = decoder, chunk_points
-        ctx.save_for_backward(latent, query_pos, tokens_pos)
-        ctx.set_materialize_grads(False)
-        return decoder._laplacian_jets("sample_laplacian_autograd", latent.detach(), query_pos, tokens_pos, chunk_points)
+        latent = _sample_latent_setup(ctx, latent, decoder, query_pos, tokens_pos, chunk_points)
+        return decoder._laplacian_jets("sample_laplacian_autograd", latent, query_pos, tokens_pos, chunk_points)
 
     @staticmethod
     def backward(ctx, dpred: Optional[Tensor], djac: Optional[Tensor], dlap: Optional[Tensor]):
-        latent, query_pos, tokens_pos = ctx.saved_tensors
-        if dpred is None and djac is None and dlap is None:
-            return None, None, None, None, None
-        nq = query_pos.shape[0]
-        cot_pred = None if dpred is None else dpred.to(torch.float32).contiguous()
-        cot_jac = None if djac is None else djac.to(torch.float32).contiguous()
-        cot_lap = torch.zeros(nq, ctx.decoder.out_channels, dtype=torch.float32, device=query_pos.device) if dlap is None \
-            else dlap.to(torch.float32).contiguous()
-        g = ctx.decoder.sample_laplacian_vjp(latent, query_pos, cot_pred, cot_jac, cot_lap, tokens_pos, chunk_points=ctx.chunk_points)
-        return g.to(latent.dtype), None, None, None, None
+        return _sample_latent_backward(ctx, ctx.decoder.sample_laplacian_vjp, (dpred, djac, dlap), 2)

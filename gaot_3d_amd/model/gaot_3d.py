@@ -8,7 +8,6 @@ import torch
 import torch.nn as nn
 
 from .. import functional as GF
-from .. import ops
 from .layers.attn import Transformer, TransformerConfig
 from .layers.magno import MAGNOConfig, MAGNODecoder, MAGNOEncoder
 
@@ -215,6 +214,21 @@ class GAOT3D(nn.Module):
         lat = self._one_sample("sample_directional", latent, tokens_pos)
         return self.decoder.sample_directional(latent, query_pos.to(latent.device), dirs, lat, chunk_points=chunk_points)
 
+    def _adjoint_args(self, fn, latent, query_pos, tokens_pos, autograd_order=None, chunk_points=None):
+        """what the six adjoint methods share -> (the tokens, the queries on the latent's device): ONE sample's latent and no
+        point-sharded model; for the autograd forms (``autograd_order``: the adjoint's order 0 / 1 / 2) also a ``query_pos`` that does
+        not require grad and the refusals of the decoder's adjoint (``MAGNODecoder._adjoint_stream``), before the forward runs"""
+        lat = self._one_sample(fn, latent, tokens_pos)
+        if autograd_order is not None and query_pos.requires_grad:
+            raise ValueError(f"GAOT3D.{fn}: query_pos requires grad, but gradients flow to the latent only (no derivative in the query "
+                             "coordinates is formed: the first is sample_jacobian's); detach it")
+        if getattr(self, "_shard_group", None) is not None:
+            raise NotImplementedError(f"GAOT3D.{fn}: a point-sharded model is not supported")
+        q = query_pos.to(latent.device)
+        if autograd_order is not None:
+            self.decoder._adjoint_stream(fn, autograd_order, latent, q, lat, chunk_points)
+        return lat, q
+
     def sample_vjp(self, latent: torch.Tensor, query_pos: torch.Tensor, cotangent: torch.Tensor,
                    tokens_pos: Optional[torch.Tensor] = None, chunk_points: Optional[int] = None) -> torch.Tensor:
         """The ADJOINT of ``sample``: -> grad_latent [D*H*W, lifting_channels] (fp32) = sum_q cotangent[q] . d pred[q] / d latent for a
@@ -224,10 +238,8 @@ class GAOT3D(nn.Module):
         modes, outside autograd, bit-reproducible for a given ``chunk_points`` (not bit-identical across chunkings: a token's sum is
         split at chunk boundaries).  The decoder's parameters and the query coordinates are constants.  Routes and refusals are
         ``sample_hessian``'s / ``sample_hessian_rows``'s; a point-sharded model raises NotImplementedError."""
-        lat = self._one_sample("sample_vjp", latent, tokens_pos)
-        if getattr(self, "_shard_group", None) is not None:
-            raise NotImplementedError("GAOT3D.sample_vjp: a point-sharded model is not supported")
-        return self.decoder.sample_vjp(latent, query_pos.to(latent.device), cotangent, lat, chunk_points=chunk_points)
+        lat, q = self._adjoint_args("sample_vjp", latent, query_pos, tokens_pos)
+        return self.decoder.sample_vjp(latent, q, cotangent, lat, chunk_points=chunk_points)
 
     def sample_autograd(self, latent: torch.Tensor, query_pos: torch.Tensor, tokens_pos: Optional[torch.Tensor] = None,
                         chunk_points: Optional[int] = None) -> torch.Tensor:
@@ -239,19 +251,8 @@ class GAOT3D(nn.Module):
         ``latent`` ONLY: the decoder's parameters are constants here (train them through ``forward``), and a ``query_pos`` that
         requires grad raises ValueError -- the derivative with respect to the query is ``sample_jacobian``'s.  Configurations
         ``sample_vjp`` refuses are refused here, before the forward runs."""
-        lat = self._one_sample("sample_autograd", latent, tokens_pos)
-        if query_pos.requires_grad:
-            raise ValueError("GAOT3D.sample_autograd: query_pos requires grad, but gradients flow to the latent only (the derivative "
-                             "with respect to the query coordinates is sample_jacobian's); detach it")
-        if getattr(self, "_shard_group", None) is not None:
-            raise NotImplementedError("GAOT3D.sample_autograd: a point-sharded model is not supported")
-        q = query_pos.to(latent.device)
-        dec = self.decoder
-        dec._sample_args("sample_autograd", chunk_points)
-        with torch.no_grad(), ops.fp32_arithmetic():      # sample_vjp's refusals, before anything runs
-            dec._jet2_stream("sample_autograd", latent.detach(), q, lat, chunk_points, rows=dec.decoder_strategy != "knn",
-                             what="the adjoint of the sampled field", jets=False)
-        return GF.SampleLatentFn.apply(latent, dec, q, lat, chunk_points)
+        lat, q = self._adjoint_args("sample_autograd", latent, query_pos, tokens_pos, 0, chunk_points)
+        return GF.SampleLatentFn.apply(latent, self.decoder, q, lat, chunk_points)
 
     def sample_jacobian_vjp(self, latent: torch.Tensor, query_pos: torch.Tensor, cot_pred: Optional[torch.Tensor],
                             cot_jac: torch.Tensor, tokens_pos: Optional[torch.Tensor] = None,
@@ -264,10 +265,8 @@ class GAOT3D(nn.Module):
         weight gradients.  ``MAGNODecoder.sample_jacobian_vjp``: exact fp32 in both precision modes, outside autograd,
         bit-reproducible for a given ``chunk_points``.  The decoder's parameters and the query coordinates are constants.  Routes and
         refusals are ``sample_vjp``'s."""
-        lat = self._one_sample("sample_jacobian_vjp", latent, tokens_pos)
-        if getattr(self, "_shard_group", None) is not None:
-            raise NotImplementedError("GAOT3D.sample_jacobian_vjp: a point-sharded model is not supported")
-        return self.decoder.sample_jacobian_vjp(latent, query_pos.to(latent.device), cot_pred, cot_jac, lat, chunk_points=chunk_points)
+        lat, q = self._adjoint_args("sample_jacobian_vjp", latent, query_pos, tokens_pos)
+        return self.decoder.sample_jacobian_vjp(latent, q, cot_pred, cot_jac, lat, chunk_points=chunk_points)
 
     def sample_jacobian_autograd(self, latent: torch.Tensor, query_pos: torch.Tensor, tokens_pos: Optional[torch.Tensor] = None,
                                  chunk_points: Optional[int] = None):
@@ -280,22 +279,8 @@ class GAOT3D(nn.Module):
         ONLY: the decoder's parameters are constants here, and a ``query_pos`` that requires grad raises ValueError (no second
         derivative in the query is formed).  Configurations ``sample_jacobian_vjp`` refuses are refused here, before the forward
         runs."""
-        fn = "sample_jacobian_autograd"
-        lat = self._one_sample(fn, latent, tokens_pos)
-        if query_pos.requires_grad:
-            raise ValueError(f"GAOT3D.{fn}: query_pos requires grad, but gradients flow to the latent only; detach it")
-        if getattr(self, "_shard_group", None) is not None:
-            raise NotImplementedError(f"GAOT3D.{fn}: a point-sharded model is not supported")
-        q = query_pos.to(latent.device)
-        dec = self.decoder
-        dec._sample_args(fn, chunk_points)
-        with torch.no_grad(), ops.fp32_arithmetic():      # sample_jacobian_vjp's refusals, before anything runs
-            dec._jet2_stream(fn, latent.detach(), q, lat, chunk_points, rows=dec.decoder_strategy != "knn",
-                             what="the adjoint of the field's Jacobian", jets=False)
-            if dec.projection.non_linearity not in dec.JAC_VJP_ACTS:
-                raise NotImplementedError(f"GAOT3D.{fn}: the second derivative of the projection's activation "
-                                          f"{dec.projection.non_linearity!r} is not written (covered: {dec.JAC_VJP_ACTS})")
-        return GF.SampleJacobianLatentFn.apply(latent, dec, q, lat, chunk_points)
+        lat, q = self._adjoint_args("sample_jacobian_autograd", latent, query_pos, tokens_pos, 1, chunk_points)
+        return GF.SampleJacobianLatentFn.apply(latent, self.decoder, q, lat, chunk_points)
 
     def sample_laplacian_vjp(self, latent: torch.Tensor, query_pos: torch.Tensor, cot_pred: Optional[torch.Tensor],
                              cot_jac: Optional[torch.Tensor], cot_lap: torch.Tensor, tokens_pos: Optional[torch.Tensor] = None,
@@ -310,11 +295,8 @@ class GAOT3D(nn.Module):
         ``chunk_points``.  The decoder's parameters and the query coordinates are constants.  Routes and refusals are
         ``sample_laplacian``'s on a 'knn' decoder and ``sample_laplacian_rows``'s on 'radius' / 'bidirectional'; a transform that is
         not 'linear' and a point-sharded model raise NotImplementedError."""
-        lat = self._one_sample("sample_laplacian_vjp", latent, tokens_pos)
-        if getattr(self, "_shard_group", None) is not None:
-            raise NotImplementedError("GAOT3D.sample_laplacian_vjp: a point-sharded model is not supported")
-        return self.decoder.sample_laplacian_vjp(latent, query_pos.to(latent.device), cot_pred, cot_jac, cot_lap, lat,
-                                                 chunk_points=chunk_points)
+        lat, q = self._adjoint_args("sample_laplacian_vjp", latent, query_pos, tokens_pos)
+        return self.decoder.sample_laplacian_vjp(latent, q, cot_pred, cot_jac, cot_lap, lat, chunk_points=chunk_points)
 
     def sample_laplacian_autograd(self, latent: torch.Tensor, query_pos: torch.Tensor, tokens_pos: Optional[torch.Tensor] = None,
                                   chunk_points: Optional[int] = None):
@@ -326,17 +308,8 @@ class GAOT3D(nn.Module):
         bit.  An output that received no gradient contributes no cotangent.  Gradients flow to ``latent`` ONLY: the decoder's
         parameters are constants here, and a ``query_pos`` that requires grad raises ValueError (no third derivative in the query is
         formed).  Configurations ``sample_laplacian_vjp`` refuses are refused here, before the forward runs."""
-        fn = "sample_laplacian_autograd"
-        lat = self._one_sample(fn, latent, tokens_pos)
-        if query_pos.requires_grad:
-            raise ValueError(f"GAOT3D.{fn}: query_pos requires grad, but gradients flow to the latent only; detach it")
-        if getattr(self, "_shard_group", None) is not None:
-            raise NotImplementedError(f"GAOT3D.{fn}: a point-sharded model is not supported")
-        q = query_pos.to(latent.device)
-        dec = self.decoder
-        with torch.no_grad(), ops.fp32_arithmetic():      # sample_laplacian_vjp's refusals, before anything runs
-            dec._lap_vjp_stream(fn, latent.detach(), q, lat, chunk_points)
-        return GF.SampleLaplacianLatentFn.apply(latent, dec, q, lat, chunk_points)
+        lat, q = self._adjoint_args("sample_laplacian_autograd", latent, query_pos, tokens_pos, 2, chunk_points)
+        return GF.SampleLaplacianLatentFn.apply(latent, self.decoder, q, lat, chunk_points)
 
     def forward(self, batch, tokens_pos: Optional[torch.Tensor] = None, tokens_batch_idx: Optional[torch.Tensor] = None,
                 query_coord_pos: Optional[torch.Tensor] = None, query_coord_batch_idx: Optional[torch.Tensor] = None,

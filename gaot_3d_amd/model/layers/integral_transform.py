@@ -223,17 +223,12 @@ class IntegralTransform(nn.Module):
         32-channel pass) -- no MLP backward, no weight gradients.  The operands are prepared exactly as in ``forward_knn``
         (``_fused_passes``); exact fp32 in both precision modes; nothing is recorded for autograd.  Runs exactly when ``_fused_plan``
         is not None, the transform is 'linear' and k is in ``ops.GNO_KNN_K``; raises NotImplementedError otherwise."""
-        if int(k) not in ops.GNO_KNN_K:
-            raise NotImplementedError(f"IntegralTransform.adjoint_knn: lists of k in {ops.GNO_KNN_K} neighbours per query, got k = {k}")
-        if graph is None:
-            from ... import graph as device_graph
-            graph = device_graph.by_source((nbr, int(k)), y_pos.shape[0])
-        return self._adjoint("adjoint_knn", y_pos, x_pos, grad_out, graph, int(k))
+        return self._adjoint(y_pos, x_pos, [grad_out], graph, (nbr, k))
 
     def adjoint_rows(self, y_pos, x_pos, grad_out, graph):
         """``adjoint_knn`` on RAGGED rows: ``graph`` holds both lists of the chunk -- ``by_dst`` as ``graph.query_lists`` wrote it
         (its offsets give 1/deg; a query without neighbours contributes nothing) and ``by_src`` from ``graph.by_source``."""
-        return self._adjoint("adjoint_rows", y_pos, x_pos, grad_out, graph, None)
+        return self._adjoint(y_pos, x_pos, [grad_out], graph)
 
     def adjoint_jac_knn(self, y_pos, x_pos, nbr, k: int, grad_out, grad_jac, graph=None):
         """The ADJOINT of ``jacobian_knn`` with respect to f_y: -> grad_f_y [N_y, C] for the cotangents ``grad_out`` [N_x, C] on the
@@ -242,16 +237,11 @@ class IntegralTransform(nn.Module):
         contracted with the cotangents and reduced by source (``ops.gno_adjoint_jac``: two launches per 32-channel pass).  ``graph``,
         the preparation of the operands (the cotangent planes ride where ``grad_out`` does), exactness and refusals are
         ``adjoint_knn``'s."""
-        if int(k) not in ops.GNO_KNN_K:
-            raise NotImplementedError(f"IntegralTransform.adjoint_jac_knn: lists of k in {ops.GNO_KNN_K} neighbours per query, got k = {k}")
-        if graph is None:
-            from ... import graph as device_graph
-            graph = device_graph.by_source((nbr, int(k)), y_pos.shape[0])
-        return self._adjoint("adjoint_jac_knn", y_pos, x_pos, grad_out, graph, int(k), grad_jac)
+        return self._adjoint(y_pos, x_pos, [grad_out, grad_jac], graph, (nbr, k))
 
     def adjoint_jac_rows(self, y_pos, x_pos, grad_out, grad_jac, graph):
         """``adjoint_jac_knn`` on RAGGED rows: ``graph`` holds both lists of the chunk, as for ``adjoint_rows``."""
-        return self._adjoint("adjoint_jac_rows", y_pos, x_pos, grad_out, graph, None, grad_jac)
+        return self._adjoint(y_pos, x_pos, [grad_out, grad_jac], graph)
 
     def adjoint_jet2_knn(self, y_pos, x_pos, nbr, k: int, dirs, grad_out, grad_d1, grad_d2, graph=None):
         """The ADJOINT of ``jet2_knn`` with respect to f_y: -> grad_f_y [N_y, C] for the directions ``dirs`` (host values [nd][3],
@@ -261,51 +251,47 @@ class IntegralTransform(nn.Module):
         All 1 + 2 nd planes of the 'linear' transform are linear in f_y, so this is the jet kernel's per-edge work contracted with the
         cotangents and reduced by source (``ops.gno_adjoint_jet2``: two launches per 32-channel pass).  ``graph``, the preparation of
         the operands, exactness and refusals are ``adjoint_knn``'s."""
-        if int(k) not in ops.GNO_KNN_K:
-            raise NotImplementedError(f"IntegralTransform.adjoint_jet2_knn: lists of k in {ops.GNO_KNN_K} neighbours per query, got k = {k}")
-        if graph is None:
-            from ... import graph as device_graph
-            graph = device_graph.by_source((nbr, int(k)), y_pos.shape[0])
-        return self._adjoint("adjoint_jet2_knn", y_pos, x_pos, grad_out, graph, int(k), jet2=(dirs, grad_d1, grad_d2))
+        return self._adjoint(y_pos, x_pos, [grad_out, grad_d1, grad_d2], graph, (nbr, k), dirs)
 
     def adjoint_jet2_rows(self, y_pos, x_pos, dirs, grad_out, grad_d1, grad_d2, graph):
         """``adjoint_jet2_knn`` on RAGGED rows: ``graph`` holds both lists of the chunk, as for ``adjoint_rows``."""
-        return self._adjoint("adjoint_jet2_rows", y_pos, x_pos, grad_out, graph, None, jet2=(dirs, grad_d1, grad_d2))
+        return self._adjoint(y_pos, x_pos, [grad_out, grad_d1, grad_d2], graph, None, dirs)
 
-    def _adjoint(self, fn, y_pos, x_pos, grad_out, graph, k, grad_jac=None, jet2=None):
-        """the six adjoint methods: every pass of ``_fused_passes`` (its f_y block is the cotangent's) is one ``ops.gno_adjoint`` call,
-        with ``grad_jac`` [3, N_x, C] one ``ops.gno_adjoint_jac`` call on the same channels of every plane, or with ``jet2`` = (dirs,
-        grad_d1 [nd, N_x, C], grad_d2 [nd or 1, N_x, C]) one ``ops.gno_adjoint_jet2`` call"""
+    def _adjoint(self, y_pos, x_pos, cots, graph, lists=None, dirs=None):
+        """The six adjoint methods.  ``cots``: the cotangent planes [grad_out [N_x, C]], [grad_out, grad_jac [3, N_x, C]] or, with the
+        host directions ``dirs`` [nd][3], [grad_out, grad_d1 [nd, N_x, C], grad_d2 [nd or 1, N_x, C]]; ``lists``: the regular list
+        (nbr, k), whose by-source list is built here when ``graph`` is None, or None for the two lists of ``graph``.  Every pass of
+        ``_fused_passes`` (its f_y block is grad_out's) is one ``ops.gno_adjoint`` / ``gno_adjoint_jac`` / ``gno_adjoint_jet2`` call on
+        the same 32 channels of every plane, zero-padded in the last block."""
+        fn = "adjoint" + ("", "_jac", "_jet2")[len(cots) - 1] + ("_rows" if lists is None else "_knn")
+        k = None
+        if lists is not None:
+            nbr, k = lists[0], int(lists[1])
+            if k not in ops.GNO_KNN_K:
+                raise NotImplementedError(f"IntegralTransform.{fn}: lists of k in {ops.GNO_KNN_K} neighbours per query, got k = {lists[1]}")
+            if graph is None:
+                from ... import graph as device_graph
+                graph = device_graph.by_source((nbr, k), y_pos.shape[0])
+        grad_out, *planes = cots
         fcs = list(self.channel_mlp.fcs)
         with torch.no_grad():
             plan = self._fused_plan(fcs, grad_out, y_pos, x_pos) if self.transform_type == "linear" else None
             if plan is None:
                 raise NotImplementedError(f"IntegralTransform.{fn}: only the 'linear' transforms the fused kernels evaluate (_fused_plan); "
                                           f"transform_type = {self.transform_type!r}, use_attn = {bool(self.use_attn)}")
-            if grad_jac is not None and (grad_jac.dim() != 3 or grad_jac.shape[0] != 3 or grad_jac.shape[1:] != grad_out.shape):
-                raise ValueError(f"IntegralTransform.{fn}: grad_jac must be [3, {grad_out.shape[0]}, {grad_out.shape[1]}], "
-                                 f"got {tuple(grad_jac.shape)}")
-            if jet2 is not None:
-                dirs, grad_d1, grad_d2 = jet2
-                nd = len(dirs)
-                for name, t, lead in (("grad_d1", grad_d1, (nd,)), ("grad_d2", grad_d2, (nd, 1))):
-                    if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.shape[0] not in lead or t.shape[1:] != grad_out.shape:
-                        raise ValueError(f"IntegralTransform.{fn}: {name} must be [{' or '.join(str(n) for n in lead)}, "
-                                         f"{grad_out.shape[0]}, {grad_out.shape[1]}], got "
-                                         f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+            leads = [(3,)] if dirs is None else [(len(dirs),), (len(dirs), 1)]
+            for name, t, lead in zip(("grad_jac",) if dirs is None else ("grad_d1", "grad_d2"), planes, leads):
+                if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.shape[0] not in lead or t.shape[1:] != grad_out.shape:
+                    raise ValueError(f"IntegralTransform.{fn}: {name} must be [{' or '.join(str(n) for n in lead)}, "
+                                     f"{grad_out.shape[0]}, {grad_out.shape[1]}], got "
+                                     f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+            run = (ops.gno_adjoint, ops.gno_adjoint_jac, ops.gno_adjoint_jet2)[len(planes)]
             y3, x3, _, (w0, b0, *mid), blocks = self._fused_passes(fcs, y_pos, x_pos, grad_out, *plan)
             outs = []
             for i, (wb, bb, gb, n) in enumerate(blocks):
                 ws, bs = [w0.contiguous(), *mid[0::2], wb.contiguous()], [b0, *mid[1::2], bb.contiguous()]
-                if jet2 is not None:
-                    p1, p2 = (t if t.shape[2] == 32 else torch.nn.functional.pad(t[:, :, 32 * i:32 * i + n], (0, 32 - n))
-                              for t in (grad_d1, grad_d2))
-                    o = ops.gno_adjoint_jet2(ws, bs, y3, x3, dirs, gb.contiguous(), p1.contiguous(), p2.contiguous(), graph, k)
-                elif grad_jac is None:
-                    o = ops.gno_adjoint(ws, bs, y3, x3, gb.contiguous(), graph, k)
-                else:
-                    jb = grad_jac if grad_jac.shape[2] == 32 else torch.nn.functional.pad(grad_jac[:, :, 32 * i:32 * i + n], (0, 32 - n))
-                    o = ops.gno_adjoint_jac(ws, bs, y3, x3, gb.contiguous(), jb.contiguous(), graph, k)
+                pb = [t if t.shape[2] == 32 else torch.nn.functional.pad(t[:, :, 32 * i:32 * i + n], (0, 32 - n)) for t in planes]
+                o = run(ws, bs, y3, x3, *(() if dirs is None else (dirs,)), gb.contiguous(), *(p.contiguous() for p in pb), graph, k)
                 outs.append(o if n == 32 else o[:, :n])
             return outs[0].contiguous() if len(outs) == 1 else torch.cat(outs, dim=1)
 

@@ -865,50 +865,7 @@ class MAGNODecoder(nn.Module):
         the cotangent g [rows, out_channels], in exact fp32 on the GEMM / activation kernels: z = x W_1^T + b_1,
         dh = (g W_2) * act'(z), dx = dh W_1.  Rows in blocks, so that the [rows, projection_channels] tensors stay no larger than x
         itself (``_project_into``)."""
-        from ... import ops
-        fc1, fc2 = self.projection.fcs
-        w1, w2 = GF._w2d(fc1.weight).contiguous(), GF._w2d(fc2.weight).contiguous()
-        act = ops.ACT[self.projection.non_linearity]
-        n, c = x.shape
-        hid, oc = w1.shape[0], w2.shape[0]
-        dx = torch.empty_like(x)
-        step = n if hid <= c else max(1024, n * c // hid)
-        for j in range(0, n, step):
-            xb, gb = x[j:j + step], g[j:j + step]
-            m = xb.shape[0]
-            z = ops.gemm(xb, w1, m, hid, c, c, c, False, True, fc1.bias, 0, precision=0)
-            dh = ops.gemm(gb, w2, m, hid, oc, oc, hid, False, False, precision=0)
-            dz = ops.act_bwd(z, dh, act) if act else dh
-            ops.gemm(dz, w1, m, c, hid, hid, c, False, False, out=dx[j:j + step], ldc=c, precision=0)
-        return dx
-
-    def _vjp_chunk(self, rndata_flat, q, g, lat, lists):
-        """one chunk of ``sample_vjp``: -> its [M, C] part of the latent's gradient.  A call of its own, so that a chunk's rows and
-        lists are freed before the next chunk's are allocated."""
-        from ... import graph as device_graph
-        from ... import ops
-        m = lat.shape[0]
-        if isinstance(lists, tuple):                       # 'knn': every scale sees the same list, the mix is of equal operands
-            x = self._mix_equal_scales([self.gno.forward_knn(lat, q, *lists, rndata_flat)], q)[0]
-            dx = self._project_vjp(x, g)
-            del x
-            d = self._mix_equal_scales([dx], q)[0]      # (sum_s w_s) dx, formed as the forward forms sum_s w_s x
-            del dx
-            return self.gno.adjoint_knn(lat, q, *lists, d, graph=device_graph.by_source(lists, m))
-        outs = [self.gno(y_pos=lat, x_pos=q, edge_index=None, f_y=rndata_flat, graph=rows) for rows in lists]
-        if len(outs) == 1:
-            ds = [self._project_vjp(outs[0], g)]
-        elif not self.use_scale_weights:
-            ds = [self._project_vjp(_sum_scales(outs), g)] * len(outs)
-        else:                                              # the softmax weights depend on the query alone: d out_s = w_s dx
-            outs = [o.contiguous() for o in outs]
-            x, w = ops.scale_mix_fwd(outs, _scale_logits(self, q)[0].contiguous())
-            ds = ops.scale_mix_bwd(outs, w, self._project_vjp(x, g))[0]
-        part = None
-        for rows, d in zip(lists, ds):
-            p = self.gno.adjoint_rows(lat, q, d, device_graph.by_source(rows, m))
-            part = p if part is None else part.add_(p)
-        return part
+        return self._project_cot(0, [x], g)[0]
 
     @torch.no_grad()
     def sample_vjp(self, rndata_flat, query_pos, cotangent, latent_tokens_pos, chunk_points: Optional[int] = None) -> torch.Tensor:
@@ -938,28 +895,8 @@ class MAGNODecoder(nn.Module):
         projection that is not two linear layers with a named activation, and a point-sharded model raise NotImplementedError naming
         the condition; 'reverse', a non-positive ``chunk_points`` and a cotangent that is not float32 [Nq, out_channels] on the queries'
         device raise ValueError."""
-        from ... import ops
-        fn = "sample_vjp"
-        self._sample_args(fn, chunk_points)
-        nq = int(query_pos.shape[0])
-        if not isinstance(cotangent, torch.Tensor) or cotangent.dtype != torch.float32 or cotangent.device != query_pos.device \
-                or tuple(cotangent.shape) != (nq, self.out_channels):
-            got = f"{cotangent.dtype} {tuple(cotangent.shape)} on {cotangent.device}" if isinstance(cotangent, torch.Tensor) \
-                else type(cotangent).__name__
-            raise ValueError(f"MAGNODecoder.{fn}: the cotangent must be float32 [{nq}, {self.out_channels}] on the queries' device "
-                             f"({query_pos.device}), got {got}")
-        if getattr(self, "_shard_group", None) is not None:
-            raise NotImplementedError(f"MAGNODecoder.{fn}: a point-sharded model is not supported (every rank would hold a partial sum)")
-        rndata_flat, query_pos, cotangent = rndata_flat.detach(), query_pos.detach(), cotangent.detach().contiguous()
-        rows = self.decoder_strategy != "knn"
-        with ops.fp32_arithmetic():
-            grid, chunk = self._jet2_stream(fn, rndata_flat, query_pos, latent_tokens_pos, chunk_points, rows=rows,
-                                            what="the adjoint of the sampled field", jets=False)
-            f = rndata_flat.to(torch.float32).contiguous()
-            grad = torch.zeros_like(f)
-            for sl, q, lists in self._stream_chunks(grid, query_pos, chunk, "rows" if rows else "knn", lead=False):
-                grad.add_(self._vjp_chunk(f, q.contiguous(), cotangent[sl], latent_tokens_pos, lists))
-        return grad
+        return self._adjoint("sample_vjp", 0, rndata_flat, query_pos, [("the cotangent", cotangent, (), False)], latent_tokens_pos,
+                             chunk_points)
 
     # the projection activations ``sample_jacobian_vjp`` differentiates twice: act' and act'' as plain fp32 tensor operations
     JAC_VJP_ACTS = (None, "none", "gelu", "relu")
@@ -983,77 +920,7 @@ class MAGNODecoder(nn.Module):
             dz = act'(z) * a + act''(z) * sum_d u_d * a_d,   dx = dz W_1;      du_d = act'(z) * a_d,   dx'_d = du_d W_1
         Exact fp32: three GEMMs per row block on the four planes STACKED ([4 rows, .]: one launch per product, precision 0) and the
         elementwise middle as plain fp32 tensor operations (``_act_jets``).  Rows in blocks sized as in ``_project_vjp``."""
-        from ... import ops
-        fc1, fc2 = self.projection.fcs
-        w1, w2 = GF._w2d(fc1.weight).contiguous(), GF._w2d(fc2.weight).contiguous()
-        act = self.projection.non_linearity
-        n, c = planes[0].shape
-        hid, oc = w1.shape[0], w2.shape[0]
-        outs = [torch.empty_like(planes[0]) for _ in range(4)]
-        step = n if hid <= c else max(1024, n * c // hid)
-        for j in range(0, n, step):
-            m = planes[0][j:j + step].shape[0]
-            x4 = torch.cat([p[j:j + step] for p in planes])
-            g0 = gy[j:j + step] if gy is not None else gj.new_zeros(m, oc)
-            g4 = torch.cat([g0] + [gj[j:j + step, :, d] for d in range(3)])
-            zu = ops.gemm(x4, w1, 4 * m, hid, c, c, c, False, True, precision=0)          # [z - b_1; u_0; u_1; u_2]
-            a4 = ops.gemm(g4, w2, 4 * m, hid, oc, oc, hid, False, False, precision=0)     # [a; a_0; a_1; a_2]
-            del x4, g4
-            z = zu[:m]
-            if fc1.bias is not None:
-                z += fc1.bias
-            d1, d2 = self._act_jets(z, act)
-            if d2 is not None:
-                s = zu[m:2 * m] * a4[m:2 * m]
-                for d in (1, 2):
-                    s += zu[(1 + d) * m:(2 + d) * m] * a4[(1 + d) * m:(2 + d) * m]
-                s *= d2
-            del zu, z
-            if d1 is not None:                       # a4 becomes [dz; du_0; du_1; du_2] in place
-                a4.view(4, m, hid).mul_(d1)
-            if d2 is not None:
-                a4[:m] += s
-                del s
-            dx4 = ops.gemm(a4, w1, 4 * m, c, hid, hid, c, False, False, precision=0)
-            for p in range(4):
-                outs[p][j:j + step] = dx4[p * m:(p + 1) * m]
-        return outs
-
-    def _jac_vjp_chunk(self, rndata_flat, q, gy, gj, lat, lists):
-        """one chunk of ``sample_jacobian_vjp``: -> its [M, C] part of the latent's gradient.  A call of its own, so that a chunk's
-        planes and lists are freed before the next chunk's are allocated."""
-        from ... import graph as device_graph
-        m = lat.shape[0]
-        planes = self._jet_planes(rndata_flat, q, lat, lists)      # the mixed [x, x'_0, x'_1, x'_2], recomputed at fp32
-        d = self._project_jac_vjp(planes, gy, gj)
-        del planes
-        if isinstance(lists, tuple):                       # 'knn': equal operands, the weights' tangents drop out (``sample_jacobian``)
-            d = self._mix_equal_scales(d, q)
-            return self.gno.adjoint_jac_knn(lat, q, *lists, d[0], torch.stack(d[1:]), graph=device_graph.by_source(lists, m))
-        ns = len(lists)
-        if ns == 1 or not self.use_scale_weights:          # one scale, or summed scales: every scale gets the planes as they are
-            per = [(d[0], torch.stack(d[1:]))] * ns
-        else:
-            # x = sum_s w_s o_s and x'_d = sum_s (w_s o'_s,d + w'_s,d o_s) with w = softmax(l(q)), a function of the query alone:
-            # G_s = w_s dx + sum_d w'_s,d dx'_d on o_s,  J_s,d = w_s dx'_d on o'_s,d
-            sw = self.scale_weighting
-            logits, hdn = _scale_logits(self, q)
-            w = torch.softmax(logits, dim=1)
-            dls = _logit_tangents((hdn > 0).to(hdn.dtype), sw[0].weight, sw[2].weight, lambda x, wt: GF.linear(x, wt, None, precision=0))
-            dws = [_softmax_weight_jets(w, dl)[0] for dl in dls]
-            per = []
-            for s in range(ns):
-                ws = w[:, s:s + 1]
-                g = ws * d[0]
-                for di, dw in enumerate(dws):
-                    g += dw[:, s:s + 1] * d[1 + di]
-                per.append((g, torch.stack([ws * d[1 + di] for di in range(3)])))
-        del d
-        part = None
-        for rows, (g, jc) in zip(lists, per):
-            p = self.gno.adjoint_jac_rows(lat, q, g, jc, device_graph.by_source(rows, m))
-            part = p if part is None else part.add_(p)
-        return part
+        return self._project_cot(1, planes, gy, gj)
 
     @torch.no_grad()
     def sample_jacobian_vjp(self, rndata_flat, query_pos, cot_pred, cot_jac, latent_tokens_pos,
@@ -1080,35 +947,8 @@ class MAGNODecoder(nn.Module):
         ``chunk_points``; not bit-identical across chunkings (a token's sum is split at the chunk boundaries).  Routes and refusals
         are ``sample_vjp``'s; in addition a projection activation outside ``JAC_VJP_ACTS`` raises NotImplementedError naming it, and
         cotangents of the wrong dtype, shape or device raise ValueError."""
-        from ... import ops
-        fn = "sample_jacobian_vjp"
-        self._sample_args(fn, chunk_points)
-        nq, oc = int(query_pos.shape[0]), self.out_channels
-        for name, cot, shape, optional in (("cot_pred", cot_pred, (nq, oc), True), ("cot_jac", cot_jac, (nq, oc, 3), False)):
-            if cot is None and optional:
-                continue
-            if not isinstance(cot, torch.Tensor) or cot.dtype != torch.float32 or cot.device != query_pos.device \
-                    or tuple(cot.shape) != shape:
-                got = f"{cot.dtype} {tuple(cot.shape)} on {cot.device}" if isinstance(cot, torch.Tensor) else type(cot).__name__
-                raise ValueError(f"MAGNODecoder.{fn}: {name} must be float32 {list(shape)} on the queries' device "
-                                 f"({query_pos.device}){' or None' if optional else ''}, got {got}")
-        if getattr(self, "_shard_group", None) is not None:
-            raise NotImplementedError(f"MAGNODecoder.{fn}: a point-sharded model is not supported (every rank would hold a partial sum)")
-        rndata_flat, query_pos, cot_jac = rndata_flat.detach(), query_pos.detach(), cot_jac.detach()
-        cot_pred = None if cot_pred is None else cot_pred.detach()
-        rows = self.decoder_strategy != "knn"
-        with ops.fp32_arithmetic():
-            grid, chunk = self._jet2_stream(fn, rndata_flat, query_pos, latent_tokens_pos, chunk_points, rows=rows,
-                                            what="the adjoint of the field's Jacobian", jets=False)
-            if self.projection.non_linearity not in self.JAC_VJP_ACTS:
-                raise NotImplementedError(f"MAGNODecoder.{fn}: the second derivative of the projection's activation "
-                                          f"{self.projection.non_linearity!r} is not written (covered: {self.JAC_VJP_ACTS})")
-            f = rndata_flat.to(torch.float32).contiguous()
-            grad = torch.zeros_like(f)
-            for sl, q, lists in self._stream_chunks(grid, query_pos, chunk, "rows" if rows else "knn", lead=False):
-                grad.add_(self._jac_vjp_chunk(f, q.contiguous(), None if cot_pred is None else cot_pred[sl], cot_jac[sl],
-                                              latent_tokens_pos, lists))
-        return grad
+        return self._adjoint("sample_jacobian_vjp", 1, rndata_flat, query_pos,
+                             [("cot_pred", cot_pred, (), True), ("cot_jac", cot_jac, (3,), False)], latent_tokens_pos, chunk_points)
 
     def _project_lap_vjp(self, planes, gy, gj, gl):
         """The cotangent of the projection's input LAPLACIAN jet: for the mixed GNO planes ``planes`` = [x, x'_0, x'_1, x'_2, x''_0,
@@ -1122,94 +962,217 @@ class MAGNODecoder(nn.Module):
         Exact fp32: three GEMMs per row block on the planes STACKED (one launch per product, precision 0) and the elementwise middle
         as ONE kernel (``ops.mlp2_lap_cot_mid``, erf-GELU: the only projection ``_jet2_stream`` admits), written over the cotangent
         stack.  Rows in blocks sized as in ``_project_jac_vjp``."""
-        from ... import ops
-        fc1, fc2 = self.projection.fcs
-        w1, w2 = GF._w2d(fc1.weight).contiguous(), GF._w2d(fc2.weight).contiguous()
-        b1 = fc1.bias.detach().to(torch.float32).contiguous()
-        n, c = planes[0].shape
-        hid, oc = w1.shape[0], w2.shape[0]
-        outs = [torch.empty_like(planes[0]) for _ in range(5)]
-        step = n if hid <= c else max(1024, n * c // hid)
-        for j in range(0, n, step):
-            m = planes[0][j:j + step].shape[0]
-            xs = torch.add(planes[4][j:j + step] + planes[5][j:j + step], planes[6][j:j + step])   # (x''_0 + x''_1) + x''_2
-            x5 = torch.cat([p[j:j + step] for p in planes[:4]] + [xs])
-            del xs
-            g = ([] if gy is None else [gy[j:j + step]]) + [gj[j:j + step, :, d] for d in range(3)] + [gl[j:j + step]]
-            ng = len(g)
-            g = torch.cat(g)
-            zus = ops.gemm(x5, w1, 5 * m, hid, c, c, c, False, True, precision=0)            # [z - b_1; u_0; u_1; u_2; s]
-            a = ops.gemm(g, w2, ng * m, hid, oc, oc, hid, False, False, precision=0)         # [A;] A_0; A_1; A_2; A_L
-            del x5, g
-            zus, a = zus.view(5, m, hid), a.view(ng, m, hid)
-            if gy is None:                           # no A plane: the result goes over the z stack
-                mid = ops.mlp2_lap_cot_mid(zus, None, a[:3], a[3], b1, out=zus)
-            else:                                    # [A; A_d; A_L] becomes [dz; du_d; ds] in place
-                mid = ops.mlp2_lap_cot_mid(zus, a[0], a[1:4], a[4], b1, out=a)
-            dx5 = ops.gemm(mid.view(5 * m, hid), w1, 5 * m, c, hid, hid, c, False, False, precision=0)
-            del zus, a, mid
-            for p in range(5):
-                outs[p][j:j + step] = dx5[p * m:(p + 1) * m]
-        return outs
+        return self._project_cot(2, planes, gy, gj, gl)
 
     LAP_VJP_DIRS = HESSIAN_DIRS[:3]       # the three axes: D_v^2 along them sums to the Laplacian
 
-    def _lap_vjp_chunk(self, rndata_flat, q, gy, gj, gl, lat, lists):
-        """one chunk of ``sample_laplacian_vjp``: -> its [M, C] part of the latent's gradient.  A call of its own, so that a chunk's
-        planes and lists are freed before the next chunk's are allocated."""
-        from ... import graph as device_graph
-        m = lat.shape[0]
-        dirs = self.LAP_VJP_DIRS
-        planes = self._jet_planes(rndata_flat, q, lat, lists, dirs)     # [x, x'_d, x''_d] mixed, recomputed at fp32
-        d = self._project_lap_vjp(planes, gy, gj, gl)                   # [dx, dx'_0, dx'_1, dx'_2, dx'']
-        del planes
-        if isinstance(lists, tuple):                       # 'knn': equal operands, the weights' jets drop out (``sample_laplacian``)
-            d = self._mix_equal_scales(d, q)
-            return self.gno.adjoint_jet2_knn(lat, q, *lists, dirs, d[0], torch.stack(d[1:4]), d[4].unsqueeze(0),
-                                             graph=device_graph.by_source(lists, m))
-        ns = len(lists)
-        if ns == 1 or not self.use_scale_weights:          # one scale, or summed scales: every scale gets the planes as they are
-            per = [(d[0], torch.stack(d[1:4]), d[4].unsqueeze(0))] * ns
-        else:
-            # x = sum_s w_s o_s,  x'_d = sum_s (w_s o'_s,d + w'_s,d o_s),  x''_d = sum_s (w_s o''_s,d + 2 w'_s,d o'_s,d + w''_s,d o_s) with
-            # w = softmax(l(q)), a function of the query alone; with G = dx, G'_d = dx'_d and L = dx'' on every x''_d:
-            #   G_s = w_s G + sum_d w'_s,d G'_d + (sum_d w''_s,d) L,   G'_s,d = w_s G'_d + 2 w'_s,d L,   L_s = w_s L
-            sw = self.scale_weighting
-            logits, hdn = _scale_logits(self, q)
-            w = torch.softmax(logits, dim=1)
-            dls = _logit_tangents((hdn > 0).to(hdn.dtype), sw[0].weight, sw[2].weight, lambda x, wt: GF.linear(x, wt, None, precision=0))
-            jets = [_softmax_weight_jets(w, dl, second=True) for dl in dls]
-            dws = [j[0] for j in jets]
-            lw = torch.add(jets[0][1] + jets[1][1], jets[2][1])          # the Laplacian of the weights
-            per = []
-            for s in range(ns):
-                ws = w[:, s:s + 1]
-                g = ws * d[0]
-                for di, dw in enumerate(dws):
-                    g += dw[:, s:s + 1] * d[1 + di]
-                g += lw[:, s:s + 1] * d[4]
-                p1 = torch.stack([ws * d[1 + di] + (2.0 * dws[di][:, s:s + 1]) * d[4] for di in range(3)])
-                per.append((g, p1, (ws * d[4]).unsqueeze(0)))
-        del d
-        part = None
-        for rows, (g, p1, p2) in zip(lists, per):
-            p = self.gno.adjoint_jet2_rows(lat, q, dirs, g, p1, p2, device_graph.by_source(rows, m))
-            part = p if part is None else part.add_(p)
-        return part
+    # ---- ONE host path for the three adjoints, by ``order``: 0 the value (``sample_vjp``), 1 and d/dx (``sample_jacobian_vjp``), 2 and
+    # the Laplacian (``sample_laplacian_vjp``).  A step is shared where the orders run the same operations; where sharing it would
+    # change an operation's rounding or its launch the order keeps its branch (bit-equality outranks uniformity).
+    ADJOINT_WHAT = ("the adjoint of the sampled field", "the adjoint of the field's Jacobian", "the adjoint of the field's Laplacian")
 
-    def _lap_vjp_stream(self, fn, rndata_flat, query_pos, lat, chunk_points):
-        """the refusals of ``sample_laplacian_vjp``, before anything runs: ``sample_laplacian``'s / ``sample_laplacian_rows``'s
-        (``_jet2_stream``), a point-sharded model and a transform that is not 'linear' -> (grid, chunk, rows)"""
+    def _project_cot(self, order, planes, gy, gj=None, gl=None):
+        """The skeleton of ``_project_vjp`` / ``_project_jac_vjp`` / ``_project_lap_vjp`` (their docstrings hold the formulas): rows in
+        blocks sized so that the [rows, projection_channels] tensors stay no larger than the planes; per block the planes STACKED,
+        [z; u ...] = X W_1^T, [A ...] = G W_2, the elementwise middle, dX = mid W_1 (one GEMM launch per product, precision 0) and the
+        stack taken apart -> the cotangent planes.  Per order: the stack -- [x], [x, x'_d], [x, x'_d, sum_d x''_d] -- and the middle --
+        ``ops.act_bwd`` on z with b_1 from the GEMM's epilogue; the torch expressions of ``_act_jets`` after z += b_1; the one kernel
+        ``ops.mlp2_lap_cot_mid``, which adds b_1 itself.  The one plane of order 0 is read and written in place (no stack)."""
+        from ... import ops
+        fc1, fc2 = self.projection.fcs
+        w1, w2 = GF._w2d(fc1.weight).contiguous(), GF._w2d(fc2.weight).contiguous()
+        act = self.projection.non_linearity
+        n, c = planes[0].shape
+        hid, oc = w1.shape[0], w2.shape[0]
+        npl = (1, 4, 5)[order]
+        outs = [torch.empty_like(planes[0]) for _ in range(npl)]
+        step = n if hid <= c else max(1024, n * c // hid)
+        b1 = fc1.bias.detach().to(torch.float32).contiguous() if order == 2 else None
+        for j in range(0, n, step):
+            sl = slice(j, j + step)
+            m = planes[0][sl].shape[0]
+            if order == 0:
+                x, g, ng = planes[0][sl], gy[sl], 1
+            else:
+                xs = [p[sl] for p in planes[:4]]
+                if order == 2:
+                    xs.append(torch.add(planes[4][sl] + planes[5][sl], planes[6][sl]))         # (x''_0 + x''_1) + x''_2
+                g = [gj[sl, :, d] for d in range(3)] + ([gl[sl]] if order == 2 else [])
+                if gy is not None or order == 1:         # order 1 always stacks a value plane; order 2 runs without the A plane
+                    g.insert(0, gy[sl] if gy is not None else gj.new_zeros(m, oc))
+                x, g, ng = torch.cat(xs), torch.cat(g), len(g)
+                del xs
+            zu = ops.gemm(x, w1, npl * m, hid, c, c, c, False, True, fc1.bias if order == 0 else None, precision=0)
+            a = ops.gemm(g, w2, ng * m, hid, oc, oc, hid, False, False, precision=0)
+            del x, g
+            if order == 0:
+                mid = ops.act_bwd(zu, a, ops.ACT[act]) if ops.ACT[act] else a
+            elif order == 1:                             # a = [A; A_0; A_1; A_2] becomes [dz; du_0; du_1; du_2] in place
+                z = zu[:m]
+                if fc1.bias is not None:
+                    z += fc1.bias
+                d1, d2 = self._act_jets(z, act)
+                if d2 is not None:
+                    s = zu[m:2 * m] * a[m:2 * m]
+                    for d in (1, 2):
+                        s += zu[(1 + d) * m:(2 + d) * m] * a[(1 + d) * m:(2 + d) * m]
+                    s *= d2
+                del z
+                zu = None
+                if d1 is not None:
+                    a.view(4, m, hid).mul_(d1)
+                if d2 is not None:
+                    a[:m] += s
+                    del s
+                mid = a
+            else:
+                zu, a = zu.view(5, m, hid), a.view(ng, m, hid)
+                if gy is None:                           # no A plane: the result goes over the z stack
+                    mid = ops.mlp2_lap_cot_mid(zu, None, a[:3], a[3], b1, out=zu)
+                else:                                    # [A; A_d; A_L] becomes [dz; du_d; ds] in place
+                    mid = ops.mlp2_lap_cot_mid(zu, a[0], a[1:4], a[4], b1, out=a)
+                mid = mid.view(5 * m, hid)
+            dx = ops.gemm(mid, w1, npl * m, c, hid, hid, c, False, False, out=outs[0][sl] if order == 0 else None, ldc=c, precision=0)
+            del zu, a, mid
+            for p in range(npl if order else 0):
+                outs[p][sl] = dx[p * m:(p + 1) * m]
+        return outs
+
+    def _check_cotangents(self, fn, query_pos, cots) -> None:
+        """``cots``: (name, tensor, the shape's tail after [Nq, out_channels], may be None) per cotangent; ValueError unless each is
+        float32, of that shape and on the queries' device"""
+        nq = int(query_pos.shape[0])
+        for name, cot, tail, optional in cots:
+            if cot is None and optional:
+                continue
+            shape = (nq, self.out_channels, *tail)
+            if not isinstance(cot, torch.Tensor) or cot.dtype != torch.float32 or cot.device != query_pos.device \
+                    or tuple(cot.shape) != shape:
+                got = f"{cot.dtype} {tuple(cot.shape)} on {cot.device}" if isinstance(cot, torch.Tensor) else type(cot).__name__
+                raise ValueError(f"MAGNODecoder.{fn}: {name} must be float32 {list(shape)} on the queries' device "
+                                 f"({query_pos.device}){' or None' if optional else ''}, got {got}")
+
+    @torch.no_grad()
+    def _adjoint_stream(self, fn, order, rndata_flat, query_pos, lat, chunk_points):
+        """The refusals of the adjoint of ``order``, before anything runs -> (grid, chunk, rows: the route is the row lists'): the
+        argument rules, a point-sharded model, at order 2 a transform that is not 'linear' (the forward's jets cover the others, so it
+        is named before their conditions), the streaming conditions at fp32 arithmetic (``_jet2_stream``: with the jet kernels'
+        projection at order 2, else the 'linear' transform and two linear layers around a named activation), at order 1 an activation
+        whose second derivative is not written.  ``GAOT3D.sample_*_autograd`` refuse through it before their forward runs."""
+        from ... import ops
         self._sample_args(fn, chunk_points)
         if getattr(self, "_shard_group", None) is not None:
             raise NotImplementedError(f"MAGNODecoder.{fn}: a point-sharded model is not supported (every rank would hold a partial sum)")
-        rows = self.decoder_strategy != "knn"
-        what = "the adjoint of the field's Laplacian"
-        if self.gno.transform_type != "linear":          # the forward's jets cover the other transforms: named before its conditions
+        what = self.ADJOINT_WHAT[order]
+        if order == 2 and self.gno.transform_type != "linear":
             raise NotImplementedError(f"MAGNODecoder.{fn}: {what} needs the 'linear' transform (the adjoint kernel is the linear "
                                       f"transform's); transform type {self.gno.transform_type!r} is not")
-        grid, chunk = self._jet2_stream(fn, rndata_flat, query_pos, lat, chunk_points, rows=rows, what=what)
+        rows = self.decoder_strategy != "knn"
+        with ops.fp32_arithmetic():
+            grid, chunk = self._jet2_stream(fn, rndata_flat.detach(), query_pos.detach(), lat, chunk_points, rows=rows, what=what,
+                                            jets=order == 2)
+        if order == 1 and self.projection.non_linearity not in self.JAC_VJP_ACTS:
+            raise NotImplementedError(f"MAGNODecoder.{fn}: the second derivative of the projection's activation "
+                                      f"{self.projection.non_linearity!r} is not written (covered: {self.JAC_VJP_ACTS})")
         return grid, chunk, rows
+
+    def _adjoint(self, fn, order, rndata_flat, query_pos, cots, lat, chunk_points):
+        """The driver of ``sample_vjp`` / ``sample_jacobian_vjp`` / ``sample_laplacian_vjp`` (``cots`` as ``_check_cotangents`` takes
+        them, in the order value, Jacobian, Laplacian): the checks, the refusals, then at fp32 arithmetic the chunk loop of ``sample``
+        with every chunk's [M, C] part (``_adjoint_chunk``) added into the zeroed gradient in chunk order."""
+        from ... import ops
+        self._sample_args(fn, chunk_points)
+        self._check_cotangents(fn, query_pos, cots)
+        grid, chunk, rows = self._adjoint_stream(fn, order, rndata_flat, query_pos, lat, chunk_points)
+        rndata_flat, query_pos = rndata_flat.detach(), query_pos.detach()
+        cots = [None if cot is None else cot.detach() for _, cot, _, _ in cots]
+        if order == 0:
+            cots[0] = cots[0].contiguous()                # its GEMM reads the block's rows where they are
+        if order == 2 and cots[1] is None:                # the stack of ``_project_lap_vjp`` always holds the three A_d planes
+            cots[1] = torch.zeros(*cots[2].shape, 3, dtype=torch.float32, device=query_pos.device)
+        with ops.fp32_arithmetic():
+            f = rndata_flat.to(torch.float32).contiguous()
+            grad = torch.zeros_like(f)
+            for sl, q, lists in self._stream_chunks(grid, query_pos, chunk, "rows" if rows else "knn", lead=False):
+                grad.add_(self._adjoint_chunk(order, f, q.contiguous(), [None if cot is None else cot[sl] for cot in cots], lat, lists))
+        return grad
+
+    def _adjoint_chunk(self, order, rndata_flat, q, cots, lat, lists):
+        """One chunk of ``_adjoint`` -> its [M, C] part of the latent's gradient: the mixed planes recomputed -- at order 0 on the value
+        route (``forward_knn`` / the fused forward on the rows; on row lists with softmax weights through ``ops.scale_mix_fwd``, which
+        hands its weights to the mix's cotangent kernel), else ``_jet_planes`` --, the projection's cotangent (``_project_cot``), the
+        scale mix's (``_mix_cot``), then per scale ``graph.by_source`` and the transform's adjoint, the parts added in scale order.
+        A call of its own, so that a chunk's planes and lists are freed before the next chunk's are allocated."""
+        from ... import graph as device_graph
+        from ... import ops
+        m, knn = lat.shape[0], isinstance(lists, tuple)
+        dirs = self.LAP_VJP_DIRS if order == 2 else None
+        outs = w = None
+        if order:
+            planes = self._jet_planes(rndata_flat, q, lat, lists, dirs)
+        elif knn:
+            planes = self._mix_equal_scales([self.gno.forward_knn(lat, q, *lists, rndata_flat)], q)
+        else:
+            outs = [self.gno(y_pos=lat, x_pos=q, edge_index=None, f_y=rndata_flat, graph=rows) for rows in lists]
+            if len(outs) > 1 and self.use_scale_weights:
+                outs = [o.contiguous() for o in outs]
+                x, w = ops.scale_mix_fwd(outs, _scale_logits(self, q)[0].contiguous())
+            else:
+                x, outs = _mix_scales(self, outs, q), None
+            planes = [x]
+            del x
+        d = self._project_cot(order, planes, *cots)
+        del planes
+        per = self._mix_cot(d, q, knn, outs, w)
+        del d, outs, w
+        part = None
+        for rows, cot in zip([lists] if knn else lists, per):
+            p = self.gno._adjoint(lat, q, cot, device_graph.by_source(rows, m), lists if knn else None, dirs)
+            part = p if part is None else part.add_(p)
+        return part
+
+    def _mix_cot(self, d, q, knn, outs=None, w=None):
+        """The scale mix's cotangent.  ``d`` = [G], [G, G'_0, G'_1, G'_2] or [G, G'_d ..., L]: the cotangents of the mixed value, of its
+        derivative along the three axes and of EVERY second-order plane -> per scale (ONE entry on the 'knn' route) the planes as the
+        transform's adjoint takes them, [G_s], [G_s, G'_s [3, n, C]] or [G_s, G'_s, L_s [1, n, C]].
+        'knn': every scale sees the same list, the mix is of equal operands and the jets of its weights drop out
+        (``_mix_equal_scales`` on every plane: (sum_s w_s) G, formed as the forward forms sum_s w_s x).  One scale, or summed
+        scales: every scale gets the planes as they are.  Softmax weights on row lists: with x = sum_s w_s o_s,
+        x'_d = sum_s (w_s o'_s,d + w'_s,d o_s), x''_d = sum_s (w_s o''_s,d + 2 w'_s,d o'_s,d + w''_s,d o_s) and w = softmax(l(q)) a
+        function of the query alone,
+            G_s = w_s G + sum_d w'_s,d G'_d + (sum_d w''_s,d) L,   G'_s,d = w_s G'_d + 2 w'_s,d L,   L_s = w_s L
+        without the terms in L at order 1; at order 0, G_s = w_s G alone, it is the mix kernel's own backward on its operands
+        ``outs`` and weights ``w`` (``ops.scale_mix_bwd``)."""
+        from ... import ops
+        pack = lambda g, *t: [g] + ([torch.stack(t[:3])] if t else []) + [p.unsqueeze(0) for p in t[3:]]
+        ns = len(self.scales)
+        if knn:
+            return [pack(*self._mix_equal_scales(d, q))]
+        if ns == 1 or not self.use_scale_weights:
+            return [pack(*d)] * ns
+        if len(d) == 1:
+            return [[g] for g in ops.scale_mix_bwd(outs, w, d[0])[0]]
+        second = len(d) == 5
+        sw = self.scale_weighting
+        logits, hdn = _scale_logits(self, q)
+        w = torch.softmax(logits, dim=1)
+        dls = _logit_tangents((hdn > 0).to(hdn.dtype), sw[0].weight, sw[2].weight, lambda x, wt: GF.linear(x, wt, None, precision=0))
+        jets = [_softmax_weight_jets(w, dl, second=second) for dl in dls]
+        dws = [j[0] for j in jets]
+        if second:
+            lw = torch.add(jets[0][1] + jets[1][1], jets[2][1])          # the Laplacian of the weights
+        per = []
+        for s in range(ns):
+            ws = w[:, s:s + 1]
+            g = ws * d[0]
+            for di, dw in enumerate(dws):
+                g += dw[:, s:s + 1] * d[1 + di]
+            if not second:
+                per.append(pack(g, *(ws * d[1 + di] for di in range(3))))
+                continue
+            g += lw[:, s:s + 1] * d[4]
+            per.append(pack(g, *(ws * d[1 + di] + (2.0 * dws[di][:, s:s + 1]) * d[4] for di in range(3)), ws * d[4]))
+        return per
 
     @torch.no_grad()
     def sample_laplacian_vjp(self, rndata_flat, query_pos, cot_pred, cot_jac, cot_lap, latent_tokens_pos,
@@ -1238,30 +1201,9 @@ class MAGNODecoder(nn.Module):
         ``sample_laplacian``'s ('knn') / ``sample_laplacian_rows``'s ('radius', 'bidirectional'); in addition a transform that is not
         'linear' and a point-sharded model raise NotImplementedError naming it, cotangents of the wrong dtype, shape or device raise
         ValueError, and on row lists (sized by a host read) the call raises GaotError inside a stream capture before any launch."""
-        from ... import ops
-        fn = "sample_laplacian_vjp"
-        self._sample_args(fn, chunk_points)
-        nq, oc = int(query_pos.shape[0]), self.out_channels
-        for name, cot, shape, optional in (("cot_pred", cot_pred, (nq, oc), True), ("cot_jac", cot_jac, (nq, oc, 3), True),
-                                           ("cot_lap", cot_lap, (nq, oc), False)):
-            if cot is None and optional:
-                continue
-            if not isinstance(cot, torch.Tensor) or cot.dtype != torch.float32 or cot.device != query_pos.device \
-                    or tuple(cot.shape) != shape:
-                got = f"{cot.dtype} {tuple(cot.shape)} on {cot.device}" if isinstance(cot, torch.Tensor) else type(cot).__name__
-                raise ValueError(f"MAGNODecoder.{fn}: {name} must be float32 {list(shape)} on the queries' device "
-                                 f"({query_pos.device}){' or None' if optional else ''}, got {got}")
-        rndata_flat, query_pos, cot_lap = rndata_flat.detach(), query_pos.detach(), cot_lap.detach()
-        cot_pred = None if cot_pred is None else cot_pred.detach()
-        cot_jac = torch.zeros(nq, oc, 3, dtype=torch.float32, device=query_pos.device) if cot_jac is None else cot_jac.detach()
-        with ops.fp32_arithmetic():
-            grid, chunk, rows = self._lap_vjp_stream(fn, rndata_flat, query_pos, latent_tokens_pos, chunk_points)
-            f = rndata_flat.to(torch.float32).contiguous()
-            grad = torch.zeros_like(f)
-            for sl, q, lists in self._stream_chunks(grid, query_pos, chunk, "rows" if rows else "knn", lead=False):
-                grad.add_(self._lap_vjp_chunk(f, q.contiguous(), None if cot_pred is None else cot_pred[sl], cot_jac[sl], cot_lap[sl],
-                                              latent_tokens_pos, lists))
-        return grad
+        return self._adjoint("sample_laplacian_vjp", 2, rndata_flat, query_pos,
+                             [("cot_pred", cot_pred, (), True), ("cot_jac", cot_jac, (3,), True), ("cot_lap", cot_lap, (), False)],
+                             latent_tokens_pos, chunk_points)
 
     @torch.no_grad()
     def _laplacian_jets(self, fn, rndata_flat, query_pos, lat, chunk_points):

@@ -355,20 +355,12 @@ def gno_adjoint(weights, biases, y_pos: Tensor, x_pos: Tensor, grad_out: Tensor,
     zeros.  Two launches (main + fix-up; the fix-up alone without edges).  Rows are long -- every query that selected a source -- so
     most straddle the 32-edge tiles and one fix-up thread adds a row's tile partials in order: slow when the queries cluster on a
     few sources, but correct."""
-    lib = _lib.load()
     m, keep, y_pos, x_pos, grad_out, rowptr_dst, kk, e = _gno_adjoint_args("gno_adjoint", weights, biases, y_pos, x_pos, grad_out, g, k)
-    dev = x_pos.device
-    grad_f = torch.empty(g.num_src, m.channels, dtype=torch.float32, device=dev)
-    ws = _ws(lib.gaot_gno_adj_workspace_bytes(e, m.channels), dev)
-    with _timed(f"gno_adj_nh{m.n_hidden}"):
-        check(lib.gaot_gno_adj(C.byref(m), _ptr(y_pos), _ptr(x_pos), _ptr(grad_out), _ptr(rowptr_dst), kk, _ptr(g.by_src.key),
-                               _ptr(g.by_src.other), _ptr(g.by_src.rowptr), e, g.num_src, g.num_dst, _ptr(grad_f), _ptr(ws), ws.numel(),
-                               _stream()), "gaot_gno_adj")
-    return grad_f
+    return _gno_adjoint_launch("gaot_gno_adj", m, y_pos, x_pos, (_ptr(grad_out),), rowptr_dst, kk, g, e, m.channels)
 
 
 def _gno_adjoint_args(fn, weights, biases, y_pos, x_pos, grad_out, g, k):
-    """the operand rules of ``gno_adjoint`` and ``gno_adjoint_jac`` -> (the MLP struct, what keeps its arrays alive, y_pos, x_pos,
+    """the operand rules of the three ``gno_adjoint*`` entry points -> (the MLP struct, what keeps its arrays alive, y_pos, x_pos,
     grad_out, rowptr_dst or None, the k passed to the ABI, the number of edges)"""
     m, keep = _mlp_struct(weights, biases)
     y_pos = _req(y_pos, torch.float32, "y_pos")
@@ -394,6 +386,30 @@ def _gno_adjoint_args(fn, weights, biases, y_pos, x_pos, grad_out, g, k):
     return m, keep, y_pos, x_pos, grad_out, rowptr_dst, kk, e
 
 
+def _gno_adjoint_planes(fn, name, t, lead, grad_out) -> None:
+    """a stack of cotangent planes beside ``grad_out`` [n_query, 32]: contiguous float32 [one of ``lead``, n_query, 32] on its device"""
+    if not isinstance(t, Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 3 \
+            or t.shape[0] not in lead or t.shape[1:] != grad_out.shape or t.device != grad_out.device:
+        got = f"{t.dtype} {tuple(t.shape)} on {t.device}, strides {tuple(t.stride())}" if isinstance(t, Tensor) else type(t).__name__
+        raise GaotError(f"{fn}: {name} must be contiguous float32 [{' or '.join(str(n) for n in lead)}, {grad_out.shape[0]}, "
+                        f"{grad_out.shape[1]}] on {grad_out.device}, got {got}")
+
+
+def _gno_adjoint_launch(entry, m, y_pos, x_pos, cots, rowptr_dst, kk, g, e, *ws_args) -> Tensor:
+    """the launch of the three ``gno_adjoint*`` entry points: grad_f [n_src, 32] allocated, ``entry``'s workspace (sized by the edges
+    and ``ws_args``) and the call under its timing label -- ``entry`` without 'gaot_', then the number of hidden layers.  ``cots``: the
+    ABI's arguments between x_pos and rowptr_dst (the cotangent planes and, for the jets, their directions)."""
+    lib = _lib.load()
+    dev = x_pos.device
+    grad_f = torch.empty(g.num_src, m.channels, dtype=torch.float32, device=dev)
+    ws = _ws(getattr(lib, f"{entry}_workspace_bytes")(e, *ws_args), dev)
+    with _timed(f"{entry[len('gaot_'):]}_nh{m.n_hidden}"):
+        check(getattr(lib, entry)(C.byref(m), _ptr(y_pos), _ptr(x_pos), *cots, _ptr(rowptr_dst), kk, _ptr(g.by_src.key),
+                                  _ptr(g.by_src.other), _ptr(g.by_src.rowptr), e, g.num_src, g.num_dst, _ptr(grad_f), _ptr(ws),
+                                  ws.numel(), _stream()), entry)
+    return grad_f
+
+
 def gno_adjoint_jac(weights, biases, y_pos: Tensor, x_pos: Tensor, grad_out: Tensor, grad_jac: Tensor, g: BipartiteGraph,
                     k: Optional[int] = None) -> Tensor:
     """The ADJOINT of ``gno_forward_knn_jac`` / ``gno_forward_jac`` ('linear') with respect to f_y (gaot_gno_adj_jac): for cotangents
@@ -405,21 +421,10 @@ def gno_adjoint_jac(weights, biases, y_pos: Tensor, x_pos: Tensor, grad_out: Ten
     backward, no weight gradients, no f_y.  Operand rules are ``gno_adjoint``'s, with ``grad_jac`` float32, contiguous, on the
     device; exact fp32 whatever the precision mode (the same bits in both), no atomics, bit-reproducible run to run; a source
     without edges gets exact zeros.  Two launches (main + fix-up; the fix-up alone without edges)."""
-    lib = _lib.load()
-    m, keep, y_pos, x_pos, grad_out, rowptr_dst, kk, e = _gno_adjoint_args("gno_adjoint_jac", weights, biases, y_pos, x_pos, grad_out, g, k)
-    if not isinstance(grad_jac, Tensor) or not grad_jac.is_cuda or grad_jac.dtype != torch.float32 or not grad_jac.is_contiguous() \
-            or tuple(grad_jac.shape) != (3, g.num_dst, m.channels) or grad_jac.device != grad_out.device:
-        got = f"{grad_jac.dtype} {tuple(grad_jac.shape)} on {grad_jac.device}, strides {tuple(grad_jac.stride())}" \
-            if isinstance(grad_jac, Tensor) else type(grad_jac).__name__
-        raise GaotError(f"gno_adjoint_jac: grad_jac must be contiguous float32 [3, {g.num_dst}, {m.channels}] on {grad_out.device}, got {got}")
-    dev = x_pos.device
-    grad_f = torch.empty(g.num_src, m.channels, dtype=torch.float32, device=dev)
-    ws = _ws(lib.gaot_gno_adj_jac_workspace_bytes(e), dev)
-    with _timed(f"gno_adj_jac_nh{m.n_hidden}"):
-        check(lib.gaot_gno_adj_jac(C.byref(m), _ptr(y_pos), _ptr(x_pos), _ptr(grad_out), _ptr(grad_jac), _ptr(rowptr_dst), kk,
-                                   _ptr(g.by_src.key), _ptr(g.by_src.other), _ptr(g.by_src.rowptr), e, g.num_src, g.num_dst,
-                                   _ptr(grad_f), _ptr(ws), ws.numel(), _stream()), "gaot_gno_adj_jac")
-    return grad_f
+    fn = "gno_adjoint_jac"
+    m, keep, y_pos, x_pos, grad_out, rowptr_dst, kk, e = _gno_adjoint_args(fn, weights, biases, y_pos, x_pos, grad_out, g, k)
+    _gno_adjoint_planes(fn, "grad_jac", grad_jac, (3,), grad_out)
+    return _gno_adjoint_launch("gaot_gno_adj_jac", m, y_pos, x_pos, (_ptr(grad_out), _ptr(grad_jac)), rowptr_dst, kk, g, e)
 
 
 def gno_adjoint_jet2(weights, biases, y_pos: Tensor, x_pos: Tensor, dirs, grad_out: Tensor, grad_d1: Tensor, grad_d2: Tensor,
@@ -435,27 +440,16 @@ def gno_adjoint_jet2(weights, biases, y_pos: Tensor, x_pos: Tensor, dirs, grad_o
     gradients, no f_y.  Operand rules are ``gno_adjoint``'s, with the cotangent planes float32, contiguous, on the device; exact
     fp32 whatever the precision mode (the same bits in both), no atomics, bit-reproducible run to run; a source without edges gets
     exact zeros.  Two launches (main + fix-up; the fix-up alone without edges)."""
-    lib = _lib.load()
     fn = "gno_adjoint_jet2"
     m, keep, y_pos, x_pos, grad_out, rowptr_dst, kk, e = _gno_adjoint_args(fn, weights, biases, y_pos, x_pos, grad_out, g, k)
     hd, nd = _host_dirs(fn, dirs)
     if not 1 <= nd <= 6:
         raise GaotError(f"{fn}: 1..6 directions, got {nd}")
-    for name, t, lead in (("grad_d1", grad_d1, (nd,)), ("grad_d2", grad_d2, (nd, 1))):
-        if not isinstance(t, Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 3 \
-                or t.shape[0] not in lead or tuple(t.shape[1:]) != (g.num_dst, m.channels) or t.device != grad_out.device:
-            got = f"{t.dtype} {tuple(t.shape)} on {t.device}, strides {tuple(t.stride())}" if isinstance(t, Tensor) else type(t).__name__
-            raise GaotError(f"{fn}: {name} must be contiguous float32 [{' or '.join(str(n) for n in lead)}, {g.num_dst}, {m.channels}] "
-                            f"on {grad_out.device}, got {got}")
+    _gno_adjoint_planes(fn, "grad_d1", grad_d1, (nd,), grad_out)
+    _gno_adjoint_planes(fn, "grad_d2", grad_d2, (nd, 1), grad_out)
     stride2 = 0 if grad_d2.shape[0] == 1 and nd > 1 else g.num_dst * m.channels    # one direction: both forms name the same plane
-    dev = x_pos.device
-    grad_f = torch.empty(g.num_src, m.channels, dtype=torch.float32, device=dev)
-    ws = _ws(lib.gaot_gno_adj_jet2_workspace_bytes(e), dev)
-    with _timed(f"gno_adj_jet2_nh{m.n_hidden}"):
-        check(lib.gaot_gno_adj_jet2(C.byref(m), _ptr(y_pos), _ptr(x_pos), hd, nd, _ptr(grad_out), _ptr(grad_d1), _ptr(grad_d2), stride2,
-                                    _ptr(rowptr_dst), kk, _ptr(g.by_src.key), _ptr(g.by_src.other), _ptr(g.by_src.rowptr), e, g.num_src,
-                                    g.num_dst, _ptr(grad_f), _ptr(ws), ws.numel(), _stream()), "gaot_gno_adj_jet2")
-    return grad_f
+    return _gno_adjoint_launch("gaot_gno_adj_jet2", m, y_pos, x_pos, (hd, nd, _ptr(grad_out), _ptr(grad_d1), _ptr(grad_d2), stride2),
+                               rowptr_dst, kk, g, e)
 
 
 def gno_forward_knn_jac(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], src_table: Optional[Tensor],
