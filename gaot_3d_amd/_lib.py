@@ -66,6 +66,8 @@ SIGNATURES = {
     "gaot_gno_adj_jac": (_i, [C.POINTER(MlpT), _p, _p, _p, _p, _p, _i, _p, _p, _p, _i64, _i64, _i64, _p, _p, _sz, _p]),
     "gaot_gno_adj_jet2_workspace_bytes": (_sz, [_i64]),
     "gaot_gno_adj_jet2": (_i, [C.POINTER(MlpT), _p, _p, _p, _i, _p, _p, _p, _i64, _p, _i, _p, _p, _p, _i64, _i64, _i64, _p, _p, _sz, _p]),
+    "gaot_gno_adj_jet2_qd_workspace_bytes": (_sz, [_i64]),
+    "gaot_gno_adj_jet2_qd": (_i, [C.POINTER(MlpT), _p, _p, _p, _i, _p, _p, _p, _i64, _p, _i, _p, _p, _p, _i64, _i64, _i64, _p, _p, _sz, _p]),
     "gaot_gno_fwd_jet2_workspace_bytes": (_sz, [_i64, _i]),
     "gaot_gno_fwd_jet2": (_i, [C.POINTER(MlpT), _i, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _i, _p, _p, _p, _p, _sz, _p]),
     "gaot_gno_fwd_knn_jet2_qd": (_i, [C.POINTER(MlpT), _i, _p, _p, _p, _p, _p, _i, _i64, _p, _i, _p, _p, _p, _p]),
@@ -124,6 +126,7 @@ SIGNATURES = {
     "gaot_mlp2_jet2_supported": (_i, [_i, _i, _i, _i, _i]),
     "gaot_mlp2_jet2": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _i64, _p, _p, _i64, _i64, _i64, _p]),
     "gaot_mlp2_lap_cot_mid": (_i, [_p, _p, _i64, _p, _p, _p, _p, _i64, _p, _i64, _i, _p, _i64, _p]),
+    "gaot_mlp2_jet2_cot_mid": (_i, [_p, _i64, _p, _p, _p, _i64, _i, _i64, _i, _p, _i64, _p]),
     "gaot_rowlin_supported": (_i, [_p, _i, _i]),
     "gaot_rowlin_plan": (_i, [_i64, _i, _p, _p, _p]),
     "gaot_rowlin_fwd": (_i, [_p, _p, _i, _p, _p, _i64, _i, _i, _p, _p]),

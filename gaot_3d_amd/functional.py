@@ -1518,15 +1518,16 @@ def _sample_latent_setup(ctx, latent: Tensor, decoder, query_pos: Tensor, tokens
     return latent.detach()
 
 
-def _sample_latent_backward(ctx, vjp, grads, required: int, tail=()):
+def _sample_latent_backward(ctx, vjp, grads, required: Optional[int], tail=()):
     """what their backwards share: ``grads`` (one per output, None: the output received no gradient) as the cotangents of the decoder's
-    ``vjp`` -- float32, contiguous, None kept as None except the ``required``-th, which is zeros [Nq, out_channels, *tail] then -- ->
-    the gradients of forward's five arguments: the latent's, in its dtype, and four None.  No output used: five None, nothing runs."""
+    ``vjp`` -- float32, contiguous, None kept as None except the ``required``-th (None: no cotangent is required), which is zeros
+    [Nq, out_channels, *tail] then -- -> the gradients of forward's five arguments: the latent's, in its dtype, and four None.  No
+    output used: five None, nothing runs."""
     latent, query_pos, tokens_pos = ctx.saved_tensors
     if all(g is None for g in grads):
         return None, None, None, None, None
     cots = [None if g is None else g.to(torch.float32).contiguous() for g in grads]
-    if cots[required] is None:
+    if required is not None and cots[required] is None:
         cots[required] = torch.zeros(query_pos.shape[0], ctx.decoder.out_channels, *tail, dtype=torch.float32, device=query_pos.device)
     g = vjp(latent, query_pos, *cots, tokens_pos, chunk_points=ctx.chunk_points)
     return g.to(latent.dtype), None, None, None, None
@@ -1582,3 +1583,39 @@ class SampleLaplacianLatentFn(Function):
     @staticmethod
     def backward(ctx, dpred: Optional[Tensor], djac: Optional[Tensor], dlap: Optional[Tensor]):
         return _sample_latent_backward(ctx, ctx.decoder.sample_laplacian_vjp, (dpred, djac, dlap), 2)
+
+
+class SampleDirectionalLatentFn(Function):
+    """The sampled field and its first and second derivatives along PER-QUERY directions as a differentiable function of the LATENT:
+    forward = ``MAGNODecoder.sample_directional`` bit for bit -> (pred, d1, d2), backward = ``MAGNODecoder.sample_directional_vjp`` (the
+    streamed adjoint of the jet kernel with the directions read per lane).  An output that received no gradient contributes no
+    cotangent.  Nothing is saved but the latent, the query coordinates, the token tensor and the directions.  Gradients flow to
+    ``latent`` ONLY: the directions are constants of this node."""
+
+    @staticmethod
+    def forward(ctx, latent: Tensor, decoder, query_pos: Tensor, tokens_pos: Tensor, chunk_points: Optional[int], dirs: Tensor):
+        latent = _sample_latent_setup(ctx, latent, decoder, query_pos, tokens_pos, chunk_points)
+        ctx.dirs = dirs
+        return decoder.sample_directional(latent, query_pos, dirs, tokens_pos, chunk_points=chunk_points)
+
+    @staticmethod
+    def backward(ctx, dpred: Optional[Tensor], dd1: Optional[Tensor], dd2: Optional[Tensor]):
+        vjp = lambda latent, q, *rest, **kw: ctx.decoder.sample_directional_vjp(latent, q, ctx.dirs, *rest, **kw)
+        return (*_sample_latent_backward(ctx, vjp, (dpred, dd1, dd2), None), None)
+
+
+class SampleHessianLatentFn(Function):
+    """The sampled field, its spatial derivative AND its Hessian as a differentiable function of the LATENT: forward =
+    ``MAGNODecoder.sample_hessian_rows`` (on a 'knn' decoder: ``sample_hessian``) bit for bit -> (pred, jac, hess), backward =
+    ``MAGNODecoder.sample_hessian_vjp`` (the cotangents through the transpose of the polarisation, then the streamed adjoint of the jet
+    kernel along the six directions).  An output that received no gradient contributes no cotangent.  Nothing is saved but the latent,
+    the query coordinates and the token tensor.  Gradients flow to ``latent`` ONLY."""
+
+    @staticmethod
+    def forward(ctx, latent: Tensor, decoder, query_pos: Tensor, tokens_pos: Tensor, chunk_points: Optional[int]):
+        latent = _sample_latent_setup(ctx, latent, decoder, query_pos, tokens_pos, chunk_points)
+        return decoder.sample_hessian_rows(latent, query_pos, tokens_pos, chunk_points=chunk_points)
+
+    @staticmethod
+    def backward(ctx, dpred: Optional[Tensor], djac: Optional[Tensor], dhess: Optional[Tensor]):
+        return _sample_latent_backward(ctx, ctx.decoder.sample_hessian_vjp, (dpred, djac, dhess), None)

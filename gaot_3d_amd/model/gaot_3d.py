@@ -214,9 +214,10 @@ class GAOT3D(nn.Module):
         lat = self._one_sample("sample_directional", latent, tokens_pos)
         return self.decoder.sample_directional(latent, query_pos.to(latent.device), dirs, lat, chunk_points=chunk_points)
 
-    def _adjoint_args(self, fn, latent, query_pos, tokens_pos, autograd_order=None, chunk_points=None):
-        """what the six adjoint methods share -> (the tokens, the queries on the latent's device): ONE sample's latent and no
-        point-sharded model; for the autograd forms (``autograd_order``: the adjoint's order 0 / 1 / 2) also a ``query_pos`` that does
+    def _adjoint_args(self, fn, latent, query_pos, tokens_pos, autograd_order=None, chunk_points=None, what=None):
+        """what the ten adjoint methods share -> (the tokens, the queries on the latent's device): ONE sample's latent and no
+        point-sharded model; for the autograd forms (``autograd_order``: the adjoint's order 0 .. 3, ``what``: its name in the
+        refusals where the order's own does not fit) also a ``query_pos`` that does
         not require grad and the refusals of the decoder's adjoint (``MAGNODecoder._adjoint_stream``), before the forward runs"""
         lat = self._one_sample(fn, latent, tokens_pos)
         if autograd_order is not None and query_pos.requires_grad:
@@ -226,7 +227,7 @@ class GAOT3D(nn.Module):
             raise NotImplementedError(f"GAOT3D.{fn}: a point-sharded model is not supported")
         q = query_pos.to(latent.device)
         if autograd_order is not None:
-            self.decoder._adjoint_stream(fn, autograd_order, latent, q, lat, chunk_points)
+            self.decoder._adjoint_stream(fn, autograd_order, latent, q, lat, chunk_points, what)
         return lat, q
 
     def sample_vjp(self, latent: torch.Tensor, query_pos: torch.Tensor, cotangent: torch.Tensor,
@@ -310,6 +311,62 @@ class GAOT3D(nn.Module):
         formed).  Configurations ``sample_laplacian_vjp`` refuses are refused here, before the forward runs."""
         lat, q = self._adjoint_args("sample_laplacian_autograd", latent, query_pos, tokens_pos, 2, chunk_points)
         return GF.SampleLaplacianLatentFn.apply(latent, self.decoder, q, lat, chunk_points)
+
+    def sample_directional_vjp(self, latent: torch.Tensor, query_pos: torch.Tensor, dirs: torch.Tensor,
+                               cot_pred: Optional[torch.Tensor], cot_d1: Optional[torch.Tensor], cot_d2: Optional[torch.Tensor],
+                               tokens_pos: Optional[torch.Tensor] = None, chunk_points: Optional[int] = None) -> torch.Tensor:
+        """The ADJOINT of ``sample_directional``: -> grad_latent [D*H*W, lifting_channels] (fp32) for cotangents ``cot_pred``
+        [Nq, output_size] on the value and ``cot_d1`` / ``cot_d2`` [Nq, output_size, nd] on the first and second derivatives along
+        every query's own directions ``dirs`` (float32 [Nq, nd, 3] or [Nq, 3], 1 <= nd <= 6, as ``sample_directional`` takes them);
+        each cotangent may be None, but not all three -- the gradient of a loss on d^2 p / d n^2, of a boundary-layer residual in a
+        local frame (n, t1, t2), of the tangential Laplacian, with respect to the latent.  One value chain and two per direction
+        through the per-edge MLP (3 at nd = 1; the Laplacian's adjoint runs 7, the Hessian's 13).
+        ``MAGNODecoder.sample_directional_vjp``: exact fp32 in both precision modes, outside autograd, bit-reproducible for a given
+        ``chunk_points``.  The decoder's parameters, the query coordinates and the directions are constants.  Routes and refusals are
+        ``sample_laplacian_vjp``'s."""
+        lat, q = self._adjoint_args("sample_directional_vjp", latent, query_pos, tokens_pos)
+        return self.decoder.sample_directional_vjp(latent, q, dirs, cot_pred, cot_d1, cot_d2, lat, chunk_points=chunk_points)
+
+    def sample_directional_autograd(self, latent: torch.Tensor, query_pos: torch.Tensor, dirs: torch.Tensor,
+                                    tokens_pos: Optional[torch.Tensor] = None, chunk_points: Optional[int] = None):
+        """``sample_directional`` as a differentiable function of the latent: -> (pred [Nq, output_size], d1 [Nq, output_size, nd],
+        d2 [Nq, output_size, nd]) whose backward is ``sample_directional_vjp`` (``functional.SampleDirectionalLatentFn``), so that a
+        loss such as ``((d2[..., 0] - target) ** 2).mean()`` with the wall normals as directions reaches the encoder, the processor
+        and ``batch.pos`` through the ordinary autograd of ``latent``.  The forward is ``sample_directional``'s result bit for bit; an
+        output that received no gradient contributes no cotangent.  Gradients flow to ``latent`` ONLY: a ``query_pos`` or a ``dirs``
+        that requires grad raises ValueError.  Configurations ``sample_directional_vjp`` refuses are refused here, before the forward
+        runs."""
+        fn = "sample_directional_autograd"
+        if isinstance(dirs, torch.Tensor) and dirs.requires_grad:
+            raise ValueError(f"GAOT3D.{fn}: dirs requires grad, but gradients flow to the latent only (the directions are constants "
+                             "of this node); detach it")
+        dirs = self.decoder._query_dirs(fn, dirs, query_pos.to(latent.device))
+        lat, q = self._adjoint_args(fn, latent, query_pos, tokens_pos, 3, chunk_points)
+        return GF.SampleDirectionalLatentFn.apply(latent, self.decoder, q, lat, chunk_points, dirs)
+
+    def sample_hessian_vjp(self, latent: torch.Tensor, query_pos: torch.Tensor, cot_pred: Optional[torch.Tensor],
+                           cot_jac: Optional[torch.Tensor], cot_hess: Optional[torch.Tensor],
+                           tokens_pos: Optional[torch.Tensor] = None, chunk_points: Optional[int] = None) -> torch.Tensor:
+        """The ADJOINT of ``sample_hessian`` / ``sample_hessian_rows``: -> grad_latent [D*H*W, lifting_channels] (fp32) for cotangents
+        ``cot_pred`` [Nq, output_size], ``cot_jac`` [Nq, output_size, 3] and ``cot_hess`` [Nq, output_size, 3, 3] (float32; each may
+        be None, but not all three) -- the gradient of a loss on mixed second derivatives (the divergence of a viscous stress, a
+        strain-rate term, any second-order residual that is not the Laplacian) with respect to the latent.
+        ``MAGNODecoder.sample_hessian_vjp``: the cotangents through the transpose of the polarisation, then the jet adjoint along the
+        six directions (13 chains through the per-edge MLP: a loss on v^T H v of known v is ``sample_directional_vjp``'s at 3).
+        Exactness, routes and refusals are ``sample_laplacian_vjp``'s."""
+        lat, q = self._adjoint_args("sample_hessian_vjp", latent, query_pos, tokens_pos)
+        return self.decoder.sample_hessian_vjp(latent, q, cot_pred, cot_jac, cot_hess, lat, chunk_points=chunk_points)
+
+    def sample_hessian_autograd(self, latent: torch.Tensor, query_pos: torch.Tensor, tokens_pos: Optional[torch.Tensor] = None,
+                                chunk_points: Optional[int] = None):
+        """``sample_hessian`` as a differentiable function of the latent: -> (pred [Nq, output_size], jac [Nq, output_size, 3],
+        hess [Nq, output_size, 3, 3]) whose backward is ``sample_hessian_vjp`` (``functional.SampleHessianLatentFn``).  The forward is
+        ``sample_hessian``'s ('knn') / ``sample_hessian_rows``'s ('radius', 'bidirectional') result bit for bit; an output that
+        received no gradient contributes no cotangent.  Gradients flow to ``latent`` ONLY: a ``query_pos`` that requires grad raises
+        ValueError.  Configurations ``sample_hessian_vjp`` refuses are refused here, before the forward runs."""
+        lat, q = self._adjoint_args("sample_hessian_autograd", latent, query_pos, tokens_pos, 3, chunk_points,
+                                    self.decoder.HESSIAN_VJP_WHAT)
+        return GF.SampleHessianLatentFn.apply(latent, self.decoder, q, lat, chunk_points)
 
     def forward(self, batch, tokens_pos: Optional[torch.Tensor] = None, tokens_batch_idx: Optional[torch.Tensor] = None,
                 query_coord_pos: Optional[torch.Tensor] = None, query_coord_batch_idx: Optional[torch.Tensor] = None,

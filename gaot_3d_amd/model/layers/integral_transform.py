@@ -257,13 +257,22 @@ class IntegralTransform(nn.Module):
         """``adjoint_jet2_knn`` on RAGGED rows: ``graph`` holds both lists of the chunk, as for ``adjoint_rows``."""
         return self._adjoint(y_pos, x_pos, [grad_out, grad_d1, grad_d2], graph, None, dirs)
 
-    def _adjoint(self, y_pos, x_pos, cots, graph, lists=None, dirs=None):
-        """The six adjoint methods.  ``cots``: the cotangent planes [grad_out [N_x, C]], [grad_out, grad_jac [3, N_x, C]] or, with the
-        host directions ``dirs`` [nd][3], [grad_out, grad_d1 [nd, N_x, C], grad_d2 [nd or 1, N_x, C]]; ``lists``: the regular list
+    def adjoint_jet2_knn_qd(self, y_pos, x_pos, nbr, k: int, qdirs, grad_out, grad_d1, grad_d2, graph=None):
+        """``adjoint_jet2_knn`` along PER-QUERY directions: ``qdirs`` is a fp32 device tensor [N_x, nd, 3] (``jet2_knn_qd``'s); one
+        ``ops.gno_adjoint_jet2_qd`` call per 32-channel pass -- the ADJOINT of ``jet2_knn_qd`` with respect to f_y."""
+        return self._adjoint(y_pos, x_pos, [grad_out, grad_d1, grad_d2], graph, (nbr, k), qdirs, qd=True)
+
+    def adjoint_jet2_rows_qd(self, y_pos, x_pos, qdirs, grad_out, grad_d1, grad_d2, graph):
+        """``adjoint_jet2_knn_qd`` on RAGGED rows: ``graph`` holds both lists of the chunk, as for ``adjoint_rows``."""
+        return self._adjoint(y_pos, x_pos, [grad_out, grad_d1, grad_d2], graph, None, qdirs, qd=True)
+
+    def _adjoint(self, y_pos, x_pos, cots, graph, lists=None, dirs=None, qd: bool = False):
+        """The eight adjoint methods.  ``cots``: the cotangent planes [grad_out [N_x, C]], [grad_out, grad_jac [3, N_x, C]] or, with the
+        host directions ``dirs`` [nd][3] (``qd``: the per-query directions, a device tensor [N_x, nd, 3]), [grad_out, grad_d1 [nd, N_x, C], grad_d2 [nd or 1, N_x, C]]; ``lists``: the regular list
         (nbr, k), whose by-source list is built here when ``graph`` is None, or None for the two lists of ``graph``.  Every pass of
         ``_fused_passes`` (its f_y block is grad_out's) is one ``ops.gno_adjoint`` / ``gno_adjoint_jac`` / ``gno_adjoint_jet2`` call on
         the same 32 channels of every plane, zero-padded in the last block."""
-        fn = "adjoint" + ("", "_jac", "_jet2")[len(cots) - 1] + ("_rows" if lists is None else "_knn")
+        fn = "adjoint" + ("", "_jac", "_jet2")[len(cots) - 1] + ("_rows" if lists is None else "_knn") + ("_qd" if qd else "")
         k = None
         if lists is not None:
             nbr, k = lists[0], int(lists[1])
@@ -279,13 +288,16 @@ class IntegralTransform(nn.Module):
             if plan is None:
                 raise NotImplementedError(f"IntegralTransform.{fn}: only the 'linear' transforms the fused kernels evaluate (_fused_plan); "
                                           f"transform_type = {self.transform_type!r}, use_attn = {bool(self.use_attn)}")
-            leads = [(3,)] if dirs is None else [(len(dirs),), (len(dirs), 1)]
+            if qd and not (isinstance(dirs, torch.Tensor) and dirs.dim() == 3):
+                raise ValueError(f"IntegralTransform.{fn}: qdirs must be a tensor [{grad_out.shape[0]}, nd, 3]")
+            nd = 0 if dirs is None else int(dirs.shape[1]) if qd else len(dirs)
+            leads = [(3,)] if dirs is None else [(nd,), (nd, 1)]
             for name, t, lead in zip(("grad_jac",) if dirs is None else ("grad_d1", "grad_d2"), planes, leads):
                 if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.shape[0] not in lead or t.shape[1:] != grad_out.shape:
                     raise ValueError(f"IntegralTransform.{fn}: {name} must be [{' or '.join(str(n) for n in lead)}, "
                                      f"{grad_out.shape[0]}, {grad_out.shape[1]}], got "
                                      f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
-            run = (ops.gno_adjoint, ops.gno_adjoint_jac, ops.gno_adjoint_jet2)[len(planes)]
+            run = ops.gno_adjoint_jet2_qd if qd else (ops.gno_adjoint, ops.gno_adjoint_jac, ops.gno_adjoint_jet2)[len(planes)]
             y3, x3, _, (w0, b0, *mid), blocks = self._fused_passes(fcs, y_pos, x_pos, grad_out, *plan)
             outs = []
             for i, (wb, bb, gb, n) in enumerate(blocks):

@@ -240,6 +240,21 @@ def _logit_tangent_rows(dls, v):
     return dl
 
 
+def _logit_tangent_along(dls, dirs, i, like):
+    """l'_v along direction i of ``dirs`` from the axis tangents ``dls``: per-row directions [n, nd, 3] (``_logit_tangent_rows``) or host
+    values [nd][3] (an axis: that tangent itself; zeros of ``like``'s shape for the zero direction) -- ``_mix_jet2_planes``'s
+    expressions, for the transposed mix (``MAGNODecoder._mix_cot``)"""
+    if isinstance(dirs, torch.Tensor):
+        return _logit_tangent_rows(dls, dirs[:, i])
+    dl = None
+    for c, vc in enumerate(dirs[i]):
+        if vc == 0.0 or c >= len(dls):
+            continue
+        term = dls[c] if vc == 1.0 else vc * dls[c]
+        dl = term if dl is None else dl + term
+    return torch.zeros_like(like) if dl is None else dl
+
+
 def _mix_jet2_planes(w, dls, outs, d1s, d2s, dirs, second=True):
     """The softmax-weighted mix of the scales' 2-jets: ``w`` [n, scales], ``dls`` the logit tangents along the coordinate axes
     (``_logit_tangents``), ``outs[s]`` [n, C] and ``d1s[s]`` / ``d2s[s]`` [nd, n, C] the value, D_v and D_v^2 planes of scale s along
@@ -969,7 +984,10 @@ class MAGNODecoder(nn.Module):
     # ---- ONE host path for the three adjoints, by ``order``: 0 the value (``sample_vjp``), 1 and d/dx (``sample_jacobian_vjp``), 2 and
     # the Laplacian (``sample_laplacian_vjp``).  A step is shared where the orders run the same operations; where sharing it would
     # change an operation's rounding or its launch the order keeps its branch (bit-equality outranks uniformity).
-    ADJOINT_WHAT = ("the adjoint of the sampled field", "the adjoint of the field's Jacobian", "the adjoint of the field's Laplacian")
+    # order 3: the GENERAL second-order case -- nd directions (per query, or host values) with a cotangent on every first- and every
+    # second-order plane (``sample_directional_vjp``, ``sample_hessian_vjp``).  A branch beside order 2, which stays as it is.
+    ADJOINT_WHAT = ("the adjoint of the sampled field", "the adjoint of the field's Jacobian", "the adjoint of the field's Laplacian",
+                    "the adjoint of the field's directional derivatives")
 
     def _project_cot(self, order, planes, gy, gj=None, gl=None):
         """The skeleton of ``_project_vjp`` / ``_project_jac_vjp`` / ``_project_lap_vjp`` (their docstrings hold the formulas): rows in
@@ -977,22 +995,35 @@ class MAGNODecoder(nn.Module):
         [z; u ...] = X W_1^T, [A ...] = G W_2, the elementwise middle, dX = mid W_1 (one GEMM launch per product, precision 0) and the
         stack taken apart -> the cotangent planes.  Per order: the stack -- [x], [x, x'_d], [x, x'_d, sum_d x''_d] -- and the middle --
         ``ops.act_bwd`` on z with b_1 from the GEMM's epilogue; the torch expressions of ``_act_jets`` after z += b_1; the one kernel
-        ``ops.mlp2_lap_cot_mid``, which adds b_1 itself.  The one plane of order 0 is read and written in place (no stack)."""
+        ``ops.mlp2_lap_cot_mid``, which adds b_1 itself.  The one plane of order 0 is read and written in place (no stack).
+        Order 3 (``planes`` = [x, x'_0.., x''_0..] along nd directions, ``gj`` / ``gl`` [rows, out_channels, nd] on y'_i / y''_i): the
+        stack of all 1 + 2 nd planes, the middle ``ops.mlp2_jet2_cot_mid``
+            dz = a' A + a'' sum_i u_i A_i + sum_i (a''' u_i^2 + a'' s_i) B_i,   du_i = a' A_i + 2 a'' u_i B_i,   ds_i = a' B_i
+        and a block of rows cut so that a [rows, hidden] stack is never larger than order 2's five planes' worth (5 n C floats: at
+        nd = 6, 13 planes, a block is 5/13 of order 2's)."""
         from ... import ops
         fc1, fc2 = self.projection.fcs
         w1, w2 = GF._w2d(fc1.weight).contiguous(), GF._w2d(fc2.weight).contiguous()
         act = self.projection.non_linearity
         n, c = planes[0].shape
         hid, oc = w1.shape[0], w2.shape[0]
-        npl = (1, 4, 5)[order]
+        npl = len(planes) if order == 3 else (1, 4, 5)[order]
+        nd = (npl - 1) // 2
         outs = [torch.empty_like(planes[0]) for _ in range(npl)]
         step = n if hid <= c else max(1024, n * c // hid)
-        b1 = fc1.bias.detach().to(torch.float32).contiguous() if order == 2 else None
+        if order == 3 and npl > 5:                       # the stacks [npl rows, hidden] stay within order 2's bound
+            step = max(1024, step * 5 // npl)
+        b1 = fc1.bias.detach().to(torch.float32).contiguous() if order >= 2 else None
         for j in range(0, n, step):
             sl = slice(j, j + step)
             m = planes[0][sl].shape[0]
             if order == 0:
                 x, g, ng = planes[0][sl], gy[sl], 1
+            elif order == 3:
+                g = [gj[sl, :, i] for i in range(nd)] + [gl[sl, :, i] for i in range(nd)]
+                if gy is not None:
+                    g.insert(0, gy[sl])
+                x, g, ng = torch.cat([p[sl] for p in planes]), torch.cat(g), len(g)
             else:
                 xs = [p[sl] for p in planes[:4]]
                 if order == 2:
@@ -1025,6 +1056,13 @@ class MAGNODecoder(nn.Module):
                     a[:m] += s
                     del s
                 mid = a
+            elif order == 3:
+                zu, a = zu.view(npl, m, hid), a.view(ng, m, hid)
+                if gy is None:                           # no A plane: the result goes over the z stack
+                    mid = ops.mlp2_jet2_cot_mid(zu, None, a, b1, out=zu)
+                else:                                    # [A; A_i; B_i] becomes [dz; du_i; ds_i] in place
+                    mid = ops.mlp2_jet2_cot_mid(zu, a[0], a[1:], b1, out=a)
+                mid = mid.view(npl * m, hid)
             else:
                 zu, a = zu.view(5, m, hid), a.view(ng, m, hid)
                 if gy is None:                           # no A plane: the result goes over the z stack
@@ -1053,7 +1091,7 @@ class MAGNODecoder(nn.Module):
                                  f"({query_pos.device}){' or None' if optional else ''}, got {got}")
 
     @torch.no_grad()
-    def _adjoint_stream(self, fn, order, rndata_flat, query_pos, lat, chunk_points):
+    def _adjoint_stream(self, fn, order, rndata_flat, query_pos, lat, chunk_points, what=None):
         """The refusals of the adjoint of ``order``, before anything runs -> (grid, chunk, rows: the route is the row lists'): the
         argument rules, a point-sharded model, at order 2 a transform that is not 'linear' (the forward's jets cover the others, so it
         is named before their conditions), the streaming conditions at fp32 arithmetic (``_jet2_stream``: with the jet kernels'
@@ -1063,41 +1101,52 @@ class MAGNODecoder(nn.Module):
         self._sample_args(fn, chunk_points)
         if getattr(self, "_shard_group", None) is not None:
             raise NotImplementedError(f"MAGNODecoder.{fn}: a point-sharded model is not supported (every rank would hold a partial sum)")
-        what = self.ADJOINT_WHAT[order]
-        if order == 2 and self.gno.transform_type != "linear":
+        what = what or self.ADJOINT_WHAT[order]
+        if order >= 2 and self.gno.transform_type != "linear":
             raise NotImplementedError(f"MAGNODecoder.{fn}: {what} needs the 'linear' transform (the adjoint kernel is the linear "
                                       f"transform's); transform type {self.gno.transform_type!r} is not")
         rows = self.decoder_strategy != "knn"
         with ops.fp32_arithmetic():
             grid, chunk = self._jet2_stream(fn, rndata_flat.detach(), query_pos.detach(), lat, chunk_points, rows=rows, what=what,
-                                            jets=order == 2)
+                                            jets=order >= 2)
         if order == 1 and self.projection.non_linearity not in self.JAC_VJP_ACTS:
             raise NotImplementedError(f"MAGNODecoder.{fn}: the second derivative of the projection's activation "
                                       f"{self.projection.non_linearity!r} is not written (covered: {self.JAC_VJP_ACTS})")
         return grid, chunk, rows
 
-    def _adjoint(self, fn, order, rndata_flat, query_pos, cots, lat, chunk_points):
+    def _adjoint(self, fn, order, rndata_flat, query_pos, cots, lat, chunk_points, dirs=None, what=None):
         """The driver of ``sample_vjp`` / ``sample_jacobian_vjp`` / ``sample_laplacian_vjp`` (``cots`` as ``_check_cotangents`` takes
         them, in the order value, Jacobian, Laplacian): the checks, the refusals, then at fp32 arithmetic the chunk loop of ``sample``
-        with every chunk's [M, C] part (``_adjoint_chunk``) added into the zeroed gradient in chunk order."""
+        with every chunk's [M, C] part (``_adjoint_chunk``) added into the zeroed gradient in chunk order.  Order 3: ``cots`` = value, first-
+        and second-order planes along ``dirs`` -- the per-query directions [Nq, nd, 3], cut per chunk, or host values [nd][3] --, each
+        may be None but not all three; ``what`` names the call in the refusals."""
         from ... import ops
         self._sample_args(fn, chunk_points)
         self._check_cotangents(fn, query_pos, cots)
-        grid, chunk, rows = self._adjoint_stream(fn, order, rndata_flat, query_pos, lat, chunk_points)
+        if order == 3 and all(cot is None for _, cot, _, _ in cots):
+            raise ValueError(f"MAGNODecoder.{fn}: {', '.join(name for name, _, _, _ in cots)} are all None: there is nothing to pull back")
+        grid, chunk, rows = self._adjoint_stream(fn, order, rndata_flat, query_pos, lat, chunk_points, what)
         rndata_flat, query_pos = rndata_flat.detach(), query_pos.detach()
         cots = [None if cot is None else cot.detach() for _, cot, _, _ in cots]
         if order == 0:
             cots[0] = cots[0].contiguous()                # its GEMM reads the block's rows where they are
         if order == 2 and cots[1] is None:                # the stack of ``_project_lap_vjp`` always holds the three A_d planes
             cots[1] = torch.zeros(*cots[2].shape, 3, dtype=torch.float32, device=query_pos.device)
+        if order == 3:                                    # the stack of ``_project_cot`` always holds the A_i and the B_i planes
+            shape = next(cot.shape for cot in cots[1:] + cots[:1] if cot is not None)
+            for i in (1, 2):
+                if cots[i] is None:
+                    cots[i] = torch.zeros(*shape[:2], _num_dirs(dirs), dtype=torch.float32, device=query_pos.device)
+        qd = isinstance(dirs, torch.Tensor)
         with ops.fp32_arithmetic():
             f = rndata_flat.to(torch.float32).contiguous()
             grad = torch.zeros_like(f)
             for sl, q, lists in self._stream_chunks(grid, query_pos, chunk, "rows" if rows else "knn", lead=False):
-                grad.add_(self._adjoint_chunk(order, f, q.contiguous(), [None if cot is None else cot[sl] for cot in cots], lat, lists))
+                grad.add_(self._adjoint_chunk(order, f, q.contiguous(), [None if cot is None else cot[sl] for cot in cots], lat, lists,
+                                              dirs[sl] if qd else dirs))
         return grad
 
-    def _adjoint_chunk(self, order, rndata_flat, q, cots, lat, lists):
+    def _adjoint_chunk(self, order, rndata_flat, q, cots, lat, lists, dirs=None):
         """One chunk of ``_adjoint`` -> its [M, C] part of the latent's gradient: the mixed planes recomputed -- at order 0 on the value
         route (``forward_knn`` / the fused forward on the rows; on row lists with softmax weights through ``ops.scale_mix_fwd``, which
         hands its weights to the mix's cotangent kernel), else ``_jet_planes`` --, the projection's cotangent (``_project_cot``), the
@@ -1106,7 +1155,9 @@ class MAGNODecoder(nn.Module):
         from ... import graph as device_graph
         from ... import ops
         m, knn = lat.shape[0], isinstance(lists, tuple)
-        dirs = self.LAP_VJP_DIRS if order == 2 else None
+        if order != 3:
+            dirs = self.LAP_VJP_DIRS if order == 2 else None
+        qd = isinstance(dirs, torch.Tensor)               # order 3 with the chunk's per-query directions [n, nd, 3]: the ..._qd kernels
         outs = w = None
         if order:
             planes = self._jet_planes(rndata_flat, q, lat, lists, dirs)
@@ -1123,15 +1174,15 @@ class MAGNODecoder(nn.Module):
             del x
         d = self._project_cot(order, planes, *cots)
         del planes
-        per = self._mix_cot(d, q, knn, outs, w)
+        per = self._mix_cot(d, q, knn, outs, w, dirs if order == 3 else None)
         del d, outs, w
         part = None
         for rows, cot in zip([lists] if knn else lists, per):
-            p = self.gno._adjoint(lat, q, cot, device_graph.by_source(rows, m), lists if knn else None, dirs)
+            p = self.gno._adjoint(lat, q, cot, device_graph.by_source(rows, m), lists if knn else None, dirs, qd=qd)
             part = p if part is None else part.add_(p)
         return part
 
-    def _mix_cot(self, d, q, knn, outs=None, w=None):
+    def _mix_cot(self, d, q, knn, outs=None, w=None, dirs=None):
         """The scale mix's cotangent.  ``d`` = [G], [G, G'_0, G'_1, G'_2] or [G, G'_d ..., L]: the cotangents of the mixed value, of its
         derivative along the three axes and of EVERY second-order plane -> per scale (ONE entry on the 'knn' route) the planes as the
         transform's adjoint takes them, [G_s], [G_s, G'_s [3, n, C]] or [G_s, G'_s, L_s [1, n, C]].
@@ -1142,9 +1193,17 @@ class MAGNODecoder(nn.Module):
         function of the query alone,
             G_s = w_s G + sum_d w'_s,d G'_d + (sum_d w''_s,d) L,   G'_s,d = w_s G'_d + 2 w'_s,d L,   L_s = w_s L
         without the terms in L at order 1; at order 0, G_s = w_s G alone, it is the mix kernel's own backward on its operands
-        ``outs`` and weights ``w`` (``ops.scale_mix_bwd``)."""
+        ``outs`` and weights ``w`` (``ops.scale_mix_bwd``).
+        With ``dirs`` (order 3: per-row directions [n, nd, 3] or host values [nd][3]) ``d`` = [G, P_0.., S_0..] holds a cotangent per
+        first- and per second-order plane -> [G_s, P_s [nd, n, C], S_s [nd, n, C]]; with w'_s,i and w''_s,i the derivatives of the
+        weights along direction i (``_logit_tangent_along``, ``_softmax_weight_jets``) the transposes of ``_mix_jet2_planes`` are
+            G_s = w_s G + sum_i w'_s,i P_i + sum_i w''_s,i S_i,   P_s,i = w_s P_i + 2 w'_s,i S_i,   S_s,i = w_s S_i"""
         from ... import ops
-        pack = lambda g, *t: [g] + ([torch.stack(t[:3])] if t else []) + [p.unsqueeze(0) for p in t[3:]]
+        nd = 0 if dirs is None else _num_dirs(dirs)
+        if nd:
+            pack = lambda g, *t: [g, torch.stack(t[:nd]), torch.stack(t[nd:])]
+        else:
+            pack = lambda g, *t: [g] + ([torch.stack(t[:3])] if t else []) + [p.unsqueeze(0) for p in t[3:]]
         ns = len(self.scales)
         if knn:
             return [pack(*self._mix_equal_scales(d, q))]
@@ -1152,11 +1211,23 @@ class MAGNODecoder(nn.Module):
             return [pack(*d)] * ns
         if len(d) == 1:
             return [[g] for g in ops.scale_mix_bwd(outs, w, d[0])[0]]
-        second = len(d) == 5
+        second = len(d) == 5 or nd > 0
         sw = self.scale_weighting
         logits, hdn = _scale_logits(self, q)
         w = torch.softmax(logits, dim=1)
         dls = _logit_tangents((hdn > 0).to(hdn.dtype), sw[0].weight, sw[2].weight, lambda x, wt: GF.linear(x, wt, None, precision=0))
+        if nd:
+            jets = [_softmax_weight_jets(w, _logit_tangent_along(dls, dirs, i, w), second=True) for i in range(nd)]
+            per = []
+            for s in range(ns):
+                ws = w[:, s:s + 1]
+                g = ws * d[0]
+                for i, (dw, ddw) in enumerate(jets):
+                    g += dw[:, s:s + 1] * d[1 + i]
+                    g += ddw[:, s:s + 1] * d[1 + nd + i]
+                per.append(pack(g, *(ws * d[1 + i] + (2.0 * jets[i][0][:, s:s + 1]) * d[1 + nd + i] for i in range(nd)),
+                                *(ws * d[1 + nd + i] for i in range(nd))))
+            return per
         jets = [_softmax_weight_jets(w, dl, second=second) for dl in dls]
         dws = [j[0] for j in jets]
         if second:
@@ -1204,6 +1275,83 @@ class MAGNODecoder(nn.Module):
         return self._adjoint("sample_laplacian_vjp", 2, rndata_flat, query_pos,
                              [("cot_pred", cot_pred, (), True), ("cot_jac", cot_jac, (3,), True), ("cot_lap", cot_lap, (), False)],
                              latent_tokens_pos, chunk_points)
+
+    @torch.no_grad()
+    def sample_directional_vjp(self, rndata_flat, query_pos, dirs, cot_pred, cot_d1, cot_d2, latent_tokens_pos,
+                               chunk_points: Optional[int] = None) -> torch.Tensor:
+        """The ADJOINT of ``sample_directional``: -> grad_latent [M, C] (fp32)
+            = sum_q cot_pred[q] . d pred[q] / d rndata_flat + sum_q,i cot_d1[q, :, i] . d d1[q, :, i] / d rndata_flat
+              + sum_q,i cot_d2[q, :, i] . d d2[q, :, i] / d rndata_flat
+        for the derivatives along every query's OWN directions -- the gradient of a loss on d^2 p / d n^2 (a curvature or
+        second-normal-derivative term of a wall model), of a boundary-layer residual in a local frame (n, t_1, t_2), of the tangential
+        Laplacian D^2_{t1} + D^2_{t2}.  ``dirs``: float32 [Nq, nd, 3] or [Nq, 3] on the queries' device, 1 <= nd <= 6, used as given
+        (``sample_directional``'s rules); ``cot_pred``: float32 [Nq, out_channels] or None; ``cot_d1`` / ``cot_d2``: float32
+        [Nq, out_channels, nd], each may be None, but not all three.  The decoder's parameters, the query coordinates and the
+        directions are CONSTANTS here.
+
+        Streamed through the chunk loop of ``sample_laplacian_vjp``, as its general second-order case (order 3 of ``_adjoint``): per
+        chunk the mixed planes [x, x'_i, x''_i] along the chunk's directions (``_jet_planes``: the ..._qd jet kernels), the
+        projection's cotangent with a second-order cotangent per direction (``_project_cot``: one ``ops.mlp2_jet2_cot_mid`` between
+        the GEMMs), the scale mix's (``_mix_cot``: on row lists with the weights' derivatives along every row's own direction), then
+        per scale ``graph.by_source`` and the adjoint of the jet kernel with the direction of a pass loaded per lane
+        (``IntegralTransform.adjoint_jet2_knn_qd`` / ``adjoint_jet2_rows_qd``: one value chain and two per direction -- 3 at nd = 1
+        where the Laplacian's adjoint runs 7).  Exactness, reproducibility, routes and refusals are ``sample_laplacian_vjp``'s; a bad
+        ``dirs`` and three None cotangents raise ValueError."""
+        fn = "sample_directional_vjp"
+        self._sample_args(fn, chunk_points)
+        dirs = self._query_dirs(fn, dirs, query_pos)
+        nd = int(dirs.shape[1])
+        return self._adjoint(fn, 3, rndata_flat, query_pos,
+                             [("cot_pred", cot_pred, (), True), ("cot_d1", cot_d1, (nd,), True), ("cot_d2", cot_d2, (nd,), True)],
+                             latent_tokens_pos, chunk_points, dirs)
+
+    HESSIAN_VJP_WHAT = "the adjoint of the field's Hessian"
+
+    def _polarise_cot(self, cot_jac, cot_hess):
+        """The transpose of ``_polarise``: the cotangents ``cot_jac`` [n, out_channels, 3] and ``cot_hess`` [n, out_channels, 3, 3] (each
+        may be None) of its results as cotangents (P, S) [n, out_channels, 6] of the jets along ``HESSIAN_DIRS``.  ``_polarise`` writes
+        jac = d1[..., :3], H_aa = d2_a and H_ab = H_ba = (d2_{3+n} - d2_a - d2_b) / 2 for pair n = (a, b), so with
+        Cs = (C + C^T) / 2 the loss sum_ij C_ij H_ij is sum_a C_aa d2_a + sum_n Cs_ab (d2_{3+n} - d2_a - d2_b):
+            P_a = cot_jac[..., a], P_{3+n} = 0;      S_a = C_aa - sum_{b != a} Cs_ab,      S_{3+n} = Cs_ab"""
+        p = s = None
+        if cot_jac is not None:
+            p = cot_jac.new_zeros(*cot_jac.shape[:2], 6)
+            p[:, :, :3] = cot_jac
+        if cot_hess is not None:
+            sym = 0.5 * (cot_hess + cot_hess.transpose(2, 3))
+            s = sym.new_empty(*sym.shape[:2], 6)
+            for a in range(3):
+                s[:, :, a] = sym[:, :, a, a]
+            for n, (a, b) in enumerate(self.HESSIAN_PAIRS):
+                s[:, :, 3 + n] = sym[:, :, a, b]
+                s[:, :, a] -= sym[:, :, a, b]
+                s[:, :, b] -= sym[:, :, a, b]
+        return p, s
+
+    @torch.no_grad()
+    def sample_hessian_vjp(self, rndata_flat, query_pos, cot_pred, cot_jac, cot_hess, latent_tokens_pos,
+                           chunk_points: Optional[int] = None) -> torch.Tensor:
+        """The ADJOINT of ``sample_hessian`` / ``sample_hessian_rows``: -> grad_latent [M, C] (fp32)
+            = sum_q cot_pred[q] . d pred[q] / d rndata_flat + sum_q cot_jac[q] . d jac[q] / d rndata_flat
+              + sum_q cot_hess[q] . d hess[q] / d rndata_flat
+        -- the gradient of a loss on mixed second derivatives (the divergence of a viscous stress, a strain-rate term, any
+        second-order residual that is not the Laplacian).  ``cot_pred``: float32 [Nq, out_channels]; ``cot_jac``: [Nq, out_channels, 3];
+        ``cot_hess``: [Nq, out_channels, 3, 3] (need not be symmetric: hess[..., i, j] and hess[..., j, i] are one value, and the two
+        cotangents add); each may be None, but not all three.
+
+        The cotangents go through the transpose of the polarisation (``_polarise_cot``) and the call runs as the general
+        second-order adjoint along the six host directions ``HESSIAN_DIRS`` (order 3 of ``_adjoint``, the host-direction jet adjoint
+        ``IntegralTransform.adjoint_jet2_knn`` / ``adjoint_jet2_rows`` with a second-order plane per direction: 13 chains through the
+        per-edge MLP; the three first-order planes of the sum directions carry zeros and are not skipped).  Exactness, reproducibility,
+        routes and refusals are ``sample_laplacian_vjp``'s."""
+        fn = "sample_hessian_vjp"
+        self._sample_args(fn, chunk_points)
+        cots = [("cot_pred", cot_pred, (), True), ("cot_jac", cot_jac, (3,), True), ("cot_hess", cot_hess, (3, 3), True)]
+        self._check_cotangents(fn, query_pos, cots)
+        p, s = self._polarise_cot(cot_jac, cot_hess)
+        return self._adjoint(fn, 3, rndata_flat, query_pos,
+                             [("cot_pred", cot_pred, (), True), ("cot_jac", p, (6,), True), ("cot_hess", s, (6,), True)],
+                             latent_tokens_pos, chunk_points, self.HESSIAN_DIRS, self.HESSIAN_VJP_WHAT)
 
     @torch.no_grad()
     def _laplacian_jets(self, fn, rndata_flat, query_pos, lat, chunk_points):

@@ -452,6 +452,28 @@ def gno_adjoint_jet2(weights, biases, y_pos: Tensor, x_pos: Tensor, dirs, grad_o
                                rowptr_dst, kk, g, e)
 
 
+def gno_adjoint_jet2_qd(weights, biases, y_pos: Tensor, x_pos: Tensor, qdirs: Tensor, grad_out: Tensor, grad_d1: Tensor,
+                        grad_d2: Tensor, g: BipartiteGraph, k: Optional[int] = None) -> Tensor:
+    """``gno_adjoint_jet2`` along PER-QUERY directions (gaot_gno_adj_jet2_qd): the ADJOINT of ``gno_forward_knn_jet2_qd`` /
+    ``gno_forward_jet2_qd`` ('linear') with respect to f_y.  ``qdirs`` is a DEVICE tensor [n_query, nd, 3] (1..6 directions per query,
+    used as given, read by the kernel: no host read, capturable) -> grad_f_y [n_src, 32] with
+        grad_f_y[t] = sum over the edges e of source t of (K_e * grad_out[q_e] + sum_i D_v K_e * grad_d1[i, q_e]
+                                                           + sum_i D_v^2 K_e * grad_d2[i, q_e]) / deg(q_e),   v = qdirs[q_e, i]
+    Everything else is ``gno_adjoint_jet2``'s: the cotangent planes (``grad_d2`` [nd or 1, n_query, 32]), the lists, the degrees,
+    exact fp32 whatever the precision mode, no atomics, bit-reproducible, exact zeros for a source without edges, two launches.  With
+    the same directions on every query the result is ``gno_adjoint_jet2``'s on those directions, bit for bit."""
+    fn = "gno_adjoint_jet2_qd"
+    m, keep, y_pos, x_pos, grad_out, rowptr_dst, kk, e = _gno_adjoint_args(fn, weights, biases, y_pos, x_pos, grad_out, g, k)
+    qdirs, nd = _query_dirs(fn, qdirs, x_pos, g.num_dst)
+    if not 1 <= nd <= 6:
+        raise GaotError(f"{fn}: 1..6 directions, got {nd}")
+    _gno_adjoint_planes(fn, "grad_d1", grad_d1, (nd,), grad_out)
+    _gno_adjoint_planes(fn, "grad_d2", grad_d2, (nd, 1), grad_out)
+    stride2 = 0 if grad_d2.shape[0] == 1 and nd > 1 else g.num_dst * m.channels    # one direction: both forms name the same plane
+    return _gno_adjoint_launch("gaot_gno_adj_jet2_qd", m, y_pos, x_pos,
+                               (_ptr(qdirs), nd, _ptr(grad_out), _ptr(grad_d1), _ptr(grad_d2), stride2), rowptr_dst, kk, g, e)
+
+
 def gno_forward_knn_jac(mode, weights, biases, y_pos: Tensor, x_pos: Tensor, f_y: Optional[Tensor], src_table: Optional[Tensor],
                         nbr: Tensor, k: int):
     """``gno_forward_knn`` with the spatial derivative of its result (gaot_gno_fwd_knn_jac): -> (out [n_query, 32],
@@ -2040,6 +2062,39 @@ def mlp2_lap_cot_mid(zus: Tensor, a: Optional[Tensor], ad: Tensor, al: Tensor, b
     with _timed(f"mlp2_lap_cot_mid_h{hid}"):
         check(lib.gaot_mlp2_lap_cot_mid(_ptr(zus[0]), _ptr(zus[1]), n, _ptr(zus[4]), _ptr(b1), _ptr(a), _ptr(ad), n, _ptr(al), rows, hid,
                                         _ptr(out), n, _stream()), "gaot_mlp2_lap_cot_mid")
+    return out
+
+
+def mlp2_jet2_cot_mid(zus: Tensor, a: Optional[Tensor], ab: Tensor, b1: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """``mlp2_lap_cot_mid`` with a second-order cotangent PER DIRECTION, one launch for nd = 1..6 (include/gaot3d_hip.h:
+    gaot_mlp2_jet2_cot_mid).  ``zus`` [1 + 2 nd, rows, hidden]: the stack [z - b1; u_0..; s_0..] one product with W1 gives (``b1``
+    [hidden] or None is added to z here); ``a`` [rows, hidden] or None (no cotangent on the value); ``ab`` [2 nd, rows, hidden]: the
+    cotangents of y'_i, then of y''_i, pulled to hidden width -> ``out`` [1 + 2 nd, rows, hidden] = [dz; du_0..; ds_0..] (erf-GELU).
+    ``out`` may be the storage of the stack [a; ab] or ``zus`` itself.  Everything float32, contiguous, on one device; hidden a
+    multiple of 4.  Bad operands raise GaotError before the launch."""
+    lib = _lib.load()
+    fn = "mlp2_jet2_cot_mid"
+    if not isinstance(zus, Tensor) or zus.dim() != 3 or zus.shape[0] % 2 != 1 or not 1 <= zus.shape[0] // 2 <= 6:
+        raise GaotError(f"{fn}: zus must be [1 + 2 nd, rows, hidden] with nd in 1..6, got "
+                        f"{tuple(zus.shape) if isinstance(zus, Tensor) else type(zus).__name__}")
+    nd, rows, hid = int(zus.shape[0]) // 2, int(zus.shape[1]), int(zus.shape[2])
+    if hid < 4 or hid % 4:
+        raise GaotError(f"{fn}: hidden must be a positive multiple of 4, got {hid}")
+    if out is None:
+        out = torch.empty_like(zus)
+    for name, t, shape, optional in (("zus", zus, (1 + 2 * nd, rows, hid), False), ("a", a, (rows, hid), True),
+                                     ("ab", ab, (2 * nd, rows, hid), False), ("b1", b1, (hid,), True),
+                                     ("out", out, (1 + 2 * nd, rows, hid), False)):
+        if t is None and optional:
+            continue
+        if not isinstance(t, Tensor) or not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() \
+                or t.device != zus.device or t.data_ptr() % 16:
+            got = f"{t.dtype} {tuple(t.shape)} on {t.device}, strides {tuple(t.stride())}" if isinstance(t, Tensor) else type(t).__name__
+            raise GaotError(f"{fn}: {name} must be contiguous, 16-byte aligned float32 {list(shape)} on {zus.device}, got {got}")
+    n = rows * hid
+    with _timed(f"mlp2_jet2_cot_mid_h{hid}_d{nd}"):
+        check(lib.gaot_mlp2_jet2_cot_mid(_ptr(zus), n, _ptr(b1), _ptr(a), _ptr(ab), n, nd, rows, hid, _ptr(out), n, _stream()),
+              "gaot_mlp2_jet2_cot_mid")
     return out
 
 

@@ -280,6 +280,26 @@ int gaot_gno_adj_jet2(const gaot_mlp_t* mlp /* host */, const float* y_pos, cons
                       int64_t num_queries, float* grad_f_y /* [num_sources, channels] */, void* workspace, size_t workspace_bytes,
                       gaot_stream_t stream);
 
+/* gaot_gno_adj_jet2 with PER-QUERY directions (csrc/gno_jet2_adj_qd.hip): the adjoint of gaot_gno_fwd_knn_jet2_qd /
+ * gaot_gno_fwd_jet2_qd (mode 0) with respect to f_y,
+ *   grad_f_y[t][c] = sum over row t of the SOURCE-sorted list of
+ *       ( K_c grad_out[q_e][c] + sum_i D_{v_i(q_e)} K_c grad_d1[i][q_e][c] + sum_i D^2_{v_i(q_e)} K_c grad_d2[i][q_e][c] ) / deg(q_e)
+ * -- the pull-back of a loss on a derivative along a query's own direction (a wall normal, a local frame).  `dirs`: DEVICE pointer
+ * [num_queries][nd][3], nd = 1..6, read by the kernel: a lane loads the direction of its own edge's query at the top of a direction
+ * pass.  Everything else is gaot_gno_adj_jet2's, argument for argument: the planes, grad_d2_stride (num_queries * channels or 0), the
+ * lists, the degrees, the workspace (gaot_gno_adj_jet2_qd_workspace_bytes = gaot_gno_adj_jet2_workspace_bytes), the fixed summation
+ * order, exact fp32, no atomics, exact zeros for a source without edges, two launches.  With the same nd directions on every query the
+ * result is gaot_gno_adj_jet2's bit for bit.  Argument errors before any launch (GAOT_ERR_ARG): those of gaot_gno_adj_jet2, with
+ * a HOST pointer as dirs (or a null one with queries) in place of a device one. */
+size_t gaot_gno_adj_jet2_qd_workspace_bytes(int64_t num_edges);
+int gaot_gno_adj_jet2_qd(const gaot_mlp_t* mlp /* host */, const float* y_pos, const float* x_pos,
+                         const float* dirs /* DEVICE, [num_queries][nd][3] */, int nd, const float* grad_out /* [num_queries, channels] */,
+                         const float* grad_d1 /* [nd, num_queries, channels] */, const float* grad_d2 /* [nd or 1, num_queries, channels] */,
+                         int64_t grad_d2_stride, const int32_t* rowptr_dst /* or null with k > 0 */, int k,
+                         const int32_t* src_sorted /* by source */, const int32_t* dst_sorted /* by source */, const int32_t* rowptr_src,
+                         int64_t num_edges, int64_t num_sources, int64_t num_queries, float* grad_f_y /* [num_sources, channels] */,
+                         void* workspace, size_t workspace_bytes, gaot_stream_t stream);
+
 /* gaot_gno_fwd_knn_jet2's directional 2-jets on RAGGED rows (csrc/gno_jet2.hip): the value, D_v and D_v^2 planes of the by-query list
  * of any graph, as gaot_gno_fwd_jac gives the value and the Jacobian -- the lists, the padding edges, the row reduction (every one
  * of the 1 + 2 nd planes through its own two partial slots per tile) and the empty rows (exact zeros in every plane) are that entry
@@ -850,6 +870,21 @@ int gaot_mlp2_jet2(const float* x, const float* dx0, const float* dx1, const flo
 int gaot_mlp2_lap_cot_mid(const float* z, const float* u, int64_t u_stride, const float* s, const float* b1, const float* a,
                           const float* a_d, int64_t ad_stride, const float* a_l, int64_t num_rows, int hidden, float* out,
                           int64_t out_stride, gaot_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * That middle with a second-order cotangent PER DIRECTION (csrc/mlp2_jet2_cot.hip; the projection under sample_directional_vjp and
+ * sample_hessian_vjp), one launch for nd = 1..6, fp32.  With u_i = W1 x'_i, s_i = W1 x''_i and A = g_y W2, A_i = g_d1,i W2,
+ * B_i = g_d2,i W2:
+ *   dz = a' A + a'' sum_i u_i A_i + sum_i (a''' u_i^2 + a'' s_i) B_i,   du_i = a' A_i + 2 a'' u_i B_i,   ds_i = a' B_i
+ * both sums in ascending i, one fma per term.  zus: the 1 + 2 nd planes [z WITHOUT its bias (b1 [hidden] or NULL is added here);
+ * u_0..; s_0..] at zus + p * z_stride; a: the plane A or NULL (zero); ab: the 2 nd planes [A_0..; B_0..] at ab + p * a_stride;
+ * out: the 1 + 2 nd planes [dz; du_0..; ds_0..] at out + p * out_stride, ready for ONE product with W1.  Every plane is dense
+ * [num_rows, hidden], 16-byte aligned, hidden a multiple of 4.  out may alias the z stack or the stack [A; A_i; B_i] plane for plane
+ * (an element of the result depends on that element of each input alone, and a plane is written after the planes under it have been
+ * read).  No workspace, no atomics; num_rows == 0 is a no-op.
+ * ------------------------------------------------------------------------------------------- */
+int gaot_mlp2_jet2_cot_mid(const float* zus, int64_t z_stride, const float* b1, const float* a, const float* ab, int64_t a_stride,
+                           int nd, int64_t num_rows, int hidden, float* out, int64_t out_stride, gaot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Thin fp32 linears over many rows in one pass (csrc/rowlinear.hip):  y = act([x_0 | x_1 | ...] W^T + b),

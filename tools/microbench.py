@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Kernel microbenchmarks at the configs[1] shapes (for rocprofv3 / quick A-B): attention fwd+bwd, GEMM shapes, GNO, PointNet GeoEmbed,
-the attention-weighted GNO, the forward-only decoder (decoder_sample), the sampled field's Jacobian (decoder_jacobian), the projection MLP's tangent alone (projection_jvp), the sampled field's Hessian and Laplacian (decoder_hessian), its derivatives along per-query directions (decoder_directional), its adjoint with respect to the latent (decoder_adjoint), the adjoint of its Jacobian (decoder_jacobian_adjoint), the adjoint of its Laplacian (decoder_laplacian_adjoint)."""
+the attention-weighted GNO, the forward-only decoder (decoder_sample), the sampled field's Jacobian (decoder_jacobian), the projection MLP's tangent alone (projection_jvp), the sampled field's Hessian and Laplacian (decoder_hessian), its derivatives along per-query directions (decoder_directional), its adjoint with respect to the latent (decoder_adjoint), the adjoint of its Jacobian (decoder_jacobian_adjoint), the adjoint of its Laplacian (decoder_laplacian_adjoint), the adjoints of its directional derivatives and of its Hessian (decoder_directional_adjoint, decoder_hessian_adjoint)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 if os.environ.get("MB_TREE"):      # measure another checkout's package (gno_weighted: the parent commit's) with this script
@@ -1331,6 +1331,207 @@ elif what == "decoder_laplacian_adjoint":
                       f"this : gaot_mlp2_lap_cot_mid = {m / km[0]:.2f}", flush=True)
             del zus, a5
         del q, gy, gj, gl, qc
+elif what in ("decoder_directional_adjoint", "decoder_hessian_adjoint"):
+    # The adjoints of the field's directional derivatives (MAGNODecoder.sample_directional_vjp, per-query directions) and of its
+    # Hessian (sample_hessian_vjp) on decoder_laplacian_adjoint's decoders -- configs[1] (knn, k = 8), or with
+    # `--strategy radius|bidirectional` the reference YAML's decoder on row lists -- at 500 K and 8 M random query points with random
+    # unit directions and random cotangents, fp32 mode.  There is no older route to beat; the yardsticks are the existing calls,
+    # alternated with the new ones round by round in this one process after a warm-up of each:
+    #   directional: (a1) sample_directional_vjp nd = 1;  (a3) nd = 3;  (b) sample_directional nd = 3;  (c) sample_laplacian_vjp;
+    #                (j) sample_jacobian_vjp
+    #   hessian:     (a) sample_hessian_vjp;  (b) sample_hessian / sample_hessian_rows;  (c) sample_laplacian_vjp;  (j) sample_jacobian_vjp
+    #   (d) the split of the new call (nd = 3 / the six directions) into its stages, one chunk at a time with device events (one scale);
+    #   (e) the kernel alone on one chunk's lists: gaot_gno_adj_jet2_qd against gaot_gno_adj_jet2 on the same by-source list, the same
+    #       directions on every query (the results are compared bit for bit), nd = 1, 3, 6, a second-order plane per direction;
+    #   (f) the projection cotangent's elementwise middle on one block's rows: gaot_mlp2_jet2_cot_mid against the same expression as
+    #       fp32 tensor operations.
+    # Device events around synchronised work; `reps` rounds (7 for the kept output); a row is the median with max - min, the peak is
+    # the rise of allocated memory over the inputs.  Kept in profiles/decoder_{directional,hessian}_adjoint[_rows]_microbench.txt.
+    from gaot_3d_amd import graph as device_graph
+    from gaot_3d_amd.data import latent_grid
+    from gaot_3d_amd.model.layers.magno import MAGNOConfig, MAGNODecoder
+    gaot_3d_amd.set_precision("fp32")
+    latent = (64, 64, 32)
+    strategy = sys.argv[sys.argv.index("--strategy") + 1] if "--strategy" in sys.argv else "knn"
+    if strategy not in ("knn", "radius", "bidirectional"):
+        sys.exit(f"--strategy must be knn, radius or bidirectional, got {strategy}")
+    rows = strategy != "knn"
+    hessian = what == "decoder_hessian_adjoint"
+    cfg = MAGNOConfig(gno_coord_dim=3, lifting_channels=32, mlp_type="linear", use_geoembed=[True, False],
+                      neighbor_strategy=["knn", strategy] if rows else "knn", k_neighbors=1 if rows else 8, gno_radius=0.033,
+                      out_gno_channel_mlp_hidden_layers=[64, 64], precompute_edges=False)
+    dec = MAGNODecoder(in_channels=32, out_channels=1, gno_config=cfg).to(dev).eval()
+    dec.latent_dims = latent
+    tokens = latent_grid(latent).to(dev)
+    m_tok = tokens.shape[0]
+    rn = torch.randn(m_tok, 32, device=dev)
+    chunk = int(os.environ["MB_CHUNK"]) if os.environ.get("MB_CHUNK") else None
+    step = chunk or dec.SAMPLE_CHUNK
+    tag = f"fp32{' ' + strategy if rows else ''}"
+    fcs = list(dec.gno.channel_mlp.fcs)
+    kw_, kb_ = [fc.weight.detach() for fc in fcs], [fc.bias.detach() for fc in fcs]
+    hid = dec.projection.fcs[0].weight.shape[0]
+    sizes = [int(a) for a in os.environ["MB_NQ"].split(",")] if os.environ.get("MB_NQ") else [500000, 8000000]
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); out = fn(); e1.record()
+        torch.cuda.synchronize()
+        peak = torch.cuda.max_memory_allocated() - base
+        return e0.elapsed_time(e1), peak, out
+
+    def median(ts):
+        ts = sorted(ts)
+        return ts[len(ts) // 2], ts[0], ts[-1]
+
+    def staged(q, dirs, gy, g1, g2):
+        """the new call's chunk loop with device events between its stages (one scale) -> ({stage: ms}, grad); ``dirs``: the
+        per-query directions [Nq, nd, 3] or the six host directions"""
+        ev = lambda: torch.cuda.Event(enable_timing=True)
+        marks, grad = [], torch.zeros_like(rn)
+        qd = isinstance(dirs, torch.Tensor)
+        with torch.no_grad():
+            grid = dec._stream_grid(rn, q, tokens)
+            for i in range(0, q.shape[0], step):
+                qc, dc = q[i:i + step], dirs[i:i + step] if qd else dirs
+                es = [ev() for _ in range(7)]
+                es[0].record()
+                lists = (device_graph.knn_to_grid(qc, grid, 8), 8) if not rows else \
+                    [device_graph.query_lists(strategy, qc, grid, dec.gno_radius, int(dec.k_neighbors))]
+                es[1].record()
+                planes = dec._jet_planes(rn, qc, tokens, lists, dc)
+                es[2].record()
+                d = dec._project_cot(3, planes, gy[i:i + step], g1[i:i + step], g2[i:i + step])
+                per = dec._mix_cot(d, qc, not rows, None, None, dc)[0]
+                es[3].record()
+                gs = device_graph.by_source(lists if not rows else lists[0], m_tok)
+                es[4].record()
+                part = dec.gno._adjoint(tokens, qc, per, gs, lists if not rows else None, dc, qd=qd)
+                es[5].record()
+                grad.add_(part)
+                es[6].record()
+                marks.append(es)
+                del lists, planes, d, per, gs, part
+        torch.cuda.synchronize()
+        nd = dirs.shape[1] if qd else len(dirs)
+        names = ("neighbour search", f"recomputed planes (value + {nd} x 2 jets)", "projection cotangent", "by_source",
+                 "adjoint kernel + fix-up", "accumulation")
+        return {n: sum(es[j].elapsed_time(es[j + 1]) for es in marks) for j, n in enumerate(names)}, grad
+
+    def mid_as_tensor_ops(zus, a, ab, b1):
+        """gaot_mlp2_jet2_cot_mid's expression as fp32 tensor operations -> [1 + 2 nd, rows, hidden]"""
+        nd = ab.shape[0] // 2
+        z = zus[0] + b1
+        phi = torch.exp(-0.5 * z * z) * 0.3989422804014327
+        a1 = 0.5 * (1.0 + torch.erf(z * 0.7071067811865476)) + z * phi
+        a2, a3 = phi * (2.0 - z * z), phi * z * (z * z - 4.0)
+        u, sv, ad, bd = zus[1:1 + nd], zus[1 + nd:], ab[:nd], ab[nd:]
+        dz = a1 * a + a2 * (u * ad).sum(0) + ((a3 * u * u + a2 * sv) * bd).sum(0)
+        return torch.cat([dz[None], a1 * ad + (2.0 * a2) * u * bd, a1 * bd])
+
+    for nq in sizes:
+        q = torch.rand(nq, 3, device=dev) * 2 - 1
+        v = torch.nn.functional.normalize(torch.randn(nq, 3, 3, device=dev), dim=2)
+        v1 = v[:, :1].contiguous()
+        gy, gj, gl = torch.randn(nq, 1, device=dev), torch.randn(nq, 1, 3, device=dev), torch.randn(nq, 1, device=dev)
+        g1, g2 = torch.randn(nq, 1, 3, device=dev), torch.randn(nq, 1, 3, device=dev)
+        g11, g21 = g1[:, :, :1].contiguous(), g2[:, :, :1].contiguous()
+        gh = torch.randn(nq, 1, 3, 3, device=dev)
+        if hessian:
+            hess_fwd = dec.sample_hessian_rows if rows else dec.sample_hessian
+            new = "(a) sample_hessian_vjp"
+            routes = {new: lambda: dec.sample_hessian_vjp(rn, q, gy, gj, gh, tokens, chunk_points=chunk),
+                      "(b) sample_hessian": lambda: hess_fwd(rn, q, tokens, chunk_points=chunk)}
+            p6, s6 = dec._polarise_cot(gj, gh)
+            split_args = (dec.HESSIAN_DIRS, gy, p6, s6)
+            counts = "13 + 13 plane-chains against the Laplacian adjoint's 7 + 7"
+        else:
+            new = "(a3) sample_directional_vjp nd=3"
+            routes = {"(a1) sample_directional_vjp nd=1": lambda: dec.sample_directional_vjp(rn, q, v1, gy, g11, g21, tokens, chunk_points=chunk),
+                      new: lambda: dec.sample_directional_vjp(rn, q, v, gy, g1, g2, tokens, chunk_points=chunk),
+                      "(b) sample_directional nd=3": lambda: dec.sample_directional(rn, q, v, tokens, chunk_points=chunk)}
+            split_args = (v, gy, g1, g2)
+            counts = "nd = 1: 3 + 3 plane-chains, nd = 3: 7 + 7, against the Laplacian adjoint's 7 + 7"
+        routes["(c) sample_laplacian_vjp"] = lambda: dec.sample_laplacian_vjp(rn, q, gy, gj, gl, tokens, chunk_points=chunk)
+        routes["(j) sample_jacobian_vjp"] = lambda: dec.sample_jacobian_vjp(rn, q, gy, gj, tokens, chunk_points=chunk)
+        warm = {n: timed(f)[2] for n, f in routes.items()}
+        same = torch.equal(warm[new], staged(q, *split_args)[1])
+        del warm
+        ts, pk = {n: [] for n in routes}, {n: 0 for n in routes}
+        split = []
+        for _ in range(reps):
+            for n, f in routes.items():
+                t, p, _o = timed(f); ts[n].append(t); pk[n] = max(pk[n], p); del _o
+            split.append(staged(q, *split_args)[0])
+        med = {n: median(ts[n]) for n in routes}
+        for n in routes:
+            m, lo, hi = med[n]
+            print(f"Nq={nq} {tag}: {n:34s} (chunk {step}) {m:9.3f} ms (max - min {hi - lo:.3f} ms = {100 * (hi - lo) / m:.1f} %), "
+                  f"peak {pk[n] / 2**20:9.1f} MiB")
+        mc = med["(c) sample_laplacian_vjp"][0]
+        print(f"Nq={nq} {tag}: " + ", ".join(f"{n.split()[0]} : (c) = {med[n][0] / mc:.2f}" for n in routes if n[1] == "a")
+              + f" in time (by count: {counts}); the staged loop of (d) returns {new.split()[0]}'s bits: {same}")
+        tot = sum(median([s_[n] for s_ in split])[0] for n in split[0])
+        for n in split[0]:
+            m, lo, hi = median([s_[n] for s_ in split])
+            print(f"Nq={nq} {tag}: (d) {n:38s} {m:9.3f} ms (max - min {hi - lo:.3f} ms) = {100 * m / tot:5.1f} % of the stages' sum {tot:.3f} ms")
+        with torch.no_grad():
+            # (e) the kernels alone, on the lists of the first chunk
+            qc = q[:step].contiguous()
+            nc = qc.shape[0]
+            grid = dec._stream_grid(rn, qc, tokens)
+            if rows:
+                lists = device_graph.query_lists(strategy, qc, grid, dec.gno_radius, int(dec.k_neighbors))
+                gboth, kk, ne = device_graph.by_source(lists, m_tok), None, lists.by_dst.num_edges
+            else:
+                nbr = device_graph.knn_to_grid(qc, grid, 8)
+                gboth, kk, ne = device_graph.by_source((nbr, 8), m_tok), 8, nbr.numel()
+            print(f"Nq={nq} {tag}: (e) one chunk of {nc} queries, {ne} edges, {len(fcs) - 1} hidden layers")
+            for nd in (1, 3, 6):
+                hd = dec.HESSIAN_DIRS[:nd]
+                vd = torch.tensor(hd, device=dev)[None].expand(nc, nd, 3).contiguous()
+                gc, pc, sc = torch.randn(nc, 32, device=dev), torch.randn(nd, nc, 32, device=dev), torch.randn(nd, nc, 32, device=dev)
+                kern = {"gaot_gno_adj_jet2_qd": lambda: ops.gno_adjoint_jet2_qd(kw_, kb_, tokens, qc, vd, gc, pc, sc, gboth, kk),
+                        "gaot_gno_adj_jet2": lambda: ops.gno_adjoint_jet2(kw_, kb_, tokens, qc, hd, gc, pc, sc, gboth, kk)}
+                bits = torch.equal(*(f() for f in kern.values()))
+                kt = {n: [] for n in kern}
+                for _ in range(reps):
+                    for n, f in kern.items():
+                        t, _p, _o = timed(f); kt[n].append(t); del _o
+                kh = median(kt["gaot_gno_adj_jet2"])
+                for n in kern:
+                    m, lo, hi = median(kt[n])
+                    print(f"Nq={nq} {tag}: (e) nd={nd} {n:22s} {m:9.3f} ms (max - min {hi - lo:.3f} ms); this : gaot_gno_adj_jet2 = "
+                          f"{m / kh[0]:.3f}; the same bits: {bits}", flush=True)
+                del vd, gc, pc, sc
+            del gboth
+            # (f) the projection cotangent's middle alone, on the rows of one of _project_cot's blocks
+            b1 = dec.projection.fcs[0].bias.detach()
+            for nd in (1, 3, 6):
+                npl = 1 + 2 * nd
+                mr = nc if hid <= 32 else max(1024, nc * 32 // hid)
+                if npl > 5:
+                    mr = max(1024, mr * 5 // npl)
+                zus, acot = torch.randn(npl, mr, hid, device=dev), torch.randn(npl, mr, hid, device=dev)
+                mids = {"gaot_mlp2_jet2_cot_mid": lambda: ops.mlp2_jet2_cot_mid(zus, acot[0], acot[1:], b1),
+                        "tensor operations": lambda: mid_as_tensor_ops(zus, acot[0], acot[1:], b1)}
+                close = (mids["gaot_mlp2_jet2_cot_mid"]() - mids["tensor operations"]()).abs().max().item()
+                mt, mp = {n: [] for n in mids}, {n: 0 for n in mids}
+                for _ in range(reps):
+                    for n, f in mids.items():
+                        t, p, _o = timed(f); mt[n].append(t); mp[n] = max(mp[n], p); del _o
+                km = median(mt["gaot_mlp2_jet2_cot_mid"])
+                print(f"Nq={nq} {tag}: (f) nd={nd}: the middle on [{mr}, {hid}] planes ({3 * npl * mr * hid * 4 / 2**20:.0f} MiB read and "
+                      f"written); max |kernel - tensor operations| = {close:.2e}")
+                for n in mids:
+                    m, lo, hi = median(mt[n])
+                    print(f"Nq={nq} {tag}: (f) nd={nd} {n:24s} {m:9.3f} ms (max - min {hi - lo:.3f} ms), peak {mp[n] / 2**20:8.1f} MiB; "
+                          f"this : gaot_mlp2_jet2_cot_mid = {m / km[0]:.2f}", flush=True)
+                del zus, acot
+        del q, v, v1, gy, gj, gl, g1, g2, g11, g21, gh, qc
 elif what == "projection_jvp":
     # The projection MLP's forward-mode tangent on its own (LinearChannelMLP 32 -> 256 -> out, out in {1, 4}, three tangent planes, fp32
     # mode, random rows), as MAGNODecoder.sample_jacobian calls it: SAMPLE_CHUNK rows at a time into preallocated pred [N, out] and
