@@ -132,6 +132,10 @@ SIGNATURES = {
     "gaot_rowlin_fwd": (_i, [_p, _p, _i, _p, _p, _i64, _i, _i, _p, _p]),
     "gaot_rowlin_bwd": (_i, [_p, _p, _i, _p, _p, _p, _i64, _i, _i, _p, _p, _p, _p]),
     "gaot_mlp2_bwd": (_i, [_p, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "gaot_mlp2_bwd_f32_supported": (_i, [_i, _i, _i, _i]),
+    "gaot_mlp2_bwd_f32_workspace_bytes": (_sz, [_i, _i]),
+    "gaot_mlp2_bwd_f32_parts": (_i64, [_i64]),
+    "gaot_mlp2_bwd_f32": (_i, [_p, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "gaot_knn_grid": (_i, [_p, _i64, _p, _p, _i, _p, _p]),
     "gaot_radius_grid_count": (_i, [_p, _i64, _p, _p, _f, _i, _p, _p]),
     "gaot_radius_grid_fill": (_i, [_p, _i64, _p, _p, _f, _i, _p, _p, _p, _p]),

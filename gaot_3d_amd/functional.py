@@ -1537,7 +1537,8 @@ class SampleLatentFn(Function):
     """The sampled field as a differentiable function of the LATENT: forward = ``MAGNODecoder.sample`` at fp32 arithmetic in both
     precision modes (``torch.equal`` to ``sample`` called in fp32 mode), backward = ``MAGNODecoder.sample_vjp`` (the streamed adjoint:
     no edge list, no decoder autograd graph, no ``gno_bwd``).  Nothing is saved but the latent, the query coordinates and the token
-    tensor.  Gradients flow to ``latent`` ONLY: the decoder's parameters and the query coordinates are constants of this node."""
+    tensor.  Gradients flow to ``latent`` ONLY: the decoder's parameters and the query coordinates are constants of this node
+    (``SampleTrainFn``, behind ``GAOT3D.sample_autograd_params``, differentiates the parameters too)."""
 
     @staticmethod
     def forward(ctx, latent: Tensor, decoder, query_pos: Tensor, tokens_pos: Tensor, chunk_points: Optional[int]):
@@ -1548,6 +1549,34 @@ class SampleLatentFn(Function):
     @staticmethod
     def backward(ctx, dout: Optional[Tensor]):
         return _sample_latent_backward(ctx, ctx.decoder.sample_vjp, (dout,), 0)
+
+
+class SampleTrainFn(Function):
+    """``SampleLatentFn`` with the DECODER's parameters as differentiable inputs: the forward is ``SampleLatentFn``'s (the same call, the
+    same bits), the backward runs ``MAGNODecoder.sample_vjp_params`` ONCE and returns the latent's gradient (None when it is not
+    needed) and the gradient of every parameter in ``params`` that requires grad (None for the others).  ``params``: the decoder's
+    ``named_parameters()`` values in that order.  Nothing is saved but the latent, the query coordinates and the token tensor (the
+    parameters are read from the decoder when the backward runs).  The query coordinates are constants of this node."""
+
+    @staticmethod
+    def forward(ctx, latent: Tensor, decoder, query_pos: Tensor, tokens_pos: Tensor, chunk_points: Optional[int], *params: Tensor):
+        latent = _sample_latent_setup(ctx, latent, decoder, query_pos, tokens_pos, chunk_points)
+        with ops.fp32_arithmetic():
+            return decoder.sample(latent, query_pos, tokens_pos, chunk_points=chunk_points)
+
+    @staticmethod
+    def backward(ctx, dout: Optional[Tensor]):
+        latent, query_pos, tokens_pos = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if dout is None:
+            return (None,) * len(need)
+        g, grads = ctx.decoder.sample_vjp_params(latent, query_pos, dout.to(torch.float32).contiguous(), tokens_pos,
+                                                 chunk_points=ctx.chunk_points)
+        named = list(ctx.decoder.named_parameters())
+        if len(named) != len(need) - 5:
+            raise GaotError("SampleTrainFn: the decoder's parameters changed between the forward and the backward")
+        return (g.to(latent.dtype) if need[0] else None, None, None, None, None,
+                *(grads[name].to(p.dtype) if need[5 + i] else None for i, (name, p) in enumerate(named)))
 
 
 class SampleJacobianLatentFn(Function):

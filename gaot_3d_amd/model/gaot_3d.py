@@ -242,6 +242,19 @@ class GAOT3D(nn.Module):
         lat, q = self._adjoint_args("sample_vjp", latent, query_pos, tokens_pos)
         return self.decoder.sample_vjp(latent, q, cotangent, lat, chunk_points=chunk_points)
 
+    def sample_vjp_params(self, latent: torch.Tensor, query_pos: torch.Tensor, cotangent: torch.Tensor,
+                          tokens_pos: Optional[torch.Tensor] = None, chunk_points: Optional[int] = None):
+        """``sample_vjp`` WITH the decoder's parameters: -> (grad_latent [D*H*W, lifting_channels] (fp32), grads), ``grads`` a dict
+        keyed as ``self.decoder.named_parameters()`` keys them with the fp32 gradient of EVERY decoder parameter -- one call trains
+        the decoder through the streamed field at the memory of one chunk, where ``forward(query_coord_pos=...)`` carries its edge
+        list and the decoder's autograd graph.  ``MAGNODecoder.sample_vjp_params``: the projection's backward is one exact-fp32
+        launch (``gaot_mlp2_bwd_f32``), the kernel MLP's gradients and the latent's come from the exact-fp32 ``gaot_gno_bwd``; the
+        same bits in both precision modes, outside autograd, bit-reproducible for a given ``chunk_points``.  The scale-weighting
+        MLP's gradients are exact zeros on a 'knn' decoder (its mix is of equal operands).  Refusals are ``sample_vjp``'s, plus a
+        kernel MLP with four hidden layers."""
+        lat, q = self._adjoint_args("sample_vjp_params", latent, query_pos, tokens_pos)
+        return self.decoder.sample_vjp_params(latent, q, cotangent, lat, chunk_points=chunk_points)
+
     def sample_autograd(self, latent: torch.Tensor, query_pos: torch.Tensor, tokens_pos: Optional[torch.Tensor] = None,
                         chunk_points: Optional[int] = None) -> torch.Tensor:
         """``sample`` as a differentiable function of the latent: -> pred [Nq, output_size] whose backward is ``sample_vjp``
@@ -249,10 +262,26 @@ class GAOT3D(nn.Module):
         the ordinary autograd of ``latent`` -- at the memory of one chunk, without ``forward(query_coord_pos=...)``'s edge list and
         decoder graph.  The forward is the streamed value at fp32 arithmetic in BOTH precision modes (``torch.equal`` to ``sample``
         called in fp32 mode); only the latent, the queries and the token tensor are kept for the backward.  Gradients flow to
-        ``latent`` ONLY: the decoder's parameters are constants here (train them through ``forward``), and a ``query_pos`` that
-        requires grad raises ValueError -- the derivative with respect to the query is ``sample_jacobian``'s.  Configurations
-        ``sample_vjp`` refuses are refused here, before the forward runs."""
+        ``latent`` ONLY: the decoder's parameters are constants here (train them through ``sample_autograd_params``, or through
+        ``forward``), and a ``query_pos`` that requires grad raises ValueError -- the derivative with respect to the query is
+        ``sample_jacobian``'s.  Configurations ``sample_vjp`` refuses are refused here, before the forward runs."""
         lat, q = self._adjoint_args("sample_autograd", latent, query_pos, tokens_pos, 0, chunk_points)
+        return GF.SampleLatentFn.apply(latent, self.decoder, q, lat, chunk_points)
+
+    def sample_autograd_params(self, latent: torch.Tensor, query_pos: torch.Tensor, tokens_pos: Optional[torch.Tensor] = None,
+                               chunk_points: Optional[int] = None) -> torch.Tensor:
+        """``sample_autograd`` as a complete training route: -> pred [Nq, output_size], ``torch.equal`` to ``sample_autograd``'s, whose
+        backward runs ``sample_vjp_params`` once (``functional.SampleTrainFn``) and hands autograd the latent's gradient (when it is
+        needed) AND the gradient of every decoder parameter that requires grad; a parameter with ``requires_grad=False`` keeps
+        ``.grad`` None.  Only the latent, the queries and the token tensor are kept for the backward.  With no decoder parameter
+        requiring grad (or with grad disabled) the node, the launches and the bits are ``sample_autograd``'s.  A ``query_pos`` that
+        requires grad raises ValueError.  Refusals are ``sample_autograd``'s, plus a kernel MLP with four hidden layers
+        (``MAGNODecoder.sample_vjp_params``), all before the forward runs."""
+        lat, q = self._adjoint_args("sample_autograd_params", latent, query_pos, tokens_pos, 0, chunk_points)
+        params = [p for _, p in self.decoder.named_parameters()]
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            self.decoder._param_adjoint_layers("sample_autograd_params")
+            return GF.SampleTrainFn.apply(latent, self.decoder, q, lat, chunk_points, *params)
         return GF.SampleLatentFn.apply(latent, self.decoder, q, lat, chunk_points)
 
     def sample_jacobian_vjp(self, latent: torch.Tensor, query_pos: torch.Tensor, cot_pred: Optional[torch.Tensor],
@@ -277,7 +306,7 @@ class GAOT3D(nn.Module):
         ``sample_jacobian(..., row_lists=True)``'s result bit for bit (the flag changes nothing on a 'knn' decoder); an output that
         received no gradient contributes a zero cotangent.  A normal derivative needs no API of its own:
         ``(jac * n[:, None, :]).sum(-1)`` in ordinary autograd hands the backward cot_jac = g (x) n.  Gradients flow to ``latent``
-        ONLY: the decoder's parameters are constants here, and a ``query_pos`` that requires grad raises ValueError (no second
+        ONLY: the decoder's parameters are constants here (``sample_autograd_params`` trains them through the value), and a ``query_pos`` that requires grad raises ValueError (no second
         derivative in the query is formed).  Configurations ``sample_jacobian_vjp`` refuses are refused here, before the forward
         runs."""
         lat, q = self._adjoint_args("sample_jacobian_autograd", latent, query_pos, tokens_pos, 1, chunk_points)

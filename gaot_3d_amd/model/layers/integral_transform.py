@@ -307,6 +307,44 @@ class IntegralTransform(nn.Module):
                 outs.append(o if n == 32 else o[:, :n])
             return outs[0].contiguous() if len(outs) == 1 else torch.cat(outs, dim=1)
 
+    def _param_adjoint(self, y_pos, x_pos, f_y, grad_out, graph, add):
+        """The backward of the 'linear' transform on the lists of ``graph`` (``by_dst``: the by-query offsets, ``by_src``: the
+        by-source list) with respect to f_y AND the kernel MLP: -> grad_f_y [N_y, C]; the parameters' gradients go to
+        ``add(parameter, gradient)``.  Every pass of ``_fused_passes`` is ONE exact-fp32 ``ops.gno_backward`` launch (precision 0) on
+        the operands ``GnoFn`` sees in that pass: the padded weights' gradients are cut back to the parameters' shapes (the transpose
+        of the zero padding), the layers before the last receive every pass's part in pass order, the last layer and f_y their
+        32-channel block.  Outside autograd; raises NotImplementedError unless ``_fused_plan`` takes the 'linear' transform with at
+        most three hidden layers."""
+        fcs = list(self.channel_mlp.fcs)
+        with torch.no_grad():
+            plan = self._fused_plan(fcs, f_y, y_pos, x_pos) if self.transform_type == "linear" and len(fcs) <= 4 else None
+            if plan is None:
+                raise NotImplementedError("IntegralTransform._param_adjoint: only the 'linear' transforms the fused kernels evaluate "
+                                          f"(_fused_plan) with at most three hidden layers; transform_type = {self.transform_type!r}, "
+                                          f"use_attn = {bool(self.use_attn)}, {len(fcs) - 1} hidden layers")
+            cd = plan[0]
+            y3, x3, _, (w0, b0, *mid), blocks = self._fused_passes(fcs, y_pos, x_pos, f_y, *plan)
+            dims = [(fc.weight.shape[0], fc.weight.shape[1]) for fc in fcs]
+            outs = []
+            for i, (wb, bb, fb, n) in enumerate(blocks):
+                ws, bs = [w0.contiguous(), *mid[0::2], wb.contiguous()], [b0, *mid[1::2], bb.contiguous()]
+                gb = grad_out if (n == 32 and grad_out.shape[1] == 32) else torch.nn.functional.pad(grad_out[:, 32 * i:32 * i + n], (0, 32 - n))
+                gf, gw, gbias = ops.gno_backward(ws, bs, y3, x3, fb.contiguous(), gb.contiguous(), graph, precision=0)
+                outs.append(gf if n == 32 else gf[:, :n])
+                g0 = gw[0][:dims[0][0]]
+                add(fcs[0].weight, g0 if cd == 3 else torch.cat([g0[:, :cd], g0[:, 3:3 + cd]], dim=1))
+                add(fcs[0].bias, gbias[0][:dims[0][0]])
+                for l in range(1, len(fcs) - 1):
+                    add(fcs[l].weight, gw[l][:dims[l][0], :dims[l][1]])
+                    add(fcs[l].bias, gbias[l][:dims[l][0]])
+                last = torch.zeros(dims[-1], dtype=torch.float32, device=gf.device)
+                last[32 * i:32 * i + n] = gw[-1][:n, :dims[-1][1]]
+                add(fcs[-1].weight, last)
+                lastb = torch.zeros(dims[-1][0], dtype=torch.float32, device=gf.device)
+                lastb[32 * i:32 * i + n] = gbias[-1][:n]
+                add(fcs[-1].bias, lastb)
+            return outs[0].contiguous() if len(outs) == 1 else torch.cat(outs, dim=1)
+
     def _on_lists(self, fn, y_pos, x_pos, f_y, lists, order: int, dirs=None, qd: bool = False):
         """The seven list methods: the forward-mode routes on the regular list ``lists`` = (nbr, k) or on the by-query list of the graph
         ``lists``, at ``order`` 0 (value), 1 (and Jacobian) or 2 (and 2-jets along ``dirs``: host values [nd][3], or with ``qd`` a

@@ -888,7 +888,8 @@ class MAGNODecoder(nn.Module):
         product of the sampled field with respect to the latent for a cotangent [Nq, out_channels] -- the gradient of any number
         computed from sampled values (an integrated load sum_q a_q n_q p(x_q), a misfit at sensor points), which the autograd of
         ``GAOT3D.latent`` carries on into the encoder, the processor and the sample's coordinates.  The decoder's parameters and the
-        query coordinates are CONSTANTS here (the derivative with respect to the query is ``sample_jacobian``'s).
+        query coordinates are CONSTANTS here (the derivative with respect to the query is ``sample_jacobian``'s).  ``sample_vjp_params`` returns
+        the parameters' gradients as well (``GAOT3D.sample_autograd_params``).
 
         Streamed as ``sample`` is, ``chunk_points`` queries at a time through the same chunk loop: per chunk the lists
         (``knn_to_grid``, or ``graph.query_lists`` per scale), the GNO rows recomputed at fp32 arithmetic and mixed, the cotangent
@@ -912,6 +913,157 @@ class MAGNODecoder(nn.Module):
         device raise ValueError."""
         return self._adjoint("sample_vjp", 0, rndata_flat, query_pos, [("the cotangent", cotangent, (), False)], latent_tokens_pos,
                              chunk_points)
+
+    @torch.no_grad()
+    def sample_vjp_params(self, rndata_flat, query_pos, cotangent, latent_tokens_pos, chunk_points: Optional[int] = None):
+        """``sample_vjp`` WITH the decoder's parameters: -> (grad_latent [M, C] (fp32), grads), ``grads`` a dict keyed as
+        ``named_parameters()`` keys them that holds, for EVERY parameter of this decoder, sum_q cotangent[q] . d pred[q] / d parameter
+        in fp32 -- what trains the decoder through the streamed field, at the memory of one chunk.
+
+        The chunk loop, the checks and the refusals are ``sample_vjp``'s (``_adjoint`` at order 0).  Per chunk: the lists and the GNO
+        rows recomputed and mixed as ``_adjoint_chunk`` does; the projection's backward -- ONE ``ops.mlp2_backward_f32`` launch over the
+        chunk's rows for the erf-GELU family 32 -> {64, 128, 256} -> 1..4 (the hidden layer never reaches memory), else the GEMM chain
+        in the row blocks of ``_project_cot`` (``ops.gemm_dw`` / ``ops.colsum`` / ``ops.act_bwd``), d_b2 by ``ops.colsum``; the scale
+        mix's cotangent, whose ``dlogits`` (``ops.scale_mix_bwd``) go on through the 3 -> 16 -> scales weighting MLP on row lists;
+        ``graph.by_source``; then per scale and 32-channel pass of ``_fused_passes`` ONE exact-fp32 ``ops.gno_backward`` launch, which
+        gives the kernel MLP's weight gradients and the latent's part together (``gaot_gno_adj`` is not run here), padded and cut as
+        ``GnoFn``'s passes are.  On a regular list the by-query offsets are q k.  The chunk's parts are added in fp32 and in chunk
+        order into ``grad_latent`` and one accumulator per parameter.
+
+        On the 'knn' route every scale sees the same list: the mix is of EQUAL operands, sum_s w_s = 1 whatever the logits, so the
+        gradient of the scale-weighting MLP is identically zero and its entries are exact zeros.
+
+        Exact fp32 in both precision modes (the same bits), outside autograd, bit-reproducible for a given ``chunk_points``, NOT
+        bit-identical across chunkings; ``grad_latent`` is not bit-identical to ``sample_vjp``'s (another kernel, another order of
+        summation).  Refusals are ``sample_vjp``'s, and a kernel MLP with four hidden layers raises NotImplementedError (the exact-fp32
+        ``gaot_gno_bwd`` has no such instantiation); everything is refused before any launch."""
+        from ... import ops
+        fn = "sample_vjp_params"
+        self._sample_args(fn, chunk_points)
+        self._check_cotangents(fn, query_pos, [("the cotangent", cotangent, (), False)])
+        self._param_adjoint_layers(fn)
+        grid, chunk, rows = self._adjoint_stream(fn, 0, rndata_flat, query_pos, latent_tokens_pos, chunk_points,
+                                                 "the adjoint of the sampled field with the decoder's parameters")
+        rndata_flat, query_pos, cot = rndata_flat.detach(), query_pos.detach(), cotangent.detach().contiguous()
+        names = {id(p): name for name, p in self.named_parameters()}
+        grads = {name: torch.zeros(p.shape, dtype=torch.float32, device=p.device) for name, p in self.named_parameters()}
+
+        def add(p, g):
+            if p is not None:
+                grads[names[id(p)]].add_(g.reshape(p.shape))
+
+        with ops.fp32_arithmetic():
+            f = rndata_flat.to(torch.float32).contiguous()
+            grad = torch.zeros_like(f)
+            for sl, q, lists in self._stream_chunks(grid, query_pos, chunk, "rows" if rows else "knn", lead=False):
+                grad.add_(self._param_adjoint_chunk(f, q.contiguous(), cot[sl], latent_tokens_pos, lists, add))
+        return grad, grads
+
+    def _param_adjoint_layers(self, fn) -> None:
+        """the refusal ``sample_vjp_params`` adds to ``sample_vjp``'s: the kernel MLP's gradients come from the exact-fp32
+        ``gaot_gno_bwd``, which is instantiated for one to three hidden layers"""
+        nfc = len(list(self.gno.channel_mlp.fcs))
+        if nfc > 4:
+            raise NotImplementedError(f"MAGNODecoder.{fn}: the decoder's parameter gradients with a kernel MLP of {nfc - 1} hidden layers "
+                                      "are not supported: the exact-fp32 backward of the transform (gaot_gno_bwd) takes three at most")
+
+    def _project_bwd(self, x, g, add, fused: bool = True):
+        """the projection's backward for ``sample_vjp_params``: -> dx [rows, C]; the gradients of its parameters go to ``add``.  One
+        ``ops.mlp2_backward_f32`` launch when the fused kernel takes the shape, else (or with ``fused`` False: the measurement's other
+        side) the GEMM chain in ``_project_cot``'s row blocks with the blocks' weight gradients added in block order."""
+        from ... import ops
+        fc1, fc2 = self.projection.fcs
+        w1, w2 = GF._w2d(fc1.weight).detach().contiguous(), GF._w2d(fc2.weight).detach().contiguous()
+        act = ops.ACT[self.projection.non_linearity]
+        n, c = x.shape
+        hid, oc = w1.shape[0], w2.shape[0]
+        if fc2.bias is not None:
+            add(fc2.bias, ops.colsum(g, n, oc, oc))
+        if fused and act == ops.ACT["gelu"] and fc1.bias is not None and ops.mlp2_bwd_f32_supported(c, hid, oc, act):
+            dx, dw1, db1, dw2 = ops.mlp2_backward_f32(x, w1, fc1.bias.detach().contiguous(), w2, g)
+            add(fc1.weight, dw1), add(fc1.bias, db1), add(fc2.weight, dw2)
+            return dx
+        dx = torch.empty_like(x)
+        step = n if hid <= c else max(1024, n * c // hid)
+        for j in range(0, n, step):
+            xb, gb = x[j:j + step], g[j:j + step]
+            m = xb.shape[0]
+            if act > 3:
+                z = ops.gemm(xb, w1, m, hid, c, c, c, False, True, fc1.bias, 0, precision=0)
+                h = ops.act_fwd(z, act)
+            elif act:
+                h, z = ops.gemm(xb, w1, m, hid, c, c, c, False, True, fc1.bias, act, want_preact=True, precision=0)
+            else:
+                h = z = ops.gemm(xb, w1, m, hid, c, c, c, False, True, fc1.bias, 0, precision=0)
+            if oc == 1:     # the wide dimension on the tile rows (LinearFn.backward)
+                add(fc2.weight, ops.gemm_dw(h, gb, hid, 1, m, hid, 1, precision=0))
+            else:
+                add(fc2.weight, ops.gemm_dw(gb, h, oc, hid, m, oc, hid, precision=0))
+            del h
+            a = ops.gemm(gb, w2, m, hid, oc, oc, hid, False, False, precision=0)
+            dz = ops.act_bwd(z, a, act) if act else a
+            del z, a
+            add(fc1.weight, ops.gemm_dw(dz, xb, hid, c, m, hid, c, precision=0))
+            if fc1.bias is not None:
+                add(fc1.bias, ops.colsum(dz, m, hid, hid))
+            ops.gemm(dz, w1, m, c, hid, hid, c, False, False, out=dx[j:j + step], ldc=c, precision=0)
+            del dz
+        return dx
+
+    def _scale_weighting_bwd(self, q, dlogits, add) -> None:
+        """the cotangent ``dlogits`` [n, scales] of the scale weights' logits l = W_2 relu(W_1 q + b_1) + b_2 carried into the four
+        parameters of the weighting MLP: two ``gemm_dw``, two ``colsum`` and the ReLU mask (relu'(h) read from h itself)"""
+        from ... import ops
+        sw = self.scale_weighting
+        n, ns = dlogits.shape
+        w1, w2 = sw[0].weight.detach().contiguous(), sw[2].weight.detach().contiguous()
+        hd, cd = w1.shape
+        h = _scale_logits(self, q)[1].contiguous()
+        dl = dlogits.contiguous()
+        add(sw[2].weight, ops.gemm_dw(dl, h, ns, hd, n, ns, hd, precision=0))
+        add(sw[2].bias, ops.colsum(dl, n, ns, ns))
+        dh = ops.gemm(dl, w2, n, hd, ns, ns, hd, False, False, precision=0)
+        dz = ops.act_bwd(h, dh, ops.ACT["relu"])
+        add(sw[0].weight, ops.gemm_dw(dz, q, hd, cd, n, hd, cd, precision=0))
+        add(sw[0].bias, ops.colsum(dz, n, hd, hd))
+
+    def _param_adjoint_chunk(self, rndata_flat, q, cot, lat, lists, add):
+        """One chunk of ``sample_vjp_params`` -> its [M, C] part of the latent's gradient; the chunk's parameter gradients go to
+        ``add``.  A call of its own, so that a chunk's rows and lists are freed before the next chunk's are allocated."""
+        from ... import graph as device_graph
+        from ... import ops
+        m, knn = lat.shape[0], isinstance(lists, tuple)
+        outs = w = None
+        if knn:
+            x = self._mix_equal_scales([self.gno.forward_knn(lat, q, *lists, rndata_flat)], q)[0]
+        else:
+            outs = [self.gno(y_pos=lat, x_pos=q, edge_index=None, f_y=rndata_flat, graph=rows) for rows in lists]
+            if len(outs) > 1 and self.use_scale_weights:
+                outs = [o.contiguous() for o in outs]
+                x, w = ops.scale_mix_fwd(outs, _scale_logits(self, q)[0].contiguous())
+            else:
+                x, outs = _mix_scales(self, outs, q), None
+        d = self._project_bwd(x.contiguous(), cot, add)
+        del x
+        if knn:
+            per = self._mix_equal_scales([d], q)        # (sum_s w_s) d: the weighting MLP's gradient is identically zero
+        elif w is not None:
+            per, dlogits = ops.scale_mix_bwd(outs, w, d)
+            self._scale_weighting_bwd(q, dlogits, add)
+            del dlogits
+        else:
+            per = [d] * len(lists)
+        del d, outs, w
+        part = None
+        for rows, g in zip([lists] if knn else lists, per):
+            graph = device_graph.by_source(rows, m)
+            if knn:                                      # a regular list: query q's edges are q k .. q k + k - 1 (only the offsets are read)
+                n, k = int(q.shape[0]), int(lists[1])
+                offs = torch.arange(0, (n + 1) * k, k, dtype=torch.int32, device=q.device)
+                graph = ops.BipartiteGraph(ops.SortedEdges(offs, None, None, lists[0].reshape(-1), n), graph.by_src, m, n)
+            p = self.gno._param_adjoint(lat, q, rndata_flat, g, graph, add)
+            part = p if part is None else part.add_(p)
+        return part
 
     # the projection activations ``sample_jacobian_vjp`` differentiates twice: act' and act'' as plain fp32 tensor operations
     JAC_VJP_ACTS = (None, "none", "gelu", "relu")

@@ -2132,6 +2132,47 @@ def mlp2_backward(x: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, dout: Tensor, d
     return dx, dw1, db1, dw2
 
 
+def mlp2_bwd_f32_supported(in_dim: int, hidden: int, out_dim: int, act: int) -> bool:
+    return bool(_lib.load().gaot_mlp2_bwd_f32_supported(int(in_dim), int(hidden), int(out_dim), int(act)))
+
+
+def mlp2_backward_f32(x: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, dout: Tensor):
+    """-> (dx, dw1, db1, dw2) of out = w2 gelu(w1 x + b1) + b2 in exact fp32, ONE launch plus the fixed-order completion of the
+    weight-gradient partials (include/gaot3d_hip.h: gaot_mlp2_bwd_f32): x dense fp32 [rows, 32], dout dense fp32 [rows, out], hidden
+    in {64, 128, 256}, out in 1..4; d_b2 is ``colsum(dout)``.  Every operand is checked BEFORE a launch; a shape outside the family
+    raises GaotError (``mlp2_bwd_f32_supported``).  rows == 0 launches nothing and gives zeros."""
+    fn = "mlp2_backward_f32"
+    for name, t in (("x", x), ("w1", w1), ("b1", b1), ("w2", w2), ("dout", dout)):
+        if not isinstance(t, Tensor) or t.dtype != torch.float32 or not t.is_contiguous():
+            raise GaotError(f"{fn}: {name}: a contiguous float32 tensor expected, got "
+                            f"{(t.dtype, tuple(t.shape)) if isinstance(t, Tensor) else type(t).__name__}")
+    if x.dim() != 2 or w1.dim() != 2 or w2.dim() != 2 or b1.dim() != 1 or dout.dim() != 2:
+        raise GaotError(f"{fn}: x [rows, 32], w1 [hidden, 32], b1 [hidden], w2 [out, hidden], dout [rows, out] expected, got "
+                        f"{tuple(x.shape)}, {tuple(w1.shape)}, {tuple(b1.shape)}, {tuple(w2.shape)}, {tuple(dout.shape)}")
+    rows, hid, oc = int(x.shape[0]), int(w1.shape[0]), int(w2.shape[0])
+    if tuple(w1.shape) != (hid, x.shape[1]) or tuple(b1.shape) != (hid,) or tuple(w2.shape) != (oc, hid) or tuple(dout.shape) != (rows, oc):
+        raise GaotError(f"{fn}: shapes do not fit: x {tuple(x.shape)}, w1 {tuple(w1.shape)}, b1 {tuple(b1.shape)}, w2 {tuple(w2.shape)}, "
+                        f"dout {tuple(dout.shape)}")
+    lib = _lib.load()
+    if not lib.gaot_mlp2_bwd_f32_supported(int(x.shape[1]), hid, oc, 1):
+        raise GaotError(f"{fn}: supported shapes are in = 32, hidden in {{64, 128, 256}}, out in 1..4 (got {x.shape[1]} -> {hid} -> {oc})")
+    for name, t in (("x", x), ("w1", w1), ("b1", b1), ("w2", w2), ("dout", dout)):
+        if not t.is_cuda:
+            raise GaotError(f"{fn}: {name}: expected a tensor on the GPU (the HIP path has no CPU fallback), got {t.device}")
+    if rows == 0:
+        return torch.zeros_like(x), torch.zeros_like(w1), torch.zeros_like(b1), torch.zeros_like(w2)
+    if x.data_ptr() % 16:
+        raise GaotError(f"{fn}: x must be 16-byte aligned")
+    dx = torch.empty_like(x)
+    dw1, db1, dw2 = torch.empty_like(w1), torch.empty_like(b1), torch.empty_like(w2)
+    ws = _ws(lib.gaot_mlp2_bwd_f32_workspace_bytes(hid, oc), x.device)
+    with _timed(f"mlp2_bwd_f32_h{hid}"):
+        check(lib.gaot_mlp2_bwd_f32(_ptr(x), rows, 32, hid, oc, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(dout), _ptr(dx), None, None, None,
+                                    _ptr(ws), ws.numel(), _stream()), "gaot_mlp2_bwd_f32")
+        _finish_tables(ws, (dw1, db1, dw2), int(lib.gaot_mlp2_bwd_f32_parts(rows)), 4, False)
+    return dx, dw1, db1, dw2
+
+
 def _pointnet_args(source_pos: Tensor, query_pos: Tensor, g: BipartiteGraph, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, mode: int):
     source_pos = _req(source_pos, torch.float32, "source_pos")
     query_pos = _req(query_pos, torch.float32, "query_pos")

@@ -827,6 +827,25 @@ int gaot_mlp2_bwd(const float* x, int64_t num_rows, int in_dim, int hidden, int 
                   size_t workspace_bytes, gaot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The same backward in EXACT fp32, one launch (csrc/mlp2_bwd_f32.hip; the projection under MAGNODecoder.sample_vjp_params, which
+ * trains the decoder through the streamed field).  in_dim = 32, hidden in {64, 128, 256}, out_dim in 1..4, erf-GELU
+ * (gaot_mlp2_bwd_f32_supported: 1 for exactly this family, act being the activation id 1 = GELU).  x [rows, 32], d_out [rows, out]
+ * dense row-major; x and d_x 16-byte aligned.  Writes d_x [rows, 32], d_w1 [hidden, 32], d_b1 [hidden], d_w2 [out, hidden]; d_b2 is
+ * the column sum of d_out (gaot_colsum).  Every product is v_mfma_f32_32x32x2_f32; z, gelu(z), gelu'(z) and dz never reach HBM.  No
+ * atomics: the weight-gradient partials go per workgroup into the workspace as three tables of P = gaot_mlp2_bwd_f32_parts(num_rows)
+ * rows, [P][hidden * 32] | [P][hidden] | [P][out * hidden], summed in a fixed order by gaot_reduce_multi with lanes = 4 -- in the call
+ * (ONE more launch), or by the caller when d_w1 == d_b1 == d_w2 == NULL, bit-identical.  Bit-reproducible for a given num_rows; a
+ * row's d_x depends on that row alone (not on num_rows, the row's position or its workgroup).  num_rows == 0 launches nothing
+ * (gaot_mlp2_bwd_f32_parts gives 0) and clears the three weight gradients when they are given.
+ * ------------------------------------------------------------------------------------------- */
+int gaot_mlp2_bwd_f32_supported(int in_dim, int hidden, int out_dim, int act);
+size_t gaot_mlp2_bwd_f32_workspace_bytes(int hidden, int out_dim);
+int64_t gaot_mlp2_bwd_f32_parts(int64_t num_rows);
+int gaot_mlp2_bwd_f32(const float* x, int64_t num_rows, int in_dim, int hidden, int out_dim, const float* w1, const float* b1,
+                      const float* w2, const float* d_out, float* d_x, float* d_w1, float* d_b1, float* d_w2, void* workspace,
+                      size_t workspace_bytes, gaot_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Forward-mode tangents of the same two-layer MLP in one pass, exact fp32 (csrc/mlp2_jvp.hip; the projection under
  * sample_jacobian):  y = W2 gelu(W1 x + b1) + b2  and, for num_tangents = 0..3 planes dx_d [rows, 32],
  * dy_d = W2 (gelu'(W1 x + b1) * (W1 dx_d)).  in_dim = 32, hidden in {64, 128, 256}, out_dim in 1..4, erf-GELU

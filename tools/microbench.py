@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Kernel microbenchmarks at the configs[1] shapes (for rocprofv3 / quick A-B): attention fwd+bwd, GEMM shapes, GNO, PointNet GeoEmbed,
-the attention-weighted GNO, the forward-only decoder (decoder_sample), the sampled field's Jacobian (decoder_jacobian), the projection MLP's tangent alone (projection_jvp), the sampled field's Hessian and Laplacian (decoder_hessian), its derivatives along per-query directions (decoder_directional), its adjoint with respect to the latent (decoder_adjoint), the adjoint of its Jacobian (decoder_jacobian_adjoint), the adjoint of its Laplacian (decoder_laplacian_adjoint), the adjoints of its directional derivatives and of its Hessian (decoder_directional_adjoint, decoder_hessian_adjoint)."""
+the attention-weighted GNO, the forward-only decoder (decoder_sample), the sampled field's Jacobian (decoder_jacobian), the projection MLP's tangent alone (projection_jvp), the sampled field's Hessian and Laplacian (decoder_hessian), its derivatives along per-query directions (decoder_directional), its adjoint with respect to the latent (decoder_adjoint), the adjoint of its Jacobian (decoder_jacobian_adjoint), the adjoint of its Laplacian (decoder_laplacian_adjoint), the adjoints of its directional derivatives and of its Hessian (decoder_directional_adjoint, decoder_hessian_adjoint), the projection MLP's exact-fp32 backward alone (projection_bwd_f32), the streamed gradients of the latent and the decoder's parameters (decoder_param_adjoint)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 if os.environ.get("MB_TREE"):      # measure another checkout's package (gno_weighted: the parent commit's) with this script
@@ -1592,3 +1592,138 @@ elif what == "projection_jvp":
                   f"against a spread of {spread:.3f} ms; (b) faster beyond the spread: {ma - mb > spread}; y_a == y_b bit for bit: {same}, "
                   f"max|jac_a - jac_b| / peak = {dj:.1e}", flush=True)
             del x, dxs, pred, jac
+elif what == "projection_bwd_f32":
+    # The projection MLP's backward on its own (32 -> 256 -> out, out in {1, 4}, fp32 mode, random rows and cotangent), as
+    # MAGNODecoder.sample_vjp_params calls it on one chunk: d_x, d_W1, d_b1, d_W2 and d_b2.
+    #   (a) the GEMM chain (MAGNODecoder._project_bwd(fused=False)): gaot_gemm / gaot_act_bwd / gaot_colsum launches in row blocks with the
+    #       [rows, hidden] tensors in memory;
+    #   (b) one gaot_mlp2_bwd_f32 launch and its fixed-order completion (ops.mlp2_backward_f32), d_b2 by gaot_colsum.
+    # (a) and (b) alternate in this one process after a warm-up of each; device events around synchronised work; `reps` rounds (7 for the
+    # kept output); a row is the median with max - min, the peak is the rise of allocated memory over the operands.  Kept in
+    # profiles/projection_bwd_f32_microbench.txt.
+    from gaot_3d_amd.model.layers.magno import MAGNOConfig, MAGNODecoder
+    gaot_3d_amd.set_precision("fp32")
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); out = fn(); e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), torch.cuda.max_memory_allocated() - base, out
+
+    def median(ts):
+        ts = sorted(ts)
+        return ts[len(ts) // 2], ts[0], ts[-1]
+
+    for oc in (1, 4):
+        cfg = MAGNOConfig(gno_coord_dim=3, lifting_channels=32, mlp_type="linear", use_geoembed=[True, False], neighbor_strategy="knn",
+                          k_neighbors=8, out_gno_channel_mlp_hidden_layers=[64, 64], precompute_edges=False)
+        dec = MAGNODecoder(in_channels=32, out_channels=oc, gno_config=cfg).to(dev).eval()
+        for n in (1 << 20, 8000000):
+            x, g = torch.randn(n, 32, device=dev), torch.randn(n, oc, device=dev)
+
+            def run(fused):
+                got = {id(p): torch.zeros_like(p) for p in dec.projection.parameters()}      # sample_vjp_params' accumulators
+                with torch.no_grad(), ops.fp32_arithmetic():
+                    dx = dec._project_bwd(x, g, lambda p, t: got[id(p)].add_(t.reshape(p.shape)), fused=fused)
+                return [dx] + [got[id(p)] for p in dec.projection.parameters()]
+            ra, rb = timed(lambda: run(False))[2], timed(lambda: run(True))[2]
+            err = max(((a - b).abs().max() / a.abs().max()).item() for a, b in zip(ra, rb))
+            del ra, rb
+            ta, tb, pa, pb = [], [], 0, 0
+            for _ in range(reps):
+                t, p, _o = timed(lambda: run(False)); ta.append(t); pa = max(pa, p); del _o
+                t, p, _o = timed(lambda: run(True)); tb.append(t); pb = max(pb, p); del _o
+            (ma, lo_a, hi_a), (mb, lo_b, hi_b) = median(ta), median(tb)
+            spread = max(hi_a - lo_a, hi_b - lo_b)
+            print(f"N={n} out={oc} fp32: (a) the GEMM chain        {ma:9.3f} ms (max - min {hi_a - lo_a:.3f} ms), peak {pa / 2**20:9.1f} MiB")
+            print(f"N={n} out={oc} fp32: (b) gaot_mlp2_bwd_f32     {mb:9.3f} ms (max - min {hi_b - lo_b:.3f} ms), peak {pb / 2**20:9.1f} MiB  = {mb / ma:.3f} x (a) "
+                  f"in time; (a) - (b) = {ma - mb:.3f} ms against max - min {spread:.3f} ms of the rounds; (b) faster beyond it: {ma - mb > spread}; "
+                  f"max |(a) - (b)| / peak over the five results = {err:.1e}", flush=True)
+            del x, g
+elif what == "decoder_param_adjoint":
+    # The streamed gradients of the latent AND the decoder's parameters (MAGNODecoder.sample_vjp_params) on decoder_adjoint's decoders --
+    # configs[1] (knn, k = 8), or with `--strategy bidirectional|radius` the reference YAML's decoder on row lists -- at 500 K and 8 M random
+    # query points with a random cotangent, fp32 mode.  In this one process, alternated round by round after a warm-up of each:
+    #   (a) sample_vjp_params, streamed in chunks;
+    #   (b) the only other route to these gradients: the general decoder on an edge list for ALL queries under autograd (what
+    #       forward(query_coord_pos=..) runs), then torch.autograd.grad of <cotangent, pred> to the latent and the decoder's parameters;
+    #   (c) sample_vjp (the latent alone): what the parameters cost;
+    #   (d) the split of (a) by the library's timing keys (device events around every launch group, one more pass).
+    # Device events around synchronised work; `reps` rounds (7 for the kept output); a row is the median with max - min, the peak is the
+    # rise of allocated memory over the inputs.  Kept in profiles/decoder_param_adjoint_microbench.txt.
+    from gaot_3d_amd.data import latent_grid
+    from gaot_3d_amd.model.layers.magno import MAGNOConfig, MAGNODecoder
+    gaot_3d_amd.set_precision("fp32")
+    latent = (64, 64, 32)
+    strategy = sys.argv[sys.argv.index("--strategy") + 1] if "--strategy" in sys.argv else "knn"
+    if strategy not in ("knn", "radius", "bidirectional"):
+        sys.exit(f"--strategy must be knn, radius or bidirectional, got {strategy}")
+    rows = strategy != "knn"
+    cfg = MAGNOConfig(gno_coord_dim=3, lifting_channels=32, mlp_type="linear", use_geoembed=[True, False],
+                      neighbor_strategy=["knn", strategy] if rows else "knn", k_neighbors=1 if rows else 8, gno_radius=0.033,
+                      out_gno_channel_mlp_hidden_layers=[64, 64], precompute_edges=False)
+    dec = MAGNODecoder(in_channels=32, out_channels=1, gno_config=cfg).to(dev).eval()
+    dec.latent_dims = latent
+    tokens = latent_grid(latent).to(dev)
+    m_tok = tokens.shape[0]
+    rn = torch.randn(m_tok, 32, device=dev)
+    chunk = int(os.environ["MB_CHUNK"]) if os.environ.get("MB_CHUNK") else None
+    tag = f"fp32{' ' + strategy if rows else ''}"
+    names = [n for n, _ in dec.named_parameters()]
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); out = fn(); e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), torch.cuda.max_memory_allocated() - base, out
+
+    def median(ts):
+        ts = sorted(ts)
+        return ts[len(ts) // 2], ts[0], ts[-1]
+
+    def replaced(q, g):
+        leaf = rn.detach().clone().requires_grad_(True)
+        zq = torch.zeros(q.shape[0], dtype=torch.long, device=dev)
+        zl = torch.zeros(m_tok, dtype=torch.long, device=dev)
+        pred = dec._decode(leaf, q, zq, tokens, zl, None, False)
+        gl, *gp = torch.autograd.grad((pred * g).sum(), [leaf] + [p for _, p in dec.named_parameters()])
+        return gl, dict(zip(names, gp))
+
+    for nq in (500000, 8000000):
+        q = torch.rand(nq, 3, device=dev) * 2 - 1
+        g = torch.randn(nq, 1, device=dev)
+        routes = {"(a) sample_vjp_params": lambda: dec.sample_vjp_params(rn, q, g, tokens, chunk_points=chunk),
+                  "(b) decoder on an edge list + autograd.grad": lambda: replaced(q, g),
+                  "(c) sample_vjp (the latent alone)": lambda: dec.sample_vjp(rn, q, g, tokens, chunk_points=chunk)}
+        warm = {n: timed(f)[2] for n, f in routes.items()}
+        (al, ap), (bl, bp) = warm["(a) sample_vjp_params"], warm["(b) decoder on an edge list + autograd.grad"]
+        err = max([((al - bl).abs().max() / bl.abs().max()).item()] + [((ap[n] - bp[n]).abs().max() / bp[n].abs().max()).item() for n in names])
+        del warm, al, ap, bl, bp
+        ts, pk = {n: [] for n in routes}, {n: 0 for n in routes}
+        for _ in range(reps):
+            for n, f in routes.items():
+                t, p, _o = timed(f); ts[n].append(t); pk[n] = max(pk[n], p); del _o
+        med = {n: median(ts[n]) for n in routes}
+        for n in routes:
+            m, lo, hi = med[n]
+            print(f"Nq={nq} {tag}: {n:45s} {m:9.3f} ms (max - min {hi - lo:.3f} ms = {100 * (hi - lo) / m:.1f} %), peak {pk[n] / 2**20:9.1f} MiB")
+        ka, kb, kc = list(routes)
+        print(f"Nq={nq} {tag}: (a) : (b) = {med[ka][0] / med[kb][0]:.2f} in time, {pk[ka] / max(pk[kb], 1):.3f} in peak memory "
+              f"((a) {'below' if pk[ka] < pk[kb] else 'NOT below'} (b)); (a) : (c) = {med[ka][0] / med[kc][0]:.2f} in time, "
+              f"{pk[ka] / max(pk[kc], 1):.2f} in peak memory; worst max |(a) - (b)| / max |(b)| over the latent and {len(names)} parameters = {err:.2e}")
+        ops.timing_reset(True)
+        dec.sample_vjp_params(rn, q, g, tokens, chunk_points=chunk)
+        torch.cuda.synchronize()
+        split = ops.timing_summary()
+        ops.timing_reset(False)
+        tot = sum(ms for _, ms in split.values())
+        for key, (calls, ms) in sorted(split.items(), key=lambda kv: -kv[1][1]):
+            print(f"Nq={nq} {tag}: (d) {key:24s} {calls:3d} calls {ms:9.3f} ms = {100 * ms / tot:5.1f} % of the timed launches' sum {tot:.3f} ms")
+        sys.stdout.flush()
+        del q, g
